@@ -168,6 +168,39 @@ def graph_check(model, opt, x, use_teacher):
             "compared": f"loss, {len(ge)} gradients, {len(pg)} updated tensors, bit for bit, from the state the timed region left"}
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: at most 64 MB in all, the .npy headers included
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy in float32 - ``loss``, the assignment the loss
+    was taken against (``q``, model.last_aux), and per trainable tensor its value as the optimizer left it (``param.<name>``) and the
+    gradient of that step (``grad.<name>``).  Over DUMP_BUDGET_BYTES in all (the larger architectures), every array of more than 4096
+    elements keeps the same fraction of its flattened elements, at sorted indices drawn by a generator seeded with the array's name: the
+    same elements in every run, so that two builds compare output for output."""
+    import zlib
+
+    import numpy as np
+
+    core = _core(model)
+    arrays = {"loss": loss.detach()}
+    aux = getattr(core, "last_aux", None) or {}
+    if torch.is_tensor(aux.get("q")):
+        arrays["q"] = aux["q"].detach()
+    for n, p in core.named_parameters():
+        if p.requires_grad:
+            arrays[f"param.{n}"] = p.detach()
+            if p.grad is not None:
+                arrays[f"grad.{n}"] = p.grad.detach()
+    frac = min(1.0, DUMP_BUDGET_BYTES / (4.0 * sum(t.numel() for t in arrays.values())))
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        v = t.float().cpu().numpy()
+        if frac < 1.0 and v.size > 4096:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            v = v.reshape(-1)[np.sort(rng.choice(v.size, max(4096, int(v.size * frac)), replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 DTYPE_NAMES = {"f16x3": "f32-split(f16x3)", "bf16x6": "f32-split(bf16x6)"}   # (the other modes are named by their mode string)
 
 
@@ -518,8 +551,13 @@ def main():
                          "and stay launch by launch), off with N > 1")
     ap.add_argument("--no_exchange_autotune", action="store_true",
                     help="N > 1: keep the default exchange (all-gather Sinkhorn, 4 gradient buckets) instead of timing the variants first")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, assignment, updated parameters, their gradients) "
+                         "as DIR/<name>.npy in float32, at most 64 MB in all")
     ap.add_argument("--exchange_probe_child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     global USE_MASK
     USE_MASK = a.use_mask
 
@@ -630,6 +668,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, loss)   # (before anything below moves the state on)
 
     # the replayed step against the eager one (same state), and the eager step's own time beside the replayed one's
     check = None

@@ -1,6 +1,12 @@
 import os
 import sys
 
+# MKL rounds fp32 matrix products differently from one code path to the next, and outside a reproducible mode it picks the path by CPU
+# vendor and by buffer alignment.  The oracle tests hold the torch-CPU oracle to the reference's outputs at 1e-12, so MKL is pinned to
+# its COMPATIBLE branch, the one that gives the same bits on every x86 CPU; the reference outputs those tests read were generated on it
+# (tests/test_oracle_golden.py).  Set before torch loads MKL; spawned rank processes inherit it.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
 import numpy as np
 import pytest
 

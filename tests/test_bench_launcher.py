@@ -66,3 +66,39 @@ def test_the_launcher_parent_never_touches_the_gpu():
     else:
         raise AssertionError("main() no longer calls launch_ranks")
     assert not gpu_touching(head)
+
+
+def test_dump_outputs_writes_the_last_step_within_budget(tmp_path, monkeypatch):
+    """``--dump-outputs``: loss, assignment, every trainable tensor and its gradient as float32 .npy; over the byte budget the large arrays
+    keep a fixed sample of their elements - the same one in every run."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    model = torch.nn.Linear(300, 100)
+    model.bias.requires_grad_(False)
+    for p in model.parameters():
+        p.grad = torch.randn(p.shape, generator=g)
+    model.last_aux = {"q": torch.rand(2, 50, 20, generator=g, dtype=torch.float64)}
+    loss = torch.tensor(1.25)
+
+    bench.dump_outputs(str(tmp_path / "full"), model, loss)
+    full = {f[:-4]: np.load(tmp_path / "full" / f) for f in os.listdir(tmp_path / "full")}
+    assert sorted(full) == ["grad.weight", "loss", "param.weight", "q"]
+    assert all(v.dtype == np.float32 for v in full.values())
+    assert full["loss"] == np.float32(1.25) and np.array_equal(full["q"], model.last_aux["q"].float().numpy())
+    assert np.array_equal(full["param.weight"], model.weight.detach().numpy()) and np.array_equal(full["grad.weight"], model.weight.grad.numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 15000)   # 62 001 floats in all: the weight and its gradient are sampled
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), model, loss)
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert sum(v.size for v in a.values()) <= 15000 + 4096 and a["q"].shape == (2, 50, 20)
+    assert a["param.weight"].size < 30000 and all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.isin(a["param.weight"], full["param.weight"]).all()

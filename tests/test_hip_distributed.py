@@ -127,9 +127,10 @@ def _worker(rank, W, port, ret, backend="gloo"):
 
 
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize("backend,W", [("gloo", 2), ("gloo", 4), ("gloo", 8), ("nccl", 2)])
+# (the largest gloo soak is 5 ranks: with this pytest process they are the 6 processes the suite lets hold the GPU at once)
+@pytest.mark.parametrize("backend,W", [("gloo", 2), ("gloo", 4), ("gloo", 5), ("nccl", 2)])
 def test_two_ranks_equal_single_process_on_concatenated_batch(backend, W):
-    """W ranks (2, and a 4- / 8-rank soak on the shared device) against ONE process on the concatenated batch: loss, assignment, gradients;
+    """W ranks (2, and a 4- / 5-rank soak on the shared device) against ONE process on the concatenated batch: loss, assignment, gradients;
     the exchange each rank issued (bucket order, bytes); and the persistent flat buckets of the second step."""
     import torch.multiprocessing as mp
 

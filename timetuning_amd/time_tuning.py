@@ -488,6 +488,13 @@ class TimeT(nn.Module):
             keep = (self._queue_rows_pushed, self._queue_seen, self.last_aux)
             ops._bump_param_epoch()
             torch.cuda.synchronize(x.device)
+            # no automatic garbage collection inside the capture (torch.cuda.graph collects once on entry): a collection there runs the
+            # finalizers of unrelated GPU objects - events, streams - whose HIP calls are illegal while the stream captures, and the
+            # runtime aborts the process
+            import gc
+
+            gc_on = gc.isenabled()
+            gc.disable()
             try:
                 with torch.cuda.graph(g):
                     loss, grads = self._run_step(xs, hp, True)
@@ -499,6 +506,9 @@ class TimeT(nn.Module):
                 ops._bump_param_epoch()   # operands 'converted' by launches that never ran are stale
                 torch.set_rng_state(rng)
                 return None
+            finally:
+                if gc_on:
+                    gc.enable()
             rec = self._step_graphs[key] = dict(graph=g, x=xs, loss=loss, grads=grads, aux=self.last_aux, m=m, labels=lab)
         else:
             rec["x"].copy_(x)
