@@ -516,6 +516,40 @@ int tt_img_color(unsigned char* img, int F, int H, int W, int mode, float factor
 int tt_img_box_blur(const unsigned char* in, unsigned char* out, int F, int H, int W, int direction, int radius, unsigned ww, unsigned fw,
                     tt_stream_t stream);
 
+/* ---- N5: linear-probe fine-tuning, linear_finetune.py - a 1x1-conv head on frozen features
+ *      (linear_finetune.py:13-31), CrossEntropyLoss(ignore_index=255) at mask resolution and torch.optim.SGD (:66-86).
+ *      The reference upsamples the D-channel features to R x R and then applies the conv; both are linear and the bilinear
+ *      weights sum to 1, so here the head runs at token resolution on C channels and only the C logits are upsampled.
+ *   Shapes: B images, g x g tokens (g <= 64), D feature channels (D % 4 == 0, D <= 1024), C classes (1..256), R x R masks
+ *   (R <= 1024); anything else returns TT_EINVAL before any launch.
+ *   tt_probe_logits             logits [rows, C] = feats [rows, D] W^T + b, W = the conv weight [C, D, 1, 1] as [C, D]; b may be
+ *                               NULL (linear_finetune.py:30, in the commuted order).  fp32 FMA, one pass over feats.
+ *   tt_probe_upsample_ce        nn.functional.interpolate(logits, (R,R), mode="bilinear") -> CrossEntropyLoss(ignore_index=255)
+ *                               -> backward (linear_finetune.py:26-30,81-84), fused: logits_low [B, g*g, C], labels int64
+ *                               [B, R, R] -> loss_out[1] (mean over the valid pixels; NaN if there are none), dlogits_low
+ *                               [B, g*g, C] = d loss / d logits_low (0 if there are no valid pixels), counts_out int64[2] =
+ *                               {valid pixels, invalid labels (outside [0, C) and not 255)}.  Invalid labels are only counted.
+ *                               The mask-resolution logits are never written; no float atomics (bitwise repeatable).  Two
+ *                               launches.  workspace: tt_probe_upsample_ce_workspace_bytes(B, g).
+ *   tt_bilinear_adjoint_tokens  d_low [B, g*g, C] from d_hi [B, R*R, C]: the adjoint of tt_upsample_bilinear_tokens (autograd of
+ *                               linear_finetune.py:26-27 in the commuted order), the same deterministic gather.
+ *   tt_probe_wgrad              dw [C, D] = dlogits^T feats, db [C] = column sums of dlogits (db may be NULL), over `rows` rows,
+ *                               times *scale_device if it is not NULL (the incoming gradient of the loss).  Split rows, fixed
+ *                               fold order, no atomics.  workspace: tt_probe_wgrad_workspace_bytes(rows, D, C).
+ *   tt_sgd_step                 torch.optim.SGD (linear_finetune.py:66,85; dampening 0, no Nesterov) over up to TT_MAX_TENSORS
+ *                               tt_adamw_tensor entries: d = g + weight_decay p; with momentum != 0, m = d if first_step else
+ *                               momentum m + d, and d = m (m is the momentum buffer, v is unused); p -= lr d. */
+int tt_probe_logits(const float* feats, const float* weight, const float* bias, float* logits, long long rows, int D, int C,
+                    tt_stream_t stream);
+size_t tt_probe_upsample_ce_workspace_bytes(int B, int g);
+int tt_probe_upsample_ce(const float* logits_low, const int64_t* labels, float* dlogits_low, float* loss_out, long long* counts_out,
+                         int B, int g, int C, int R, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+int tt_bilinear_adjoint_tokens(const float* d_hi, float* d_low, int B, int g, int C, int R, tt_stream_t stream);
+size_t tt_probe_wgrad_workspace_bytes(long long rows, int D, int C);
+int tt_probe_wgrad(const float* dlogits, const float* feats, const float* scale_device, float* dw, float* db, long long rows, int D,
+                   int C, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+int tt_sgd_step(const tt_adamw_tensor* tensors, int count, float momentum, int first_step, tt_stream_t stream);
+
 /* ---- Coarse entry points: whole reference functions as ONE call each.  They sequence the op-level entry
  *      points above on `stream` (same kernels, same results bit for bit as calling those one by one; they honour
  *      their `precision` argument / tt_vit_params.precision the way tt_linear_fwd does) and add nothing but the scratch layout.  Parameter tables are HOST

@@ -1532,3 +1532,96 @@ def adamw_ema_step_(entries: Sequence[tuple], step: int, beta1=0.9, beta2=0.999,
     _lib.check(lib.tt_adamw_ema_step(arr, len(entries), int(step), float(beta1), float(beta2), float(eps), _p(prototypes), K, dim,
                                      _p(teacher_flat) if n_flat else None, _p(student_flat) if n_flat else None, n_flat, _p(teacher_prototypes),
                                      float(momentum), _stream()), "tt_adamw_ema_step")
+
+
+# ---- N5: linear-probe fine-tuning (linear_finetune.py; include/timetuning_hip.h "N5") ---------------------------------------------------
+
+def probe_logits(feats, weight, bias=None):
+    """feats [rows, D], weight [C, D] (the 1x1 conv weight viewed as a matrix), bias [C] -> logits [rows, C]."""
+    lib = _lib.load()
+    _chk(feats, "feats"); _chk(weight, "weight")
+    if bias is not None:
+        _chk(bias, "bias")
+    rows, D = feats.shape
+    Cc = weight.shape[0]
+    if weight.shape[1] != D:
+        raise ValueError(f"probe_logits: weight has {weight.shape[1]} input channels, feats has {D}")
+    out = torch.empty((rows, Cc), dtype=f32, device=feats.device)
+    _lib.check(lib.tt_probe_logits(_p(feats), _p(weight), _p(bias), _p(out), rows, D, Cc, _stream()), "tt_probe_logits")
+    return out
+
+
+def probe_upsample_ce(logits_low, labels):
+    """logits_low [B, g*g, C], labels int64 [B, R, R] -> (loss [1] = mean CE(ignore_index=255) of the bilinear upsampling to R x R,
+    dlogits_low [B, g*g, C], counts int64 [2] = (valid pixels, invalid labels)).  Nothing is synchronised: read counts[1] to find
+    out whether a label was outside [0, C) and not 255 (such labels are only counted)."""
+    lib = _lib.load()
+    _chk(logits_low, "logits_low"); _chk(labels, "labels", torch.int64)
+    B, n, Cc = logits_low.shape
+    g = int(round(n ** 0.5))
+    if g * g != n:
+        raise ValueError(f"probe_upsample_ce: {n} tokens are not a square grid")
+    if labels.dim() != 3 or labels.shape[0] != B or labels.shape[1] != labels.shape[2]:
+        raise ValueError(f"probe_upsample_ce: labels must be [B, R, R], got {tuple(labels.shape)}")
+    R = labels.shape[1]
+    dev = logits_low.device
+    loss = torch.empty((1,), dtype=f32, device=dev)
+    counts = torch.empty((2,), dtype=torch.int64, device=dev)
+    dlow = torch.empty_like(logits_low)
+    nb = lib.tt_probe_upsample_ce_workspace_bytes(B, g)
+    ws = _ws(nb, dev)
+    _lib.check(lib.tt_probe_upsample_ce(_p(logits_low), _p(labels), _p(dlow), _p(loss), _p(counts), B, g, Cc, R, _p(ws), nb, _stream()),
+               "tt_probe_upsample_ce")
+    return loss, dlow, counts
+
+
+def bilinear_adjoint_tokens(d_hi, g: int):
+    """d_hi [B, R*R, C] -> d_low [B, g*g, C]: the adjoint (backward) of ``upsample_bilinear_tokens``."""
+    lib = _lib.load()
+    _chk(d_hi, "d_hi")
+    B, m, Cc = d_hi.shape
+    R = int(round(m ** 0.5))
+    if R * R != m:
+        raise ValueError(f"bilinear_adjoint_tokens: {m} pixels are not a square mask")
+    out = torch.empty((B, g * g, Cc), dtype=f32, device=d_hi.device)
+    _lib.check(lib.tt_bilinear_adjoint_tokens(_p(d_hi), _p(out), B, int(g), Cc, R, _stream()), "tt_bilinear_adjoint_tokens")
+    return out
+
+
+def probe_wgrad(dlogits, feats, scale=None, need_bias=True):
+    """dlogits [rows, C], feats [rows, D] -> (dW [C, D] = dlogits^T feats, db [C] = colsum(dlogits) or None), both times the
+    one-element device tensor ``scale`` if given."""
+    lib = _lib.load()
+    _chk(dlogits, "dlogits"); _chk(feats, "feats")
+    if scale is not None:
+        _chk(scale, "scale")
+    rows, Cc = dlogits.shape
+    if feats.shape[0] != rows:
+        raise ValueError("probe_wgrad: dlogits and feats need the same number of rows")
+    D = feats.shape[1]
+    dev = feats.device
+    dw = torch.empty((Cc, D), dtype=f32, device=dev)
+    db = torch.empty((Cc,), dtype=f32, device=dev) if need_bias else None
+    nb = lib.tt_probe_wgrad_workspace_bytes(rows, D, Cc)
+    ws = _ws(nb, dev)
+    _lib.check(lib.tt_probe_wgrad(_p(dlogits), _p(feats), _p(scale), _p(dw), _p(db), rows, D, Cc, _p(ws), nb, _stream()), "tt_probe_wgrad")
+    return dw, db
+
+
+def sgd_step_(entries: Sequence[tuple], momentum: float = 0.0, first_step: bool = False):
+    """torch.optim.SGD (dampening 0, no Nesterov) over (param, grad, momentum_buffer or None, lr, weight_decay) tuples, fp32 GPU
+    contiguous; ``first_step``: the buffers are (re)initialised to the step direction, as SGD does for a tensor's first step."""
+    _bump_param_epoch()
+    lib = _lib.load()
+    cap = 40
+    for i in range(0, len(entries), cap):
+        chunk = entries[i:i + cap]
+        arr = (_lib.AdamwTensor * len(chunk))()
+        for j, (p, g, buf, lr, wd) in enumerate(chunk):
+            _chk(p, "param"); _chk(g, "grad")
+            if buf is not None:
+                _chk(buf, "momentum_buffer")
+            if g.numel() != p.numel() or (buf is not None and buf.numel() != p.numel()):
+                raise ValueError("sgd_step_: param, grad and momentum buffer need the same size")
+            arr[j] = _lib.AdamwTensor(p.data_ptr(), g.data_ptr(), _p(buf), None, p.numel(), float(lr), float(wd))
+        _lib.check(lib.tt_sgd_step(arr, len(chunk), float(momentum), int(bool(first_step)), _stream()), "tt_sgd_step")
