@@ -479,7 +479,9 @@ int tt_foreground_mask_from_probs(const float* cls_probs, float* mask_out, float
  *                               mode="bilinear").float() (clustering.py:34-36).
  *   tt_upsample_argmax_f32      fp32 twin of tt_upsample_argmax for proto_clustering's prototype scores (clustering.py:101-104).
  *   tt_kmeans_assign            labels[p] = argmin_j |x_p - c_j|^2 (first minimum) over centroids [k, d]; dist2 optional.
- *   tt_kmeans_accumulate        sums[k, d] (fp64) and counts[k] of the points per label, deterministic (no atomics). */
+ *   tt_kmeans_accumulate        sums[k, d] (fp64) and counts[k] of the points per label, deterministic (no atomics).
+ *   Both hold the centroids in LDS: k * d <= 16384 (k * d + k for the accumulation), and for d <= 64 the assignment's LDS
+ *   (k * d + 256 (d | 1) floats) <= 128 KB - k = 300 at d = 50, the N6 over-clustering, fits. */
 int tt_affine_cols_inplace(float* x, const float* scale, const float* shift, long long rows, int cols,
                            tt_stream_t stream); /* x[r][c] = x[r][c] * scale[c] + shift[c] (StandardScaler.transform) */
 size_t tt_col_moments_workspace_bytes(long long rows, int cols);
@@ -549,6 +551,41 @@ size_t tt_probe_wgrad_workspace_bytes(long long rows, int D, int C);
 int tt_probe_wgrad(const float* dlogits, const float* feats, const float* scale_device, float* dw, float* db, long long rows, int D,
                    int C, void* workspace, size_t workspace_bytes, tt_stream_t stream);
 int tt_sgd_step(const tt_adamw_tensor* tensors, int count, float momentum, int first_step, tt_stream_t stream);
+
+/* ---- N6: cluster-based foreground extraction, cluster_based_foreground_extraction.py - over-cluster maps scored
+ *      against the ViT-attention foreground, a precision cut tuned on the train set, foreground masks on the val set.  Everything the
+ *      reference computes with per-image, per-cluster Python loops reduces to per-(image, cluster) integer counts.
+ *   Shapes: M images of P = R * R pixels (P <= 2^24), k clusters (1..4096); anything else returns TT_EINVAL before any launch.
+ *   range_flag: a device int the kernels set to 1 when a cluster id lies outside [0, k) (the caller zeroes and reads it).
+ *   tt_cbfe_cluster_stats       clusters, attn, gt: int64 [M, P] -> stats int32 [M, k, 3] = {n, tp_attn, tp_gt} per (image, cluster):
+ *                               pixels of the cluster, of those the ones with attn == 1, and the ones in the GT foreground;
+ *                               gt_fg int32 [M] = GT foreground pixels per image.  GT foreground is gt != 0 (ignore < 0) or
+ *                               gt != 0 && gt != ignore (eval_jac's with_boundary True / False, :117-120).  attn and gt may
+ *                               be NULL (their counts are 0).  Pixels with an out-of-range id raise range_flag and are not counted.  Integer
+ *                               LDS atomics, one workgroup per image: the result is independent of the order of the adds.
+ *                               Replaces get_cluster_precs' loops (:85-101) and eval_jac's sums (:117-125).
+ *   tt_cbfe_cluster_precs       stats -> precs fp64 [k], occurrences int32 [k]: get_cluster_precs (:85-107) bit for bit - per cluster
+ *                               the sum of tp_attn / n (fp64, IEEE division) over the images with n > 0 in increasing image order,
+ *                               divided by the occurrence count (NaN for a cluster that never occurs).
+ *   tt_cbfe_cut_jaccard         find_good_threshold's Jaccards (:140-153 through eval_jac, :111-129): candidate c marks the clusters
+ *                               order[starts[c] .. k) as foreground; per image inter = the suffix sum of tp_gt, union = gt_fg +
+ *                               suffix(n) - inter, iou = float(inter) / float(union) (fp32, correctly rounded; 0 / 0 = NaN);
+ *                               jac [C] = the sequential fp32 sum of iou over the images in order, divided by M in fp32.  iou
+ *                               (optional, fp32 [C, M]) receives the per-image values.  order int32 [k], starts int32 [C]; the
+ *                               kernel never sorts.  workspace: tt_cbfe_cut_jaccard_workspace_bytes(M, C).
+ *   tt_cbfe_apply_fg            make_post_matching_maps (:221-227): mask int64 [total] = fg_table[clusters[i]] (uint8 [k], 0 / 1).
+ *   tt_nearest_upsample_labels  token labels int32 [M, g * g] -> pixel labels int64 [M, R * R] through the row / column tables iy, ix
+ *                               (int32 [R], entries in [0, g)) of F.interpolate(mode="nearest") (:229-235 applied to labels). */
+int tt_cbfe_cluster_stats(const int64_t* clusters, const int64_t* attn, const int64_t* gt, int32_t* stats, int32_t* gt_fg, int M, long long P,
+                          int k, long long ignore, int* range_flag, tt_stream_t stream);
+int tt_cbfe_cluster_precs(const int32_t* stats, double* precs, int32_t* occurrences, int M, int k, tt_stream_t stream);
+size_t tt_cbfe_cut_jaccard_workspace_bytes(int M, int C);
+int tt_cbfe_cut_jaccard(const int32_t* stats, const int32_t* gt_fg, const int32_t* order, const int32_t* starts, float* jac, float* iou,
+                        int M, int k, int C, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+int tt_cbfe_apply_fg(const int64_t* clusters, const uint8_t* fg_table, int64_t* mask, long long total, int k, int* range_flag,
+                     tt_stream_t stream);
+int tt_nearest_upsample_labels(const int32_t* tok, const int32_t* iy, const int32_t* ix, int64_t* out, int M, int g, int R,
+                               tt_stream_t stream);
 
 /* ---- Coarse entry points: whole reference functions as ONE call each.  They sequence the op-level entry
  *      points above on `stream` (same kernels, same results bit for bit as calling those one by one; they honour

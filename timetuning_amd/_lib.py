@@ -162,6 +162,12 @@ SIGNATURES = {
     "tt_probe_wgrad_workspace_bytes": (c_sz, [c_ll, c_i, c_i]),
     "tt_probe_wgrad": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_vp, c_sz, c_vp]),
     "tt_sgd_step": (c_i, [C.POINTER(AdamwTensor), c_i, c_f, c_i, c_vp]),
+    "tt_cbfe_cluster_stats": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_ll, c_i, c_ll, c_vp, c_vp]),
+    "tt_cbfe_cluster_precs": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_vp]),
+    "tt_cbfe_cut_jaccard_workspace_bytes": (c_sz, [c_i, c_i]),
+    "tt_cbfe_cut_jaccard": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
+    "tt_cbfe_apply_fg": (c_i, [c_vp, c_vp, c_vp, c_ll, c_i, c_vp, c_vp]),
+    "tt_nearest_upsample_labels": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp]),
 }
 
 _lib = None

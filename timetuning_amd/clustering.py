@@ -124,7 +124,12 @@ class Kmeans:
             raise RuntimeError(f"Number of training points ({n}) should be at least as large as number of clusters ({k})")
         if n > k * self.max_points_per_centroid:  # subsample_training_set
             x = x[self._perm(n, self.seed)[: k * self.max_points_per_centroid].to(x.device)].contiguous()
-            n = x.shape[0]
+        return self._lloyd(x, init_indices)
+
+    def _lloyd(self, x: torch.Tensor, init_indices=None) -> float:
+        """The redos of Lloyd iterations on the (subsampled) training points x [n, d]."""
+        n, d = x.shape
+        k = self.k
         best_obj, best = float("inf"), None
         self.obj = []
         for redo in range(self.nredo):
@@ -156,6 +161,60 @@ class Kmeans:
             x = x.cuda()
         labels, dist2 = ops.kmeans_assign(x.contiguous(), self._centroids_dev, return_dist=True)
         return dist2, labels.long()
+
+    # -- points that are the nearest upsampling of token grids ---------------------------------------------------------------------
+    # Nearest upsampling from a g x g token grid to R x R only repeats token vectors: point (m, y, x) of the upsampled set is token
+    # (m, iy[y], ix[x]).  The two methods below take the tokens [M, g*g, d] and never build the [M * R * R, d] points; the training
+    # subsample gathers the same rows ``train`` would pick from the materialised tensor (flattened as (m, y, x), the reference's
+    # create_overclustering_maps layout, cluster_based_foreground_extraction.py:268-279), and the assignment runs once per token.
+    # Labels and centroids are bit-identical to ``train`` / ``assign`` on the materialised tensor; faiss parity stays unpinned.
+
+    def _virtual_rows(self, p: torch.Tensor, M: int, g: int, R: int) -> torch.Tensor:
+        iy, ix = nearest_index_table(g, R)
+        iy, ix = torch.from_numpy(iy.astype(np.int64)), torch.from_numpy(ix.astype(np.int64))
+        m, rem = p // (R * R), p % (R * R)
+        return m * (g * g) + iy[rem // R] * g + ix[rem % R]
+
+    def train_upsampled(self, tokens: torch.Tensor, resolution: int, init_indices=None) -> float:
+        """``train`` on the nearest upsampling of tokens [M, g*g, d] to resolution x resolution, without materialising it."""
+        tokens = torch.as_tensor(tokens, dtype=torch.float32)   # (tokens on the host stay there: only the subsample moves)
+        M, n_tok, d = tokens.shape
+        g = int(round(n_tok ** 0.5))
+        if g * g != n_tok:
+            raise ValueError(f"train_upsampled: {n_tok} tokens are not a square grid")
+        R = int(resolution)
+        n, k = M * R * R, self.k
+        if n < k:
+            raise RuntimeError(f"Number of training points ({n}) should be at least as large as number of clusters ({k})")
+        p = self._perm(n, self.seed)[: k * self.max_points_per_centroid] if n > k * self.max_points_per_centroid else torch.arange(n)
+        rows = self._virtual_rows(p, M, g, R).to(tokens.device)
+        x = tokens.reshape(M * n_tok, d)[rows].cuda().contiguous()
+        return self._lloyd(x, init_indices)
+
+    def assign_upsampled(self, tokens: torch.Tensor, resolution: int) -> torch.Tensor:
+        """Labels int64 [M, R*R] of the nearest upsampling of tokens [M, g*g, d]: one assignment per token, then the labels are
+        upsampled (tt_nearest_upsample_labels)."""
+        tokens = torch.as_tensor(tokens, dtype=torch.float32)
+        if not tokens.is_cuda:
+            tokens = tokens.cuda()
+        M, n_tok, d = tokens.shape
+        g = int(round(n_tok ** 0.5))
+        labels = ops.kmeans_assign(tokens.reshape(M * n_tok, d).contiguous(), self._centroids_dev)
+        iy, ix = nearest_index_table(g, resolution, device=tokens.device)
+        return ops.nearest_upsample_labels(labels.view(M, n_tok), iy, ix)
+
+
+def nearest_index_table(g: int, R: int, device=None):
+    """Row / column source indices of ``F.interpolate(mode="nearest")`` from g x g to R x R, read off torch itself (an index grid
+    interpolated on the host): int32 numpy arrays (iy, ix), or int32 tensors on ``device``."""
+    import torch.nn.functional as F
+
+    grid = torch.arange(g * g, dtype=torch.float64).view(1, 1, g, g)
+    up = F.interpolate(grid, size=(R, R), mode="nearest")[0, 0].long()
+    iy, ix = (up[:, 0] // g).numpy().astype(np.int32), (up[0, :] % g).numpy().astype(np.int32)
+    if device is None:
+        return iy, ix
+    return torch.from_numpy(iy).to(device), torch.from_numpy(ix).to(device)
 
 
 # ------------------------------------------------------------------------------------------------

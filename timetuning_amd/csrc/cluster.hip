@@ -16,7 +16,8 @@ namespace tt {
 
 constexpr int CL_THREADS = 256;
 constexpr int CL_MAXD = 1024;     // feature columns for the moments
-constexpr int KM_MAXKD = 8192;    // k * d floats of centroids held in LDS (32 KB)
+constexpr int KM_MAXKD = 16384;   // k * d floats of centroids held in LDS (64 KB; k = 300 at d = 50 for the CBFE over-clustering)
+constexpr size_t KM_MAX_LDS = 128 * 1024;   // dynamic LDS a k-means workgroup may ask for (the attribute raised below)
 
 // ---- column moments: partial[b][0][c] = sum_r x[r][c], partial[b][1][c] = sum_r x[r][c]^2 over the block's rows (fp64)
 __global__ __launch_bounds__(CL_THREADS) void col_moments_stage1(const float* __restrict__ x, double* __restrict__ partial, long long rows,
@@ -264,9 +265,13 @@ extern "C" int tt_kmeans_assign(const float* x, const float* centroids, int32_t*
   TT_REQUIRE(x && centroids && labels && P > 0 && d > 0 && k > 0, "kmeans_assign: bad arguments");
   TT_REQUIRE((long long)k * d <= KM_MAXKD, "kmeans_assign: k * d = %d exceeds %d", k * d, KM_MAXKD);
   const size_t lds = sizeof(float) * ((size_t)k * d + (d <= 64 ? (size_t)CL_THREADS * (d | 1) : 0));
-  static const bool lds_attr_set = [] {  // the d <= 64 tile needs up to 32 KB of centroids + 65 KB of points
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_assign_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               128 * 1024) == hipSuccess;
+  TT_REQUIRE(lds <= KM_MAX_LDS, "kmeans_assign: k = %d, d = %d need %zu bytes of LDS (at most %zu)", k, d, lds, KM_MAX_LDS);
+  static const bool lds_attr_set = [] {  // centroids (up to 64 KB) + the d <= 64 tile's points (up to 65 KB)
+    bool ok = true;
+    for (const void* f : {reinterpret_cast<const void*>(&kmeans_assign_kernel<16>), reinterpret_cast<const void*>(&kmeans_assign_kernel<64>),
+                          reinterpret_cast<const void*>(&kmeans_assign_kernel<0>)})
+      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_MAX_LDS) == hipSuccess;
+    return ok;
   }();
   TT_REQUIRE(lds_attr_set, "kmeans_assign: could not raise the dynamic LDS limit");
   long long blocks = (P + CL_THREADS - 1) / CL_THREADS;
@@ -291,6 +296,9 @@ extern "C" int tt_kmeans_accumulate(const float* x, const int32_t* labels, doubl
   TT_REQUIRE(x && labels && sums && counts && workspace && P > 0 && d > 0 && k > 0, "kmeans_accumulate: bad arguments");
   TT_REQUIRE((long long)k * d + k <= KM_MAXKD, "kmeans_accumulate: k * d = %d exceeds %d", k * d, KM_MAXKD);
   TT_REQUIRE(workspace_bytes >= tt_kmeans_accumulate_workspace_bytes(P, d, k), "kmeans_accumulate: workspace too small");
+  static const bool lds_attr_set = hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_accumulate_stage1),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_MAX_LDS) == hipSuccess;
+  TT_REQUIRE(lds_attr_set, "kmeans_accumulate: could not raise the dynamic LDS limit");
   hipStream_t s = as_stream(stream);
   const int blocks = accumulate_blocks(P);
   const long long ppb = (P + blocks - 1) / blocks;

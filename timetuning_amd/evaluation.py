@@ -1,14 +1,19 @@
 """Evaluator with the reference's surface (``evaluation.py:250-310,312-486``): features without head -> clustering ->
 matched mIoU, for the three protocols (frame-wise / sample-wise / dataset-wise).  Dataset readers, video / GIF logging and
-the wandb plumbing are out of scope; the loader is any iterable of ``(data, annotations[, label])`` batches."""
+the wandb plumbing are out of scope; the loader is any iterable of ``(data, annotations[, label])`` batches.
+
+``use_mask=True`` evaluates masked features as the reference does (``evaluation.py:411-424,461-462``): with ``fg_masks`` given to the
+constructor (the foreground masks of cluster_based_foreground_extraction, [N, R', R']) the dataset-wise features are multiplied by
+the masks' nearest downsampling to the token grid; otherwise by the attention foreground (``models.apply_attention_mask``)."""
 from __future__ import annotations
 
 import torch
 import torch.nn.functional as F
 
-from .clustering import cluster_features, proto_clustering
+from . import hip_ops as ops
+from .clustering import cluster_features, nearest_index_table, proto_clustering
 from .metrics import PredsmIoU
-from .models import FeatureExtractor
+from .models import FeatureExtractor, apply_attention_mask
 
 
 def evaluate_localizations(PredsEval, gts, preds, evaluation_protocol, logging_directory=None, many_to_one=False, precision_based=False):
@@ -42,20 +47,47 @@ def evaluate_localizations(PredsEval, gts, preds, evaluation_protocol, logging_d
 
 class Evaluator:
     """``Evaluator(model, data_loader, num_prototypes, device, logger, clustering_algorithm)`` (``evaluation.py:312-371``) reduced
-    to what ``evaluate`` needs."""
+    to what ``evaluate`` needs.  ``fg_masks`` ([N, R', R'] or [N, 1, R', R'], one per frame of the loader in order): the reference's
+    foreground masks for ``evaluate(use_mask=True)`` (``evaluation.py:325,340``)."""
 
     def __init__(self, model, data_loader, num_prototypes=21, device="cuda", logger=None, clustering_algorithm="k-means", uvos_flag=False,
-                 involve_bg=False):
+                 involve_bg=False, fg_masks=None):
         self.model, self.data_loader, self.device = model, data_loader, device
         self.clustering_algorithm = clustering_algorithm
         self.uvos_flag = uvos_flag
         self.PredsEval = PredsmIoU(num_prototypes, num_prototypes, involve_bg=involve_bg)
+        self.fg_masks = fg_masks
 
-    def _features(self, data):
+    def _features(self, data, with_attention=False):
         fe = self.model if isinstance(self.model, FeatureExtractor) else self.model.feature_extractor
         bs, fs, c, h, w = data.shape
-        feats, _ = fe(data.view(bs * fs, c, h, w).to(self.device), use_head=False)
-        return feats.view(bs, fs, feats.shape[1], feats.shape[2]), fe.spatial_resolution
+        feats, attn = fe(data.view(bs * fs, c, h, w).to(self.device), use_head=False)
+        feats = feats.view(bs, fs, feats.shape[1], feats.shape[2])
+        if with_attention:
+            return feats, fe.spatial_resolution, attn
+        return feats, fe.spatial_resolution
+
+    def _attention_masked(self, data):
+        """features * the attention foreground (evaluation.py:411-413,461-462)."""
+        feats, g, attn = self._features(data, with_attention=True)
+        if attn is None:
+            raise ValueError("evaluate(use_mask=True) without fg_masks needs the attention probabilities: build the FeatureExtractor "
+                             "with return_attention=True")
+        return apply_attention_mask(feats, attn, g)[0], g
+
+    def _apply_fg_masks(self, features, spatial_resolution):
+        """features [bs, fs, g*g, dim] times the nearest downsampling of fg_masks to g x g (evaluation.py:415-424)."""
+        bs, fs, n, dim = features.shape
+        m = torch.as_tensor(self.fg_masks)
+        Rm = m.shape[-1]
+        if m.numel() != bs * fs * Rm * Rm:
+            raise ValueError(f"fg_masks hold {m.numel() // (Rm * Rm)} masks, the loader {bs * fs} frames")
+        iy, ix = nearest_index_table(Rm, spatial_resolution)
+        iy, ix = torch.from_numpy(iy.astype("int64")), torch.from_numpy(ix.astype("int64"))
+        m = m.reshape(bs * fs, Rm, Rm).to(self.device)
+        small = m[:, iy.to(m.device)][:, :, ix.to(m.device)].reshape(bs * fs * n).float().contiguous()
+        out = ops.scale_rows_(features.detach().contiguous().float().clone().view(bs * fs * n, dim), small)
+        return out.view(bs, fs, n, dim)
 
     def _cluster(self, features, spatial_resolution, eval_resolution, protocol, num_clusters, annotations):
         if self.clustering_algorithm == "k-means":
@@ -71,8 +103,6 @@ class Evaluator:
     def evaluate(self, many_to_one=False, evaluation_protocol="frame-wise", eval_resolution=None, num_clusters=10, use_mask=False,
                  use_annotations=False, precision_based=False):
         """``evaluation.py:373-480``.  Batches are ``(data [bs,(1,)fs,3,H,W], annotations [bs,(1,)fs,H,W] integer labels[, label])``."""
-        if use_mask:
-            raise NotImplementedError("evaluation on attention-masked features is not part of this build")
         self.model.eval()
         if evaluation_protocol == "dataset-wise":
             feats, anns = [], []
@@ -80,17 +110,19 @@ class Evaluator:
                 data, annotations = batch[0], batch[1]
                 if data.dim() == 6:
                     data, annotations = data.squeeze(1), annotations.squeeze(1)
-                f, g = self._features(data)
+                f, g = self._attention_masked(data) if (use_mask and self.fg_masks is None) else self._features(data)
                 feats.append(f)
                 anns.append(annotations.long())
             features, annotations = torch.cat(feats, dim=0), torch.cat(anns, dim=0)
+            if use_mask and self.fg_masks is not None:
+                features = self._apply_fg_masks(features, g)
             annotations = F.interpolate(annotations.double(), size=(eval_resolution, eval_resolution), mode="nearest").long().to(self.device)
             maps = self._cluster(features, g, eval_resolution, evaluation_protocol, num_clusters, annotations if use_annotations else None)
             return evaluate_localizations(self.PredsEval, annotations, maps, evaluation_protocol, None, many_to_one, precision_based)
         scores = []
         for batch in self.data_loader:
             data, annotations = batch[0].squeeze(1), batch[1].squeeze(1).long()
-            features, g = self._features(data)
+            features, g = self._attention_masked(data) if use_mask else self._features(data)
             if self.uvos_flag:
                 annotations = (annotations > 0).long()
             annotations = F.interpolate(annotations.double(), size=(eval_resolution, eval_resolution), mode="nearest").long().to(self.device)

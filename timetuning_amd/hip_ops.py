@@ -1625,3 +1625,98 @@ def sgd_step_(entries: Sequence[tuple], momentum: float = 0.0, first_step: bool 
                 raise ValueError("sgd_step_: param, grad and momentum buffer need the same size")
             arr[j] = _lib.AdamwTensor(p.data_ptr(), g.data_ptr(), _p(buf), None, p.numel(), float(lr), float(wd))
         _lib.check(lib.tt_sgd_step(arr, len(chunk), float(momentum), int(bool(first_step)), _stream()), "tt_sgd_step")
+
+
+# ---- N6: cluster-based foreground extraction (cluster_based_foreground_extraction.py; include/timetuning_hip.h "N6") ------------------
+
+class ClusterRangeError(_lib.HipLibraryError):
+    """A cluster id outside [0, k) reached one of the N6 kernels."""
+
+
+def _raise_cluster_range(flag, what: str, k: int) -> None:
+    if int(flag.item()):
+        raise ClusterRangeError(f"{what}: a cluster id lies outside [0, {k})")
+
+
+def cbfe_cluster_stats(clusters, attn, gt, k: int, ignore: int = -1, check: bool = True, range_flag=None):
+    """clusters, attn (or None), gt (or None): int64 [M, P] -> (stats int32 [M, k, 3] = {n, tp_attn, tp_gt}, gt_fg int32 [M]).  GT foreground is
+    ``gt != 0`` (``ignore < 0``) or ``gt != 0 and gt != ignore``.  An id outside [0, k) raises ClusterRangeError when ``check`` (a
+    synchronisation); with ``check=False`` the caller's ``range_flag`` (device int32, zeroed) receives it instead."""
+    lib = _lib.load()
+    _chk(clusters, "clusters", torch.int64)
+    for name, t in (("gt", gt), ("attn", attn)):
+        if t is not None:
+            _chk(t, name, torch.int64)
+    M = clusters.shape[0]
+    P = clusters.numel() // max(M, 1)
+    for name, t in (("gt", gt), ("attn", attn)):
+        if t is not None and (t.shape[0] != M or t.numel() != clusters.numel()):
+            raise ValueError(f"cbfe_cluster_stats: {name} must have the shape of clusters")
+    dev = clusters.device
+    stats = torch.empty((M, k, 3), dtype=torch.int32, device=dev)
+    gt_fg = torch.empty((M,), dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev) if range_flag is None else _chk(range_flag, "range_flag", torch.int32)
+    _lib.check(lib.tt_cbfe_cluster_stats(_p(clusters), _p(attn), _p(gt), _p(stats), _p(gt_fg), int(M), int(P), int(k), int(ignore), _p(flag),
+                                         _stream()), "tt_cbfe_cluster_stats")
+    if check:
+        _raise_cluster_range(flag, "tt_cbfe_cluster_stats", k)
+    return stats, gt_fg
+
+
+def cbfe_cluster_precs(stats):
+    """stats int32 [M, k, 3] -> (precs fp64 [k], occurrences int32 [k]): get_cluster_precs' averages, bit for bit."""
+    lib = _lib.load()
+    _chk(stats, "stats", torch.int32)
+    M, k, _ = stats.shape
+    precs = torch.empty((k,), dtype=torch.float64, device=stats.device)
+    occ = torch.empty((k,), dtype=torch.int32, device=stats.device)
+    _lib.check(lib.tt_cbfe_cluster_precs(_p(stats), _p(precs), _p(occ), int(M), int(k), _stream()), "tt_cbfe_cluster_precs")
+    return precs, occ
+
+
+def cbfe_cut_jaccard(stats, gt_fg, order, starts, return_iou: bool = False):
+    """stats [M, k, 3], gt_fg [M], order int32 [k] (cluster ids, ascending precision), starts int32 [C] -> jac fp32 [C] (and the per-image
+    IoU fp32 [C, M]): candidate c marks order[starts[c]:] as foreground; eval_jac's fp32 mean over the images, in image order."""
+    lib = _lib.load()
+    _chk(stats, "stats", torch.int32); _chk(gt_fg, "gt_fg", torch.int32); _chk(order, "order", torch.int32); _chk(starts, "starts", torch.int32)
+    M, k, _ = stats.shape
+    if order.numel() != k or gt_fg.numel() != M:
+        raise ValueError("cbfe_cut_jaccard: order needs k entries and gt_fg M entries")
+    Cn = starts.numel()
+    dev = stats.device
+    jac = torch.empty((Cn,), dtype=f32, device=dev)
+    iou = torch.empty((Cn, M), dtype=f32, device=dev) if return_iou else None
+    nb = lib.tt_cbfe_cut_jaccard_workspace_bytes(M, Cn)
+    ws = _ws(nb, dev)
+    _lib.check(lib.tt_cbfe_cut_jaccard(_p(stats), _p(gt_fg), _p(order), _p(starts), _p(jac), _p(iou), int(M), int(k), int(Cn), _p(ws), nb,
+                                       _stream()), "tt_cbfe_cut_jaccard")
+    return (jac, iou) if return_iou else jac
+
+
+def cbfe_apply_fg(clusters, fg_table, check: bool = True):
+    """clusters int64 (any shape), fg_table uint8 [k] -> mask int64 of the same shape (1 where the cluster is foreground)."""
+    lib = _lib.load()
+    _chk(clusters, "clusters", torch.int64); _chk(fg_table, "fg_table", torch.uint8)
+    k = fg_table.numel()
+    out = torch.empty_like(clusters)
+    flag = torch.zeros(1, dtype=torch.int32, device=clusters.device)
+    _lib.check(lib.tt_cbfe_apply_fg(_p(clusters), _p(fg_table), _p(out), clusters.numel(), int(k), _p(flag), _stream()), "tt_cbfe_apply_fg")
+    if check:
+        _raise_cluster_range(flag, "tt_cbfe_apply_fg", k)
+    return out
+
+
+def nearest_upsample_labels(tok, iy, ix):
+    """tok int32 [M, g*g], iy / ix int32 [R] (entries in [0, g): the tables of ``nearest_index_table``) -> int64 [M, R*R]."""
+    lib = _lib.load()
+    _chk(tok, "tok", torch.int32); _chk(iy, "iy", torch.int32); _chk(ix, "ix", torch.int32)
+    M, n = tok.shape
+    g = int(round(n ** 0.5))
+    if g * g != n:
+        raise ValueError(f"nearest_upsample_labels: {n} tokens are not a square grid")
+    R = iy.numel()
+    if ix.numel() != R:
+        raise ValueError("nearest_upsample_labels: iy and ix need the same length")
+    out = torch.empty((M, R * R), dtype=torch.int64, device=tok.device)
+    _lib.check(lib.tt_nearest_upsample_labels(_p(tok), _p(iy), _p(ix), _p(out), int(M), g, int(R), _stream()), "tt_nearest_upsample_labels")
+    return out

@@ -200,6 +200,29 @@ class _ExtractorFunction(torch.autograd.Function):
         return (None, None, None, *[grads.get(p) for p in ctx.params])
 
 
+def process_attentions(attentions: torch.Tensor, spatial_res: int, threshold: float = 0.65, blur_sigma: float = 0.6) -> torch.Tensor:
+    """models.py:93-131: the last block's attention probabilities [bs, heads, N, N] (N = 1 + spatial_res^2) -> the 0/1 foreground mask
+    [bs, 1, spatial_res, spatial_res] fp32 (head mean of the cls row, Gaussian blur, the ``threshold`` share of the mass, components
+    of at most 2 pixels removed), on ``tt_foreground_mask_from_probs``."""
+    if attentions is None:
+        raise ValueError("process_attentions: no attention probabilities - build the FeatureExtractor with return_attention=True")
+    bs = attentions.shape[0]
+    cls_probs = attentions[:, :, 0, :].contiguous().float()
+    mask = ops.foreground_mask_from_probs(cls_probs, spatial_res, threshold=threshold, blur_sigma=blur_sigma)
+    return mask.view(bs, 1, spatial_res, spatial_res)
+
+
+def apply_attention_mask(features: torch.Tensor, attentions: torch.Tensor, spatial_resolution: int):
+    """models.py:133-144: features [bs, fs, num_patches, dim] times the attention foreground mask of each frame -> (masked features,
+    the mask [bs, fs, num_patches] squeezed as the reference squeezes it)."""
+    mask = process_attentions(attentions, spatial_resolution)
+    bs, fs, num_patches, dim = features.shape
+    mask = mask.view(bs, fs, num_patches, 1)
+    out = ops.scale_rows_(features.detach().contiguous().float().clone().view(bs * fs * num_patches, dim),
+                          mask.reshape(bs * fs * num_patches).contiguous())
+    return out.view(bs, fs, num_patches, dim), mask.squeeze()
+
+
 class _DDPStandIn(nn.Module):
     """Stands where ``torch.nn.parallel.DistributedDataParallel`` stands in the reference: one attribute, ``module``, so
     that the wrapper's state_dict keys read ``model.module.<...>`` exactly as the reference's multi-GPU checkpoints do."""
