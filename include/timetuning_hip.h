@@ -587,6 +587,25 @@ int tt_cbfe_apply_fg(const int64_t* clusters, const uint8_t* fg_table, int64_t* 
 int tt_nearest_upsample_labels(const int32_t* tok, const int32_t* iy, const int32_t* ix, int64_t* out, int M, int g, int R,
                                tt_stream_t stream);
 
+/* ---- N7: DAVIS J&F, the semi-supervised VOS metrics of mask_propagation.py:501-715 (db_eval_iou, db_eval_boundary /
+ *      f_measure / _seg2bmap) as integer counts; the host turns them into J and F with the reference's fp64 expressions.
+ *   tt_davis_jf_counts   pred, gt: label maps [T, H, W] of dtype 0 = uint8 or 1 = int64 (pred_dtype / gt_dtype, independently);
+ *                        void_mask: uint8 [T, H, W] or NULL (non-zero = void).  Object o (1..O) is label == o; any other value is
+ *                        "not object o" (no range error).  counts: int64 [O, T, 6] = {J intersection, J union, n_fg, n_gt, fg_match,
+ *                        gt_match}: the J pixels are the non-void ones; for F both masks are multiplied by "not void" first, their
+ *                        boundary maps are _seg2bmap's (interior s^e | s^s | s^se, last row s^e, last column s^s, bottom-right 0 -
+ *                        at the image edge), and fg_match = |fg_boundary & dilate(gt_boundary)|, gt_match the other way round, with
+ *                        cv2.dilate's rule (dst(y, x) = OR over the set (i, j) of src(y + i - anchor_y, x + j - anchor_x), pixels
+ *                        outside the image contribute nothing).  The structuring element is passed from the HOST as spans (int
+ *                        [el_rows][2] = first, last set column of each row; first > last: an empty row) with its anchor (cv2's default
+ *                        is (rows / 2, cols / 2)); el_rows, el_cols <= 127 (a disk of radius 63: 4K frames at bound_th 0.008), and the
+ *                        anchor at most 63 columns from either side; a larger element returns TT_EINVAL.  The call clears counts
+ *                        (hipMemsetAsync on `stream`), then adds per-tile sums with 64-bit integer atomics: deterministic.
+ *   tt_davis_seg2bmap    seg uint8 [T, H, W] (non-zero = set) -> bmap uint8 [T, H, W] in {0, 1}: _seg2bmap (:582-638) per frame. */
+int tt_davis_jf_counts(const void* pred, int pred_dtype, const void* gt, int gt_dtype, const uint8_t* void_mask, long long* counts, int T,
+                       int H, int W, int O, const int* spans, int el_rows, int el_cols, int anchor_y, int anchor_x, tt_stream_t stream);
+int tt_davis_seg2bmap(const uint8_t* seg, uint8_t* bmap, int T, int H, int W, tt_stream_t stream);
+
 /* ---- Coarse entry points: whole reference functions as ONE call each.  They sequence the op-level entry
  *      points above on `stream` (same kernels, same results bit for bit as calling those one by one; they honour
  *      their `precision` argument / tt_vit_params.precision the way tt_linear_fwd does) and add nothing but the scratch layout.  Parameter tables are HOST

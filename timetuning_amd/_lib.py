@@ -168,6 +168,8 @@ SIGNATURES = {
     "tt_cbfe_cut_jaccard": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
     "tt_cbfe_apply_fg": (c_i, [c_vp, c_vp, c_vp, c_ll, c_i, c_vp, c_vp]),
     "tt_nearest_upsample_labels": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp]),
+    "tt_davis_jf_counts": (c_i, [c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, C.POINTER(c_i), c_i, c_i, c_i, c_i, c_vp]),
+    "tt_davis_seg2bmap": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_vp]),
 }
 
 _lib = None

@@ -1720,3 +1720,66 @@ def nearest_upsample_labels(tok, iy, ix):
     out = torch.empty((M, R * R), dtype=torch.int64, device=tok.device)
     _lib.check(lib.tt_nearest_upsample_labels(_p(tok), _p(iy), _p(ix), _p(out), int(M), g, int(R), _stream()), "tt_nearest_upsample_labels")
     return out
+
+
+# ---- N7: DAVIS J&F counts ----------------------------------------------------------------------------------------------
+
+DAVIS_MAX_ELEMENT = 127   # rows and columns of the structuring element tt_davis_jf_counts accepts
+_DAVIS_DTYPES = {torch.uint8: 0, torch.int64: 1}
+
+
+def davis_element_spans(element):
+    """A 2-D 0 / 1 structuring element -> (spans [(first, last set column)] per row ((1, 0) for an empty row), its (rows, cols),
+    the anchor (rows // 2, cols // 2): cv2's default).  The set pixels of each row must be contiguous, as a disk's are."""
+    el = torch.as_tensor(element).cpu().numpy() != 0
+    if el.ndim != 2 or el.shape[0] < 1 or el.shape[1] < 1:
+        raise ValueError(f"davis: the structuring element must be a non-empty 2-D array, got shape {el.shape}")
+    spans = []
+    for row in el:
+        idx = row.nonzero()[0]
+        if idx.size and idx[-1] - idx[0] + 1 != idx.size:
+            raise ValueError("davis: every row of the structuring element must be one contiguous run")
+        spans.append((int(idx[0]), int(idx[-1])) if idx.size else (1, 0))
+    return spans, el.shape, (el.shape[0] // 2, el.shape[1] // 2)
+
+
+def davis_jf_counts(pred, gt, num_objects: int, element, void=None):
+    """pred, gt: label maps [T, H, W] (uint8 or int64, independently), void: uint8 [T, H, W] (non-zero = void) or None; objects
+    1..num_objects; element: the 2-D 0 / 1 structuring element of the dilation (at most DAVIS_MAX_ELEMENT rows and columns) ->
+    int64 [O, T, 6] = {J intersection, J union, n_fg, n_gt, fg_match, gt_match}."""
+    lib = _lib.load()
+    for name, t in (("pred", pred), ("gt", gt)):
+        if t.dtype not in _DAVIS_DTYPES:
+            raise TypeError(f"{name}: expected torch.uint8 or torch.int64, got {t.dtype}")
+        _chk(t, name, t.dtype)
+        if t.dim() != 3:
+            raise ValueError(f"davis_jf_counts: {name} must be [T, H, W], got {tuple(t.shape)}")
+    if gt.shape != pred.shape:
+        raise ValueError(f"davis_jf_counts: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ")
+    if void is not None:
+        _chk(void, "void", torch.uint8)
+        if void.shape != pred.shape:
+            raise ValueError(f"davis_jf_counts: void {tuple(void.shape)} and pred {tuple(pred.shape)} differ")
+    if int(num_objects) < 1:
+        raise ValueError(f"davis_jf_counts: num_objects must be >= 1, got {num_objects}")
+    T, H, W = pred.shape
+    O = int(num_objects)
+    spans, (rows, cols), (ay, ax) = davis_element_spans(element)
+    flat = [v for sp in spans for v in sp]
+    counts = torch.empty((O, T, 6), dtype=torch.int64, device=pred.device)
+    _lib.check(lib.tt_davis_jf_counts(_p(pred), _DAVIS_DTYPES[pred.dtype], _p(gt), _DAVIS_DTYPES[gt.dtype], _p(void), _p(counts), T, H, W, O,
+                                      (C.c_int * len(flat))(*flat), rows, cols, ay, ax, _stream()),
+               "tt_davis_jf_counts")
+    return counts
+
+
+def davis_seg2bmap(seg):
+    """seg uint8 [T, H, W] (non-zero = set) -> uint8 [T, H, W] boundary map (``_seg2bmap`` per frame)."""
+    lib = _lib.load()
+    _chk(seg, "seg", torch.uint8)
+    if seg.dim() != 3:
+        raise ValueError(f"davis_seg2bmap: seg must be [T, H, W], got {tuple(seg.shape)}")
+    T, H, W = seg.shape
+    out = torch.empty_like(seg)
+    _lib.check(lib.tt_davis_seg2bmap(_p(seg), _p(out), T, H, W, _stream()), "tt_davis_seg2bmap")
+    return out

@@ -5,11 +5,20 @@
 ``propagate_labels`` -> bilinear upsampling -> arg-max) and ``jaccard`` scores the propagated masks.  The evaluation
 driver reproduces the reference's flag set (``:849-871``, DAVIS protocol defaults ``--n_last_frames 4
 --size_mask_neighborhood 12 --topk 5``); dataset readers are out of scope, so it runs on synthetic clips.
+
+The DAVIS metrics (``:501-715``) keep the reference's names, signatures and return types: ``db_eval_iou`` (J),
+``db_eval_boundary`` / ``f_measure`` / ``_seg2bmap`` (F), ``db_statistics`` and ``evaluate_semisupervised``; ``davis_jf``
+scores every object of label maps in one launch.  The counts come from ``tt_davis_jf_counts`` on the GPU; J and F are formed
+from them on the host with the reference's fp64 expressions and branches, so they are the reference's to the bit.
 """
 from __future__ import annotations
 
 import argparse
+import sys
+import warnings
 from typing import List, Optional, Tuple
+
+import numpy as np
 
 import torch
 import torch.nn.functional as F
@@ -78,9 +87,232 @@ def jaccard(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, involve_bg: 
     return (float(iou[valid].mean()) if valid.any() else float("nan")), iou
 
 
+# ---- DAVIS J&F (mask_propagation.py:501-715) -------------------------------------------------------------------------------
+
+def disk(radius) -> np.ndarray:
+    """The disk structuring element ``f_measure`` takes from ``skimage.morphology.disk``: over the grid ``arange(-radius, radius + 1)``
+    in both directions, the points with X^2 + Y^2 <= radius^2, uint8.  A non-integer radius (``bound_th >= 1`` is used as is) gives
+    an even size, e.g. 2.5 -> 6 x 6, whose dilation anchor (rows // 2, cols // 2) is off centre."""
+    L = np.arange(-radius, radius + 1)
+    X, Y = np.meshgrid(L, L)
+    return (X ** 2 + Y ** 2 <= radius ** 2).astype(np.uint8)
+
+
+def _bound_pix(bound_th, shape):
+    """Dilation radius of ``f_measure``: ``bound_th`` itself when >= 1, else ceil(bound_th * ||(H, W)||)."""
+    return bound_th if bound_th >= 1 else np.ceil(bound_th * np.linalg.norm(shape))
+
+
+def _device_tensor(x) -> torch.Tensor:
+    if isinstance(x, torch.Tensor):
+        t = x
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    return t.to(torch.device("cuda", torch.cuda.current_device()) if not t.is_cuda else t.device)
+
+
+def _binary(x) -> torch.Tensor:
+    """Any mask -> uint8 0 / 1 on the GPU (non-zero is set: the reference's ``astype(bool)``)."""
+    return (_device_tensor(x) != 0).to(torch.uint8).contiguous()
+
+
+def _labels(x) -> torch.Tensor:
+    t = _device_tensor(x)
+    if t.dtype in (torch.uint8, torch.int64):
+        return t.contiguous()
+    if t.dtype == torch.bool or not (t.dtype.is_floating_point or t.dtype.is_complex):
+        return t.long().contiguous()
+    raise TypeError(f"davis_jf: label maps must be integer, got {t.dtype}")
+
+
+def _binary_counts(gt_mask, fg_mask, void_pixels, bound_th) -> np.ndarray:
+    """Binary masks [..., H, W] -> int64 counts [N, 6] over the N = prod(...) frames, one launch."""
+    gt_b, fg_b = _binary(gt_mask), _binary(fg_mask)
+    if gt_b.dim() < 2:
+        raise ValueError(f"masks need at least 2 dimensions, got {gt_b.dim()}")
+    H, W = gt_b.shape[-2:]
+    gt_b, fg_b = gt_b.reshape(-1, H, W), fg_b.reshape(-1, H, W)
+    void = None if void_pixels is None else _binary(void_pixels).reshape(-1, H, W)
+    element = disk(_bound_pix(bound_th, (H, W)))
+    return ops.davis_jf_counts(fg_b, gt_b, 1, element, void)[0].cpu().numpy()
+
+
+def _f_from_counts(n_fg, n_gt, fg_match, gt_match):
+    """F of ``f_measure`` from its four counts, with its branches and fp64 expressions."""
+    if n_fg == 0 and n_gt > 0:
+        precision, recall = 1, 0
+    elif n_fg > 0 and n_gt == 0:
+        precision, recall = 0, 1
+    elif n_fg == 0 and n_gt == 0:
+        precision, recall = 1, 1
+    else:
+        precision = fg_match / float(n_fg)
+        recall = gt_match / float(n_gt)
+    if precision + recall == 0:
+        return 0
+    return 2 * precision * recall / (precision + recall)
+
+
+def _f_table(counts: np.ndarray) -> np.ndarray:
+    """counts [..., 6] -> F [...] fp64."""
+    flat = counts.reshape(-1, 6)
+    f = np.zeros(flat.shape[0])
+    for i, c in enumerate(flat):
+        f[i] = _f_from_counts(c[2], c[3], c[4], c[5])
+    return f.reshape(counts.shape[:-1])
+
+
+def _j_table(counts: np.ndarray) -> np.ndarray:
+    """counts [..., 6] -> J [...] fp64: intersection / union, 1 where the union is empty."""
+    inter, union = counts[..., 0], counts[..., 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        j = inter / union
+    j[union == 0] = 1
+    return j
+
+
+def db_eval_iou(annotation, segmentation, void_pixels=None):
+    """Region similarity J (``mask_propagation.py:670-700``) of binary masks [..., H, W] (non-zero is set), numpy or torch:
+    |A & S & !void| / |(A | S) & !void| per frame, 1 where that union is empty.  A scalar for 2-D masks (the int 1 for an
+    empty union, as the reference), an array of shape [...] otherwise."""
+    assert tuple(annotation.shape) == tuple(segmentation.shape), \
+        f"Annotation({tuple(annotation.shape)}) and segmentation:{tuple(segmentation.shape)} dimensions do not match."
+    if void_pixels is not None:
+        assert tuple(annotation.shape) == tuple(void_pixels.shape), \
+            f"Annotation({tuple(annotation.shape)}) and void pixels:{tuple(void_pixels.shape)} dimensions do not match."
+    counts = _binary_counts(annotation, segmentation, void_pixels, 0.008)
+    if len(annotation.shape) == 2:
+        inter, union = counts[0, 0], counts[0, 1]
+        return 1 if union == 0 else inter / union
+    return _j_table(counts).reshape(tuple(annotation.shape[:-2]))
+
+
+def f_measure(foreground_mask, gt_mask, void_pixels=None, bound_th=0.008):
+    """Boundary F-measure (``mask_propagation.py:519-579``) of one binary frame [H, W]: the boundaries of both masks times
+    "not void", each dilated by ``disk(bound_pix)`` and matched against the other.  Counts on the GPU, F on the host."""
+    assert len(foreground_mask.shape) == 2, "f_measure takes one [H, W] frame"
+    assert tuple(foreground_mask.shape) == tuple(gt_mask.shape)
+    c = _binary_counts(gt_mask, foreground_mask, void_pixels, bound_th)[0]
+    return _f_from_counts(c[2], c[3], c[4], c[5])
+
+
+def db_eval_boundary(annotation, segmentation, void_pixels=None, bound_th=0.008):
+    """Boundary F (``mask_propagation.py:501-515``): [T, H, W] masks -> fp64 [T] (one launch for all frames), [H, W] ->
+    ``f_measure(segmentation, annotation)``."""
+    assert tuple(annotation.shape) == tuple(segmentation.shape)
+    if void_pixels is not None:
+        assert tuple(annotation.shape) == tuple(void_pixels.shape)
+    if len(annotation.shape) == 3:
+        return _f_table(_binary_counts(annotation, segmentation, void_pixels, bound_th))
+    if len(annotation.shape) == 2:
+        return f_measure(segmentation, annotation, void_pixels, bound_th=bound_th)
+    raise ValueError(f"db_eval_boundary does not support tensors with {len(annotation.shape)} dimensions")
+
+
+def _seg2bmap(seg, width=None, height=None):
+    """Binary boundary map of a 2-D segmentation (``mask_propagation.py:582-638``): pixel (y, x) is set where seg differs from its
+    right, lower or lower-right neighbour; the last row compares only to the right, the last column only downwards, and the
+    bottom-right pixel is 0.  Returns a bool array [H, W].  The reference's rescale to another ``width`` / ``height`` is used by
+    no caller and raises NotImplementedError here."""
+    assert len(seg.shape) == 2, "_seg2bmap takes one [H, W] map"
+    h, w = seg.shape
+    if (width is not None and width != w) or (height is not None and height != h):
+        raise NotImplementedError("_seg2bmap: rescaling the boundary map to another width / height is not part of this build")
+    return ops.davis_seg2bmap(_binary(seg).view(1, h, w))[0].cpu().numpy().astype(bool)
+
+
+def db_statistics(per_frame_values):
+    """Mean, recall (fraction > 0.5) and decay (first quarter minus last quarter) of per-frame values (``mask_propagation.py:
+    641-666``), NaN-aware.  The quarter boundaries go through uint8 as in the reference, so past 255 frames they wrap round."""
+    v = per_frame_values
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        M = np.nanmean(v)
+        O = np.nanmean(v > 0.5)
+    edges = (np.round(np.linspace(1, len(v), 4 + 1) + 1e-10) - 1).astype(np.uint8)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        first = v[edges[0]:edges[1] + 1]
+        last = v[edges[3]:edges[4] + 1]
+        D = np.nanmean(first) - np.nanmean(last)
+    return M, O, D
+
+
+def evaluate_semisupervised(all_gt_masks, all_res_masks, all_void_masks, metric):
+    """Per-object, per-frame J and F tables [O, T] (``mask_propagation.py:702-715``) of binary masks [O, T, H, W] and void
+    [T, H, W] (or None).  Missing predicted objects are zero masks; more predicted than GT objects ends the program, as the
+    reference.  Every (object, frame) is counted in one launch."""
+    n_gt, n_res = all_gt_masks.shape[0], all_res_masks.shape[0]
+    if n_res > n_gt:
+        sys.stdout.write("\nIn your PNG files there is an index higher than the number of objects in the sequence!")
+        sys.exit()
+    res = _binary(all_res_masks)
+    if n_res < n_gt:
+        res = torch.cat([res, torch.zeros((n_gt - n_res, *res.shape[1:]), dtype=res.dtype, device=res.device)], 0)
+    gt = _binary(all_gt_masks)
+    O, T, H, W = gt.shape
+    void = None if all_void_masks is None else _binary(all_void_masks).reshape(1, T, H, W).expand(O, T, H, W)
+    j_res, f_res = np.zeros((O, T)), np.zeros((O, T))
+    if "J" in metric or "F" in metric:
+        counts = _binary_counts(gt, res, void, 0.008).reshape(O, T, 6)
+        if "J" in metric:
+            j_res[:] = _j_table(counts)
+        if "F" in metric:
+            f_res[:] = _f_table(counts)
+    return j_res, f_res
+
+
+def davis_jf(pred, gt, num_objects: int, void=None, bound_th: float = 0.008):
+    """J and F of objects 1..num_objects of label maps pred, gt [T, H, W] (uint8 or int64 labels; void [T, H, W] or None),
+    numpy or torch, from ONE launch of ``tt_davis_jf_counts``: (J, F) fp64 [O, T], each the reference's ``db_eval_iou`` /
+    ``db_eval_boundary`` of the masks ``label == o`` to the bit."""
+    p, g = _labels(pred), _labels(gt)
+    if p.dim() == 2:
+        p, g = p.unsqueeze(0), g.unsqueeze(0)
+    if p.shape != g.shape:
+        raise ValueError(f"davis_jf: pred {tuple(p.shape)} and gt {tuple(g.shape)} differ")
+    vd = None if void is None else _binary(void).reshape(p.shape)
+    counts = ops.davis_jf_counts(p, g, int(num_objects), disk(_bound_pix(bound_th, tuple(p.shape[-2:]))), vd).cpu().numpy()
+    return _j_table(counts), _f_table(counts)
+
+
+def synthetic_davis_labels(T: int, H: int, W: int, num_objects: int, seed: int):
+    """Seeded label maps for the DAVIS metrics: (gt, pred, void) uint8 [T, H, W].  gt has blobby objects 1..num_objects (unions
+    of ellipses) with holes, object 1 also covers a band along every image edge, and 1-pixel objects sit in the last row and the
+    last column; pred is gt moved by a few pixels with some labels flipped; void marks a few rectangles (DAVIS' 255 regions)."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    gt = np.zeros((T, H, W), np.uint8)
+    pred = np.zeros((T, H, W), np.uint8)
+    void = np.zeros((T, H, W), np.uint8)
+    for t in range(T):
+        g = gt[t]
+        bw = max(1, min(H, W) // 16)
+        band = (yy < bw) | (yy >= H - bw) | (xx < bw) | (xx >= W - bw)
+        g[band & (rng.random((H, W)) < 0.7)] = 1
+        for o in range(1, num_objects + 1):
+            for _ in range(int(rng.integers(1, 4))):
+                cy, cx = rng.uniform(-0.1, 1.1) * H, rng.uniform(-0.1, 1.1) * W
+                ry, rx = rng.uniform(0.05, 0.3) * H + 0.5, rng.uniform(0.05, 0.3) * W + 0.5
+                g[((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1] = o
+            hy, hx = rng.uniform(0, H), rng.uniform(0, W)
+            g[((yy - hy) / (0.04 * H + 0.5)) ** 2 + ((xx - hx) / (0.04 * W + 0.5)) ** 2 <= 1] = 0   # a hole
+        g[H - 1, int(rng.integers(0, W))] = int(rng.integers(1, num_objects + 1))
+        g[int(rng.integers(0, H)), W - 1] = int(rng.integers(1, num_objects + 1))
+        dy, dx = (int(v) for v in rng.integers(-3, 4, 2))
+        p = np.roll(g, (dy, dx), (0, 1))
+        flip = rng.random((H, W)) < 0.01
+        p[flip] = rng.integers(0, num_objects + 2, int(flip.sum()))   # num_objects + 1 is no object
+        pred[t] = p
+        for _ in range(2):
+            y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
+            void[t, y0:y0 + max(1, H // 8), x0:x0 + max(1, W // 8)] = 1
+    return gt, pred, void
+
+
 def build_parser() -> argparse.ArgumentParser:
     """Flag names and defaults of ``mask_propagation.py:849-871`` (``type=bool`` flags keep the any-non-empty-string-is-True
-    quirk).  ``--dataset synthetic`` and ``--num_clips`` are additions: the dataset readers are out of scope."""
+    quirk).  ``--dataset synthetic``, ``--num_clips`` and ``--davis_metrics`` are additions: the dataset readers are out of scope."""
     p = argparse.ArgumentParser()
     p.add_argument("--architecture", type=str, default="dino-s16")
     p.add_argument("--model_path", type=str, default="../models/leopart_vits16.ckpt")
@@ -104,6 +336,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--use_projection_head", type=bool, default=True)
     p.add_argument("--use_optical_flow", type=bool, default=False)
     p.add_argument("--num_clips", type=int, default=4, help="synthetic data only")
+    p.add_argument("--davis_metrics", action="store_true",
+                   help="also print DAVIS J / F mean, recall and decay and J&F-Mean per clip and overall (addition)")
     return p
 
 
@@ -136,7 +370,9 @@ def synthetic_tracking_clip(fs: int, resolution: int, seed: int, objects: int = 
 
 
 def mask_propagation(args) -> float:
-    """The evaluation loop of ``mask_propagation.py:757-846`` on synthetic clips; returns the mean J over clips."""
+    """The evaluation loop of ``mask_propagation.py:757-846`` on synthetic clips; returns the mean J over clips.  With
+    ``--davis_metrics`` it also prints the DAVIS statistics (``db_statistics`` over each object's frames) per clip and over all
+    objects of all clips; the return value is the same."""
     from .models import FeatureExtractor
     from .time_tuning import TimeT
 
@@ -148,6 +384,7 @@ def mask_propagation(args) -> float:
     fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], return_attention=False)  # "" = synthetic weights
     model = TimeT(fe, 200).to(device).eval()
     scores = []
+    davis = []   # per object: (J_M, J_R, J_D, F_M, F_R, F_D)
     for i in range(args.num_clips):
         clip, masks = synthetic_tracking_clip(args.num_frames, args.input_resolution, seed=i + 1)
         if args.uvos:  # all objects become one foreground class (:797-799)
@@ -158,9 +395,23 @@ def mask_propagation(args) -> float:
         j, _ = jaccard(pred, masks[1:].to(device), C)
         scores.append(j)
         print(f"clip {i}: J = {j:.4f}")
+        if getattr(args, "davis_metrics", False) and C > 1:
+            J, Fb = davis_jf(pred, masks[1:].to(device), C - 1)
+            rows = [db_statistics(J[o]) + db_statistics(Fb[o]) for o in range(C - 1)]
+            davis.extend(rows)
+            print(f"clip {i}: " + _davis_line(np.array(rows, np.float64)))
     mean = sum(scores) / len(scores)
     print(f"mean J over {len(scores)} clips: {mean:.4f}")
+    if davis:
+        print(f"DAVIS over {len(davis)} objects of {len(scores)} clips: " + _davis_line(np.array(davis, np.float64)))
     return mean
+
+
+def _davis_line(rows: np.ndarray) -> str:
+    """rows [objects, 6] of (J_M, J_R, J_D, F_M, F_R, F_D) -> their means over the objects, and J&F-Mean."""
+    m = rows.mean(0)
+    return (f"J&F-Mean {(m[0] + m[3]) / 2:.4f}  J_M {m[0]:.4f} J_R {m[1]:.4f} J_D {m[2]:.4f}  "
+            f"F_M {m[3]:.4f} F_R {m[4]:.4f} F_D {m[5]:.4f}")
 
 
 if __name__ == "__main__":
