@@ -129,14 +129,17 @@ def test_attention_fwd_bwd(ops, Fr, N, H):
     assert rel_err(probs.cpu(), p_ref.detach()) < TOL   # N > 256: the row-per-wave probabilities kernel
     dqkv = ops.attention_bwd(dev(qkv), out, dev(do), lse, H)
     assert rel_err(dqkv.cpu(), qd.grad) < 5e-5
-    # the "f16x3" mode's backward (tt_attention_bwd_pairs: S and dP on three fp16 MFMAs per term): the same bound, not worse than the
-    # fp32-MFMA kernels by more than rounding noise - also on a gradient of 1e-7 (the power-of-two scale of dout) - and the same amax slot
+    # the "f16x3" mode's backward (tt_attention_bwd_pairs: S and dP on three fp16 MFMAs per term): the same bound, its relative L2 error
+    # within 2x the fp32-MFMA kernels' - also on a gradient of 1e-7 (the power-of-two scale of dout) - and the same amax slot.  It does
+    # NOT meet DESIGN section 3's f32-class rule (not above the f32 kernels' own): measured pair / f32 relative L2 at these shapes, scale 1
+    # unless noted, 7.31e-7 / 6.62e-7 (3-197-6), 6.20e-7 / 4.96e-7 (2-50-2), 6.82e-7 / 6.71e-7 (1-256-1, scale 1e-7), 6.58e-7 / 5.74e-7
+    # (2-120-3), 6.23e-7 / 4.11e-7 (1-17-12): 1.02 - 1.52x, systematic rather than one point's luck (tests/test_hip_sweep.py: up to 1.81x)
     for gs in (1.0, 1e-7):
         e32 = rel_l2(ops.attention_bwd(dev(qkv), out, dev(do * gs), lse, H).cpu(), qd.grad * gs)
         slot = torch.zeros(ops.AmaxPool.get(torch.device("cuda")).SLOT, device="cuda")
         dq_p = ops.attention_bwd(dev(qkv), out, dev(do * gs), lse, H, amax_out=slot, pair_products=True)
         assert rel_err(dq_p.cpu(), qd.grad * gs) < 5e-5, gs
-        assert rel_l2(dq_p.cpu(), qd.grad * gs) < max(2.0 * e32, 2e-6), (gs, rel_l2(dq_p.cpu(), qd.grad * gs), e32)
+        assert rel_l2(dq_p.cpu(), qd.grad * gs) <= 2.0 * e32, (gs, rel_l2(dq_p.cpu(), qd.grad * gs), e32)
         assert slot.max().item() == dq_p.abs().max().item()
     ops.check_pair_range()
 

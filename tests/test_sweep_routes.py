@@ -1,0 +1,214 @@
+"""The sweep's case table (tests/_sweep_cases.py) reaches every route of the kernels it checks - without a GPU.
+
+The route queries are host logic: tt_linear_fwd_route, tt_linear_fwd_pairs_route, tt_linear_fwd_planes_route, tt_linear_bwd_weight_pairs_tn_ok
+(hip_ops.linear_bwd_data_pairs_is_persistent, hip_ops.attention_pairs_ok).  With no device they assume 256 CUs, the MI355X's count.  Where a
+launcher branches without a host query - the persistent pair GEMM's tile regimes, Sinkhorn's columns per lane and workgroup counts - its rule
+is restated here with the line it comes from."""
+import itertools
+
+import pytest
+
+from _sweep_cases import PAIR_EPILOGUES, table
+from timetuning_amd import _lib, hip_ops
+
+NCU = 256
+CASES = table()
+
+
+def _of(op):
+    return [p for o, p in CASES if o == op]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _lib.load()
+
+
+def test_linear_f32_every_tile_on_both_kernels(lib):
+    # every value tt_linear_fwd_route (gemm_f32.hip) returns over a wide grid of shapes: 4 tiles x {general, lean whole-tile kernel}
+    grid = {lib.tt_linear_fwd_route(M, N, K) for M, N, K in itertools.product(list(range(1, 200, 13)) + list(range(200, 40000, 397)),
+                                                                              (8, 50, 64, 72, 128, 192, 200, 256, 384, 700, 768, 1152, 2304),
+                                                                              (1, 16, 20, 384))}
+    assert grid == {0, 1, 2, 3, 256, 257, 258, 259}
+    assert {lib.tt_linear_fwd_route(p["M"], p["N"], p["K"]) for p in _of("linear_f32")} == grid
+    assert {(p["act"], p["res"]) for p in _of("linear_f32")} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+
+
+def pairs8_regime(M, N, K):
+    """gemm_pairs8.hip, pairs8_plan (the symmetric kernel, default knobs: TT_Q8_KSPLIT 1, TT_Q8_MIN_TILES 128, TT_P8_NO_HALF 0): None = the
+    general kernel; otherwise how the left-over tiles of the last round are dealt - "ksplit" (Q8Args::ks_S, the K-split estimate),
+    "half" (2 * rem <= CUs: half tiles), "round_robin" (whole tiles)."""
+    if N % 128 or K % 32 or M < 256:
+        return None
+    ntiles = ((M + 255) // 256) * (N // 128)
+    R, rem = divmod(ntiles, NCU)
+    ks = 0
+    if rem > 0 and R > 0:
+        U = K // 32
+        S = min(NCU // rem, U, 6)
+        if S >= 2:
+            t_tile = 1.3 * (K // 32) + 3.0
+            t_slice = 1.3 * ((U + S - 1) // S) + 3.0 + 9.0 + 1.0 * S
+            t_else = 0.86 * t_tile if 2 * rem <= NCU else t_tile
+            if t_slice < 0.9 * t_else:
+                ks = S
+    if ntiles < 128 and ks == 0:
+        return None
+    if ks:
+        return "ksplit"
+    return "half" if (rem > 0 and 2 * rem <= NCU) else "round_robin"
+
+
+def _pairs_route(lib, p):
+    e = PAIR_EPILOGUES[p["epi"]]
+    return lib.tt_linear_fwd_pairs_route(p["M"], p["N"], p["K"], e["act"], 1, e["res"], e["out_f32"], e["out_pairs"], e["save_pre"])
+
+
+def test_linear_pairs_every_kernel_regime_and_epilogue(lib):
+    cases = _of("linear_pairs")
+    routes = {_pairs_route(lib, p) for p in cases}
+    assert routes == {0, 8}
+    # the restatement agrees with the library wherever the epilogue is one the persistent kernel compiles (plain fp32 output)
+    for p in cases:
+        assert (pairs8_regime(p["M"], p["N"], p["K"]) is not None) == (lib.tt_linear_fwd_pairs_route(p["M"], p["N"], p["K"], 0, 1, 0, 1, 0, 0) == 8), p
+    assert {pairs8_regime(p["M"], p["N"], p["K"]) for p in cases if _pairs_route(lib, p) == 8} == {"ksplit", "half", "round_robin"}
+    for r in (0, 8):
+        assert {p["epi"] for p in cases if _pairs_route(lib, p) == r} >= ({"y", "y_res", "pairs_gelu"} if r == 8 else
+                                                                         {"y", "y_res", "y_pairs", "y_pairs_gelu_pre", "pairs_gelu"})
+    assert any(p["M"] < 256 for p in cases) and any(p["M"] >= 256 and pairs8_regime(p["M"], p["N"], p["K"]) is None for p in cases)
+    assert any(p["N"] % 128 for p in cases) and any(p["K"] % 96 for p in cases)           # 64-wide column tiles; K not whole triples
+
+
+def test_linear_planes_both_kernels(lib):
+    cases = _of("linear_planes")
+    got = {(p["P"], lib.tt_linear_fwd_planes_route(p["P"], p["M"], p["N"], p["K"], p["act"], 1, p["res"], 1, 0, 0)) for p in cases}
+    assert got == {(1, 0), (1, 8), (3, 0), (3, 8)}
+
+
+def test_backward_pairs_every_route(lib):
+    cases = _of("bwd_pairs")
+    seen = set()
+    for p in cases:
+        M, N, K = p["M"], p["N"], p["K"]
+        assert hip_ops.bwd_pairs_ok(M, N, K)
+        tn_ok = bool(lib.tt_linear_bwd_weight_pairs_tn_ok(N, K, M))
+        seen.add((hip_ops.linear_bwd_data_pairs_is_persistent(M, N, K), bool(p["tn"]) and tn_ok, p["mag"], p["gelu"]))
+    for persistent, tn in itertools.product((False, True), (False, True)):
+        assert any(s[0] == persistent and s[1] == tn for s in seen), (persistent, tn)
+    assert {s[2] for s in seen} == {1e-3, 3e-8} and {s[3] for s in seen} == {0, 1}
+    # the transposed-pair weight gradient both because TN_WGRAD is off and because the shape is not the TN kernel's
+    assert any(not p["tn"] and lib.tt_linear_bwd_weight_pairs_tn_ok(p["N"], p["K"], p["M"]) for p in cases)
+    assert any(p["tn"] and not lib.tt_linear_bwd_weight_pairs_tn_ok(p["N"], p["K"], p["M"]) for p in cases)
+
+
+def test_attention_resident_and_kv_tiled():
+    cases = _of("attention")
+    assert all(hip_ops.attention_pairs_ok(p["N"], 64) for p in cases)          # head_dim 64: the only one the attention kernels take
+    # attention_pairs.hip: K / V resident in LDS up to 256 tokens, the KV-tiled kernel beyond - or forced (knob TT_ATTN_PAIRS_FLASH)
+    kinds = {("kv_tiled" if (p["N"] > 256 or p["flash"]) else "resident", p["N"] > 256) for p in cases}
+    assert kinds == {("resident", False), ("kv_tiled", False), ("kv_tiled", True)}
+    Ns = {p["N"] for p in cases}
+    assert {1, 256, 257} <= Ns and max(Ns) >= 850
+    assert any(p["Fr"] * p["H"] > NCU for p in cases)      # more (frame, head) items than CUs: the resident kernel's persistent loop
+
+
+def test_ce_every_width():
+    cases = _of("ce")
+    assert {p["K"] for p in cases} >= {1, 63, 64, 65, 200, 256, 257, 511, 512}
+    assert {p["weighted"] for p in cases} == {0, 1}
+
+
+# ---- Sinkhorn: sinkhorn.hip
+def sk_default_cap(B):                      # sk_default_cap
+    c = (B // 98 + 63) // 64 * 64
+    if B >= 4096 and c < 128:
+        c = 128
+    return max(64, min(256, c))
+
+
+def sk_wgs(B):                              # sk_wgs: >= 2 rows per wave, at most the cap
+    w = (B + 31) // 32
+    return max(1, min(w, sk_default_cap(B)))
+
+
+def sk_kpl(K):                              # SK_LAUNCH_KPL: 4 columns per lane up to K = 256, 8 beyond
+    return 4 if K <= 256 else 8
+
+
+def skp_grid(B, K):
+    """tt_sinkhorn_persistent_grid under TT_SK_PERSIST = 1 (sk_persistent_kernel: skp_lds_rows, G <= CUs and G <= SK_MAXWG / 2)."""
+    kpad = (K + 63) // 64 * 64
+    rows = (38400 - 64 * 8 - 16 * kpad) // K
+    G = (B + rows - 1) // rows if rows > 0 else NCU + 1
+    return G if (G <= NCU and G <= 128) else 0
+
+
+def _empty_wgs(B, G):
+    rows = (B + G - 1) // G
+    return G - (B + rows - 1) // rows
+
+
+def test_sinkhorn_every_launch_regime():
+    cases = _of("sinkhorn")
+    per_it = cases + [dict(p, persist=0) for p in cases if p["persist"] and skp_grid(p["B"], p["K"]) == 0]
+    # the launch-per-iteration kernels: both KPLs; workgroup counts below, at and beyond the cap; a workgroup that gets no rows
+    assert {sk_kpl(p["K"]) for p in per_it} == {4, 8}
+    w = lambda B: (B + 31) // 32
+    assert any(w(p["B"]) < sk_default_cap(p["B"]) for p in per_it)
+    assert any(w(p["B"]) == sk_default_cap(p["B"]) for p in per_it)
+    assert any(w(p["B"]) > sk_default_cap(p["B"]) for p in per_it)
+    assert any(sk_wgs(p["B"]) == 256 for p in per_it)
+    assert any(_empty_wgs(p["B"], sk_wgs(p["B"])) > 0 for p in per_it)
+    # windows and iteration counts
+    assert {p["iters"] for p in cases} >= {0, 1}
+    assert any(p["row0"] > 0 for p in cases) and any(p["row0"] + p["rows_out"] < p["B"] for p in cases)
+    assert any(p["rows_out"] > 8192 for p in cases)        # the output launch's own workgroup count (SK_LAST_WIDE up to 8192 rows)
+    # the one-launch solve: taken and refused; odd B * K; both KPLs; more than one workgroup; iters 0 and 1; windows
+    pers = [p for p in cases if p["persist"]]
+    taken = [p for p in pers if skp_grid(p["B"], p["K"])]
+    assert taken and len(taken) < len(pers)
+    assert any(p["B"] * p["K"] % 2 for p in taken)
+    assert {sk_kpl(p["K"]) for p in taken} == {4, 8}
+    assert any(skp_grid(p["B"], p["K"]) > 1 for p in taken)
+    # (no workgroup of the one-launch solve is ever empty: G = ceil(B / cap) gives B > (G - 1) * cap >= (G - 1) * ceil(B / G))
+    assert all(_empty_wgs(p["B"], skp_grid(p["B"], p["K"])) == 0 for p in taken)
+    assert {0, 1} <= {p["iters"] for p in taken}
+    assert any(p["row0"] > 0 and p["row0"] + p["rows_out"] < p["B"] for p in taken)
+
+
+def test_sinkhorn_entries_and_queue():
+    fq = _of("sinkhorn_from_q")
+    assert {p["transposed"] for p in fq} == {0, 1} and {sk_kpl(p["K"]) for p in fq} == {4, 8}
+    loc = _of("sinkhorn_local")
+    assert {sk_kpl(p["K"]) for p in loc} == {4, 8} and 0 in {p["iters"] for p in loc}
+    assert any(p["B"] % 32 for p in loc) and any(_empty_wgs(p["B"], sk_wgs(p["B"])) > 0 for p in loc)
+    qp = _of("queue_push")
+    assert any(p["m"] == 1 for p in qp) and any(p["m"] == p["Q"] for p in qp) and any(1 < p["m"] < p["Q"] for p in qp)
+
+
+def test_rows_ops_edges():
+    ln = _of("layernorm")
+    assert {(p["drop"], p["pairs"]) for p in ln} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    assert any(p["D"] % 32 for p in ln)
+    l2 = _of("l2norm")
+    assert any(p["zero_row"] for p in l2) and any(not p["zero_row"] for p in l2) and max(p["D"] for p in l2) == 1024
+
+
+# ---- the Sinkhorn workspace layout (the one-launch solve's 8-byte granules)
+@pytest.mark.parametrize("B,K", [(777, 333), (6272, 200), (1, 1), (50176, 200), (3, 511), (1001, 255)])
+def test_sinkhorn_workspace_places_the_granules_on_an_8_byte_boundary(lib, B, K):
+    off, nb = lib.tt_sinkhorn_partials_offset(B, K), lib.tt_sinkhorn_workspace_bytes(B, K)
+    assert off % 256 == 0 and off >= B * K * 4                       # (the old rule put them at B * K * 4 bytes: 4-byte aligned when B * K is odd)
+    assert off + 2 * 256 * K * 4 + 16 <= nb                          # both partial buffers, then the status block
+    assert nb - 256 == off + 2 * 256 * K * 4                         # the status word hip_ops.sinkhorn reads
+    assert lib.tt_sinkhorn_local_workspace_bytes(B, K) == nb
+
+
+def test_sinkhorn_persistent_grid_follows_the_knob(lib):
+    assert lib.tt_sinkhorn_persistent_grid(777, 333) == 0            # the knob is off by default
+    hip_ops.set_tuning_knob("TT_SK_PERSIST", 1)
+    try:
+        for B, K in [(777, 333), (50176, 200), (6272, 200), (33, 511), (1705, 1)]:
+            assert lib.tt_sinkhorn_persistent_grid(B, K) == skp_grid(B, K), (B, K)
+    finally:
+        hip_ops.set_tuning_knob("TT_SK_PERSIST", 0)

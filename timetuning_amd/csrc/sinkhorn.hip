@@ -472,8 +472,27 @@ __global__ __launch_bounds__(256) void mean_kernel(const float* __restrict__ v, 
 
 using namespace tt;
 
+// Workspace layout: E [B_total][K] floats | padding to a 256-byte boundary | two partial buffers [SK_MAXWG][K] floats (the persistent kernel's
+// granules [2][G][K] of 8 bytes each live there) | a 256-byte block whose first word is the persistent kernel's status.  The partial region
+// starts on the boundary whatever B_total * K is: the granules are 8-byte atomics, and with E's B_total * K floats in front of them an odd
+// count left them 4-byte aligned (a misaligned 8-byte store is not seen whole or not at all).
+extern "C" size_t tt_sinkhorn_partials_offset(int B_total, int K) { return ((size_t)B_total * K * sizeof(float) + 255) / 256 * 256; }
+
 extern "C" size_t tt_sinkhorn_workspace_bytes(int B_total, int K) {
-  return ((size_t)B_total * K + 2ull * SK_MAXWG * K) * sizeof(float) + 256;   // E | two partial buffers | the persistent kernel's counter block
+  return tt_sinkhorn_partials_offset(B_total, K) + 2ull * SK_MAXWG * K * sizeof(float) + 256;   // ... | the status block
+}
+
+// The grid of the one-launch solve (sk_persistent_kernel) for a tt_sinkhorn call of this shape, or 0 when the call takes the launch-per-iteration
+// kernels (knob TT_SK_PERSIST off, or the rows of E do not fit the chip's LDS).  tt_sinkhorn_from_q never takes it.
+extern "C" int tt_sinkhorn_persistent_grid(int B_total, int K) {
+  if (B_total <= 0 || K <= 0 || K > 64 * SK_KPL || tuning_knob(KNOB_SK_PERSIST) == 0) return 0;
+  const int ncu = device_cu_count();
+  const int cap = skp_lds_rows(K);
+  static const int rows_env = [] { const char* e = getenv("TT_SKP_ROWS"); return e ? atoi(e) : 0; }();   // tuning aid
+  int rows = rows_env > 0 ? rows_env : cap;
+  if (rows > cap) rows = cap;
+  const int G = rows > 0 ? (B_total + rows - 1) / rows : ncu + 1;
+  return (G <= ncu && G <= SK_MAXWG / 2) ? G : 0;
 }
 
 static int sinkhorn_impl(const float* scores, const float* Q, int q_rows_are_columns, float* q_out, int B_total, int K, int row0,
@@ -501,23 +520,20 @@ static int sinkhorn_impl(const float* scores, const float* Q, int q_rows_are_col
   TT_REQUIRE(workspace_bytes >= tt_sinkhorn_workspace_bytes(B_total, K), "sinkhorn: workspace too small");
   hipStream_t s = as_stream(stream);
   float* Ews = static_cast<float*>(workspace);
-  float* part[2] = {Ews + (size_t)B_total * K, Ews + (size_t)B_total * K + (size_t)SK_MAXWG * K};
+  float* part0 = reinterpret_cast<float*>(static_cast<char*>(workspace) + tt_sinkhorn_partials_offset(B_total, K));
+  float* part[2] = {part0, part0 + (size_t)SK_MAXWG * K};
   // E [B][K]: built in the workspace, or - when the caller already holds the positive matrix in that layout - read in place
   const float* E = (Q && q_rows_are_columns) ? Q : Ews;
   // ---- one persistent launch (sk_persistent_kernel): from scores, every workgroup resident at once with its rows of E in LDS, the
   // granule buffers inside the workspace's partial region.  Knob TT_SK_PERSIST: 0 never, 1 whenever it applies.
-  if (!Q && tuning_knob(KNOB_SK_PERSIST) != 0) {
-    const int ncu = device_cu_count();
-    const int cap = skp_lds_rows(K);
-    static const int rows_env = [] { const char* e = getenv("TT_SKP_ROWS"); return e ? atoi(e) : 0; }();   // tuning aid
-    int rows = rows_env > 0 ? rows_env : cap;
-    if (rows > cap) rows = cap;
-    const int G = rows > 0 ? (B_total + rows - 1) / rows : ncu + 1;
-    if (G <= ncu && G <= SK_MAXWG / 2) {
-      rows = (B_total + G - 1) / G;             // even shares
-      unsigned long long* gran = reinterpret_cast<unsigned long long*>(part[0]);
-      unsigned* status = reinterpret_cast<unsigned*>(Ews + (size_t)B_total * K + 2ull * SK_MAXWG * K);
-      // tags start at 1: zeroed granules never match.  The status word sits right behind the partial region: one memset for both
+  if (!Q) {
+    if (const int G = tt_sinkhorn_persistent_grid(B_total, K)) {
+      TT_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "sinkhorn: the workspace must be 8-byte aligned");
+      const int rows = (B_total + G - 1) / G;   // even shares
+      unsigned long long* gran = reinterpret_cast<unsigned long long*>(part0);
+      unsigned* status = reinterpret_cast<unsigned*>(part0 + 2ull * SK_MAXWG * K);
+      // tags start at 1: zeroed granules never match.  The status word sits right behind the partial region: one memset for both.
+      // The host reads it back (hip_ops.sinkhorn) and raises when a gather gave up.
       if (hipMemsetAsync(gran, 0, 2ull * SK_MAXWG * K * sizeof(float) + 16, s) != hipSuccess) { set_error("sinkhorn: hipMemsetAsync failed"); return TT_ELAUNCH; }
       SkpArgs a{scores, gran, status, q_out, B_total, K, G, rows, row0, rows_out, iters, eps, B_total};
       hipLaunchKernelGGL(sk_persistent_kernel, dim3(G), dim3(SK_THREADS), 0, s, a);

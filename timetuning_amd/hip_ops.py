@@ -582,6 +582,12 @@ def sinkhorn(scores, iters: int, eps: float = 0.05, row0: int = 0, rows_out: Opt
     nb = lib.tt_sinkhorn_workspace_bytes(B, K)
     ws = _ws(nb, scores.device)
     _lib.check(lib.tt_sinkhorn(_p(scores), _p(q), B, K, row0, rows_out, float(eps), int(iters), _p(ws), nb, _stream()), "tt_sinkhorn")
+    # the one-launch solve (knob TT_SK_PERSIST) waits for the other workgroups' partial sums; a wait that gave up leaves q wrong and says so in
+    # the status word at the workspace's last 256 bytes.  Read it (a synchronisation: the knob is off by default) - not under a graph capture
+    if lib.tt_sinkhorn_persistent_grid(B, K) and not torch.cuda.is_current_stream_capturing():
+        if int(ws[nb - 256:nb - 252].view(torch.int32).item()) != 0:
+            raise _lib.HipLibraryError(f"tt_sinkhorn: the one-launch solve (TT_SK_PERSIST) missed a partial-sum exchange (B_total {B}, K {K}); "
+                                       "its q is not valid")
     return q
 
 
