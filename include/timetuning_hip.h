@@ -615,6 +615,21 @@ int tt_davis_jf_counts(const void* pred, int pred_dtype, const void* gt, int gt_
                        int H, int W, int O, const int* spans, int el_rows, int el_cols, int anchor_y, int anchor_x, tt_stream_t stream);
 int tt_davis_seg2bmap(const uint8_t* seg, uint8_t* bmap, int T, int H, int W, tt_stream_t stream);
 
+/* ---- N8: the boundary F1 score of bfscore.py:21-165 (calc_precision_recall / bfscore / evaluate_bf_score) as
+ *      integer counts; the host forms precision, recall and F1 with the reference's fp64 expressions and branches.
+ *   tt_bf_counts   gt, pr: binary maps uint8 [P, H, W] (any non-zero value is set), P (image, class) pairs.  counts: int64 [P, 4] =
+ *                  {n_pr, hit_pr, n_gt, hit_gt}.  n = the number of contour points of the map as cv2.findContours(RETR_LIST,
+ *                  CHAIN_APPROX_NONE) lists them over all its borders, with multiplicity (zero-padded image, 8-connected
+ *                  foreground): the sum over the set pixels of m(p), a table of the 8 neighbour bits (0 inside, 1 for an isolated
+ *                  pixel, up to 4).  hit = the same sum over the pixels p that have a pixel q of the OTHER map with m(q) > 0 and
+ *                  (q - p) in the element: calc_precision_recall's hits (d < t^2).  The element is centred and symmetric, passed from
+ *                  the HOST as spans (int [el_rows][2] = first, last set column of each row, columns 0..el_rows - 1 with the centre
+ *                  at el_rows / 2; first > last: an empty row); el_rows = 2 r + 1 <= 127 (t <= 64), anything else returns
+ *                  TT_EINVAL.  The call clears counts (hipMemsetAsync on `stream`), then adds per-tile sums with 64-bit integer
+ *                  atomics: deterministic.  No workspace, no allocation, no synchronisation. */
+int tt_bf_counts(const uint8_t* gt, const uint8_t* pr, long long* counts, int P, int H, int W, const int* spans, int el_rows,
+                 tt_stream_t stream);
+
 /* ---- Coarse entry points: whole reference functions as ONE call each.  They sequence the op-level entry
  *      points above on `stream` (same kernels, same results bit for bit as calling those one by one; they honour
  *      their `precision` argument / tt_vit_params.precision the way tt_linear_fwd does) and add nothing but the scratch layout.  Parameter tables are HOST

@@ -172,6 +172,7 @@ SIGNATURES = {
     "tt_nearest_upsample_labels": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp]),
     "tt_davis_jf_counts": (c_i, [c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, C.POINTER(c_i), c_i, c_i, c_i, c_i, c_vp]),
     "tt_davis_seg2bmap": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_vp]),
+    "tt_bf_counts": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, C.POINTER(c_i), c_i, c_vp]),
 }
 
 _lib = None

@@ -19,8 +19,9 @@ set's upsampled features are built, on the host as in the reference (its feature
 ``get_foreground_masks`` returns them; the train set's never exist.
 
 The token grid is read off the features (g = sqrt(tokens)); the reference takes it from ``spatial_resolution``, which is 14 for
-``dino-s16`` whatever the input size.  Out of scope: the boundary F-score (``evaluate_bf_score`` / ``bfscore.py``, built on
-``cv2.findContours``), which the reference only prints; it cannot be pinned here, and no stand-in number is printed.  Dataset readers
+``dino-s16`` whatever the input size.  The boundary F-score the reference prints on every run (``evaluate_bf_score``,
+``bfscore.py``) runs when ``bf_score=True`` (CLI ``--bf_score``) from ``timetuning_amd.bfscore`` (one launch of ``tt_bf_counts`` for
+all images; its cv2 border following pinned through a stand-in, N8); by default it is skipped and the output is unchanged.  Dataset readers
 are out of scope as for the other entry points: ``main`` runs on synthetic data (``--dataset synthetic``).
 """
 from __future__ import annotations
@@ -34,6 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
+from .bfscore import evaluate_bf_score
 from .clustering import Kmeans, nearest_index_table, normalize_and_transform
 from .models import FeatureExtractor, process_attentions
 
@@ -143,8 +145,13 @@ class UpsampledFeatures(NamedTuple):
 class ClusterBasedForegroundExtraction(nn.Module):
     """:156-279.  ``model`` is a FeatureExtractor (or holds one as ``feature_extractor``) built with ``return_attention=True``."""
 
-    def __init__(self, model, k_fg_extraction, eval_resolution=100, eval_feature_dim=50, train_loader=None, val_loader=None, device="cuda"):
+    with_bf_score = False   # bf_score=True: evaluate_bf_score before the Jaccard score (:193), its result in bf_score
+    bf_score = None
+
+    def __init__(self, model, k_fg_extraction, eval_resolution=100, eval_feature_dim=50, train_loader=None, val_loader=None, device="cuda",
+                 *, bf_score=False):
         super().__init__()
+        self.with_bf_score = bf_score
         self.model = model
         self.k_fg_extraction = k_fg_extraction
         self.eval_resolution = eval_resolution
@@ -180,6 +187,8 @@ class ClusterBasedForegroundExtraction(nn.Module):
         set_attentions = F.interpolate(set_attentions.float(), size=(R, R), mode="nearest").long()
         attn_mask_soft = self.create_soft_masks(set_attentions, set_annotations, UpsampledFeatures(set_tokens, R), threshold)
         resized_set_features = self.interpolate(set_tokens, R)
+        if self.with_bf_score:
+            self.bf_score = evaluate_bf_score(attn_mask_soft, set_annotations.flatten(0, 1))
         score = eval_jac(set_annotations.flatten(0, 1), attn_mask_soft, with_boundary=True)
         print(f"Jaccard score is {score}")
         return attn_mask_soft, set_annotations, resized_set_features
@@ -323,6 +332,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--EMA_decay", type=float, default=0.999)
     p.add_argument("--num_train_images", type=int, default=64, help="synthetic data only")
     p.add_argument("--num_val_images", type=int, default=32, help="synthetic data only")
+    p.add_argument("--bf_score", action="store_true", help="also print the boundary F-score of the val masks (evaluate_bf_score)")
     return p
 
 
@@ -350,7 +360,8 @@ def main(args=None) -> float:
     x_va, y_va = synthetic_segmentation(args.num_val_images, args.input_resolution, 21, seed=2)
     train_loader = _batches(x_tr, y_tr, args.batch_size)
     val_loader = _batches(x_va, y_va.clone(), args.batch_size)
-    cbfe = ClusterBasedForegroundExtraction(model, args.k_fg_extraction, eval_resolution, 50, train_loader, val_loader)
+    cbfe = ClusterBasedForegroundExtraction(model, args.k_fg_extraction, eval_resolution, 50, train_loader, val_loader,
+                                            bf_score=args.bf_score)
     set_soft_masks, set_annotations, _ = cbfe.get_foreground_masks("val")
     # the Evaluator reads integer labels: the val annotations as process_data_group made them
     eval_loader = [(x[:, None], (y * 255).long()) for x, y in _batches(x_va, y_va, args.batch_size)]

@@ -1789,3 +1789,47 @@ def davis_seg2bmap(seg):
     out = torch.empty_like(seg)
     _lib.check(lib.tt_davis_seg2bmap(_p(seg), _p(out), T, H, W, _stream()), "tt_davis_seg2bmap")
     return out
+
+
+# ---- N8: boundary F1 (bfscore) counts ----------------------------------------------------------------------------------
+
+BF_MAX_RADIUS = 63   # element radius tt_bf_counts accepts: t <= 64
+
+
+def bf_element_spans(threshold):
+    """The element of calc_precision_recall's test ``d < threshold * threshold`` (d an integer squared distance, the bound a Python
+    float, as the reference evaluates it) -> (spans [(first, last set column)] per row, (1, 0) for an empty row; radius r), columns
+    0..2r with the centre at r.  Raises ValueError beyond BF_MAX_RADIUS."""
+    tt = float(threshold) * float(threshold)
+    r = 0
+    while (r + 1) * (r + 1) < tt:
+        r += 1
+        if r > BF_MAX_RADIUS:
+            raise ValueError(f"bf_counts: threshold {threshold} needs an element of radius > {BF_MAX_RADIUS} (t <= 64 is supported)")
+    spans = []
+    for dy in range(-r, r + 1):
+        w = -1
+        while (w + 1) * (w + 1) + dy * dy < tt:
+            w += 1
+        spans.append((r - w, r + w) if w >= 0 else (1, 0))
+    return spans, r
+
+
+def bf_counts(gt, pr, threshold):
+    """gt, pr: binary maps uint8 [P, H, W] (non-zero = set) on the GPU; threshold: calc_precision_recall's t (|t| <= 64) ->
+    int64 [P, 4] = {n_pr, hit_pr, n_gt, hit_gt}: contour points with multiplicity and those within the threshold of the other map's
+    contour (include/timetuning_hip.h, N8)."""
+    lib = _lib.load()
+    _chk(gt, "gt", torch.uint8)
+    _chk(pr, "pr", torch.uint8)
+    if gt.dim() != 3 or gt.shape != pr.shape:
+        raise ValueError(f"bf_counts: gt {tuple(gt.shape)} and pr {tuple(pr.shape)} must be the same [P, H, W]")
+    P, H, W = gt.shape
+    spans, r = bf_element_spans(threshold)
+    flat = [v for sp in spans for v in sp]
+    counts = torch.empty((P, 4), dtype=torch.int64, device=gt.device)
+    if P == 0:
+        return counts
+    _lib.check(lib.tt_bf_counts(_p(gt), _p(pr), _p(counts), int(P), int(H), int(W), (C.c_int * len(flat))(*flat), 2 * r + 1, _stream()),
+               "tt_bf_counts")
+    return counts
