@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the TimeTuning training hot path on MI355X (driver contract: see the task statement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the K steps, writes ``--dump-outputs`` if asked and prints the line: nothing else.  ``--full``
+adds every secondary measurement and check after the timed steps (each with steps or processes of its own, none enters ``value``):
+the replayed-against-eager check and the eager step time, the per-GEMM roofline pass, the other precision modes, the Sinkhorn rate,
+the CPU baseline and the one-rank RCCL probe; ``--no_alt_precision``, ``--no_cpu_baseline`` and ``--no_exchange_probe`` trim it.
 
 With N > 1 and no external launcher (no WORLD_SIZE in the environment) the script starts the N rank processes itself, one
 per GPU, over RCCL (``launch_ranks``); under ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`` it is
@@ -14,8 +19,9 @@ timed region.  Prints ONE JSON line on rank 0:
   metric/value   clip-frames/sec, whole job (N GPUs x 32 clips x 4 frames per step), weak scaling
   dtype          the arithmetic of the timed step.  Default (round 4): "f32-split(f16x3)" - every nn.Linear and attention product of the
                  step on fp16-pair operands, three fp16 MFMAs per term into fp32 accumulators, per-op error at or under the exact-f32
-                 MFMA kernels' own (tests/test_hip_pairs.py) and every golden / oracle test at unchanged fp32 tolerances; the exact-f32
-                 MFMA step ("f32", rounds 1-3's headline) is reported beside it under ``alt_precision`` with its own roofline block.
+                 MFMA kernels' own (tests/test_hip_pairs.py) and every golden / oracle test at unchanged fp32 tolerances; with --full the
+                 exact-f32 MFMA step ("f32", rounds 1-3's headline) is reported beside it under ``alt_precision`` with its own roofline block.
+and with --full:
   roofline       the dominant GEMM kernel (largest time share): algorithmic flops of its launches in one instrumented step / their
                  HIP-event durations, against the peak of the arithmetic it runs in (2.5 PFLOP/s dense fp16 MFMA / 3 products per term
                  = 833 TFLOP/s for the pair kernels; 157.3 TFLOP/s for the f32 MFMA kernels)
@@ -525,6 +531,88 @@ def dry_rank(a, world: int, rank: int) -> None:
     dist.destroy_process_group()
 
 
+def full_report(a, model, opt, x, device, world, rank, step_graph, elapsed):
+    """--full: the secondary measurements and checks after the timed steps.  Every rank runs it (the instrumented and the alt-precision
+    steps contain the step's collectives); returns the line's extra fields on rank 0, {} on the other ranks."""
+    import torch.distributed as dist
+
+    from timetuning_amd import engine, hip_ops
+
+    bs, fs, K = a.batch_size, a.num_frames, a.num_clusters
+    # the replayed step against the eager one (same state), and the eager step's own time beside the replayed one's
+    check = None
+    eager_ms = None
+    if step_graph:
+        check = graph_check(model, opt, x, a.use_teacher)
+        if not check["replay_equals_eager"]:
+            raise SystemExit(f"bench.py: the replayed step is NOT the eager step: {check}")
+        model._step_graph_on = False
+        for _ in range(2):
+            train_step(model, opt, x, a.use_teacher)
+        torch.cuda.synchronize()
+        te = time.perf_counter()
+        for _ in range(a.steps):
+            train_step(model, opt, x, a.use_teacher)
+        torch.cuda.synchronize()
+        eager_ms = (time.perf_counter() - te) / a.steps * 1e3
+        model._step_graph_on = True
+
+    # the instrumented step contains the step's collectives (score all-gather, gradient all-reduce): EVERY rank runs it
+    prof, headline_waits = instrumented_step(model, opt, x, a.use_teacher)
+    # secondary, clearly-labelled measurements of the other arithmetic modes (same step); `value` is always the --precision
+    # mode.  Every rank takes part (collectives).  The exact-f32 line and the other fp32-accurate split carry their own roofline blocks.
+    alt = {}
+    if a.precision in ("f16x3", "f32") and not a.no_alt_precision:
+        for mode in [m for m in ("f32", "f16x3", "bf16x6", "bf16") if m != a.precision]:
+            hip_ops.set_gemm_precision(mode)
+            for _ in range(2):
+                train_step(model, opt, x, a.use_teacher)
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            ta = time.perf_counter()
+            for _ in range(5):
+                la = train_step(model, opt, x, a.use_teacher)
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            dt = time.perf_counter() - ta
+            if world > 1:
+                tt_ = torch.tensor([dt], device=device, dtype=torch.float64)
+                dist.all_reduce(tt_, op=dist.ReduceOp.MAX)
+                dt = float(tt_.item())
+            alt[mode] = {"clip_frames_per_sec": round(world * bs * fs * 5 / dt, 1), "ms_per_step": round(dt / 5 * 1e3, 3), "loss": round(float(la.item()), 5),
+                         "dtype": DTYPE_NAMES.get(mode, mode), "note": ALT_NOTES[mode]}
+            if mode in ("f32", "f16x3", "bf16x6"):
+                aprof, _ = instrumented_step(model, opt, x, a.use_teacher)
+                if rank == 0:
+                    alt[mode]["roofline"] = roofline_block(aprof, dt / 5, mode)
+        hip_ops.set_gemm_precision(a.precision)
+    if rank != 0:
+        return {}
+    sk_rate, sk_gbs, sk_swept = sinkhorn_rate(device) if world == 1 else (None, None, None)
+    out = {
+        "ms_per_step_eager": None if eager_ms is None else round(eager_ms, 3),   # the same step launch by launch (what an N > 1 rank runs), same process
+        "graph_check": check,             # the replayed step == the eager step from the same state, bit for bit (asserted)
+        # N > 1: the plain line's `rccl` plus the compute stream's exposed wait per collective in the instrumented step
+        "rccl": dict(rccl_report(dist, headline_waits), exchange_autotune=engine.EXCHANGE_CHOICE) if world > 1 else None,
+        "roofline": roofline_block(prof, elapsed / a.steps, a.precision),
+        "alt_precision": alt or None,
+        "sinkhorn": None if sk_rate is None else {"iters_per_sec": round(sk_rate, 1), "algorithmic_GBps": round(sk_gbs, 1),
+                                                  "swept_GBps": round(sk_swept, 1),
+                                                  "note": "algorithmic = SURVEY 8(d)'s 4 K B (2 iters + 2) bytes; swept = the 13 sweeps the "
+                                                          "scaling-vector kernel really makes (iters + 3); the 5 MB matrix is cache-resident",
+                                                  "shape": "K=200 x B=6272, 10 iterations"},
+    }
+    if world == 1 and not a.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(fs, K, arch=a.architecture, precision=a.precision)
+    else:
+        out["cpu_baseline"] = None
+    if world == 1 and not a.no_exchange_probe:
+        out["rccl_single_rank_probe"] = single_rank_exchange_probe([v for v in sys.argv[1:] if v != "--exchange_probe_child"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -538,13 +626,16 @@ def main():
     ap.add_argument("--use_queue", action="store_true")
     ap.add_argument("--queue_size", type=int, default=16384, help="global queue rows (the reference's default); each rank holds queue_size // world")
     ap.add_argument("--use_mask", action="store_true", help="time the --use_mask variant (attention foreground masks) instead")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary measurements and checks (replay check and eager step time, "
+                         "roofline pass, other precision modes, Sinkhorn rate, CPU baseline, one-rank RCCL probe); none enters `value`")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "f32", "bf16x6", "bf16x3", "bf16"],
                     help="arithmetic of the matrix products of the TIMED region (default f16x3 = the fp32-accurate split mode: per-op error "
                          "under the f32-MFMA kernels' own, every parity test at fp32 tolerances; f32 = exact fp32 MFMA; "
                          "hip_ops.set_gemm_precision documents the others)")
-    ap.add_argument("--no_alt_precision", action="store_true", help="skip the secondary measurements in the other precision modes")
-    ap.add_argument("--no_exchange_probe", action="store_true", help="skip the one-rank RCCL probe of the exchange path (1-GPU runs)")
+    ap.add_argument("--no_alt_precision", action="store_true", help="--full: skip the secondary measurements in the other precision modes")
+    ap.add_argument("--no_exchange_probe", action="store_true", help="--full: skip the one-rank RCCL probe of the exchange path (1-GPU runs)")
     ap.add_argument("--step_graph", default="auto", choices=["auto", "on", "off"],
                     help="replay the step's launch sequence as ONE captured hipGraph (TimeT.enable_step_graph, the driver's default too): "
                          "auto = one GPU AND a launch-bound step (at most 10 k token rows: C1 2.0 against 3.5 ms; C2 - C5 are equal either way "
@@ -671,59 +762,8 @@ def main():
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, model, loss)   # (before anything below moves the state on)
 
-    # the replayed step against the eager one (same state), and the eager step's own time beside the replayed one's
-    check = None
-    eager_ms = None
-    if step_graph:
-        check = graph_check(model, opt, x, a.use_teacher)
-        if not check["replay_equals_eager"]:
-            raise SystemExit(f"bench.py: the replayed step is NOT the eager step: {check}")
-        model._step_graph_on = False
-        for _ in range(2):
-            train_step(model, opt, x, a.use_teacher)
-        torch.cuda.synchronize()
-        te = time.perf_counter()
-        for _ in range(a.steps):
-            train_step(model, opt, x, a.use_teacher)
-        torch.cuda.synchronize()
-        eager_ms = (time.perf_counter() - te) / a.steps * 1e3
-        model._step_graph_on = True
-
-    out = None
-    # the instrumented step contains the step's collectives (score all-gather, gradient all-reduce): EVERY rank runs it
-    prof, headline_waits = instrumented_step(model, opt, x, a.use_teacher)
-    # secondary, clearly-labelled measurements of the other arithmetic modes (same step); `value` above is always the --precision
-    # mode.  Every rank takes part (collectives).  The exact-f32 line and the other fp32-accurate split carry their own roofline blocks.
-    alt = {}
-    if a.precision in ("f16x3", "f32") and not a.no_alt_precision:
-        for mode in [m for m in ("f32", "f16x3", "bf16x6", "bf16") if m != a.precision]:
-            hip_ops.set_gemm_precision(mode)
-            for _ in range(2):
-                train_step(model, opt, x, a.use_teacher)
-            torch.cuda.synchronize()
-            if world > 1:
-                dist.barrier()
-            ta = time.perf_counter()
-            for _ in range(5):
-                la = train_step(model, opt, x, a.use_teacher)
-            torch.cuda.synchronize()
-            if world > 1:
-                dist.barrier()
-            dt = time.perf_counter() - ta
-            if world > 1:
-                tt_ = torch.tensor([dt], device=device, dtype=torch.float64)
-                dist.all_reduce(tt_, op=dist.ReduceOp.MAX)
-                dt = float(tt_.item())
-            alt[mode] = {"clip_frames_per_sec": round(world * bs * fs * 5 / dt, 1), "ms_per_step": round(dt / 5 * 1e3, 3), "loss": round(float(la.item()), 5),
-                         "dtype": DTYPE_NAMES.get(mode, mode), "note": ALT_NOTES[mode]}
-            if mode in ("f32", "f16x3", "bf16x6"):
-                aprof, _ = instrumented_step(model, opt, x, a.use_teacher)
-                if rank == 0:
-                    alt[mode]["roofline"] = roofline_block(aprof, dt / 5, mode)
-        hip_ops.set_gemm_precision(a.precision)
+    full = full_report(a, model, opt, x, device, world, rank, step_graph, elapsed) if a.full else {}
     if rank == 0:
-        roof = roofline_block(prof, elapsed / a.steps, a.precision)
-        sk_rate, sk_gbs, sk_swept = sinkhorn_rate(device) if world == 1 else (None, None, None)
         workload = ("C2: " if (a.architecture, bs, fs, K, a.use_teacher, a.use_queue) == ("dino-s16", 32, 4, 200, False, False) else
                     "C3 (per-GPU share): " if (a.architecture, bs, fs, K, a.use_teacher, a.use_queue) == ("dino-s16", 32, 4, 200, True, True) else
                     "C4 (per-GPU share): " if (a.architecture, bs, fs, K) == ("dino-b16", 16, 8, 400) else
@@ -739,25 +779,11 @@ def main():
                        "global_batch": bs * world, "parallelism": f"dp{world}"},
             "loss": round(final_loss, 5),
             "step_graph": bool(step_graph),   # True: the timed steps replay ONE captured hipGraph of the step's launch sequence (+ the eager optimizer call)
-            "ms_per_step_eager": None if eager_ms is None else round(eager_ms, 3),   # the same step launch by launch (what an N > 1 rank runs), same process
-            "graph_check": check,             # the replayed step == the eager step from the same state, bit for bit (asserted)
-            # proof of what carried the exchange: RCCL ("nccl") saw this many ranks (None for the single-process run)
-            # with the compute stream's exposed wait per collective in the instrumented step
-            "rccl": dict(rccl_report(dist, headline_waits), exchange_autotune=engine.EXCHANGE_CHOICE) if world > 1 else None,
-            "roofline": roof,
-            "alt_precision": alt or None,
-            "sinkhorn": None if sk_rate is None else {"iters_per_sec": round(sk_rate, 1), "algorithmic_GBps": round(sk_gbs, 1),
-                                                      "swept_GBps": round(sk_swept, 1),
-                                                      "note": "algorithmic = SURVEY 8(d)'s 4 K B (2 iters + 2) bytes; swept = the 13 sweeps the "
-                                                              "scaling-vector kernel really makes (iters + 3); the 5 MB matrix is cache-resident",
-                                                      "shape": "K=200 x B=6272, 10 iterations"},
+            # what carried the exchange: RCCL ("nccl") saw this many ranks (None for the single-process run), and the exchange the
+            # start-up probe chose; --full adds the compute stream's exposed wait per collective in the instrumented step
+            "rccl": {"world_size": dist.get_world_size(), "backend": dist.get_backend(), "exchange_autotune": engine.EXCHANGE_CHOICE} if world > 1 else None,
         }
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(fs, K, arch=a.architecture, precision=a.precision)
-        else:
-            out["cpu_baseline"] = None
-        if world == 1 and not a.no_exchange_probe:
-            out["rccl_single_rank_probe"] = single_rank_exchange_probe([v for v in sys.argv[1:] if v != "--exchange_probe_child"])
+        out.update(full)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -102,3 +102,29 @@ def test_dump_outputs_writes_the_last_step_within_budget(tmp_path, monkeypatch):
     assert sum(v.size for v in a.values()) <= 15000 + 4096 and a["q"].shape == (2, 50, 20)
     assert a["param.weight"].size < 30000 and all(np.array_equal(a[k], b[k]) for k in a)
     assert np.isin(a["param.weight"], full["param.weight"]).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_line_is_the_headline_and_full_adds_the_rest():
+    """A plain one-GPU run prints the headline line and nothing measured outside the timed steps; ``--full`` adds the replay check, the
+    eager step time, the roofline pass, the other precision modes and the Sinkhorn rate (C1-sized: the timed steps are graph replays)."""
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch_size", "2", "--num_frames", "2", "--num_clusters", "50"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no_cpu_baseline", "--no_exchange_probe"])):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), *args, *extra], env=env, capture_output=True, text=True, timeout=400)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout
+        lines[name] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    extras = {"ms_per_step_eager", "graph_check", "roofline", "alt_precision", "sinkhorn", "cpu_baseline", "rccl_single_rank_probe"}
+    assert not extras & set(plain)
+    assert plain["metric"] == "clip-frames/sec" and plain["unit"] == "clip-frames/sec" and plain["higher_is_better"] is True
+    assert plain["dtype"] == "f32-split(f16x3)" and plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["rccl"] is None
+    assert set(plain) < set(full) and extras - {"rccl_single_rank_probe"} <= set(full)
+    if full["step_graph"]:
+        assert full["graph_check"]["replay_equals_eager"] and full["ms_per_step_eager"] > 0
+    assert full["roofline"]["achieved"] > 0 and sorted(full["alt_precision"]) == ["bf16", "bf16x6", "f32"]
+    assert full["sinkhorn"]["iters_per_sec"] > 0 and full["cpu_baseline"] is None

@@ -273,7 +273,7 @@ def test_bench_gpus_2_through_its_own_launcher():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch_size", "2",
-                        "--num_frames", "2", "--num_clusters", "50", "--no_cpu_baseline", "--no_alt_precision"],
+                        "--num_frames", "2", "--num_clusters", "50", "--full", "--no_cpu_baseline", "--no_alt_precision"],
                        env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -12,7 +12,7 @@ O=$R/gpurun_out/final_$T
 mkdir -p "$O"
 cd "$R"
 python -m pytest tests -m gpu -q 2>&1 | tail -8 > "$O/tests.log"
-B="python bench.py"
+B="python bench.py --full"
 $B --steps 20 --warmup 5 > "$O/c2.json" 2> "$O/c2.err"                                                   # headline: f32-split(f16x3), alt: f32 / bf16x6 / bf16
 $B --steps 50 --warmup 10 --batch_size 2 --num_frames 2 --num_clusters 50 --no_exchange_probe > "$O/c1.json" 2> "$O/c1.err"
 $B --steps 20 --warmup 5 --use_teacher --use_queue --queue_size 2048 --no_cpu_baseline --no_alt_precision > "$O/c3.json" 2> "$O/c3.err"
@@ -20,7 +20,7 @@ $B --steps 10 --warmup 3 --architecture dino-b16 --num_frames 8 --num_clusters 4
 $B --steps 10 --warmup 3 --architecture dino-b16 --num_frames 8 --num_clusters 400 --batch_size 16 --precision bf16 --no_alt_precision --no_exchange_probe > "$O/c4_bf16.json" 2> "$O/c4_bf16.err"
 $B --steps 10 --warmup 3 --architecture dino-s8 --batch_size 16 --no_cpu_baseline --no_exchange_probe > "$O/c5.json" 2> "$O/c5.err"
 cd /tmp && export TMPDIR=/tmp
-P="--no_cpu_baseline --no_alt_precision --no_exchange_probe"
+P="--full --no_cpu_baseline --no_alt_precision --no_exchange_probe"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_c2" -o c2 -- python3 "$R/bench.py" --steps 20 --warmup 5 $P > "$O/prof_c2.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_c2f32" -o c2f32 -- python3 "$R/bench.py" --steps 20 --warmup 5 --precision f32 $P > "$O/prof_c2f32.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_c4" -o c4 -- python3 "$R/bench.py" --steps 10 --warmup 3 --architecture dino-b16 --num_frames 8 --num_clusters 400 --batch_size 16 $P > "$O/prof_c4.log" 2>&1

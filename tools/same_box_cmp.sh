@@ -11,7 +11,8 @@ prepare)
   (cd _oldtree && python -c "import __graft_entry__ as g; g.build()") ;;
 run)
   O=$R/gpurun_out/same_box; mkdir -p "$O"; P="--no_cpu_baseline --no_alt_precision --no_exchange_probe"
-  one() { (cd "$1" && python bench.py $3 $P > "$O/$2.json" 2> "$O/$2.err"); }
+  # --full for the roofline columns below (a tree older than that option prints them without it)
+  one() { F=; grep -q -- '"--full"' "$1/bench.py" && F=--full; (cd "$1" && python bench.py $F $3 $P > "$O/$2.json" 2> "$O/$2.err"); }
   for rep in 1 2 3; do one $R/_oldtree c2_old_$rep "--steps 20 --warmup 5"; one $R c2_new_$rep "--steps 20 --warmup 5"; done
   C1="--steps 50 --warmup 10 --batch_size 2 --num_frames 2 --num_clusters 50"; one $R/_oldtree c1_old "$C1"; one $R c1_new "$C1"
   C3="--steps 20 --warmup 5 --use_teacher --use_queue --queue_size 2048"; one $R/_oldtree c3_old "$C3"; one $R c3_new "$C3"
