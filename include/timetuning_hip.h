@@ -418,6 +418,22 @@ int tt_upsample_argmax(const double* maps, int64_t* labels_out, int M, int g, in
 int tt_confusion_counts(const int64_t* pred, const int64_t* gt, long long n, int C, unsigned long long* counts,
                         tt_stream_t stream);
 
+/* ---- N9: the evaluation propagation on RECTANGULAR token grids (frames at native size, e.g. 480 x 848 -> 30 x 53 tokens at patch 16)
+ *   tt_label_propagate_grid_maps  tt_label_propagate_maps on a gh x gw grid (n = gh * gw, row-major tokens): xn [fs, bs, n, D], seg0
+ *                                 [bs, n, K], pmap_all [fs-1, bs, n, K] fp64.  The window is restrict_neighborhood(gh, gw, radius)
+ *                                 (mask_propagation.py:377-391), clipped at the row and the column edges separately; radius 0 is the
+ *                                 unrestricted variant (no mask: the top-k over all ctx * n sources).  No cap on the candidates of a
+ *                                 query; n_last_frames <= 7.  Workspace: tt_label_propagate_grid_workspace_bytes(...), the
+ *                                 [ctx, n, n] fp32 similarities of each target frame held at once (as tt_label_propagate_maps'; about
+ *                                 0.8 GB per target frame at 60 x 106 tokens with n_last_frames 4).
+ *   tt_upsample_argmax_hw         tt_upsample_argmax for a gh x gw grid and an H x W output: maps [M, gh*gw, K] fp64 -> labels_out
+ *                                 [M, H, W] int64 (bilinear, align_corners = False, then the first maximum over K). */
+size_t tt_label_propagate_grid_workspace_bytes(int bs, int fs, int gh, int gw, int D, int K, int n_last_frames, int radius);
+int tt_label_propagate_grid_maps(const float* xn, const float* seg0, double* pmap_all, int bs, int fs, int gh, int gw, int D, int K,
+                                 int n_last_frames, int radius, int topk, float temperature, int precision, void* workspace,
+                                 size_t workspace_bytes, tt_stream_t stream);
+int tt_upsample_argmax_hw(const double* maps, int64_t* labels_out, int M, int gh, int gw, int K, int H, int W, tt_stream_t stream);
+
 /* ---- k15: CrossEntropyLoss(scores/temp, labels), mean over patches then batch
  *      (time_tuning.py:296-302), with its gradient w.r.t. scores.
  *   scores [rows,K]; labels int64[rows]; loss_out[1]; dscores [rows,K] (= d loss / d scores).

@@ -14,6 +14,9 @@
 // Because at most a handful of sources survive per query, step 2 is a sparse gather, not a GEMM.  Frame t's
 // maps become context for frame t+1, so the frames are sequential; everything inside a frame is parallel.
 // The last frame also emits argmax_K (the hard labels the loss consumes, time_tuning.py:296).
+// N9 (tt_label_propagate_grid_maps, tt_upsample_argmax_hw): the evaluation propagation on a gh x gw grid - frames at native size -
+// with the same similarity GEMMs (lp_sims_chunk) and a per-query kernel that streams its candidates from the similarity rows, so
+// neither the window (radius 0: the whole grid) nor the number of context frames is bounded by registers or LDS.
 #include "common.hpp"
 #include <cstdlib>
 
@@ -362,6 +365,35 @@ static size_t lp_workspace(int T, int bs, int fs, size_t n, int K, int n_last) {
   return ((sims + 255) / 256) * 256 + segs;
 }
 
+// ---- cosine similarities of target frames [t0, t1), sims[t - t0][b][j] = xn[t][b] @ xn[ctx_j(t)][b]^T with ctx(t) = {0} + [lo_t, t),
+//      lo_t = max(1, t - n_last)  (mask_propagation.py:480-487: the first frame and the queue of the last n_last frames)
+static int lp_sims_chunk(const float* xn, float* sims, int t0, int t1, int bs, int n, int D, int cmax, int n_last_frames, int sims_bf16,
+                         hipStream_t s) {
+  const long long nn = (long long)n * n, frame = (long long)bs * n * D, per_t = (long long)bs * cmax * nn;
+  // slot 0, the pairs (t, 0) of every t in the chunk: inner batch = clip, outer = t
+  int rc = launch_gemm_plain2(xn + t0 * frame, xn, sims, n, n, D, D, D, n, bs, t1 - t0, (long long)n * D, (long long)n * D,
+                              (long long)cmax * nn, frame, 0, per_t, sims_bf16, s);
+  if (rc != TT_OK) return rc;
+  for (int d = 1; d <= n_last_frames; ++d) {
+    // pairs (t, t - d), t - d >= 1.  While the queue is still filling (t <= n_last + 1: lo_t = 1) the slot is j = t - d and
+    // moves with t; afterwards (lo_t = t - n_last) it is j = 1 + n_last - d
+    const int a0 = t0 > d + 1 ? t0 : d + 1;
+    const int a1 = t1 < n_last_frames + 2 ? t1 : n_last_frames + 2;
+    if (a1 > a0) {
+      rc = launch_gemm_plain2(xn + a0 * frame, xn + (a0 - d) * frame, sims + (a0 - t0) * per_t + (a0 - d) * nn, n, n, D, D, D, n, bs,
+                              a1 - a0, (long long)n * D, (long long)n * D, (long long)cmax * nn, frame, frame, per_t + nn, sims_bf16, s);
+      if (rc != TT_OK) return rc;
+    }
+    const int b0 = a0 > n_last_frames + 2 ? a0 : n_last_frames + 2;
+    if (t1 > b0) {
+      rc = launch_gemm_plain2(xn + b0 * frame, xn + (b0 - d) * frame, sims + (b0 - t0) * per_t + (1 + n_last_frames - d) * nn, n, n, D, D,
+                              D, n, bs, t1 - b0, (long long)n * D, (long long)n * D, (long long)cmax * nn, frame, frame, per_t, sims_bf16, s);
+      if (rc != TT_OK) return rc;
+    }
+  }
+  return TT_OK;
+}
+
 }  // namespace tt
 
 using namespace tt;
@@ -402,7 +434,7 @@ static int lp_run(const char* who, const float* xn, const float* seg0, int64_t* 
   // the fp64 maps of frames 1..fs-1: the caller's buffer when all of them are wanted, the workspace otherwise
   double* segs = pmap_all ? pmap_all : reinterpret_cast<double*>(static_cast<char*>(workspace) + sims_bytes);
   const long long fstride = (long long)bs * n * K;
-  const long long nn = (long long)n * n, frame = (long long)bs * n * D, per_t = (long long)bs * cmax * nn;
+  const long long per_t = (long long)bs * cmax * ((long long)n * n);
   if (phase != 0 && T < fs - 1) {
     if (phase == 1) return 1;   // (more than one chunk: nothing written - the caller runs the whole propagation in one call)
     set_error("%s: the similarities of %d target frames do not fit one chunk of this workspace (chunk %d)", who, fs - 1, T);
@@ -410,28 +442,10 @@ static int lp_run(const char* who, const float* xn, const float* seg0, int64_t* 
   }
   for (int t0 = 1; t0 < fs; t0 += T) {
     const int t1 = t0 + T < fs ? t0 + T : fs;
-    // ---- cosine similarities of the chunk, sims[t - t0][b][j] = xn[t][b] @ xn[ctx_j(t)][b]^T with ctx(t) = {0} + [lo_t, t),
-    //      lo_t = max(1, t - n_last)  (mask_propagation.py:480-487: the first frame and the queue of the last n_last frames)
-    // slot 0, the pairs (t, 0) of every t in the chunk: inner batch = clip, outer = t
-    int rc = phase == 2 ? TT_OK : launch_gemm_plain2(xn + t0 * frame, xn, sims, n, n, D, D, D, n, bs, t1 - t0, (long long)n * D, (long long)n * D,
-                                                     (long long)cmax * nn, frame, 0, per_t, sims_bf16, s);
-    if (rc != TT_OK) return rc;
-    for (int d = 1; d <= n_last_frames && phase != 2; ++d) {
-      // pairs (t, t - d), t - d >= 1.  While the queue is still filling (t <= n_last + 1: lo_t = 1) the slot is j = t - d and
-      // moves with t; afterwards (lo_t = t - n_last) it is j = 1 + n_last - d
-      const int a0 = t0 > d + 1 ? t0 : d + 1;
-      const int a1 = t1 < n_last_frames + 2 ? t1 : n_last_frames + 2;
-      if (a1 > a0) {
-        rc = launch_gemm_plain2(xn + a0 * frame, xn + (a0 - d) * frame, sims + (a0 - t0) * per_t + (a0 - d) * nn, n, n, D, D, D, n, bs,
-                                a1 - a0, (long long)n * D, (long long)n * D, (long long)cmax * nn, frame, frame, per_t + nn, sims_bf16, s);
-        if (rc != TT_OK) return rc;
-      }
-      const int b0 = a0 > n_last_frames + 2 ? a0 : n_last_frames + 2;
-      if (t1 > b0) {
-        rc = launch_gemm_plain2(xn + b0 * frame, xn + (b0 - d) * frame, sims + (b0 - t0) * per_t + (1 + n_last_frames - d) * nn, n, n, D, D,
-                                D, n, bs, t1 - b0, (long long)n * D, (long long)n * D, (long long)cmax * nn, frame, frame, per_t, sims_bf16, s);
-        if (rc != TT_OK) return rc;
-      }
+    // ---- cosine similarities of the chunk (not in phase 2: phase 1 left them in the workspace)
+    if (phase != 2) {
+      const int rc = lp_sims_chunk(xn, sims, t0, t1, bs, n, D, cmax, n_last_frames, sims_bf16, s);
+      if (rc != TT_OK) return rc;
     }
     if (phase == 1) return TT_OK;
     // ---- the maps, frame by frame: frame t's map is context for frame t + 1
@@ -503,6 +517,209 @@ extern "C" int tt_label_propagate_maps(const float* xn, const float* seg0, doubl
                 precision, workspace, workspace_bytes, stream);
 }
 
+// ---- N9: the evaluation propagation on a gh x gw token grid (rows x cols: frames at native size, not squashed to a square), with
+// no cap on the candidates of a query - so the DAVIS protocol's radius 12 with n_last_frames 7 (25 x 25 x 8 = 5 000 candidates) and
+// the unrestricted variant (radius 0: no mask, the top-k over all ctx * n sources, mask_propagation.py:422-429) run too.  The
+// similarities are the same batched GEMMs as lp_run's (lp_sims_chunk); the per-query work streams the candidates from the similarity
+// rows instead of holding them in registers, so its cost grows with the window but nothing is bounded by it.
+namespace tt {
+struct LpGridArgs {
+  const float* sims;        // [bs][cs][n][n]  (target, source); slots j < c used
+  const float* seg0;        // [bs][n][K] fp32 (frame 0 labels)
+  const double* seg_prev;   // base of fp64 maps: frame f (>=1) at seg_prev + (f-1) * bs*n*K
+  double* seg_out;          // [bs][n][K] this frame's map
+  int ctx_frame[LP_MAXC];
+  int c, cs, bs, gh, gw, K, radius, topk;   // radius 0: the whole grid is the window
+  float temp;
+};
+
+// One workgroup per (clip, query).  Every pass re-reads the query's window of similarity rows (L2-resident between passes: 20 KB at
+// 5 000 candidates) and recomputes exp(sim / temp), so the passes see the same fp32 affinities:
+//   1. the k-th largest with multiplicity: at most topk passes, each the block maximum of the affinities below the previous one together
+//      with its number of occurrences, until the occurrences reach topk (threshold 0 with fewer than topk candidates: the masked zeros);
+//   2. the fp32 column sum of the kept affinities (>= threshold, ties kept);
+//   3. 256 candidates at a time, the kept ones are compacted into LDS in candidate order and their label rows added into the map in fp64
+//      (thread k owns channels k, k + 256, ...: it alone reads and writes them, so the map accumulates in place).
+__global__ __launch_bounds__(256) void label_prop_grid_kernel(LpGridArgs a) {
+  __shared__ float s_val[4];
+  __shared__ int s_cnt[4];
+  __shared__ float s_sum[4];
+  __shared__ int keep_src[256];   // ctx * n + source patch
+  __shared__ float keep_w[256];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = a.gh * a.gw;
+  const long long nn = (long long)n * n;
+  const int qi = blockIdx.x, b = blockIdx.y;
+  const int qy = qi / a.gw, qx = qi - qy * a.gw;
+  const int r = a.radius > 0 ? a.radius : (a.gh > a.gw ? a.gh : a.gw);
+  const int y0 = max(0, qy - r), y1 = min(a.gh - 1, qy + r);
+  const int x0 = max(0, qx - r), x1 = min(a.gw - 1, qx + r);
+  const int ww = x1 - x0 + 1, wh = y1 - y0 + 1;
+  const int per_ctx = ww * wh, total = per_ctx * a.c;
+  const float* rows = a.sims + (long long)b * a.cs * nn + (long long)qi * n;   // context j's row at rows + j * nn
+  // candidate -> (source id, affinity): context-major, then window row, then window column (mask_propagation.py:422-429)
+  auto cand_val = [&](int cand, int& src) -> float {
+    const int j = cand / per_ctx, w = cand - j * per_ctx;
+    const int wy = w / ww;
+    const int sp = (y0 + wy) * a.gw + x0 + (w - wy * ww);
+    src = j * n + sp;
+    return expf(rows[j * nn + sp] / a.temp);
+  };
+
+  // ---- 1. k-th largest with multiplicity
+  float thr = 0.f;
+  if (total >= a.topk) {
+    float prev = 0.f;
+    for (int got = 0, first = 1; got < a.topk; first = 0) {
+      float bv = -1.f;   // below every affinity (exp >= 0)
+      int bc = 0;
+      for (int cand = tid; cand < total; cand += 256) {
+        int src;
+        const float v = cand_val(cand, src);
+        if (first || v < prev) {
+          if (v > bv) {
+            bv = v;
+            bc = 1;
+          } else if (v == bv) {
+            ++bc;
+          }
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oc = __shfl_xor(bc, o, 64);
+        if (ov > bv) {
+          bv = ov;
+          bc = oc;
+        } else if (ov == bv) {
+          bc += oc;
+        }
+      }
+      if (lane == 0) {
+        s_val[wave] = bv;
+        s_cnt[wave] = bc;
+      }
+      __syncthreads();
+      bv = s_val[0];
+      bc = s_cnt[0];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) {
+        if (s_val[w] > bv) {
+          bv = s_val[w];
+          bc = s_cnt[w];
+        } else if (s_val[w] == bv) {
+          bc += s_cnt[w];
+        }
+      }
+      __syncthreads();
+      if (bc == 0) break;   // (only NaN affinities left: they are never kept)
+      thr = prev = bv;
+      got += bc;
+    }
+  }
+
+  // ---- 2. keep >= threshold (ties kept): fp32 column sum
+  float mysum = 0.f;
+  for (int cand = tid; cand < total; cand += 256) {
+    int src;
+    const float v = cand_val(cand, src);
+    if (v >= thr) mysum += v;
+  }
+  const float wsum = wave_sum(mysum);
+  if (lane == 0) s_sum[wave] = wsum;
+  __syncthreads();
+  const float colsum = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+
+  // ---- 3. seg_tar[:, q] = sum_s segs[:, s] * aff[s, q] in fp64 (mask_propagation.py:442-444), aff / aff.sum(0) in fp32 (:436)
+  double* out = a.seg_out + ((long long)b * n + qi) * a.K;
+  for (int k = tid; k < a.K; k += 256) out[k] = 0.0;
+  const long long fstride = (long long)a.bs * n * a.K;
+  for (int base = 0; base < total; base += 256) {
+    const int cand = base + tid;
+    int src = -1;
+    const float v = cand < total ? cand_val(cand, src) : -1.f;
+    const bool keep = cand < total && v >= thr;
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) s_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int off = __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) off += s_cnt[w];
+    const int nk = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    if (keep) {
+      keep_src[off] = src;
+      keep_w[off] = v / colsum;
+    }
+    __syncthreads();
+    if (nk > 0) {
+      for (int k = tid; k < a.K; k += 256) {
+        double acc = out[k];
+        for (int e = 0; e < nk; ++e) {
+          const int j = keep_src[e] / n, sp = keep_src[e] - j * n;
+          const int fr = a.ctx_frame[j];
+          const long long o = ((long long)b * n + sp) * a.K + k;
+          const double sv = (fr == 0) ? (double)a.seg0[o] : a.seg_prev[(long long)(fr - 1) * fstride + o];
+          acc += sv * (double)keep_w[e];
+        }
+        out[k] = acc;
+      }
+    }
+    __syncthreads();   // keep_src / keep_w / s_cnt are rewritten by the next chunk
+  }
+}
+}  // namespace tt
+
+extern "C" size_t tt_label_propagate_grid_workspace_bytes(int bs, int fs, int gh, int gw, int D, int K, int n_last_frames, int radius) {
+  (void)D;
+  (void)radius;   // the similarity buffer is the whole [n, n] product per context slot whatever the window
+  if (bs <= 0 || fs < 2 || gh <= 0 || gw <= 0 || K <= 0 || n_last_frames < 0) return 0;
+  const size_t n = (size_t)gh * gw;
+  return lp_workspace(lp_chunk(bs, fs, (int)n, n_last_frames), bs, fs, n, K, n_last_frames);
+}
+
+extern "C" int tt_label_propagate_grid_maps(const float* xn, const float* seg0, double* pmap_all, int bs, int fs, int gh, int gw, int D, int K,
+                                            int n_last_frames, int radius, int topk, float temperature, int precision, void* workspace,
+                                            size_t workspace_bytes, tt_stream_t stream) {
+  const char* who = "label_propagate_grid_maps";
+  TT_REQUIRE(xn && seg0 && pmap_all && workspace, "%s: null pointer", who);
+  TT_REQUIRE(precision >= TT_PRECISION_F32 && precision <= TT_PRECISION_BF16, "%s: precision must be 0, 1 or 2 (got %d)", who, precision);
+  TT_REQUIRE(bs > 0 && bs <= 65535 && fs >= 2 && gh > 0 && gw > 0 && D > 0 && K > 0, "%s: need fs >= 2 and positive sizes", who);
+  TT_REQUIRE((long long)gh * gw * LP_MAXC <= 0x7fffffffLL, "%s: grid %dx%d too large", who, gh, gw);
+  TT_REQUIRE(n_last_frames >= 0 && n_last_frames + 1 <= LP_MAXC, "%s: n_last_frames must be <= %d", who, LP_MAXC - 1);
+  TT_REQUIRE(radius >= 0, "%s: size_mask_neighborhood must be >= 0 (0: no mask)", who);
+  TT_REQUIRE(topk >= 1, "%s: topk >= 1", who);
+  TT_REQUIRE(D % 4 == 0, "%s: feature dim must be a multiple of 4", who);
+  hipStream_t s = as_stream(stream);
+  const int n = gh * gw;
+  int T = lp_chunk(bs, fs, n, n_last_frames);
+  while (T > 1 && lp_workspace(T, bs, fs, (size_t)n, K, n_last_frames) > workspace_bytes) --T;
+  TT_REQUIRE(workspace_bytes >= lp_workspace(T, bs, fs, (size_t)n, K, n_last_frames), "%s: workspace too small", who);
+  const int cmax = lp_cmax(fs, n_last_frames);
+  float* sims = static_cast<float*>(workspace);
+  const long long fstride = (long long)bs * n * K, per_t = (long long)bs * cmax * ((long long)n * n);
+  for (int t0 = 1; t0 < fs; t0 += T) {
+    const int t1 = t0 + T < fs ? t0 + T : fs;
+    const int rc = lp_sims_chunk(xn, sims, t0, t1, bs, n, D, cmax, n_last_frames, precision == TT_PRECISION_BF16, s);
+    if (rc != TT_OK) return rc;
+    for (int t = t0; t < t1; ++t) {
+      LpGridArgs a{};
+      int c = 0;
+      a.ctx_frame[c++] = 0;   // the first frame is always context (mask_propagation.py:482-483)
+      const int lo = (t - n_last_frames > 1) ? t - n_last_frames : 1;
+      for (int fr = lo; fr < t; ++fr) a.ctx_frame[c++] = fr;
+      a.sims = sims + (t - t0) * per_t;
+      a.seg0 = seg0;
+      a.seg_prev = pmap_all;
+      a.seg_out = pmap_all + (long long)(t - 1) * fstride;
+      a.c = c; a.cs = cmax; a.bs = bs; a.gh = gh; a.gw = gw; a.K = K; a.radius = radius; a.topk = topk; a.temp = temperature;
+      hipLaunchKernelGGL(label_prop_grid_kernel, dim3(n, bs), dim3(256), 0, s, a);
+      TT_CHECK_LAUNCH(who);
+    }
+  }
+  return TT_OK;
+}
+
 // ---- evaluation tail of mask_propagation.py:826-829: bilinear upsample (align_corners=False) of the fp64 maps to the
 // input resolution, then argmax over the label channel - fused, so the [M, K, R, R] fp64 tensor (77 MB per 25-frame clip
 // at K = 8) is never written.
@@ -534,6 +751,36 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const double* __re
     }
   }
   out[(long long)m * R * R + pix] = besti;
+}
+
+// N9: the same for a gh x gw grid and an H x W output (rows and columns scale separately)
+__global__ __launch_bounds__(256) void upsample_argmax_hw_kernel(const double* __restrict__ maps, int64_t* __restrict__ out, int gh, int gw,
+                                                                 int K, int H, int W) {
+  const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= (long long)H * W) return;
+  const int m = blockIdx.y, oy = (int)(pix / W), ox = (int)(pix - (long long)oy * W);
+  // area_pixel_compute_scale, align_corners = False: input / output size per dimension
+  double sy = (double)gh / (double)H * (oy + 0.5) - 0.5, sx = (double)gw / (double)W * (ox + 0.5) - 0.5;
+  sy = sy < 0.0 ? 0.0 : sy;
+  sx = sx < 0.0 ? 0.0 : sx;
+  const int y0 = (int)sy, x0 = (int)sx;
+  const int y1 = y0 + (y0 < gh - 1 ? 1 : 0), x1 = x0 + (x0 < gw - 1 ? 1 : 0);
+  const double ly = sy - y0, lx = sx - x0, hy = 1.0 - ly, hx = 1.0 - lx;
+  const double* base = maps + (long long)m * gh * gw * K;
+  const double* p00 = base + (long long)(y0 * gw + x0) * K;
+  const double* p01 = base + (long long)(y0 * gw + x1) * K;
+  const double* p10 = base + (long long)(y1 * gw + x0) * K;
+  const double* p11 = base + (long long)(y1 * gw + x1) * K;
+  double best = -INFINITY;
+  int besti = 0;
+  for (int k = 0; k < K; ++k) {
+    const double v = hy * (hx * p00[k] + lx * p01[k]) + ly * (hx * p10[k] + lx * p11[k]);
+    if (v > best) {  // torch.max: first index of the maximum
+      best = v;
+      besti = k;
+    }
+  }
+  out[(long long)m * H * W + pix] = besti;
 }
 
 // counts[gt * C + pred] += 1 over n pixels (labels outside [0, C) are ignored): the confusion matrix behind the
@@ -569,6 +816,15 @@ extern "C" int tt_upsample_argmax(const double* maps, int64_t* labels_out, int M
   TT_REQUIRE(maps && labels_out && M > 0 && g > 0 && K > 0 && R > 0, "upsample_argmax: bad arguments");
   hipLaunchKernelGGL(upsample_argmax_kernel, dim3((R * R + 255) / 256, M), dim3(256), 0, as_stream(stream), maps, labels_out, g, K, R);
   TT_CHECK_LAUNCH("upsample_argmax");
+  return TT_OK;
+}
+
+extern "C" int tt_upsample_argmax_hw(const double* maps, int64_t* labels_out, int M, int gh, int gw, int K, int H, int W, tt_stream_t stream) {
+  TT_REQUIRE(maps && labels_out && M > 0 && gh > 0 && gw > 0 && K > 0 && H > 0 && W > 0, "upsample_argmax_hw: bad arguments");
+  TT_REQUIRE(M <= 65535 && (long long)H * W <= 0x7fffffffLL, "upsample_argmax_hw: %d maps of %dx%d exceed one launch", M, H, W);
+  hipLaunchKernelGGL(upsample_argmax_hw_kernel, dim3((unsigned)(((long long)H * W + 255) / 256), M), dim3(256), 0, as_stream(stream), maps,
+                     labels_out, gh, gw, K, H, W);
+  TT_CHECK_LAUNCH("upsample_argmax_hw");
   return TT_OK;
 }
 

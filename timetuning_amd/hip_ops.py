@@ -705,6 +705,45 @@ def label_propagate_maps(xn, seg0, n_last_frames=7, radius=6, topk=5, temperatur
     return maps
 
 
+def _grid(grid, n: int, who: str):
+    gh, gw = (int(v) for v in grid)
+    if gh <= 0 or gw <= 0 or gh * gw != n:
+        raise ValueError(f"{who}: grid {gh}x{gw} does not hold the {n} tokens")
+    return gh, gw
+
+
+def label_propagate_grid_maps(xn, seg0, grid, n_last_frames=7, radius=6, topk=5, temperature=0.1):
+    """``label_propagate_maps`` on a gh x gw token grid: xn [fs,bs,n,D] normalised tokens (time-major, n = gh*gw row-major), seg0 [bs,n,K]
+    -> all propagated maps [fs-1, bs, n, K] fp64.  ``radius`` 0 is the unrestricted variant (no mask); no cap on candidates per query."""
+    lib = _lib.load()
+    _chk(xn, "xn"); _chk(seg0, "seg0")
+    fs, bs, n, D = xn.shape
+    K = seg0.shape[-1]
+    gh, gw = _grid(grid, n, "label_propagate_grid_maps")
+    if tuple(seg0.shape) != (bs, n, K):
+        raise ValueError(f"label_propagate_grid_maps: seg0 {tuple(seg0.shape)} does not match xn {tuple(xn.shape)}")
+    maps = torch.empty((max(fs - 1, 0), bs, n, K), dtype=torch.float64, device=xn.device)
+    nb = lib.tt_label_propagate_grid_workspace_bytes(bs, fs, gh, gw, D, K, n_last_frames, radius)
+    ws = _ws(nb, xn.device)
+    _lib.check(lib.tt_label_propagate_grid_maps(_p(xn), _p(seg0), _p(maps), bs, fs, gh, gw, D, K, n_last_frames, radius, topk,
+                                                float(temperature), precision_code(), _p(ws), ws.numel(), _stream()),
+               "tt_label_propagate_grid_maps")
+    return maps
+
+
+def upsample_argmax_hw(maps, grid, size):
+    """maps [M, n, K] fp64 on a gh x gw grid -> labels [M, H, W] int64 = argmax_K of the bilinear (align_corners=False) upsampling to
+    ``size`` = (H, W)."""
+    lib = _lib.load()
+    _chk(maps, "maps", torch.float64)
+    M, n, K = maps.shape
+    gh, gw = _grid(grid, n, "upsample_argmax_hw")
+    H, W = (int(v) for v in size)
+    out = torch.empty((M, max(H, 0), max(W, 0)), dtype=torch.int64, device=maps.device)
+    _lib.check(lib.tt_upsample_argmax_hw(_p(maps), _p(out), M, gh, gw, K, H, W, _stream()), "tt_upsample_argmax_hw")
+    return out
+
+
 def upsample_argmax(maps, resolution: int):
     """maps [M, n, K] fp64 -> labels [M, R, R] int64 = argmax_K of the bilinear (align_corners=False) upsampling."""
     lib = _lib.load()

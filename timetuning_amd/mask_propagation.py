@@ -6,6 +6,10 @@
 driver reproduces the reference's flag set (``:849-871``, DAVIS protocol defaults ``--n_last_frames 4
 --size_mask_neighborhood 12 --topk 5``); dataset readers are out of scope, so it runs on synthetic clips.
 
+Labels propagate on the frames' own token grid (H / P, W / P), so rectangular clips run at native size (``--frame_size H W``), and
+``--size_mask_neighborhood 0`` is the unrestricted variant (``:422``).  Shapes the square entry accepts (``square_entry_accepts``) go to
+``tt_label_propagate_maps`` / ``tt_upsample_argmax`` as before; the rest to ``tt_label_propagate_grid_maps`` / ``tt_upsample_argmax_hw``.
+
 The DAVIS metrics (``:501-715``) keep the reference's names, signatures and return types: ``db_eval_iou`` (J),
 ``db_eval_boundary`` / ``f_measure`` / ``_seg2bmap`` (F), ``db_statistics`` and ``evaluate_semisupervised``; ``davis_jf``
 scores every object of label maps in one launch.  The counts come from ``tt_davis_jf_counts`` on the GPU; J and F are formed
@@ -36,38 +40,75 @@ def to_one_hot(y_tensor: torch.Tensor, n_dims: Optional[int] = None) -> torch.Te
     return one_hot.view(h, w, n_dims).permute(2, 0, 1)
 
 
-def _maps(n_last_frames, size_mask_neighborhood, topk, model, frame_list, first_seg, features_exist):
+# the existing square entry's limits (label_prop.hip lp_run): context frames 1 + min(fs - 2, n_last_frames), window side min(2r + 1, g),
+# at most 256 * LP_CAND_MAX candidates per query
+_SQUARE_CAND_MAX = 4096
+
+
+def square_entry_accepts(grid, fs: int, n_last_frames: int, radius: int) -> bool:
+    """The routing rule: True where ``tt_label_propagate_maps`` (the square entry) takes the shape - a square grid, radius >= 1 and at most
+    4 096 candidates per query - so every result it gave before stays bit for bit the same; elsewhere ``tt_label_propagate_grid_maps``."""
+    gh, gw = (int(v) for v in grid)
+    if gh != gw or radius < 1 or n_last_frames < 0:
+        return False
+    win = min(2 * radius + 1, gh)
+    return win * win * max(1, 1 + min(fs - 2, n_last_frames)) <= _SQUARE_CAND_MAX
+
+
+def _pair(v) -> Tuple[int, int]:
+    return (int(v), int(v)) if isinstance(v, (int, np.integer)) else tuple(int(x) for x in v)
+
+
+def _maps(n_last_frames, size_mask_neighborhood, topk, model, frame_list, first_seg, features_exist, grid=None):
     fe = model.feature_extractor if hasattr(model, "feature_extractor") else model
-    g = fe.spatial_resolution
     if not features_exist:
+        P = fe.backbone.patch_embed.patch_size
+        grid = (frame_list.shape[-2] // P, frame_list.shape[-1] // P)   # the token grid of the frames themselves
         frame_list, _ = fe(frame_list, use_head=False)
+    elif grid is None:
+        grid = (fe.spatial_resolution, fe.spatial_resolution)
+    gh, gw = _pair(grid)
     fs, n, D = frame_list.shape
+    if gh * gw != n:
+        raise ValueError(f"propagate_labels: grid {gh}x{gw} does not hold the {n} tokens of a frame")
     # the seed is resized to the token grid with nearest-neighbour sampling, in fp64 as the reference (:456)
-    first_seg = F.interpolate(first_seg.double(), size=(g, g), mode="nearest")
+    first_seg = F.interpolate(first_seg.double(), size=(gh, gw), mode="nearest")
     C = first_seg.shape[1]
     xn = ops.l2norm_fwd(frame_list.reshape(fs * n, D).contiguous().float()).view(fs, 1, n, D)
     seed = first_seg.reshape(C, n).t().contiguous().float().view(1, n, C).to(xn.device)
-    return ops.label_propagate_maps(xn, seed, n_last_frames, size_mask_neighborhood, topk, 0.1), C, g  # [fs-1, 1, n, C]
+    if square_entry_accepts((gh, gw), fs, n_last_frames, size_mask_neighborhood):
+        maps = ops.label_propagate_maps(xn, seed, n_last_frames, size_mask_neighborhood, topk, 0.1)
+    else:
+        maps = ops.label_propagate_grid_maps(xn, seed, (gh, gw), n_last_frames, size_mask_neighborhood, topk, 0.1)
+    return maps, C, (gh, gw)  # [fs-1, 1, n, C]
 
 
 @torch.no_grad()
-def propagate_labels(n_last_frames, size_mask_neighborhood, topk, model, frame_list, first_seg, features_exist=False) -> List[torch.Tensor]:
+def propagate_labels(n_last_frames, size_mask_neighborhood, topk, model, frame_list, first_seg, features_exist=False, *,
+                     grid=None) -> List[torch.Tensor]:
     """frame_list [fs, n, D] backbone tokens (``features_exist=True``) or [fs, 3, H, W] frames; first_seg [1, C, h, w].
-    Returns the fs-1 propagated maps ``[C, g, g]`` fp64, as the reference (``mask_propagation.py:448-496``)."""
-    maps, C, g = _maps(n_last_frames, size_mask_neighborhood, topk, model, frame_list, first_seg, features_exist)
-    return [m[0].t().reshape(C, g, g) for m in maps]
+    Returns the fs-1 propagated maps ``[C, gh, gw]`` fp64, as the reference (``mask_propagation.py:448-496``).  The token grid is the
+    frames' own (H / P, W / P); with ``features_exist=True`` it is ``grid=(gh, gw)``, by default the square ``spatial_resolution``."""
+    maps, C, (gh, gw) = _maps(n_last_frames, size_mask_neighborhood, topk, model, frame_list, first_seg, features_exist, grid)
+    return [m[0].t().reshape(C, gh, gw) for m in maps]
 
 
 @torch.no_grad()
 def propagate_clip(model, clip: torch.Tensor, first_annotation: torch.Tensor, n_last_frames: int = 4, size_mask_neighborhood: int = 12,
-                   topk: int = 5, input_resolution: int = 224, num_classes: Optional[int] = None) -> torch.Tensor:
+                   topk: int = 5, input_resolution=224, num_classes: Optional[int] = None) -> torch.Tensor:
     """One clip of the evaluation loop (``mask_propagation.py:824-830``): clip [fs,3,H,W], first_annotation [H,W] integer
-    labels of frame 0 -> predictions [fs-1, R, R] int64 for frames 1..fs-1."""
+    labels of frame 0 -> predictions [fs-1, R, R] int64 for frames 1..fs-1, or [fs-1, H', W'] for ``input_resolution=(H', W')``.
+    The labels propagate on the clip's own token grid (H / P, W / P)."""
     fe = model.feature_extractor if hasattr(model, "feature_extractor") else model
+    P = fe.backbone.patch_embed.patch_size
+    grid = (clip.shape[-2] // P, clip.shape[-1] // P)
     feats, _ = fe(clip, use_head=False)
     seed = to_one_hot(first_annotation.unsqueeze(0), num_classes).unsqueeze(0)
-    maps, C, g = _maps(n_last_frames, size_mask_neighborhood, topk, model, feats, seed, True)
-    return ops.upsample_argmax(maps.view(maps.shape[0], g * g, C), input_resolution)
+    maps, C, (gh, gw) = _maps(n_last_frames, size_mask_neighborhood, topk, model, feats, seed, True, grid)
+    H, W = _pair(input_resolution)
+    if gh == gw and H == W:
+        return ops.upsample_argmax(maps.view(maps.shape[0], gh * gw, C), H)
+    return ops.upsample_argmax_hw(maps.view(maps.shape[0], gh * gw, C), (gh, gw), (H, W))
 
 
 @torch.no_grad()
@@ -338,35 +379,51 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_clips", type=int, default=4, help="synthetic data only")
     p.add_argument("--davis_metrics", action="store_true",
                    help="also print DAVIS J / F mean, recall and decay and J&F-Mean per clip and overall (addition)")
+    p.add_argument("--frame_size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                   help="synthetic H x W clips propagated on their native token grid (H / P, W / P) and scored at H x W; multiples of "
+                        "the patch size P (addition)")
     return p
 
 
-def synthetic_tracking_clip(fs: int, resolution: int, seed: int, objects: int = 2):
+def synthetic_tracking_clip(fs: int, resolution: int, seed: int, objects: int = 2, width: Optional[int] = None):
     """A clip with ``objects`` textured discs drifting over a textured background, and its per-frame integer masks:
-    frames [fs,3,R,R] fp32 (roughly unit-normal, like normalised images), masks [fs,R,R] int64 (0 = background)."""
+    frames [fs,3,R,W] fp32 (roughly unit-normal, like normalised images), masks [fs,R,W] int64 (0 = background); ``width``
+    defaults to R (a square clip)."""
     import numpy as np
 
     from . import synth
 
     R = resolution
-    yy, xx = np.mgrid[0:R, 0:R].astype(np.float32)
+    W = R if width is None else int(width)
+    yy, xx = np.mgrid[0:R, 0:W].astype(np.float32)
     tex = synth.normal("trk.tex", (objects + 1, 3, 8, 8), 1.0, 0.0, seed)
-    tex = np.kron(tex, np.ones((1, 1, R // 8, R // 8), np.float32))[:, :, :R, :R]
+    tex = np.kron(tex, np.ones((1, 1, R // 8, W // 8), np.float32))[:, :, :R, :W]
     pos = synth.normal("trk.pos", (objects, 4), 1.0, 0.0, seed)
     frames, masks = [], []
     for t in range(fs):
         img = tex[0].copy()
-        m = np.zeros((R, R), np.int64)
+        m = np.zeros((R, W), np.int64)
         for o in range(objects):
             cy = R * (0.3 + 0.4 * o / max(objects - 1, 1)) + 3.0 * t * np.tanh(pos[o, 0])
-            cx = R * (0.3 + 0.2 * o) + 4.0 * t * np.tanh(pos[o, 1])
-            rad = R * (0.12 + 0.03 * abs(np.tanh(pos[o, 2])))
+            cx = W * (0.3 + 0.2 * o) + 4.0 * t * np.tanh(pos[o, 1])
+            rad = min(R, W) * (0.12 + 0.03 * abs(np.tanh(pos[o, 2])))
             inside = (yy - cy) ** 2 + (xx - cx) ** 2 < rad ** 2
             img = np.where(inside[None], tex[o + 1] + 1.5 * (o + 1), img)
             m[inside] = o + 1
-        frames.append(img + 0.05 * synth.normal(f"trk.noise.{t}", (3, R, R), 1.0, 0.0, seed))
+        frames.append(img + 0.05 * synth.normal(f"trk.noise.{t}", (3, R, W), 1.0, 0.0, seed))
         masks.append(m)
     return torch.from_numpy(np.stack(frames).astype(np.float32)), torch.from_numpy(np.stack(masks))
+
+
+def clip_size(args, patch_size: int) -> Tuple[int, int]:
+    """(H, W) of the evaluation clips: ``--frame_size H W`` (each a multiple of the patch size, else ValueError) or the square
+    ``--input_resolution``."""
+    if getattr(args, "frame_size", None) is None:
+        return args.input_resolution, args.input_resolution
+    H, W = (int(v) for v in args.frame_size)
+    if H <= 0 or W <= 0 or H % patch_size or W % patch_size:
+        raise ValueError(f"--frame_size {H} {W}: both sides must be positive multiples of the patch size {patch_size}")
+    return H, W
 
 
 def mask_propagation(args) -> float:
@@ -380,18 +437,23 @@ def mask_propagation(args) -> float:
         raise NotImplementedError("dataset readers (data_loader.py) are out of scope for this build; run with --dataset synthetic")
     if args.use_optical_flow:
         raise NotImplementedError("the optical-flow baseline (cv2 Farneback, mask_propagation.py:803-815) is not part of this build")
-    device = torch.device("cuda", 0)
     fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], return_attention=False)  # "" = synthetic weights
+    H, W = clip_size(args, fe.backbone.patch_embed.patch_size)
+    native = getattr(args, "frame_size", None) is not None
+    device = torch.device("cuda", 0)
     model = TimeT(fe, 200).to(device).eval()
     scores = []
     davis = []   # per object: (J_M, J_R, J_D, F_M, F_R, F_D)
     for i in range(args.num_clips):
-        clip, masks = synthetic_tracking_clip(args.num_frames, args.input_resolution, seed=i + 1)
+        if native:
+            clip, masks = synthetic_tracking_clip(args.num_frames, H, seed=i + 1, width=W)
+        else:
+            clip, masks = synthetic_tracking_clip(args.num_frames, args.input_resolution, seed=i + 1)
         if args.uvos:  # all objects become one foreground class (:797-799)
             masks = (masks > 0).long()
         C = int(masks.max()) + 1
         pred = propagate_clip(model, clip.to(device), masks[0].to(device), args.n_last_frames, args.size_mask_neighborhood, args.topk,
-                              args.input_resolution, C)
+                              (H, W) if native else args.input_resolution, C)
         j, _ = jaccard(pred, masks[1:].to(device), C)
         scores.append(j)
         print(f"clip {i}: J = {j:.4f}")
