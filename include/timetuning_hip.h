@@ -434,6 +434,35 @@ int tt_label_propagate_grid_maps(const float* xn, const float* seg0, double* pma
                                  size_t workspace_bytes, tt_stream_t stream);
 int tt_upsample_argmax_hw(const double* maps, int64_t* labels_out, int M, int gh, int gw, int K, int H, int W, tt_stream_t stream);
 
+/* ---- N10: the optical-flow baseline of the evaluation (mask_propagation.py:265-346, :803-815; cv2 replaced, parity with cv2 unpinned)
+ *   tt_farneback_plan             (host only) the pyramid of cv2.calcOpticalFlowFarneback: levels cut to the largest k with H, W * pyr_scale^k
+ *                                 >= 32; levels_out = that k, sizes_out [2 (k + 1)] = (h, w) of levels 0..k, cvRound(side * pyr_scale^i)
+ *                                 (half to even; the caller's array holds 2 (levels + 1) ints).  0 < pyr_scale < 1, 1 <= levels <= 64.
+ *   tt_farneback_workspace_bytes  (host only) the workspace of tt_farneback_flow for F frames and P pairs of H x W (0: bad arguments):
+ *                                 about (60 F + 40 P) H W bytes plus two coarse flow fields.
+ *   tt_flow_gray_u8               replaces :807-813: clip [F, 3, H, W] fp32 RGB -> gray [F, H, W] uint8.  x 255 in fp32, torch's CPU uint8
+ *                                 cast ((int64) trunc, modulo 256), then RGB2BGR + BGR2GRAY (R 4899 + G 9617 + B 1868 + 8192) >> 14.
+ *   tt_farneback_flow             replaces dense_optical_flow's cv2.calcOpticalFlowFarneback(new, old, None, 0.5, 3, 15, 3, 5, 1.2, 0)
+ *                                 (:299) for P pairs at once: frames [F, H, W] uint8, pairs int32 [P, 2] (DEVICE) = (prev, next) frame
+ *                                 indices -> flow [P, H, W, 2] fp32 (dx, dy) with prev(x) ~ next(x + flow(x)).  Each frame's level images
+ *                                 and polynomial expansions are computed once and shared by its pairs.  flags 0 only (the box-filter
+ *                                 variant; OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN return TT_EINVAL), poly_n 5 or 7,
+ *                                 1 <= winsize <= 127, iterations >= 1; a level Gaussian above 255 taps (frames beyond ~3 400 px at
+ *                                 pyr_scale 0.5) returns TT_EINVAL.  A pair index outside [0, F) gives that pair a NaN flow and reads
+ *                                 nothing.  Workspace: tt_farneback_workspace_bytes; no allocation, no float atomics (deterministic).
+ *   tt_remap_nearest_labels       replaces interpolate_frames / propagate (:322-346): out[n, s] = cv2.remap(s == 0 ? first[n] :
+ *                                 out[n, s - 1], coords + scale * flows[n, s], INTER_NEAREST) for s = 0..steps-1; first [N, H, W],
+ *                                 flows [N, steps, H, W, 2], out [N, steps, H, W], labels uint8 (label_bytes 1) or int64 (8).  The map is
+ *                                 fp32 with separate roundings (numpy's), rounded half to even, saturated to int16; outside reads 0. */
+int tt_farneback_plan(int H, int W, double pyr_scale, int levels, int* levels_out, int* sizes_out);
+size_t tt_farneback_workspace_bytes(int F, int P, int H, int W, double pyr_scale, int levels);
+int tt_flow_gray_u8(const float* clip, uint8_t* gray, int F, int H, int W, tt_stream_t stream);
+int tt_farneback_flow(const uint8_t* frames, int F, int H, int W, const int32_t* pairs, int P, double pyr_scale, int levels, int winsize,
+                      int iterations, int poly_n, double poly_sigma, int flags, float* flow, void* workspace, size_t workspace_bytes,
+                      tt_stream_t stream);
+int tt_remap_nearest_labels(const void* first, const float* flows, void* out, int N, int steps, int H, int W, float scale, int label_bytes,
+                            tt_stream_t stream);
+
 /* ---- k15: CrossEntropyLoss(scores/temp, labels), mean over patches then batch
  *      (time_tuning.py:296-302), with its gradient w.r.t. scores.
  *   scores [rows,K]; labels int64[rows]; loss_out[1]; dscores [rows,K] (= d loss / d scores).

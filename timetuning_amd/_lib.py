@@ -176,6 +176,11 @@ SIGNATURES = {
     "tt_davis_jf_counts": (c_i, [c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, C.POINTER(c_i), c_i, c_i, c_i, c_i, c_vp]),
     "tt_davis_seg2bmap": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_vp]),
     "tt_bf_counts": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, C.POINTER(c_i), c_i, c_vp]),
+    "tt_farneback_plan": (c_i, [c_i, c_i, c_d, c_i, C.POINTER(c_i), C.POINTER(c_i)]),
+    "tt_farneback_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_d, c_i]),
+    "tt_flow_gray_u8": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_vp]),
+    "tt_farneback_flow": (c_i, [c_vp, c_i, c_i, c_i, c_vp, c_i, c_d, c_i, c_i, c_i, c_i, c_d, c_i, c_vp, c_vp, c_sz, c_vp]),
+    "tt_remap_nearest_labels": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_f, c_i, c_vp]),
 }
 
 _lib = None

@@ -1872,3 +1872,107 @@ def bf_counts(gt, pr, threshold):
     _lib.check(lib.tt_bf_counts(_p(gt), _p(pr), _p(counts), int(P), int(H), int(W), (C.c_int * len(flat))(*flat), 2 * r + 1, _stream()),
                "tt_bf_counts")
     return counts
+
+
+# ---- N10: the optical-flow baseline of the evaluation (dense Farneback flow, nearest label remap; farneback.hip) -----------------------
+
+OPTFLOW_USE_INITIAL_FLOW = 4
+OPTFLOW_FARNEBACK_GAUSSIAN = 256
+FARNEBACK_MAX_WINSIZE = 127
+FARNEBACK_MAX_LEVELS = 64
+
+
+def check_farneback_params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags) -> None:
+    """The parameters tt_farneback_flow takes: flags 0, poly_n 5 or 7, 0 < pyr_scale < 1, ints levels in [1, 64], winsize in [1, 127],
+    iterations >= 1, poly_sigma > 0.  The two flag bits raise NotImplementedError, anything else ValueError."""
+    import math
+
+    if not isinstance(flags, int) or isinstance(flags, bool):
+        raise ValueError(f"flags {flags!r}: expected an int")
+    if flags & (OPTFLOW_USE_INITIAL_FLOW | OPTFLOW_FARNEBACK_GAUSSIAN):
+        raise NotImplementedError("OPTFLOW_USE_INITIAL_FLOW and OPTFLOW_FARNEBACK_GAUSSIAN are not part of this build (flags 0 only)")
+    if flags != 0:
+        raise ValueError(f"flags {flags}: only 0 is supported")
+    for name, v, hi in (("levels", levels, FARNEBACK_MAX_LEVELS), ("winsize", winsize, FARNEBACK_MAX_WINSIZE), ("iterations", iterations, 1 << 16)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise ValueError(f"{name} {v!r}: expected an int in [1, {hi}]")
+    if isinstance(poly_n, bool) or poly_n not in (5, 7):
+        raise ValueError(f"poly_n {poly_n!r}: expected 5 or 7")
+    if isinstance(pyr_scale, bool) or not isinstance(pyr_scale, (int, float)) or not 0.0 < float(pyr_scale) < 1.0:
+        raise ValueError(f"pyr_scale {pyr_scale!r}: expected 0 < pyr_scale < 1")
+    if isinstance(poly_sigma, bool) or not isinstance(poly_sigma, (int, float)) or not (math.isfinite(poly_sigma) and poly_sigma > 0):
+        raise ValueError(f"poly_sigma {poly_sigma!r}: expected a positive number")
+
+
+def farneback_plan(H: int, W: int, pyr_scale: float = 0.5, levels: int = 3):
+    """(effective levels L, [(h_k, w_k) for k = 0..L]) of calcOpticalFlowFarneback's pyramid (host only, no GPU)."""
+    lib = _lib.load()
+    L = C.c_int(0)
+    sizes = (C.c_int * (2 * (int(levels) + 1)))()
+    _lib.check(lib.tt_farneback_plan(int(H), int(W), float(pyr_scale), int(levels), C.byref(L), sizes), "tt_farneback_plan")
+    return L.value, [(sizes[2 * k], sizes[2 * k + 1]) for k in range(L.value + 1)]
+
+
+def flow_gray_u8(clip):
+    """clip [F, 3, H, W] fp32 RGB on the GPU -> uint8 [F, H, W]: the reference's ``datum *= 255``, uint8 cast and RGB2BGR + BGR2GRAY."""
+    lib = _lib.load()
+    _chk(clip, "clip")
+    if clip.dim() != 4 or clip.shape[1] != 3:
+        raise ValueError(f"flow_gray_u8: clip {tuple(clip.shape)} is not [F, 3, H, W]")
+    F, _, H, W = clip.shape
+    out = torch.empty((F, H, W), dtype=torch.uint8, device=clip.device)
+    _lib.check(lib.tt_flow_gray_u8(_p(clip), _p(out), F, H, W, _stream()), "tt_flow_gray_u8")
+    return out
+
+
+def farneback_flow(frames, pairs, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2, flags=0, workspace=None):
+    """frames uint8 [F, H, W] on the GPU, pairs [(prev, next), ...] (host) -> flow [P, H, W, 2] fp32 of
+    cv2.calcOpticalFlowFarneback(frames[prev], frames[next], None, ...) for every pair, one launch per stage and level; each frame's
+    pyramid and expansion is computed once.  ``workspace``: an optional uint8 GPU buffer of at least tt_farneback_workspace_bytes
+    (allocated per call otherwise)."""
+    check_farneback_params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags)
+    lib = _lib.load()
+    _chk(frames, "frames", torch.uint8)
+    if frames.dim() != 3 or frames.shape[0] < 1:
+        raise ValueError(f"farneback_flow: frames {tuple(frames.shape)} is not [F >= 1, H, W]")
+    F, H, W = frames.shape
+    pr = [(int(a), int(b)) for a, b in pairs]
+    for a, b in pr:
+        if not (0 <= a < F and 0 <= b < F):
+            raise ValueError(f"farneback_flow: pair ({a}, {b}) outside the {F} frames")
+    P = len(pr)
+    flow = torch.empty((P, H, W, 2), dtype=f32, device=frames.device)
+    if P == 0:
+        return flow
+    pt = torch.tensor(pr, dtype=torch.int32).to(frames.device, non_blocking=False)
+    nb = lib.tt_farneback_workspace_bytes(F, P, H, W, float(pyr_scale), int(levels))
+    if nb == 0:
+        raise ValueError(f"farneback_flow: no workspace for F {F}, P {P}, {H} x {W}")
+    ws = _ws(nb, frames.device) if workspace is None else _chk(workspace, "workspace", torch.uint8)
+    if ws.numel() < nb:
+        raise ValueError(f"farneback_flow: workspace of {ws.numel()} bytes < {nb}")
+    _lib.check(lib.tt_farneback_flow(_p(frames), F, H, W, _p(pt), P, float(pyr_scale), int(levels), int(winsize), int(iterations), int(poly_n),
+                                     float(poly_sigma), int(flags), _p(flow), _p(ws), ws.numel(), _stream()), "tt_farneback_flow")
+    return flow
+
+
+def remap_nearest_labels(first, flows, scale: float = 1.0):
+    """first [N, H, W] labels (uint8 or int64), flows [N, steps, H, W, 2] fp32, both on the GPU -> [N, steps, H, W] of the same dtype:
+    step s remaps step s - 1 (step 0 remaps ``first``) through coords + scale * flows[:, s] with cv2.remap(INTER_NEAREST), constant-0
+    border.  ``scale`` is rounded to fp32 as numpy rounds a Python float multiplying a float32 array."""
+    lib = _lib.load()
+    if first.dtype not in (torch.uint8, torch.int64):
+        raise TypeError(f"remap_nearest_labels: labels must be uint8 or int64, got {first.dtype}")
+    _chk(first, "first", first.dtype)
+    _chk(flows, "flows")
+    if first.dim() != 3 or flows.dim() != 5 or flows.shape[0] != first.shape[0] or tuple(flows.shape[2:]) != (*first.shape[1:], 2):
+        raise ValueError(f"remap_nearest_labels: first {tuple(first.shape)} and flows {tuple(flows.shape)} are not [N, H, W] and "
+                         "[N, steps, H, W, 2]")
+    N, H, W = first.shape
+    steps = flows.shape[1]
+    out = torch.empty((N, steps, H, W), dtype=first.dtype, device=first.device)
+    if H == 0 or W == 0:
+        return out
+    _lib.check(lib.tt_remap_nearest_labels(_p(first), _p(flows), _p(out), N, steps, H, W, float(scale), first.element_size(), _stream()),
+               "tt_remap_nearest_labels")
+    return out

@@ -14,6 +14,11 @@ The DAVIS metrics (``:501-715``) keep the reference's names, signatures and retu
 ``db_eval_boundary`` / ``f_measure`` / ``_seg2bmap`` (F), ``db_statistics`` and ``evaluate_semisupervised``; ``davis_jf``
 scores every object of label maps in one launch.  The counts come from ``tt_davis_jf_counts`` on the GPU; J and F are formed
 from them on the host with the reference's fp64 expressions and branches, so they are the reference's to the bit.
+
+The optical-flow baseline (``--use_optical_flow``, ``:803-815``) keeps the reference's ``dense_optical_flow`` / ``interpolate_frames`` /
+``propagate`` (``:265-346``): OpenCV's dense Farneback flow and nearest-neighbour remap on the HIP kernels of farneback.hip, with
+``calc_optical_flow_farneback`` in place of the cv2 call.  Parity with cv2 itself is unpinned (cv2 is not a dependency); the kernels are
+held to an fp64 restatement of OpenCV's algorithm in the tests.
 """
 from __future__ import annotations
 
@@ -126,6 +131,109 @@ def jaccard(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, involve_bg: 
         valid[0] = False
     iou = torch.where(valid, inter / union.clamp(min=1), torch.full_like(inter, float("nan")))
     return (float(iou[valid].mean()) if valid.any() else float("nan")), iou
+
+
+# ---- the optical-flow baseline (mask_propagation.py:265-346, :803-815) -------------------------------------------------------------
+
+def _gpu(x) -> torch.Tensor:
+    return _device_tensor(x).contiguous()
+
+
+def calc_optical_flow_farneback(prev, next, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2, flags=0):
+    """``cv2.calcOpticalFlowFarneback(prev, next, None, ...)`` batched over the leading dimensions: prev, next uint8 [..., H, W] (numpy
+    or torch) -> flow [..., H, W, 2] fp32 (dx, dy) with prev(x) ~ next(x + flow(x)); numpy in gives numpy out, a tensor gives a tensor
+    on the GPU.  flags 0 only (OPTFLOW_USE_INITIAL_FLOW / OPTFLOW_FARNEBACK_GAUSSIAN raise NotImplementedError); see
+    ``hip_ops.check_farneback_params`` for the other rules (ValueError)."""
+    ops.check_farneback_params(pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags)
+    as_numpy = not isinstance(prev, torch.Tensor)
+    a, b = _gpu(prev), _gpu(next)
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise TypeError(f"calc_optical_flow_farneback: frames must be uint8, got {a.dtype} and {b.dtype}")
+    if a.dim() < 2 or a.shape != b.shape:
+        raise ValueError(f"calc_optical_flow_farneback: prev {tuple(a.shape)} and next {tuple(b.shape)} must be the same [..., H, W]")
+    lead, (H, W) = tuple(a.shape[:-2]), tuple(a.shape[-2:])
+    n = int(np.prod(lead)) if lead else 1
+    frames = torch.cat([a.reshape(n, H, W), b.reshape(n, H, W)], 0).contiguous()
+    flow = ops.farneback_flow(frames, [(i, n + i) for i in range(n)], pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags)
+    flow = flow.view(*lead, H, W, 2)
+    return flow.cpu().numpy() if as_numpy else flow
+
+
+def _clip_pairs(bs: int, fs: int):
+    """(new, old) = (j + 1, j) of every clip of [bs, fs] frames, frame-major: the argument order of the reference's call (:299)."""
+    return [(i * fs + j + 1, i * fs + j) for i in range(bs) for j in range(fs - 1)]
+
+
+def dense_optical_flow(data_list, params=[], to_gray=False):
+    """The reference's ``dense_optical_flow`` (``:265-319``): uint8 gray clips [bs, fs, H, W] -> the flow of every consecutive pair,
+    ``calcOpticalFlowFarneback(new, old, None, 0.5, 3, 15, 3, 5, 1.2, 0)``, all pairs of all clips in one batch.  numpy in gives nested
+    lists [bs][fs - 1] of [H, W, 2] float32 arrays, as the reference; a GPU tensor gives a GPU tensor [bs, fs - 1, H, W, 2].  ``params``
+    and ``to_gray`` are unused, as in the reference; so is its HSV visualisation, which is not built."""
+    as_numpy = not isinstance(data_list, torch.Tensor)
+    d = _gpu(data_list)
+    if d.dim() != 4 or d.dtype != torch.uint8:
+        raise ValueError(f"dense_optical_flow: expected uint8 [bs, fs, H, W], got {d.dtype} {tuple(d.shape)}")
+    bs, fs, H, W = d.shape
+    assert fs >= 2
+    flow = ops.farneback_flow(d.reshape(bs * fs, H, W), _clip_pairs(bs, fs)).view(bs, fs - 1, H, W, 2)
+    if not as_numpy:
+        return flow
+    host = flow.cpu().numpy()
+    return [[host[i, j] for j in range(fs - 1)] for i in range(bs)]
+
+
+def _label_tensor(x) -> Tuple[torch.Tensor, object]:
+    """Labels -> (uint8 or int64 GPU tensor, the dtype to give back)."""
+    t = _device_tensor(x)
+    back = t.dtype
+    if t.dtype not in (torch.uint8, torch.int64):
+        t = t.long()
+    return t.contiguous(), back
+
+
+def interpolate_frames(frame, flow, n_frames):
+    """The reference's ``interpolate_frames`` (``:322-333``): [cv2.remap(frame, coords + ((f + 1) / n_frames) * flow, None,
+    INTER_NEAREST) for f in range(n_frames)], constant-0 border.  frame [h, w] integer labels, flow [h, w, 2]; numpy in gives numpy
+    arrays of the frame's dtype, tensors give GPU tensors."""
+    as_numpy = not isinstance(frame, torch.Tensor)
+    lab, back = _label_tensor(frame)
+    fl = _device_tensor(flow).float().contiguous()
+    h, w = lab.shape
+    out = []
+    for f in range(n_frames):
+        r = ops.remap_nearest_labels(lab.view(1, h, w), fl.view(1, 1, h, w, 2), float(np.float32((f + 1) / n_frames)))[0, 0]
+        r = r.to(back)
+        out.append(r.cpu().numpy() if as_numpy else r)
+    return out
+
+
+def propagate(dataset_flow_list, annotations):
+    """The reference's ``propagate`` (``:336-346``): label_{j+1}(x) = label_j(x + flow_j(x)) from annotations[:, 0], each step from the
+    previous result, for every clip.  dataset_flow_list: ``dense_optical_flow``'s nested lists or its GPU tensor; annotations [bs, fs, h,
+    w] -> uint8 [bs, fs - 1, h, w] (on the CPU for nested lists, as the reference; on the GPU for a GPU flow tensor)."""
+    bs, fs, h, w = annotations.shape
+    if isinstance(dataset_flow_list, torch.Tensor):
+        flows, on_gpu = dataset_flow_list.float().contiguous(), True
+    else:
+        flows = torch.from_numpy(np.ascontiguousarray(np.asarray(dataset_flow_list, np.float32)))
+        flows, on_gpu = _device_tensor(flows).contiguous(), False
+    if tuple(flows.shape) != (bs, fs - 1, h, w, 2):
+        raise ValueError(f"propagate: flows {tuple(flows.shape)} do not match annotations {tuple(annotations.shape)}")
+    first, _ = _label_tensor(annotations[:, 0])
+    out = ops.remap_nearest_labels(first, flows).to(torch.uint8)
+    return out if on_gpu else out.cpu()
+
+
+@torch.no_grad()
+def propagate_clip_optical_flow(clip: torch.Tensor, first_annotation: torch.Tensor) -> torch.Tensor:
+    """The optical-flow branch of the evaluation loop for one clip (``:803-815``): clip [fs, 3, H, W] fp32 on the GPU -> 8-bit gray ->
+    Farneback flow of every (new, old) consecutive pair -> the annotation of frame 0 carried forward by nearest remapping.  Returns
+    [fs - 1, H, W] int64 predictions for frames 1..fs-1, the contract of ``propagate_clip``; no host round trip."""
+    fs, _, H, W = clip.shape
+    gray = ops.flow_gray_u8(clip.float().contiguous())
+    flows = ops.farneback_flow(gray, _clip_pairs(1, fs))
+    first = _device_tensor(first_annotation).long().contiguous().view(1, H, W)
+    return ops.remap_nearest_labels(first, flows.view(1, fs - 1, H, W, 2))[0]
 
 
 # ---- DAVIS J&F (mask_propagation.py:501-715) -------------------------------------------------------------------------------
@@ -375,7 +483,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--epsilon", default=0.05, type=float)
     p.add_argument("--sinkhorn_iterations", default=3, type=float)
     p.add_argument("--use_projection_head", type=bool, default=True)
-    p.add_argument("--use_optical_flow", type=bool, default=False)
+    p.add_argument("--use_optical_flow", type=bool, default=False,
+                   help="the dense Farneback optical-flow baseline instead of the ViT features (no backbone is built)")
     p.add_argument("--num_clips", type=int, default=4, help="synthetic data only")
     p.add_argument("--davis_metrics", action="store_true",
                    help="also print DAVIS J / F mean, recall and decay and J&F-Mean per clip and overall (addition)")
@@ -426,22 +535,31 @@ def clip_size(args, patch_size: int) -> Tuple[int, int]:
     return H, W
 
 
+# the synthetic clips' textures are 8 x 8 cells, so the optical-flow branch (which builds no backbone) takes --frame_size in multiples of 8
+_FLOW_FRAME_MULTIPLE = 8
+
+
 def mask_propagation(args) -> float:
     """The evaluation loop of ``mask_propagation.py:757-846`` on synthetic clips; returns the mean J over clips.  With
     ``--davis_metrics`` it also prints the DAVIS statistics (``db_statistics`` over each object's frames) per clip and over all
-    objects of all clips; the return value is the same."""
-    from .models import FeatureExtractor
-    from .time_tuning import TimeT
-
+    objects of all clips; the return value is the same.  ``--use_optical_flow`` runs the optical-flow baseline
+    (``propagate_clip_optical_flow``) on the same clips, with the same scoring, and builds no backbone.  Both branches score predicted
+    frame j against annotated frame j; the reference compares ``predictions[:, 1:]`` with ``annotations[:, 1:]``, one frame off."""
     if args.dataset != "synthetic":
         raise NotImplementedError("dataset readers (data_loader.py) are out of scope for this build; run with --dataset synthetic")
-    if args.use_optical_flow:
-        raise NotImplementedError("the optical-flow baseline (cv2 Farneback, mask_propagation.py:803-815) is not part of this build")
-    fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], return_attention=False)  # "" = synthetic weights
-    H, W = clip_size(args, fe.backbone.patch_embed.patch_size)
+    use_flow = bool(args.use_optical_flow)
     native = getattr(args, "frame_size", None) is not None
     device = torch.device("cuda", 0)
-    model = TimeT(fe, 200).to(device).eval()
+    if use_flow:
+        H, W = clip_size(args, _FLOW_FRAME_MULTIPLE)
+        model = None
+    else:
+        from .models import FeatureExtractor
+        from .time_tuning import TimeT
+
+        fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], return_attention=False)  # "" = synthetic weights
+        H, W = clip_size(args, fe.backbone.patch_embed.patch_size)
+        model = TimeT(fe, 200).to(device).eval()
     scores = []
     davis = []   # per object: (J_M, J_R, J_D, F_M, F_R, F_D)
     for i in range(args.num_clips):
@@ -452,8 +570,11 @@ def mask_propagation(args) -> float:
         if args.uvos:  # all objects become one foreground class (:797-799)
             masks = (masks > 0).long()
         C = int(masks.max()) + 1
-        pred = propagate_clip(model, clip.to(device), masks[0].to(device), args.n_last_frames, args.size_mask_neighborhood, args.topk,
-                              (H, W) if native else args.input_resolution, C)
+        if use_flow:
+            pred = propagate_clip_optical_flow(clip.to(device), masks[0].to(device))
+        else:
+            pred = propagate_clip(model, clip.to(device), masks[0].to(device), args.n_last_frames, args.size_mask_neighborhood, args.topk,
+                                  (H, W) if native else args.input_resolution, C)
         j, _ = jaccard(pred, masks[1:].to(device), C)
         scores.append(j)
         print(f"clip {i}: J = {j:.4f}")
