@@ -108,7 +108,8 @@ int tt_linear_fwd_planes_route(int planes, int M, int N, int K, int act, int has
  *      (dino_vision_transformer.py:214-234): bicubic resampling of the patch position table, as
  *      nn.functional.interpolate(..., scale_factor=(scale_h, scale_w), mode="bicubic") computes it (align_corners False,
  *      coordinate scale 1/scale_factor, A = -0.75, border-clamped taps); the class row is copied.
- *   pos [1 + g*g, D] -> out [1 + gh*gw, D].  The reference passes scale = (rows + 0.1) / g, (cols + 0.1) / g. */
+ *   pos [1 + g*g, D] -> out [1 + gh*gw, D].  The reference passes scale = (rows + 0.1) / g, (cols + 0.1) / g.
+ *   Accepted domain: D a multiple of 4, pos and out 16-byte aligned, positive scales; any g, gh, gw > 0 (gh != gw, 1 included). */
 int tt_pos_embed_interpolate(const float* pos, float* out, int g, int gh, int gw, int D, float scale_h, float scale_w,
                              tt_stream_t stream);
 
@@ -199,7 +200,7 @@ int tt_l2norm_fwd(const float* x, int ldx, float* xn, float* inv_norm, int rows,
 /*   dx = (dxn - xn * <xn, dxn>) * inv_norm */
 int tt_l2norm_bwd(const float* dxn, const float* xn, const float* inv_norm, float* dx, int rows, int D, float* amax_out,
                   tt_stream_t stream);
-/* ---- k18: in-place row L2 normalisation of the prototypes (time_tuning.py:124-128). */
+/* ---- k18: in-place row L2 normalisation of the prototypes (time_tuning.py:124-128).  D <= 1024 (as tt_l2norm_fwd). */
 int tt_normalize_rows_inplace(float* w, int rows, int D, tt_stream_t stream);
 
 /* ---- k12: Sinkhorn-Knopp (time_tuning.py:157-168 + my_utils.py:246-274)
@@ -410,7 +411,9 @@ int tt_label_propagate_from_sims(const float* xn, const float* seg0, int64_t* la
  *                            labels_out [M, R, R] int64; the upsampled fp64 tensor is never written.
  *   tt_confusion_counts      counts[gt*C + pred] += 1 over n pixels (labels outside [0,C) ignored), uint64 [C,C],
  *                            C <= 4096: the confusion matrix from which the Jaccard index (J) of the propagated masks and
- *                            the evaluator's matched mIoU (metrics.py:357-432) follow. */
+ *                            the evaluator's matched mIoU (metrics.py:357-432) follow.  An LDS histogram up to C = 96,
+ *                            global integer atomics beyond; any n > 0.
+ *   tt_upsample_argmax takes M <= 65535 maps per call (they ride on gridDim.y) and R <= 32768. */
 int tt_label_propagate_maps(const float* xn, const float* seg0, double* pmap_all, int bs, int fs, int g, int D, int K,
                             int n_last_frames, int radius, int topk, float temperature, int precision, void* workspace,
                             size_t workspace_bytes, tt_stream_t stream);
@@ -479,7 +482,9 @@ int tt_queue_push(float* queue, float* scratch, const float* feats, const int64_
                   tt_stream_t stream);
 
 /* ---- k17: AdamW over a table of tensors (time_tuning.py:413-429; torch.optim.AdamW defaults)
- *   Up to TT_MAX_TENSORS per call.  step is the 1-based step count of every tensor in the call. */
+ *   1 .. TT_MAX_TENSORS entries per call (tt_adamw_step and tt_scale_tensors refuse more; tt_adamw_ema_step takes any count and
+ *   walks it in chunks of TT_MAX_TENSORS).  Lengths are free and may differ: the grid is sized by the longest entry, up to 1024
+ *   workgroups, and strides.  step is the 1-based step count of every tensor in the call (>= 1). */
 #define TT_MAX_TENSORS 40
 typedef struct {
   float* p;
@@ -498,10 +503,11 @@ int tt_adamw_step(const tt_adamw_tensor* tensors, int count, int step, float bet
  * (time_tuning.py:420-423 calls backward on the scalar loss; its incoming gradient is a device scalar). */
 int tt_scale_tensors(const tt_adamw_tensor* tensors, int count, const float* scale_device, tt_stream_t stream);
 
-/* ---- k19: EMA teacher update (time_tuning.py:109-118): t = t*(1-m) + s*m over n floats. */
+/* ---- k19: EMA teacher update (time_tuning.py:109-118): t = t*(1-m) + s*m over n floats.  Any n > 0 (n & 3 trailing floats
+ *   included); both buffers 16-byte aligned. */
 int tt_ema_update(float* teacher, const float* student, long long n, double momentum, tt_stream_t stream);
 
-/* ---- misc elementwise used between the sites above */
+/* ---- misc elementwise used between the sites above (any n > 0; no alignment requirement) */
 int tt_add_inplace(float* dst, const float* src, long long n, tt_stream_t stream);
 /* Number of positions where two fp32 buffers differ BITWISE.  Decides, once, whether the EMA teacher's frozen tensors still equal the student's
  * (time_tuning.py:113-114 blends identical tensors for every frozen parameter), i.e. whether the teacher pass may reuse the
@@ -519,7 +525,10 @@ int tt_count_mismatch(const float* a, const float* b, long long n, long long* co
  *                                kernel, so attn[F,H,N,N] is never materialised.
  *   tt_foreground_mask_from_probs cls_probs [F,H,N]: row 0 of the attention probabilities, already computed.
  *   mask_out [F,g*g] floats in {0,1}; blurred_out [F,g*g] optional (the blurred mean attention);
- *   margin_out [F,g*g] optional (|cumulative mass - (1-threshold)| per pixel: how far it is from the cut). */
+ *   margin_out [F,g*g] optional (|cumulative mass - (1-threshold)| per pixel: how far it is from the cut).
+ *   Accepted domain: N = g*g + 1 with g*g <= 1024 patches (one workgroup holds a frame in LDS); ksize odd, <= 15, and
+ *   ksize / 2 < g (reflect padding: the 7-tap blur needs g >= 4); 0 < threshold < 1; sigma > 0; H > 0; any F > 0.
+ *   tt_foreground_mask also: head_dim a multiple of 4, <= 128, qkv 16-byte aligned. */
 int tt_foreground_mask(const float* qkv, float* mask_out, float* blurred_out, float* margin_out, int F, int N, int H, int hd, int g,
                        float scale, float threshold, float sigma, int ksize, tt_stream_t stream);
 int tt_foreground_mask_from_probs(const float* cls_probs, float* mask_out, float* blurred_out, float* margin_out, int F, int N,
@@ -534,8 +543,21 @@ int tt_foreground_mask_from_probs(const float* cls_probs, float* mask_out, float
  *   tt_upsample_argmax_f32      fp32 twin of tt_upsample_argmax for proto_clustering's prototype scores (clustering.py:101-104).
  *   tt_kmeans_assign            labels[p] = argmin_j |x_p - c_j|^2 (first minimum) over centroids [k, d]; dist2 optional.
  *   tt_kmeans_accumulate        sums[k, d] (fp64) and counts[k] of the points per label, deterministic (no atomics).
- *   Both hold the centroids in LDS: k * d <= 16384 (k * d + k for the accumulation), and for d <= 64 the assignment's LDS
- *   (k * d + 256 (d | 1) floats) <= 128 KB - k = 300 at d = 50, the N6 over-clustering, fits. */
+ *   Accepted domains (each refusal is a TT_EINVAL with the entry's own message; nothing is launched):
+ *     tt_col_moments              0 < cols <= 1024; any rows > 0 (1024 workgroups from 262 144 rows on).  The sums are taken about
+ *                                 the column's first row, so a small variance beside a large mean survives.
+ *     tt_upsample_bilinear_tokens, tt_upsample_argmax_f32, tt_upsample_argmax (N4): M <= 65535 maps per call (they ride on
+ *                                 gridDim.y), R <= 32768; any g, C / K > 0 - R < g (down-sampling), R = g and g = 1 included.
+ *     tt_kmeans_assign, tt_kmeans_accumulate: ONE rule for both, tt_kmeans_shape_ok(d, k) - a Lloyd iteration calls one after the
+ *                                 other, and clustering.Kmeans asks before its first assignment.  Both hold k * d <= 16384 floats
+ *                                 of centroids (sums) in LDS; for d <= 64 the assignment's tile of 256 points shares it,
+ *                                 k * d + 256 (d | 1) floats <= 128 KB, which binds at d = 64 only (k <= 252).  k = 300 at d = 50,
+ *                                 the N6 over-clustering, fits.  Any P > 0: beyond 4096 x 256 points the assignment strides, beyond
+ *                                 4096 x 128 a workgroup of the accumulation sums ceil(P / 4096) points.  Labels given to the
+ *                                 accumulation must lie in [0, k). */
+int tt_kmeans_shape_ok(int d, int k);   /* 1 when tt_kmeans_assign and tt_kmeans_accumulate take (d, k), else 0 */
+int tt_kmeans_assign_route(int d);      /* which kernel tt_kmeans_assign runs at d: 16 / 64 = the point in that many registers, 0 = rows
+                                           read in place (d > 64).  The three compute the same bits; for tests and profilers' labels. */
 int tt_affine_cols_inplace(float* x, const float* scale, const float* shift, long long rows, int cols,
                            tt_stream_t stream); /* x[r][c] = x[r][c] * scale[c] + shift[c] (StandardScaler.transform) */
 size_t tt_col_moments_workspace_bytes(long long rows, int cols);
@@ -742,7 +764,7 @@ int tt_adamw_ema_step(const tt_adamw_tensor* tensors, int count, int step, float
                       int K, int dim, float* teacher_flat, const float* student_flat, long long n_flat, float* teacher_prototypes,
                       double momentum, tt_stream_t stream);
 
-/* features * mask[..., None] (models.py:142) and its backward: x[r][:] *= row_scale[r], cols % 4 == 0. */
+/* features * mask[..., None] (models.py:142) and its backward: x[r][:] *= row_scale[r], cols % 4 == 0, x 16-byte aligned. */
 int tt_scale_rows_inplace(float* x, const float* row_scale, int rows, int cols, tt_stream_t stream);
 
 #ifdef __cplusplus

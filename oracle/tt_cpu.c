@@ -326,15 +326,18 @@ int tt_cpu_kmeans_assign(const float* x, const float* centroids, int32_t* labels
   return 0;
 }
 
-/* ---- StandardScaler's statistics (my_utils.py:24-28): per-column mean and population variance */
+/* ---- StandardScaler's statistics (my_utils.py:24-28): per-column mean and population variance, the sums taken about the column's first row
+ *      (as the kernel: on the raw values E[x^2] - E[x]^2 loses a small variance beside a large mean, in fp64 too) */
 int tt_cpu_col_moments(const float* x, double* mean, double* var, long long rows, int cols, void* workspace, size_t workspace_bytes,
                        tt_stream_t stream) {
   (void)workspace; (void)workspace_bytes; (void)stream;
   for (int c = 0; c < cols; ++c) {
+    const double shift = x[c];
     double s = 0.0, s2 = 0.0;
-    for (long long r = 0; r < rows; ++r) { const double v = x[r * cols + c]; s += v; s2 += v * v; }
-    mean[c] = s / (double)rows;
-    const double v = s2 / (double)rows - mean[c] * mean[c];
+    for (long long r = 0; r < rows; ++r) { const double v = (double)x[r * cols + c] - shift; s += v; s2 += v * v; }
+    const double m = s / (double)rows;
+    mean[c] = shift + m;
+    const double v = s2 / (double)rows - m * m;
     var[c] = v > 0 ? v : 0;
   }
   return 0;

@@ -93,13 +93,86 @@ def _queue_push(rng):
     return dict(Q=Q, D=_ch(rng, (1, 32, 128, 256)), m=int(rng.integers(1, Q + 1)))
 
 
+# ---- second tier: the evaluator, optimizer and mask kernels (checks: tests/_sweep_checks_eval.py, on the C twin and on the HIP library)
+KM_MAXKD = 16384          # cluster.hip: k * d floats of centroids in LDS
+
+
+def km_max_k(d: int) -> int:
+    """cluster.hip, km_shape_ok: the largest k both k-means entries take at d (k * d <= KM_MAXKD; at d <= 64 the point tile shares the LDS)."""
+    k = KM_MAXKD // d
+    if d <= 64:
+        k = min(k, (128 * 1024 // 4 - 256 * (d | 1)) // d)
+    return k
+
+
+def _kmeans_assign(rng):
+    d = _ch(rng, (1, 2, 3, 8, 9, 16, 17, 31, 50, 64, 65, 100, 128, 384))
+    k = int(rng.integers(1, min(km_max_k(d), 300) + 1))
+    return dict(P=int(rng.integers(1, 20000)), d=d, k=k, dup=_b(rng, 0.3) if k > 1 else 0)
+
+
+def _kmeans_accumulate(rng):
+    d = _ch(rng, (1, 3, 8, 16, 50, 64, 100, 257, 384))
+    k = int(rng.integers(1, min(km_max_k(d), 300) + 1))
+    return dict(P=int(rng.integers(1, 30000)), d=d, k=k, mode=_ch(rng, ("rand", "rand", "skip", "one")))
+
+
+def _col_moments(rng):
+    cols = _ch(rng, (1, 2, 9, 50, 255, 256, 257, 384, 1024))      # (a constant column needs a second one to scale the error by)
+    return dict(rows=int(rng.integers(1, 20000)), cols=cols, kind=_ch(rng, ("scaled", "const_col", "offset") if cols > 1 else ("scaled", "offset")))
+
+
+def _upsample(name):
+    def gen(rng):
+        g = int(rng.integers(1, 29))
+        R = int(rng.integers(1, 5 * g + 2))
+        return {"M": int(rng.integers(1, 4)), "g": g, "R": R, name: _ch(rng, (1, 2, 7, 21, 64, 65, 200, 255, 256, 300))}
+    return gen
+
+
+def _confusion_counts(rng):
+    return dict(n=int(rng.integers(1, 300000)), C=_ch(rng, (1, 2, 7, 21, 96, 97, 300, 1000)), stray=_b(rng))
+
+
+def _adamw(rng):
+    return dict(T=int(rng.integers(1, 100)), big=int(rng.integers(1, 400000)), step=_ch(rng, (1, 2, 37, 5000, 100000)), fused=_b(rng),
+                gscale=_ch(rng, (1.0, 0.37, 1e-3)))
+
+
+def _elementwise(rng):
+    n = int(rng.integers(1, 3000000)) if rng.random() < 0.5 else int(rng.integers(1, 5000))
+    return dict(n=n, rows=int(rng.integers(1, 40000)), cols=int(rng.integers(1, 65)) if rng.random() < 0.7 else _ch(rng, (255, 256, 1000, 1024)))
+
+
+def _foreground_mask(rng):
+    return dict(F=int(rng.integers(1, 9)), g=_ch(rng, (4, 5, 7, 13, 14, 28, 31, 32)), H=_ch(rng, (1, 3, 6, 12)), hd=_ch(rng, (4, 64, 128)),
+                th=_ch(rng, (0.3, 0.65, 0.8)), entry=_ch(rng, ("probs", "qkv")))
+
+
+def _pos_embed(rng):
+    g = _ch(rng, (14, 28))
+    while True:
+        gh, gw = int(rng.integers(1, 41)), int(rng.integers(1, 41))
+        if (gh, gw) != (g, g):      # the stored grid itself is returned as it is, not interpolated
+            return dict(g=g, gh=gh, gw=gw, D=_ch(rng, (4, 64, 384, 768)))
+
+
 DRAW = {"linear_f32": _linear_f32, "linear_pairs": _linear_pairs, "linear_planes": _linear_planes, "bwd_pairs": _bwd_pairs,
         "layernorm": _layernorm, "l2norm": _l2norm, "attention": _attention, "ce": _ce, "sinkhorn": _sinkhorn,
         "sinkhorn_from_q": _sinkhorn_from_q, "sinkhorn_local": _sinkhorn_local, "queue_push": _queue_push}
+STEP_OPS = tuple(DRAW)      # the first tier: the kernels of the training step
+# (appended: the table draws op by op from one generator, so the first tier's cases - and their ids - stay what they were)
+DRAW.update({"kmeans_assign": _kmeans_assign, "kmeans_accumulate": _kmeans_accumulate, "col_moments": _col_moments,
+             "upsample_tokens": _upsample("C"), "upsample_argmax_f32": _upsample("K"), "upsample_argmax": _upsample("K"),
+             "confusion_counts": _confusion_counts, "adamw": _adamw, "elementwise": _elementwise, "foreground_mask": _foreground_mask,
+             "pos_embed": _pos_embed})
 OPS = tuple(DRAW)
+EVAL_OPS = OPS[len(STEP_OPS):]
 
 COUNTS = {"linear_f32": 6, "linear_pairs": 8, "linear_planes": 4, "bwd_pairs": 6, "layernorm": 5, "l2norm": 3, "attention": 6, "ce": 3,
-          "sinkhorn": 6, "sinkhorn_from_q": 3, "sinkhorn_local": 3, "queue_push": 3}
+          "sinkhorn": 6, "sinkhorn_from_q": 3, "sinkhorn_local": 3, "queue_push": 3,
+          "kmeans_assign": 4, "kmeans_accumulate": 4, "col_moments": 3, "upsample_tokens": 3, "upsample_argmax_f32": 3, "upsample_argmax": 3,
+          "confusion_counts": 3, "adamw": 3, "elementwise": 3, "foreground_mask": 4, "pos_embed": 3}
 
 # The route boundaries, pinned (tests/test_sweep_routes.py names the rule each one reaches)
 PINNED = {
@@ -154,6 +227,88 @@ PINNED = {
     "sinkhorn_from_q": [dict(B=777, K=333, iters=5, transposed=0), dict(B=2049, K=256, iters=0, transposed=1), dict(B=65, K=511, iters=1, transposed=1)],
     "sinkhorn_local": [dict(B=777, K=333, iters=5), dict(B=2049, K=257, iters=0), dict(B=31, K=64, iters=1)],
     "queue_push": [dict(Q=40, D=32, m=1), dict(Q=40, D=32, m=40), dict(Q=1, D=128, m=1)],
+    # ---- second tier (cluster.hip, label_prop.hip, rowops.hip, attn_mask.hip)
+    "kmeans_assign": [
+        # tt_kmeans_assign's dispatch: d <= 16 (16 registers), d <= 64 (64 registers), wider rows read in place - either side of each edge
+        dict(P=300, d=1, k=7, dup=0), dict(P=5000, d=16, k=100, dup=0), dict(P=5000, d=17, k=100, dup=0), dict(P=20000, d=64, k=200, dup=0),
+        dict(P=20000, d=65, k=250, dup=0), dict(P=3000, d=128, k=100, dup=0), dict(P=257, d=384, k=42, dup=0), dict(P=7001, d=50, k=327, dup=0),
+        # k = 1; one point; the last tile of 256 points full, one short, one over; a duplicated centroid (first minimum: the lower index)
+        dict(P=1, d=1, k=1, dup=0), dict(P=1, d=9, k=4, dup=1), dict(P=255, d=16, k=1, dup=0), dict(P=256, d=50, k=21, dup=1),
+        dict(P=257, d=65, k=21, dup=1), dict(P=12000, d=8, k=30, dup=1),
+        # more than 4096 x 256 points: the grid-stride loop (with its __syncthreads) on each of the three kernels
+        dict(P=1100000, d=8, k=5, dup=0), dict(P=1048577, d=17, k=3, dup=1), dict(P=1048700, d=65, k=2, dup=0),
+        # the largest k * d each kernel takes (km_shape_ok): 16384 floats of centroids; at d = 64 the tile leaves room for 252
+        dict(P=3000, d=16, k=1024, dup=0), dict(P=3000, d=64, k=252, dup=0), dict(P=3000, d=128, k=128, dup=0),
+    ],
+    "kmeans_accumulate": [
+        # accumulate_blocks: ceil(P / 128) workgroups up to 4096 - beyond P = 524 288 a workgroup sums MORE than 128 points (129 here, and the
+        # last 31 workgroups get none; 147 at 600 000); under the cap every workgroup has points
+        dict(P=524289, d=8, k=5, mode="rand"), dict(P=600000, d=3, k=7, mode="skip"), dict(P=1100000, d=8, k=5, mode="rand"),
+        dict(P=524288, d=2, k=3, mode="rand"), dict(P=7001, d=50, k=21, mode="rand"), dict(P=1, d=1, k=1, mode="rand"),
+        dict(P=129, d=16, k=4, mode="rand"),
+        # a label that no point carries; every point in one cluster; d > 256 (a thread owns two columns); k * d at the accepted maximum
+        dict(P=5000, d=50, k=30, mode="skip"), dict(P=5000, d=64, k=9, mode="one"), dict(P=700000, d=4, k=3, mode="one"),
+        dict(P=3000, d=384, k=42, mode="rand"), dict(P=900, d=257, k=2, mode="skip"), dict(P=3000, d=16, k=1024, mode="rand"),
+        dict(P=3000, d=64, k=252, mode="rand"), dict(P=20000, d=1, k=16384, mode="rand"),
+    ],
+    "col_moments": [
+        # moments_blocks: ceil(rows / 256) workgroups up to 1024 (262 144 rows); one row (variance exactly 0); one column; a constant
+        # column; a column with mean 1e4 and spread 1e-2 (what a one-pass fp32 formula loses)
+        dict(rows=1, cols=9, kind="scaled"), dict(rows=300000, cols=3, kind="scaled"), dict(rows=262144, cols=2, kind="offset"),
+        dict(rows=262145, cols=1, kind="scaled"), dict(rows=5000, cols=1, kind="scaled"), dict(rows=5000, cols=384, kind="const_col"),
+        dict(rows=2000, cols=4, kind="offset"), dict(rows=300, cols=1024, kind="scaled"), dict(rows=257, cols=257, kind="const_col"),
+    ],
+    "upsample_tokens": [
+        # tt_upsample_bilinear_tokens: 64 threads up to C = 64, 128 below 256, 256 from there; g = 1; R = g; R < g; R = 1; ragged ratios
+        dict(M=2, g=1, R=5, C=1), dict(M=1, g=14, R=14, C=64), dict(M=3, g=14, R=9, C=65), dict(M=2, g=28, R=1, C=255),
+        dict(M=1, g=14, R=56, C=256), dict(M=2, g=3, R=8, C=300), dict(M=1, g=13, R=31, C=50), dict(M=1, g=28, R=60, C=7),
+        dict(M=300, g=2, R=3, C=4),
+    ],
+    "upsample_argmax_f32": [
+        dict(M=2, g=1, R=5, K=1), dict(M=1, g=14, R=14, K=64), dict(M=3, g=14, R=9, K=65), dict(M=2, g=28, R=1, K=255),
+        dict(M=1, g=14, R=56, K=256), dict(M=2, g=3, R=8, K=300), dict(M=1, g=13, R=31, K=21), dict(M=2, g=14, R=100, K=12),
+        dict(M=300, g=2, R=3, K=4),
+    ],
+    "upsample_argmax": [
+        dict(M=2, g=1, R=5, K=1), dict(M=1, g=14, R=14, K=64), dict(M=3, g=14, R=9, K=65), dict(M=2, g=28, R=1, K=255),
+        dict(M=1, g=14, R=56, K=256), dict(M=2, g=3, R=8, K=300), dict(M=1, g=13, R=31, K=21), dict(M=2, g=14, R=100, K=8),
+        dict(M=300, g=2, R=3, K=4),
+    ],
+    "confusion_counts": [
+        # tt_confusion_counts: the LDS histogram up to C = 96, global atomics beyond; ceil(n / 4096) workgroups up to 2048; labels outside
+        # [0, C) - the -1 and 255 of ignored pixels - dropped
+        dict(n=1, C=1, stray=0), dict(n=1, C=97, stray=1), dict(n=5000, C=1, stray=1), dict(n=100000, C=96, stray=1), dict(n=100000, C=97, stray=1),
+        dict(n=70000, C=300, stray=1), dict(n=2048 * 4096, C=21, stray=0), dict(n=2048 * 4096 + 5, C=7, stray=1), dict(n=2048 * 4096 + 4097, C=300, stray=1),
+    ],
+    "adamw": [
+        # tables of 1, 40 (TT_MAX_TENSORS) and more tensors - through the wrappers' chunks of 40 and through the fused entry's; lengths 1, 255,
+        # 257 and `big` round-robin, so that a length-1 tensor shares the grid of one above 1024 x 256 elements; steps 1 and 100 000
+        dict(T=1, big=1, step=1, fused=0, gscale=1.0), dict(T=1, big=300001, step=3, fused=1, gscale=0.37), dict(T=40, big=262145, step=1, fused=0, gscale=0.37),
+        dict(T=41, big=300001, step=100000, fused=0, gscale=1e-3), dict(T=85, big=1000, step=2, fused=1, gscale=0.37),
+        dict(T=81, big=70000, step=100000, fused=1, gscale=1.0), dict(T=4, big=262144, step=5000, fused=0, gscale=1.0),
+    ],
+    "elementwise": [
+        # n & 3 in {0, 1, 2, 3} below 4 and above (tt_ema_update: float4 body, the tail on workgroup 0); n either side of the caps - ema
+        # 2048 x 1024, add 4096 x 256, count_mismatch 2048 x 256; rows either side of colsum's 128 chunks of 256
+        dict(n=1, rows=1, cols=1), dict(n=2, rows=2, cols=3), dict(n=3, rows=3, cols=64), dict(n=4, rows=5, cols=65), dict(n=5, rows=255, cols=4),
+        dict(n=6, rows=256, cols=100), dict(n=7, rows=257, cols=1024), dict(n=100003, rows=32768, cols=7), dict(n=524288, rows=32769, cols=3),
+        dict(n=524289, rows=40000, cols=66), dict(n=1048576, rows=100, cols=255), dict(n=1048578, rows=1000, cols=384),
+        dict(n=2097152, rows=7, cols=2), dict(n=2097153 + 4096, rows=700, cols=1000), dict(n=3000003, rows=33, cols=33),
+    ],
+    "foreground_mask": [
+        # one workgroup per frame, everything in LDS: g up to 32 (1024 patches); the 7-tap blur reflects over up to 3 pixels, so g >= 4
+        dict(F=1, g=4, H=1, hd=4, th=0.65, entry="qkv"), dict(F=3, g=5, H=3, hd=64, th=0.3, entry="qkv"), dict(F=2, g=13, H=6, hd=128, th=0.8, entry="qkv"),
+        dict(F=5, g=14, H=12, hd=64, th=0.65, entry="qkv"), dict(F=2, g=31, H=3, hd=4, th=0.3, entry="qkv"), dict(F=2, g=32, H=6, hd=64, th=0.65, entry="qkv"),
+        dict(F=300, g=14, H=6, hd=64, th=0.65, entry="qkv"),
+        dict(F=1, g=4, H=12, hd=64, th=0.3, entry="probs"), dict(F=4, g=5, H=1, hd=64, th=0.8, entry="probs"), dict(F=3, g=13, H=3, hd=64, th=0.65, entry="probs"),
+        dict(F=2, g=14, H=6, hd=64, th=0.3, entry="probs"), dict(F=2, g=31, H=12, hd=64, th=0.65, entry="probs"), dict(F=1, g=32, H=1, hd=64, th=0.8, entry="probs"),
+        dict(F=300, g=7, H=3, hd=64, th=0.65, entry="probs"),
+    ],
+    "pos_embed": [
+        # bicubic, taps clamped at the border: gh != gw, one of them 1, down- and up-sampling, D = 4 (one float4 per token)
+        dict(g=14, gh=1, gw=7, D=4), dict(g=14, gh=20, gw=1, D=384), dict(g=14, gh=20, gw=14, D=384), dict(g=28, gh=7, gw=9, D=768),
+        dict(g=28, gh=30, gw=40, D=4), dict(g=14, gh=30, gw=40, D=768), dict(g=28, gh=14, gw=14, D=384), dict(g=14, gh=13, gw=15, D=64),
+    ],
 }
 
 

@@ -495,18 +495,7 @@ def test_scale_rows(ops):
     assert torch.equal(y.cpu(), x * w[:, None])
 
 
-def _mask_mismatch_excusable(mask, want, margin, tol=2e-6):
-    """A pixel may land on the other side of the mass cut only where its cumulative mass is within rounding of the
-    cut; such a flip can also change which neighbours form a <= 2-pixel component, so the excuse covers 3x3
-    surroundings of any near-cut pixel."""
-    mism = mask != want
-    if not mism.any():
-        return True
-    Fr, n = mask.shape
-    g = int(round(n ** 0.5))
-    near = (margin < tol).reshape(Fr, 1, g, g).float()
-    near = F.max_pool2d(near, 5, 1, 2).reshape(Fr, n).bool()   # 2 rings: the flipped pixel's neighbours' neighbours
-    return bool((~mism | near).all())
+from _sweep_checks_eval import mask_mismatch_excusable as _mask_mismatch_excusable  # noqa: E402  (shared with the sweep's mask cases)
 
 
 @pytest.mark.parametrize("g_", [14, 28, 7])

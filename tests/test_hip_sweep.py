@@ -3,6 +3,11 @@ bounds - TOL_F32 (max-normalised) and TOL_L2 (relative L2) as in tests/test_hip_
 tighter one; the f32-class rule for the split modes (not worse than the exact-f32 kernel on the same operands); 5e-5 against O.sinkhorn;
 run-to-run bit equality on the persistent kernels.  tests/test_sweep_routes.py checks, without a GPU, that the table reaches every route.
 
+The second tier - the evaluator, optimizer and mask kernels (EVAL_OPS) - runs the checks of tests/_sweep_checks_eval.py on the HIP library:
+the same inputs, fp64 references, bounds and capped excuse rules that tests/test_sweep_eval_host.py holds the plain-C twins to.  Behind it,
+the accepted domain of each of those entries at its edge: the largest size computes correctly (a case of the table or a call below), the
+first size beyond is refused by the launcher's own check, with its own message, before anything is launched.
+
 ``run_case`` is also what tools/fuzz_ops.py runs on more seeds of the same generator."""
 import json
 import os
@@ -13,7 +18,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _sweep_cases import PAIR_EPILOGUES, case_id, table
+from _sweep_cases import EVAL_OPS, PAIR_EPILOGUES, case_id, table
+from _sweep_checks_eval import HipSide, run_eval_case
 
 pytestmark = pytest.mark.gpu
 TOL_F32 = 2e-5
@@ -325,7 +331,10 @@ def run_case(op: str, params: dict, worst: dict = None) -> None:
     if worst is not None:
         WORST = worst
     try:
-        CHECK[op](ops, params, _gen(op, params), _note(op))
+        if op in EVAL_OPS:
+            run_eval_case(HipSide(), op, params, WORST)
+        else:
+            CHECK[op](ops, params, _gen(op, params), _note(op))
     finally:
         WORST = keep
 
@@ -342,3 +351,111 @@ def _report():
 @pytest.mark.parametrize("op,params", CASES, ids=[case_id(o, p) for o, p in CASES])
 def test_sweep(op, params):
     run_case(op, params)
+
+
+# ---- the accepted domains of the second tier's entries, at the edge (include/timetuning_hip.h states them).  Every refusal below is a
+# host-side TT_REQUIRE: nothing is launched.
+def _refused(match):
+    from timetuning_amd import _lib
+
+    return pytest.raises(_lib.HipLibraryError, match=match)
+
+
+def _z(*shape, dtype=torch.float32):
+    return torch.zeros(*shape, dtype=dtype, device="cuda")
+
+
+@pytest.mark.parametrize("d,k,ok", [(64, 252, True), (64, 253, False), (16, 1024, True), (16, 1025, False), (128, 128, True), (128, 129, False),
+                                    (1, 16384, True), (1, 16385, False)])
+def test_kmeans_entries_share_one_domain(d, k, ok):
+    """Largest accepted (d, k) - they compute correctly in the table above (kmeans_assign / kmeans_accumulate at k * d = 16384 and at
+    d = 64, k = 252) - and the first one beyond: BOTH entries refuse it, so that no run gets through the assignment and fails in the update."""
+    from timetuning_amd import hip_ops as ops
+
+    assert ops.kmeans_shape_ok(d, k) == ok
+    x, c, lab = _z(300, d), _z(k, d), _z(300, dtype=torch.int32)
+    if ok:
+        labels = ops.kmeans_assign(x, c)
+        assert int(labels.max()) == 0                                            # equal distances everywhere: the first centroid
+        sums, counts = ops.kmeans_accumulate(x, lab, k)
+        assert int(counts[0]) == 300 and int(counts.sum()) == 300 and float(sums.abs().max()) == 0.0
+    else:
+        msg = r"k \* d = %d exceeds 16384" % (k * d) if k * d > 16384 else r"k = %d, d = %d" % (k, d)
+        with _refused("kmeans_assign: " + msg):
+            ops.kmeans_assign(x, c)
+        with _refused("kmeans_accumulate: " + msg):
+            ops.kmeans_accumulate(x, lab, k)
+
+
+@pytest.mark.parametrize("entry", ["upsample_bilinear_tokens", "upsample_argmax_f32", "upsample_argmax"])
+def test_upsampling_takes_65535_maps_and_refuses_more(entry):
+    """M rides on gridDim.y: 65535 maps (1 x 1 each, to 2 x 2) are each resampled, 65536 are refused by the launcher."""
+    from timetuning_amd import hip_ops as ops
+
+    fn = getattr(ops, entry)
+    dt = torch.float64 if entry == "upsample_argmax" else torch.float32
+    M, K = 65535, 1 if entry == "upsample_bilinear_tokens" else 3
+    x = torch.randn(M, 1, K, generator=torch.Generator().manual_seed(5)).to(dt).cuda()
+    out = fn(x, 2)
+    if entry == "upsample_bilinear_tokens":
+        assert torch.equal(out, x.expand(M, 4, 1))                               # one source pixel: every output pixel is its value
+    else:
+        assert torch.equal(out, x.argmax(-1).view(M, 1, 1).expand(M, 2, 2))
+    with _refused(f"{entry}: 65536 maps of 2x2 exceed one launch"):
+        fn(_z(65536, 1, K, dtype=dt), 2)
+
+
+def test_table_and_class_limits():
+    from timetuning_amd import _lib, hip_ops as ops
+
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    # TT_MAX_TENSORS = 40 per table (40 and, through the wrappers' chunks, more: the adamw cases above); 41 in one call is refused
+    tab = (_lib.AdamwTensor * 41)()
+    one = _z(4)
+    for j in range(41):
+        tab[j] = _lib.AdamwTensor(one.data_ptr(), one.data_ptr(), one.data_ptr(), one.data_ptr(), 4, 0.0, 0.0)
+    with _refused(r"adamw: need 1\.\.40 tensors"):
+        _lib.check(lib.tt_adamw_step(tab, 41, 1, 0.9, 0.999, 1e-8, st), "tt_adamw_step")
+    with _refused(r"scale_tensors: need 1\.\.40 tensors"):
+        _lib.check(lib.tt_scale_tensors(tab, 41, one.data_ptr(), st), "tt_scale_tensors")
+    with _refused("adamw: need"):
+        _lib.check(lib.tt_adamw_step(tab, 1, 0, 0.9, 0.999, 1e-8, st), "tt_adamw_step")          # step counts from 1
+    # C <= 4096 classes: 4096 counts correctly (global atomics), 4097 is refused
+    g = torch.Generator().manual_seed(6)
+    pred, gt = torch.randint(0, 4096, (20000,), generator=g), torch.randint(0, 4096, (20000,), generator=g)
+    want = torch.bincount(gt * 4096 + pred, minlength=4096 * 4096).view(4096, 4096)
+    assert torch.equal(ops.confusion_counts(pred.cuda(), gt.cuda(), 4096).cpu(), want)
+    with _refused(r"confusion_counts: need 0 < classes <= 4096 \(got 4097\)"):
+        ops.confusion_counts(pred.cuda(), gt.cuda(), 4097)
+    # 1024 feature columns for the moments (a case above); 1025 refused
+    with _refused("col_moments: need 0 < cols <= 1024"):
+        ops.col_moments(_z(3, 1025))
+
+
+def test_mask_position_and_row_op_limits():
+    from timetuning_amd import hip_ops as ops
+
+    # 1024 patches (g = 32: cases above), 33 x 33 refused; the 7-tap blur reflects over 3 pixels: g = 3 refused; head_dim <= 128, % 4
+    with _refused(r"foreground_mask_from_probs: need N = g\*g \+ 1 <= 1025 \(got N=1090 g=33\)"):
+        ops.foreground_mask_from_probs(_z(1, 2, 33 * 33 + 1), 33)
+    with _refused("foreground_mask_from_probs: blur kernel 7 needs odd size"):
+        ops.foreground_mask_from_probs(_z(1, 2, 10), 3)
+    with _refused("foreground_mask: blur kernel 7 needs odd size"):
+        ops.foreground_mask(_z(1, 10, 3 * 8), 2, 3)
+    with _refused("foreground_mask: head_dim 132 must be a multiple of 4, <= 128"):
+        ops.foreground_mask(_z(1, 17, 3 * 132), 1, 4)
+    with _refused("foreground_mask: head_dim 6 must be a multiple of 4"):
+        ops.foreground_mask(_z(1, 17, 3 * 6), 1, 4)
+    # D % 4 for the position table; 16-byte alignment for it and for the EMA; cols % 4 for the row scale; D <= 1024 for the row normalisation
+    with _refused("pos_embed_interpolate: D must be a multiple of 4"):
+        ops.pos_embed_interpolate(_z(1 + 4, 6), 3, 3)
+    with _refused("pos_embed_interpolate: D must be a multiple of 4, buffers 16-byte aligned"):
+        ops.pos_embed_interpolate(_z(1 + (1 + 4) * 4)[1:].view(1 + 4, 4), 3, 3)
+    with _refused("ema: buffers must be 16-byte aligned"):
+        ops.ema_update_(_z(9)[1:], _z(8), 0.5)
+    with _refused("scale_rows: cols must be a multiple of 4"):
+        ops.scale_rows_(_z(3, 6), _z(3))
+    with _refused("l2norm_fwd: bad arguments"):
+        ops.normalize_rows_(_z(2, 1025))
+    assert rel_err(ops.normalize_rows_(torch.full((2, 1024), 2.0, device="cuda")), torch.full((2, 1024), 2.0 / 64.0)) < TOL_F32

@@ -8,7 +8,7 @@ import itertools
 
 import pytest
 
-from _sweep_cases import PAIR_EPILOGUES, table
+from _sweep_cases import EVAL_OPS, KM_MAXKD, PAIR_EPILOGUES, STEP_OPS, case_id, km_max_k, table
 from timetuning_amd import _lib, hip_ops
 
 NCU = 256
@@ -212,3 +212,160 @@ def test_sinkhorn_persistent_grid_follows_the_knob(lib):
             assert lib.tt_sinkhorn_persistent_grid(B, K) == skp_grid(B, K), (B, K)
     finally:
         hip_ops.set_tuning_knob("TT_SK_PERSIST", 0)
+
+
+# ---- the second tier: the evaluator, optimizer and mask kernels.  Their launchers branch without a host query, so each rule is restated
+# here with the place it comes from.
+def test_second_tier_is_appended_and_complete():
+    assert STEP_OPS == ("linear_f32", "linear_pairs", "linear_planes", "bwd_pairs", "layernorm", "l2norm", "attention", "ce", "sinkhorn",
+                        "sinkhorn_from_q", "sinkhorn_local", "queue_push")
+    ops_in_order = list(dict.fromkeys(o for o, _ in CASES))
+    assert tuple(ops_in_order) == STEP_OPS + EVAL_OPS                    # appended: the first tier's draws - and case ids - are untouched
+    ids = [case_id(o, p) for o, p in CASES]
+    assert len(set(ids)) == len(ids)
+    # (the first and the last case of the first tier, as they were before the second tier existed)
+    first = [i for i, (o, _) in zip(ids, CASES) if o in STEP_OPS]
+    assert len(first) == 130 and first[0] == "linear_f32[M=1,N=64,K=20,act=0,res=0]" and first[-4] == "queue_push[Q=1,D=128,m=1]"
+
+
+def km_assign_kernel(d):                     # cluster.hip, tt_kmeans_assign: kmeans_assign_kernel<16>, <64>, <0>
+    return 16 if d <= 16 else (64 if d <= 64 else 0)
+
+
+def km_assign_strides(P):                    # tt_kmeans_assign: ceil(P / 256) workgroups, at most 4096 - then the grid-stride loop
+    return (P + 255) // 256 > 4096
+
+
+def test_kmeans_shape_rule_is_one_rule(lib):
+    # cluster.hip, km_shape_ok: k * d <= KM_MAXKD, and at d <= 64 the tile of 256 points shares the 128 KB of LDS
+    for d in list(range(1, 130)) + [255, 256, 257, 384, 1024, 16384, 16385]:
+        kmax = km_max_k(d)
+        assert (kmax == 0 or lib.tt_kmeans_shape_ok(d, kmax)) and not lib.tt_kmeans_shape_ok(d, kmax + 1), d
+    assert km_max_k(64) == 252 and km_max_k(63) == 16384 // 63 and km_max_k(65) == 252 and km_max_k(50) >= 300
+    assert not lib.tt_kmeans_shape_ok(0, 1) and not lib.tt_kmeans_shape_ok(1, 0)
+
+
+def test_kmeans_driver_refuses_before_its_first_assignment():
+    import torch
+
+    from timetuning_amd import clustering
+
+    with pytest.raises(_lib.HipLibraryError, match="k = 253 centroids of d = 64"):
+        clustering.Kmeans(64, 253)._lloyd(torch.zeros(300, 64))          # (host tensor: the refusal comes before any kernel)
+
+
+def test_kmeans_assign_every_kernel_and_the_stride_loop(lib):
+    cases = _of("kmeans_assign")
+    assert all(lib.tt_kmeans_assign_route(d) == km_assign_kernel(d) for d in range(1, 200))
+    assert all(p["k"] <= km_max_k(p["d"]) for p in cases)
+    assert {(km_assign_kernel(p["d"]), km_assign_strides(p["P"])) for p in cases} == set(itertools.product((16, 64, 0), (False, True)))
+    assert {p["d"] for p in cases} >= {1, 16, 17, 64, 65, 128, 384}
+    assert {p["P"] for p in cases} >= {1, 255, 256, 257} and any(p["k"] == 1 for p in cases)
+    assert any(p["P"] % 256 and not km_assign_strides(p["P"]) for p in cases) and any(p["P"] % 256 and km_assign_strides(p["P"]) for p in cases)
+    # the largest k * d on each kernel; the duplicated centroid on each kernel
+    for kern in (16, 64, 0):
+        assert any(km_assign_kernel(p["d"]) == kern and p["k"] == km_max_k(p["d"]) for p in cases), kern
+        assert any(km_assign_kernel(p["d"]) == kern and p["dup"] for p in cases), kern
+    assert any(p["k"] * p["d"] == KM_MAXKD for p in cases)
+
+
+def km_accumulate_grid(P):                   # cluster.hip, accumulate_blocks: (workgroups, points per workgroup, workgroups with no points)
+    b = min(4096, max(1, (P + 127) // 128))
+    ppb = (P + b - 1) // b
+    return b, ppb, b - (P + ppb - 1) // ppb
+
+
+def test_kmeans_accumulate_every_regime():
+    cases = _of("kmeans_accumulate")
+    grids = [km_accumulate_grid(p["P"]) for p in cases]
+    assert any(b < 4096 for b, _, _ in grids) and any(b == 4096 and ppb == 128 for b, ppb, _ in grids)       # under and AT the cap
+    assert any(ppb > 128 for _, ppb, _ in grids) and any(e > 0 for _, _, e in grids)                      # long fp32 sums; empty workgroups
+    assert all(e == 0 for b, _, e in grids if b < 4096)             # (under the cap no workgroup is ever empty)
+    assert {p["mode"] for p in cases} == {"rand", "skip", "one"}
+    assert any(p["mode"] == "one" and km_accumulate_grid(p["P"])[1] > 128 for p in cases)                    # the longest sums of all
+    assert any(p["d"] > 256 for p in cases) and any(p["d"] == 1 for p in cases)                              # a thread owns two columns / one
+    assert any(p["k"] * p["d"] == KM_MAXKD for p in cases) and any(p["k"] == KM_MAXKD for p in cases)
+    assert all(p["k"] <= km_max_k(p["d"]) for p in cases)
+
+
+def test_col_moments_under_at_and_over_the_cap():
+    cases = _of("col_moments")
+    blocks = lambda rows: (rows + 255) // 256                        # cluster.hip, moments_blocks: at most 1024 workgroups
+    assert any(blocks(p["rows"]) < 1024 for p in cases) and any(blocks(p["rows"]) == 1024 for p in cases)
+    assert any(blocks(p["rows"]) > 1024 for p in cases)
+    assert any(p["rows"] == 1 for p in cases) and any(p["cols"] == 1 for p in cases) and any(p["cols"] == 1024 for p in cases)
+    assert any(p["cols"] > 256 for p in cases)                        # a thread owns more than one column
+    assert {p["kind"] for p in cases} == {"scaled", "const_col", "offset"}
+    assert any(p["kind"] == "offset" and blocks(p["rows"]) >= 1024 for p in cases)
+
+
+def test_upsampling_every_ratio_and_workgroup_size():
+    threads = lambda C: 256 if C >= 256 else (128 if C > 64 else 64)   # cluster.hip, tt_upsample_bilinear_tokens
+    for op, key in (("upsample_tokens", "C"), ("upsample_argmax_f32", "K"), ("upsample_argmax", "K")):
+        cases = _of(op)
+        assert any(p["R"] < p["g"] for p in cases) and any(p["R"] == p["g"] for p in cases) and any(p["R"] > p["g"] for p in cases), op
+        assert any(p["g"] == 1 for p in cases) and any(p["R"] == 1 for p in cases), op
+        assert any(p["R"] > p["g"] and p["R"] % p["g"] for p in cases), op                  # a ragged ratio
+        assert {p[key] for p in cases} >= {1, 64, 65, 255, 256, 300}, op
+        assert any(p["M"] > NCU for p in cases) and any(p["R"] * p["R"] > 256 for p in cases), op   # gridDim.y; more than one workgroup of pixels
+    assert {threads(p["C"]) for p in _of("upsample_tokens")} == {64, 128, 256}
+    assert {p["C"] for p in _of("upsample_tokens")} >= {64, 65, 255, 256}                        # either side of both edges
+
+
+def test_confusion_counts_both_kernels_and_the_cap():
+    cases = _of("confusion_counts")
+    blocks = lambda n: (n + 4095) // 4096                             # label_prop.hip, tt_confusion_counts: at most 2048 workgroups
+    for lds in (True, False):                                         # ... the LDS histogram up to C = 96, global atomics beyond
+        sel = [p for p in cases if (p["C"] <= 96) == lds]
+        assert any(blocks(p["n"]) < 2048 for p in sel) and any(blocks(p["n"]) > 2048 for p in sel), lds
+        assert any(p["stray"] for p in sel)
+    assert any(blocks(p["n"]) == 2048 for p in cases)
+    assert {p["C"] for p in cases} >= {1, 96, 97, 300} and any(p["n"] == 1 for p in cases)
+    assert any(p["stray"] and p["C"] > 255 for p in cases) and any(p["stray"] and p["C"] <= 255 for p in cases)    # 255 a class / ignored
+
+
+def test_adamw_tables_chunks_and_grids():
+    from _sweep_checks_eval import adamw_lengths
+
+    cases = _of("adamw")
+    cap = 40                                                           # include/timetuning_hip.h: TT_MAX_TENSORS
+    for fused in (0, 1):                                              # hip_ops.adamw_step_ / scale_tensors_ chunk; pipeline.cpp chunks the fused entry
+        counts = {min(2, (p["T"] + fused - 1) // cap) for p in cases if p["fused"] == fused}
+        assert counts == {0, 1, 2} or counts == {0, 2}, (fused, counts)
+    assert {p["T"] for p in cases} >= {1, 40, 41}
+    assert {p["step"] for p in cases} >= {1, 100000}
+    # rowops.hip, tt_adamw_step: the grid is sized by the LONGEST tensor, at most 1024 workgroups of 256; a length-1 tensor rides along
+    grid = lambda p: (max(adamw_lengths(p["T"], p["big"])) + 255) // 256
+    assert any(grid(p) > 1024 and 1 in adamw_lengths(p["T"], p["big"]) and adamw_lengths(p["T"], p["big"])[0] == 1 for p in cases)
+    assert any(grid(p) == 1024 for p in cases) and any(grid(p) < 1024 for p in cases) and any(grid(p) == 1 for p in cases)
+    assert any({1, 255, 257} <= set(adamw_lengths(p["T"], p["big"])) for p in cases)
+    assert len({p["gscale"] for p in cases}) >= 3
+
+
+def test_elementwise_every_tail_and_cap():
+    cases = _of("elementwise")
+    ns = {p["n"] for p in cases}
+    assert {1, 2, 3, 4, 5, 6, 7} <= ns and {n & 3 for n in ns if n > 100000} == {0, 1, 2, 3}
+    # rowops.hip: tt_ema_update ceil(n / 4 / 256) workgroups up to 2048; tt_add_inplace ceil(n / 256) up to 4096; tt_count_mismatch up to 2048
+    for per_wg, cap in ((1024, 2048), (256, 4096), (256, 2048)):
+        wgs = lambda n: (n // 4 + 255) // 256 if per_wg == 1024 else (n + 255) // 256
+        assert any(wgs(n) < cap for n in ns) and any(wgs(n) == cap for n in ns) and any(wgs(n) > cap for n in ns), (per_wg, cap)
+    assert any(n > 2048 * 1024 and n & 3 for n in ns)                 # the tail behind a strided body
+    chunks = lambda M: (M + 255) // 256                               # rowops.hip, colsum_chunks: at most 128
+    assert any(chunks(p["rows"]) < 128 for p in cases) and any(chunks(p["rows"]) == 128 for p in cases) and any(chunks(p["rows"]) > 128 for p in cases)
+    assert any(p["cols"] % 64 for p in cases) and any(p["cols"] == 1024 for p in cases) and any(p["rows"] % 4 for p in cases)
+
+
+def test_foreground_mask_and_pos_embed_edges():
+    fm = _of("foreground_mask")
+    for entry in ("qkv", "probs"):
+        sel = [p for p in fm if p["entry"] == entry]
+        assert {p["g"] for p in sel} >= {4, 5, 13, 14, 31, 32} and {p["th"] for p in sel} == {0.3, 0.65, 0.8}, entry
+        assert {p["H"] for p in sel} >= {1, 3, 6, 12} and any(p["F"] == 1 for p in sel) and any(p["F"] > NCU for p in sel), entry
+    assert {p["hd"] for p in fm if p["entry"] == "qkv"} >= {4, 64, 128}
+    assert all(p["g"] * p["g"] <= 1024 and 7 // 2 < p["g"] for p in fm)          # attn_mask.hip, launch_foreground_mask
+    pe = _of("pos_embed")
+    assert {p["g"] for p in pe} == {14, 28} and {p["D"] for p in pe} >= {4, 384, 768}
+    assert any(p["gh"] == 1 for p in pe) and any(p["gw"] == 1 for p in pe) and all((p["gh"], p["gw"]) != (p["g"], p["g"]) for p in pe)
+    assert any(p["gh"] < p["g"] and p["gw"] < p["g"] for p in pe) and any(p["gh"] > p["g"] and p["gw"] > p["g"] for p in pe)
+    assert any((p["gh"] > p["g"]) != (p["gw"] > p["g"]) for p in pe) and any(p["gh"] != p["gw"] for p in pe)

@@ -130,6 +130,9 @@ class Kmeans:
         """The redos of Lloyd iterations on the (subsampled) training points x [n, d]."""
         n, d = x.shape
         k = self.k
+        if not ops.kmeans_shape_ok(d, k):   # refused here, not after the first assignment: both kernels share this rule
+            raise ops._lib.HipLibraryError(f"Kmeans: k = {k} centroids of d = {d} columns are beyond what the k-means kernels hold in LDS "
+                                       "(k * d <= 16384; at d = 64, k <= 252)")
         best_obj, best = float("inf"), None
         self.obj = []
         for redo in range(self.nredo):

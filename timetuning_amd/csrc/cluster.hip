@@ -18,16 +18,32 @@ constexpr int CL_THREADS = 256;
 constexpr int CL_MAXD = 1024;     // feature columns for the moments
 constexpr int KM_MAXKD = 16384;   // k * d floats of centroids held in LDS (64 KB; k = 300 at d = 50 for the CBFE over-clustering)
 constexpr size_t KM_MAX_LDS = 128 * 1024;   // dynamic LDS a k-means workgroup may ask for (the attribute raised below)
+constexpr int UP_MAXM = 65535;    // maps of one up-sampling launch (they ride on gridDim.y)
 
-// ---- column moments: partial[b][0][c] = sum_r x[r][c], partial[b][1][c] = sum_r x[r][c]^2 over the block's rows (fp64)
+// The (d, k) BOTH k-means entries take - clustering.Kmeans calls one after the other, so they share the rule (tt_kmeans_shape_ok):
+//   k * d <= KM_MAXKD floats of centroids (the assignment's LDS copy; the accumulation's sums, plus k counts: at most 128 KB at d = 1);
+//   d <= 64: the assignment's tile of 256 points (row stride d | 1) shares the LDS - k * d + 256 (d | 1) floats <= 128 KB.  That binds
+//   at d = 64 only: the tile takes 65 KB, which leaves 63 KB of centroids, k <= 252.
+// tt_kmeans_assign's kernel by d: 16 / 64 = the point's row in that many registers (tile in LDS), 0 = wider rows read in place
+static int km_assign_route(int d) { return d <= 16 ? 16 : (d <= 64 ? 64 : 0); }
+static size_t km_assign_lds(int d, int k) {
+  return sizeof(float) * ((size_t)k * d + (km_assign_route(d) ? (size_t)CL_THREADS * (d | 1) : 0));
+}
+static bool km_shape_ok(int d, int k) { return d > 0 && k > 0 && (long long)k * d <= KM_MAXKD && km_assign_lds(d, k) <= KM_MAX_LDS; }
+
+// ---- column moments: partial[b][0][c] = sum_r v, partial[b][1][c] = sum_r v^2 over the block's rows (fp64), v = x[r][c] - x[0][c].
+// The sums are taken about the column's first row: E[v^2] - E[v]^2 on the raw values subtracts two numbers of size mean^2 and loses a
+// small variance beside a large mean even in fp64 (mean 1e4, spread 1e-2 over 262 144 rows: the variance came out 10 % off).  The
+// difference of two floats is exact in fp64, so the shift costs nothing.
 __global__ __launch_bounds__(CL_THREADS) void col_moments_stage1(const float* __restrict__ x, double* __restrict__ partial, long long rows,
                                                                  int cols, long long rows_per_block) {
   const long long r0 = (long long)blockIdx.x * rows_per_block;
   const long long r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
   for (int c = threadIdx.x; c < cols; c += CL_THREADS) {
+    const double shift = (double)x[c];
     double s = 0.0, s2 = 0.0;
     for (long long r = r0; r < r1; ++r) {
-      const double v = (double)x[r * cols + c];
+      const double v = (double)x[r * cols + c] - shift;
       s += v;
       s2 += v * v;
     }
@@ -36,8 +52,9 @@ __global__ __launch_bounds__(CL_THREADS) void col_moments_stage1(const float* __
   }
 }
 
-__global__ __launch_bounds__(CL_THREADS) void col_moments_stage2(const double* __restrict__ partial, double* __restrict__ mean,
-                                                                 double* __restrict__ var, long long rows, int cols, int blocks) {
+__global__ __launch_bounds__(CL_THREADS) void col_moments_stage2(const float* __restrict__ x, const double* __restrict__ partial,
+                                                                 double* __restrict__ mean, double* __restrict__ var, long long rows, int cols,
+                                                                 int blocks) {
   const int c = blockIdx.x * CL_THREADS + threadIdx.x;
   if (c >= cols) return;
   double s = 0.0, s2 = 0.0;
@@ -45,8 +62,8 @@ __global__ __launch_bounds__(CL_THREADS) void col_moments_stage2(const double* _
     s += partial[((long long)b * 2 + 0) * cols + c];
     s2 += partial[((long long)b * 2 + 1) * cols + c];
   }
-  const double m = s / (double)rows;
-  mean[c] = m;
+  const double m = s / (double)rows;   // the mean of the shifted values
+  mean[c] = (double)x[c] + m;
   const double v = s2 / (double)rows - m * m;   // population variance, as StandardScaler (ddof = 0)
   var[c] = v > 0.0 ? v : 0.0;
 }
@@ -166,7 +183,7 @@ __global__ __launch_bounds__(CL_THREADS) void kmeans_assign_kernel(const float* 
   }
 }
 
-// ---- k-means accumulation: per-block sums[k][d] (fp32 in LDS over <= rows_per_block points, then fp64 partials)
+// ---- k-means accumulation: per-block sums[k][d] (fp32 in LDS over the block's pts_per_block points, then fp64 partials)
 __global__ __launch_bounds__(CL_THREADS) void kmeans_accumulate_stage1(const float* __restrict__ x, const int32_t* __restrict__ labels,
                                                                        double* __restrict__ part_sums, long long* __restrict__ part_cnt,
                                                                        long long P, int d, int k, long long pts_per_block) {
@@ -217,7 +234,9 @@ static int moments_blocks(long long rows) {
   return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
 }
 static int accumulate_blocks(long long P) {
-  long long b = (P + 127) / 128;  // <= 128 points per block keeps the fp32 LDS sums short
+  // 128 points per block keep the fp32 LDS sums short - up to 4096 blocks: beyond P = 524 288 a block takes ceil(P / 4096) points
+  // (269 at the 1.1 M points of the CBFE over-clustering; the sums stay within the fp32 class there: the sweep holds them to 1e-5)
+  long long b = (P + 127) / 128;
   return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
 }
 
@@ -238,14 +257,15 @@ extern "C" int tt_col_moments(const float* x, double* mean, double* var, long lo
   const long long rpb = (rows + blocks - 1) / blocks;
   double* partial = static_cast<double*>(workspace);
   hipLaunchKernelGGL(col_moments_stage1, dim3(blocks), dim3(CL_THREADS), 0, s, x, partial, rows, cols, rpb);
-  hipLaunchKernelGGL(col_moments_stage2, dim3((cols + CL_THREADS - 1) / CL_THREADS), dim3(CL_THREADS), 0, s, partial, mean, var, rows, cols,
-                     blocks);
+  hipLaunchKernelGGL(col_moments_stage2, dim3((cols + CL_THREADS - 1) / CL_THREADS), dim3(CL_THREADS), 0, s, x, partial, mean, var, rows,
+                     cols, blocks);
   TT_CHECK_LAUNCH("col_moments");
   return TT_OK;
 }
 
 extern "C" int tt_upsample_bilinear_tokens(const float* x, float* out, int M, int g, int C, int R, tt_stream_t stream) {
   TT_REQUIRE(x && out && M > 0 && g > 0 && C > 0 && R > 0, "upsample_bilinear_tokens: bad arguments");
+  TT_REQUIRE(M <= UP_MAXM && R <= 32768, "upsample_bilinear_tokens: %d maps of %dx%d exceed one launch (at most %d maps)", M, R, R, UP_MAXM);
   const int threads = C >= 256 ? 256 : (C > 64 ? 128 : 64);
   hipLaunchKernelGGL(upsample_tokens_kernel, dim3(R * R, M), dim3(threads), 0, as_stream(stream), x, out, g, C, R);
   TT_CHECK_LAUNCH("upsample_bilinear_tokens");
@@ -254,6 +274,7 @@ extern "C" int tt_upsample_bilinear_tokens(const float* x, float* out, int M, in
 
 extern "C" int tt_upsample_argmax_f32(const float* maps, int64_t* labels_out, int M, int g, int K, int R, tt_stream_t stream) {
   TT_REQUIRE(maps && labels_out && M > 0 && g > 0 && K > 0 && R > 0, "upsample_argmax_f32: bad arguments");
+  TT_REQUIRE(M <= UP_MAXM && R <= 32768, "upsample_argmax_f32: %d maps of %dx%d exceed one launch (at most %d maps)", M, R, R, UP_MAXM);
   hipLaunchKernelGGL(upsample_argmax_f32_kernel, dim3((R * R + CL_THREADS - 1) / CL_THREADS, M), dim3(CL_THREADS), 0, as_stream(stream), maps,
                      labels_out, g, K, R);
   TT_CHECK_LAUNCH("upsample_argmax_f32");
@@ -263,10 +284,10 @@ extern "C" int tt_upsample_argmax_f32(const float* maps, int64_t* labels_out, in
 extern "C" int tt_kmeans_assign(const float* x, const float* centroids, int32_t* labels, float* dist2, long long P, int d, int k,
                                 tt_stream_t stream) {
   TT_REQUIRE(x && centroids && labels && P > 0 && d > 0 && k > 0, "kmeans_assign: bad arguments");
-  TT_REQUIRE((long long)k * d <= KM_MAXKD, "kmeans_assign: k * d = %d exceeds %d", k * d, KM_MAXKD);
-  const size_t lds = sizeof(float) * ((size_t)k * d + (d <= 64 ? (size_t)CL_THREADS * (d | 1) : 0));
-  TT_REQUIRE(lds <= KM_MAX_LDS, "kmeans_assign: k = %d, d = %d need %zu bytes of LDS (at most %zu)", k, d, lds, KM_MAX_LDS);
-  static const bool lds_attr_set = [] {  // centroids (up to 64 KB) + the d <= 64 tile's points (up to 65 KB)
+  TT_REQUIRE((long long)k * d <= KM_MAXKD, "kmeans_assign: k * d = %lld exceeds %d", (long long)k * d, KM_MAXKD);
+  const size_t lds = km_assign_lds(d, k);
+  TT_REQUIRE(km_shape_ok(d, k), "kmeans_assign: k = %d, d = %d need %zu bytes of LDS (at most %zu)", k, d, lds, KM_MAX_LDS);
+  static const bool lds_attr_set = [] {  // the centroids and the d <= 64 tile's points, 128 KB together (km_shape_ok)
     bool ok = true;
     for (const void* f : {reinterpret_cast<const void*>(&kmeans_assign_kernel<16>), reinterpret_cast<const void*>(&kmeans_assign_kernel<64>),
                           reinterpret_cast<const void*>(&kmeans_assign_kernel<0>)})
@@ -277,15 +298,19 @@ extern "C" int tt_kmeans_assign(const float* x, const float* centroids, int32_t*
   long long blocks = (P + CL_THREADS - 1) / CL_THREADS;
   blocks = blocks > 4096 ? 4096 : blocks;
   hipStream_t s = as_stream(stream);
-  if (d <= 16)
+  const int route = km_assign_route(d);
+  if (route == 16)
     hipLaunchKernelGGL((kmeans_assign_kernel<16>), dim3((unsigned)blocks), dim3(CL_THREADS), lds, s, x, centroids, labels, dist2, P, d, k);
-  else if (d <= 64)
+  else if (route == 64)
     hipLaunchKernelGGL((kmeans_assign_kernel<64>), dim3((unsigned)blocks), dim3(CL_THREADS), lds, s, x, centroids, labels, dist2, P, d, k);
   else
     hipLaunchKernelGGL((kmeans_assign_kernel<0>), dim3((unsigned)blocks), dim3(CL_THREADS), lds, s, x, centroids, labels, dist2, P, d, k);
   TT_CHECK_LAUNCH("kmeans_assign");
   return TT_OK;
 }
+
+extern "C" int tt_kmeans_shape_ok(int d, int k) { return km_shape_ok(d, k) ? 1 : 0; }
+extern "C" int tt_kmeans_assign_route(int d) { return km_assign_route(d); }
 
 extern "C" size_t tt_kmeans_accumulate_workspace_bytes(long long P, int d, int k) {
   return (size_t)accumulate_blocks(P) * ((size_t)k * d * sizeof(double) + (size_t)k * sizeof(long long));
@@ -294,7 +319,9 @@ extern "C" size_t tt_kmeans_accumulate_workspace_bytes(long long P, int d, int k
 extern "C" int tt_kmeans_accumulate(const float* x, const int32_t* labels, double* sums, long long* counts, long long P, int d, int k,
                                     void* workspace, size_t workspace_bytes, tt_stream_t stream) {
   TT_REQUIRE(x && labels && sums && counts && workspace && P > 0 && d > 0 && k > 0, "kmeans_accumulate: bad arguments");
-  TT_REQUIRE((long long)k * d + k <= KM_MAXKD, "kmeans_accumulate: k * d = %d exceeds %d", k * d, KM_MAXKD);
+  TT_REQUIRE((long long)k * d <= KM_MAXKD, "kmeans_accumulate: k * d = %lld exceeds %d", (long long)k * d, KM_MAXKD);
+  TT_REQUIRE(km_shape_ok(d, k), "kmeans_accumulate: k = %d, d = %d is beyond what kmeans_assign takes (%zu bytes of LDS, at most %zu)", k, d,
+             km_assign_lds(d, k), KM_MAX_LDS);
   TT_REQUIRE(workspace_bytes >= tt_kmeans_accumulate_workspace_bytes(P, d, k), "kmeans_accumulate: workspace too small");
   static const bool lds_attr_set = hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_accumulate_stage1),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_MAX_LDS) == hipSuccess;

@@ -814,6 +814,7 @@ __global__ __launch_bounds__(256) void confusion_global_kernel(const int64_t* __
 
 extern "C" int tt_upsample_argmax(const double* maps, int64_t* labels_out, int M, int g, int K, int R, tt_stream_t stream) {
   TT_REQUIRE(maps && labels_out && M > 0 && g > 0 && K > 0 && R > 0, "upsample_argmax: bad arguments");
+  TT_REQUIRE(M <= 65535 && R <= 32768, "upsample_argmax: %d maps of %dx%d exceed one launch (at most 65535 maps)", M, R, R);
   hipLaunchKernelGGL(upsample_argmax_kernel, dim3((R * R + 255) / 256, M), dim3(256), 0, as_stream(stream), maps, labels_out, g, K, R);
   TT_CHECK_LAUNCH("upsample_argmax");
   return TT_OK;

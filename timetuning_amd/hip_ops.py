@@ -869,6 +869,11 @@ def upsample_argmax_f32(maps, resolution: int):
     return out
 
 
+def kmeans_shape_ok(d: int, k: int) -> bool:
+    """Whether ``kmeans_assign`` and ``kmeans_accumulate`` take k centroids of d columns (one rule for both: tt_kmeans_shape_ok)."""
+    return bool(_lib.load().tt_kmeans_shape_ok(int(d), int(k)))
+
+
 def kmeans_assign(x, centroids, return_dist=False):
     """x [P, d], centroids [k, d] -> labels int32 [P] (+ squared distances)."""
     lib = _lib.load()
