@@ -385,7 +385,19 @@ size_t tt_linear_bwd_weight_planes_workspace_bytes(int N, int K, int Mpad);
  *   seg0 [bs, n, K] fp32 Sinkhorn assignment of frame 0 (the seed labels)
  *   labels [bs, n] int64 = argmax_K of the propagated map of the LAST frame
  *   pmap_last [bs, n, K] fp64 optional (the map itself).
- *   workspace: tt_label_propagate_workspace_bytes(...). */
+ *   workspace: tt_label_propagate_workspace_bytes(...).
+ * Accepted domain of the square entries (tt_label_propagate, _sims, _from_sims, _maps) - anything else is refused before a launch:
+ *   fs >= 2, g, D, K, topk >= 1;  D % 4 == 0;  0 <= n_last_frames <= 7;  radius > 0 (the unrestricted variant is the grid entry's);
+ *   win^2 * contexts <= 4096 candidates per query, win = min(2 * radius + 1, g), contexts = 1 + min(fs - 2, n_last_frames);
+ *   bs <= 65535.  The per-query wave kernels (win <= 16, g * g <= 4096, K <= 512) put no bound on bs themselves, but every route
+ *   computes its similarities with one batched product of bs x chunk problems on gridDim.y - the chunk of target frames is shortened so
+ *   that bs * chunk <= 65535 - and the workgroup-per-query kernels carry bs on gridDim.y too: both limits are checked, each with a
+ *   message of its own.  topk may exceed the candidates of a query (everything is then kept).
+ * tt_label_propagate_route: the per-query kernel target frame t (1 <= t < fs) of such a call runs - 0 = the shape or the frame is
+ *   refused, 1..4 = the wave kernel for <= 3 contexts and K <= 256, <= 3 and K <= 512, <= 8 and K <= 256, <= 8 and K <= 512 (contexts
+ *   of THAT frame: 1 + min(t - 1, n_last_frames)), 5 / 6 = the workgroup kernel for <= 2048 / <= 4096 candidates.  Host only; the
+ *   launcher dispatches on this value. */
+int tt_label_propagate_route(int fs, int g, int K, int n_last_frames, int radius, int t);
 int tt_label_propagate(const float* xn, const float* seg0, int64_t* labels, double* pmap_last, int bs, int fs, int g,
                        int D, int K, int n_last_frames, int radius, int topk, float temperature, int precision, void* workspace,
                        size_t workspace_bytes, tt_stream_t stream);
@@ -426,7 +438,8 @@ int tt_confusion_counts(const int64_t* pred, const int64_t* gt, long long n, int
  *                                 [bs, n, K], pmap_all [fs-1, bs, n, K] fp64.  The window is restrict_neighborhood(gh, gw, radius)
  *                                 (mask_propagation.py:377-391), clipped at the row and the column edges separately; radius 0 is the
  *                                 unrestricted variant (no mask: the top-k over all ctx * n sources).  No cap on the candidates of a
- *                                 query; n_last_frames <= 7.  Workspace: tt_label_propagate_grid_workspace_bytes(...), the
+ *                                 query; n_last_frames <= 7, radius >= 0, D % 4 == 0, bs <= 65535 (clips ride on gridDim.y; the chunk of
+ *                                 target frames is shortened so that bs * chunk <= 65535, as on the square entries).  Workspace: tt_label_propagate_grid_workspace_bytes(...), the
  *                                 [ctx, n, n] fp32 similarities of each target frame held at once (as tt_label_propagate_maps'; about
  *                                 0.8 GB per target frame at 60 x 106 tokens with n_last_frames 4).
  *   tt_upsample_argmax_hw         tt_upsample_argmax for a gh x gw grid and an H x W output: maps [M, gh*gw, K] fp64 -> labels_out

@@ -286,27 +286,31 @@ int tt_cpu_confusion_counts(const int64_t* pred, const int64_t* gt, long long n,
 }
 
 /* ---- mask_propagation.py:828-829: F.interpolate(bilinear, align_corners=False) of fp64 maps [M, n, K] then arg-max over K */
-int tt_cpu_upsample_argmax(const double* maps, int64_t* labels_out, int M, int g, int K, int R, tt_stream_t stream) {
+int tt_cpu_upsample_argmax_hw(const double* maps, int64_t* labels_out, int M, int gh, int gw, int K, int H, int W, tt_stream_t stream) {
   (void)stream;
-  const double scale = (double)g / (double)R;
+  /* area_pixel_compute_scale, align_corners = False: input / output size per dimension */
   for (int m = 0; m < M; ++m)
-    for (int oy = 0; oy < R; ++oy)
-      for (int ox = 0; ox < R; ++ox) {
-        double sy = scale * (oy + 0.5) - 0.5, sx = scale * (ox + 0.5) - 0.5;
+    for (int oy = 0; oy < H; ++oy)
+      for (int ox = 0; ox < W; ++ox) {
+        double sy = (double)gh / (double)H * (oy + 0.5) - 0.5, sx = (double)gw / (double)W * (ox + 0.5) - 0.5;
         sy = sy < 0 ? 0 : sy; sx = sx < 0 ? 0 : sx;
-        const int y0 = (int)sy, x0 = (int)sx, y1 = y0 + (y0 < g - 1), x1 = x0 + (x0 < g - 1);
+        const int y0 = (int)sy, x0 = (int)sx, y1 = y0 + (y0 < gh - 1), x1 = x0 + (x0 < gw - 1);
         const double ly = sy - y0, lx = sx - x0, hy = 1.0 - ly, hx = 1.0 - lx;
-        const double* b = maps + (size_t)m * g * g * K;
+        const double* b = maps + (size_t)m * gh * gw * K;
         double best = -INFINITY;
         int besti = 0;
         for (int k = 0; k < K; ++k) {
-          const double v = hy * (hx * b[(size_t)(y0 * g + x0) * K + k] + lx * b[(size_t)(y0 * g + x1) * K + k]) +
-                           ly * (hx * b[(size_t)(y1 * g + x0) * K + k] + lx * b[(size_t)(y1 * g + x1) * K + k]);
+          const double v = hy * (hx * b[(size_t)(y0 * gw + x0) * K + k] + lx * b[(size_t)(y0 * gw + x1) * K + k]) +
+                           ly * (hx * b[(size_t)(y1 * gw + x0) * K + k] + lx * b[(size_t)(y1 * gw + x1) * K + k]);
           if (v > best) { best = v; besti = k; }
         }
-        labels_out[((size_t)m * R + oy) * R + ox] = besti;
+        labels_out[((size_t)m * H + oy) * W + ox] = besti;
       }
   return 0;
+}
+/* (the square entry: one scale g / R for rows and columns - the same doubles as gh = gw = g, H = W = R) */
+int tt_cpu_upsample_argmax(const double* maps, int64_t* labels_out, int M, int g, int K, int R, tt_stream_t stream) {
+  return tt_cpu_upsample_argmax_hw(maps, labels_out, M, g, g, K, R, R, stream);
 }
 
 /* ---- Lloyd assignment step of the k-means the reference delegates to faiss (clustering.py:39-41): nearest centroid, first minimum */
@@ -1618,12 +1622,14 @@ int tt_cpu_foreground_mask(const float* qkv, float* mask_out, float* blurred_out
  *      exp(<f_t(q), f_ctx(p)> / temperature) in fp32 (:418-422) inside the |dy|, |dx| <= radius window (:424-429), per query keep
  *      the top-k sources over all contexts - everything >= the k-th largest, ties kept (:432-434) -, column-normalise in fp32
  *      (:436), and the target map is the fp64 product of the context maps with it (:442-444). */
-static int lp_cpu(const float* xn, const float* seg0, int64_t* labels, double* pmap_last, double* pmap_all, int bs, int fs, int g, int D, int K,
-                  int n_last, int radius, int topk, float temperature) {
-  const int n = g * g;
+static int lp_cpu(const float* xn, const float* seg0, int64_t* labels, double* pmap_last, double* pmap_all, int bs, int fs, int gh, int gw, int D,
+                  int K, int n_last, int radius, int topk, float temperature) {
+  /* gh x gw grid (the square entries: gh = gw = g); radius 0 = no window (the grid entry's unrestricted variant) */
+  const int n = gh * gw;
+  if (radius <= 0 || radius > (gh > gw ? gh : gw)) radius = gh > gw ? gh : gw;
   const size_t fstride = (size_t)bs * n * K;
   double* segs = pmap_all ? pmap_all : (double*)malloc((size_t)(fs - 1) * fstride * sizeof(double));
-  const int cmax = 1 + n_last, win = (2 * radius + 1) * (2 * radius + 1);
+  const int cmax = 1 + n_last, wh = 2 * radius + 1 < gh ? 2 * radius + 1 : gh, ww = 2 * radius + 1 < gw ? 2 * radius + 1 : gw, win = wh * ww;
   float* aff = (float*)malloc((size_t)cmax * win * sizeof(float));
   int* src = (int*)malloc((size_t)cmax * win * sizeof(int));
   float* topv = (float*)malloc((size_t)topk * sizeof(float));
@@ -1634,17 +1640,17 @@ static int lp_cpu(const float* xn, const float* seg0, int64_t* labels, double* p
     for (int fr = (t - n_last > 1 ? t - n_last : 1); fr < t; ++fr) ctx[c++] = fr;
     for (int b = 0; b < bs; ++b)
       for (int q = 0; q < n; ++q) {
-        const int qy = q / g, qx = q % g;
+        const int qy = q / gw, qx = q % gw;
         const float* ft = xn + (((size_t)t * bs + b) * n + q) * D;
         int cnt = 0;
         for (int j = 0; j < c; ++j)
-          for (int sy = (qy - radius < 0 ? 0 : qy - radius); sy <= (qy + radius > g - 1 ? g - 1 : qy + radius); ++sy)
-            for (int sx = (qx - radius < 0 ? 0 : qx - radius); sx <= (qx + radius > g - 1 ? g - 1 : qx + radius); ++sx) {
-              const float* fsrc = xn + (((size_t)ctx[j] * bs + b) * n + sy * g + sx) * D;
+          for (int sy = (qy - radius < 0 ? 0 : qy - radius); sy <= (qy + radius > gh - 1 ? gh - 1 : qy + radius); ++sy)
+            for (int sx = (qx - radius < 0 ? 0 : qx - radius); sx <= (qx + radius > gw - 1 ? gw - 1 : qx + radius); ++sx) {
+              const float* fsrc = xn + (((size_t)ctx[j] * bs + b) * n + sy * gw + sx) * D;
               float dot = 0.f;
               for (int d = 0; d < D; ++d) dot += ft[d] * fsrc[d];
               aff[cnt] = expf(dot / temperature);
-              src[cnt++] = j * n + sy * g + sx;
+              src[cnt++] = j * n + sy * gw + sx;
             }
         /* k-th largest with multiplicity (sources outside the window have affinity 0 < every exp) */
         int nt = 0;
@@ -1683,7 +1689,7 @@ int tt_cpu_label_propagate(const float* xn, const float* seg0, int64_t* labels, 
                            int n_last_frames, int radius, int topk, float temperature, int precision, void* workspace, size_t workspace_bytes,
                            tt_stream_t stream) {
   (void)precision;
-  return lp_cpu(xn, seg0, labels, pmap_last, NULL, bs, fs, g, D, K, n_last_frames, radius, topk, temperature);
+  return lp_cpu(xn, seg0, labels, pmap_last, NULL, bs, fs, g, g, D, K, n_last_frames, radius, topk, temperature);
 }
 /* (the two-call form: the twin keeps no similarities - the first half is a no-op, the second the whole propagation) */
 int tt_cpu_label_propagate_sims(const float* xn, int bs, int fs, int g, int D, int K, int n_last_frames, int precision, void* workspace,
@@ -1694,11 +1700,20 @@ int tt_cpu_label_propagate_sims(const float* xn, int bs, int fs, int g, int D, i
 int tt_cpu_label_propagate_from_sims(const float* xn, const float* seg0, int64_t* labels, double* pmap_last, int bs, int fs, int g, int D, int K,
                                      int n_last_frames, int radius, int topk, float temperature, void* workspace, size_t workspace_bytes,
                                      tt_stream_t stream) {
-  return lp_cpu(xn, seg0, labels, pmap_last, NULL, bs, fs, g, D, K, n_last_frames, radius, topk, temperature);
+  return lp_cpu(xn, seg0, labels, pmap_last, NULL, bs, fs, g, g, D, K, n_last_frames, radius, topk, temperature);
 }
 int tt_cpu_label_propagate_maps(const float* xn, const float* seg0, double* pmap_all, int bs, int fs, int g, int D, int K, int n_last_frames,
                                 int radius, int topk, float temperature, int precision, void* workspace, size_t workspace_bytes,
                                 tt_stream_t stream) {
   (void)precision;
-  return lp_cpu(xn, seg0, NULL, NULL, pmap_all, bs, fs, g, D, K, n_last_frames, radius, topk, temperature);
+  return lp_cpu(xn, seg0, NULL, NULL, pmap_all, bs, fs, g, g, D, K, n_last_frames, radius, topk, temperature);
+}
+/* N9: the same on a gh x gw grid, radius 0 = no window, no cap on the candidates of a query */
+size_t tt_cpu_label_propagate_grid_workspace_bytes(int bs, int fs, int gh, int gw, int D, int K, int n_last_frames, int radius) { return 0; }
+int tt_cpu_label_propagate_grid_maps(const float* xn, const float* seg0, double* pmap_all, int bs, int fs, int gh, int gw, int D, int K,
+                                     int n_last_frames, int radius, int topk, float temperature, int precision, void* workspace,
+                                     size_t workspace_bytes, tt_stream_t stream) {
+  (void)precision; (void)workspace; (void)workspace_bytes; (void)stream;
+  if (radius < 0) return -1;
+  return lp_cpu(xn, seg0, NULL, NULL, pmap_all, bs, fs, gh, gw, D, K, n_last_frames, radius, topk, temperature);
 }

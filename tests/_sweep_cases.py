@@ -157,6 +157,61 @@ def _pos_embed(rng):
             return dict(g=g, gh=gh, gw=gw, D=_ch(rng, (4, 64, 384, 768)))
 
 
+
+# ---- third tier: temporal label propagation (checks: tests/_sweep_checks_prop.py, on the C twin and on the HIP library)
+LP_CAND_CAP = 4096        # label_prop.hip: 256 threads x LP_CAND_MAX candidates per query on the square entries
+LP_PRECISIONS = ("f32", "f16x3", "bf16")
+
+
+def lp_cmax(fs: int, nl: int) -> int:
+    """label_prop.hip, lp_cmax: the most context frames any target frame of the clip has."""
+    return max(1, 1 + min(fs - 2, nl))
+
+
+def lp_chunk(bs: int, fs: int, n: int, nl: int, cap_mb: int = 0) -> int:
+    """label_prop.hip, lp_chunk: target frames whose similarities are held at once (``cap_mb``: TT_LP_SIMS_CAP_MB, 0 = the 256 MB default)."""
+    per_t = bs * lp_cmax(fs, nl) * n * n * 4
+    T = ((cap_mb if cap_mb else 256) << 20) // per_t
+    return max(1, min(T, 65535 // bs, max(fs - 1, 1)))
+
+
+def lp_caps(p: dict) -> list:
+    return [int(c) for c in p["cap"].split("/")] if p["cap"] else []
+
+
+def LP(**kw) -> dict:
+    """A label_prop case: the defaults are a small clip on the wave kernel for <= 3 contexts."""
+    c = dict(bs=1, fs=3, g=14, D=16, K=5, nl=1, r=2, topk=5, prec="f32", dup=0, cap="")
+    assert set(kw) <= set(c), kw
+    c.update(kw)
+    return c
+
+
+def LPG(**kw) -> dict:
+    c = dict(bs=1, fs=4, gh=5, gw=9, D=16, K=5, nl=2, r=2, topk=5, prec="f32", dup=0)
+    assert set(kw) <= set(c), kw
+    c.update(kw)
+    return c
+
+
+def _label_prop(rng):
+    g = _ch(rng, (3, 5, 7, 10, 14))       # (win <= 14, <= 8 contexts: at most 1568 candidates, every draw is inside the domain)
+    return LP(bs=int(rng.integers(1, 4)), fs=int(rng.integers(2, 8)), g=g, D=_ch(rng, (4, 16, 20, 64)), K=_ch(rng, (1, 2, 7, 21, 64, 65, 200, 300, 513)),
+              nl=int(rng.integers(0, 8)), r=int(rng.integers(1, 9)), topk=_ch(rng, (1, 3, 5, 7)), prec=_ch(rng, LP_PRECISIONS), dup=_b(rng, 0.3))
+
+
+def _label_prop_grid(rng):
+    return LPG(bs=int(rng.integers(1, 3)), fs=int(rng.integers(2, 7)), gh=int(rng.integers(1, 13)), gw=int(rng.integers(1, 13)), D=_ch(rng, (4, 16, 64)),
+               K=_ch(rng, (1, 2, 21, 257)), nl=int(rng.integers(0, 8)), r=int(rng.integers(0, 7)), topk=_ch(rng, (1, 5, 9)), prec=_ch(rng, LP_PRECISIONS),
+               dup=_b(rng, 0.3))
+
+
+def _upsample_argmax_hw(rng):
+    gh, gw = int(rng.integers(1, 29)), int(rng.integers(1, 29))
+    return dict(M=int(rng.integers(1, 4)), gh=gh, gw=gw, K=_ch(rng, (1, 2, 7, 21, 64, 65, 200)), H=int(rng.integers(1, 4 * gh + 2)),
+                W=int(rng.integers(1, 4 * gw + 2)), dup=_b(rng, 0.3))
+
+
 DRAW = {"linear_f32": _linear_f32, "linear_pairs": _linear_pairs, "linear_planes": _linear_planes, "bwd_pairs": _bwd_pairs,
         "layernorm": _layernorm, "l2norm": _l2norm, "attention": _attention, "ce": _ce, "sinkhorn": _sinkhorn,
         "sinkhorn_from_q": _sinkhorn_from_q, "sinkhorn_local": _sinkhorn_local, "queue_push": _queue_push}
@@ -166,13 +221,17 @@ DRAW.update({"kmeans_assign": _kmeans_assign, "kmeans_accumulate": _kmeans_accum
              "upsample_tokens": _upsample("C"), "upsample_argmax_f32": _upsample("K"), "upsample_argmax": _upsample("K"),
              "confusion_counts": _confusion_counts, "adamw": _adamw, "elementwise": _elementwise, "foreground_mask": _foreground_mask,
              "pos_embed": _pos_embed})
+EVAL_OPS = tuple(DRAW)[len(STEP_OPS):]
+# (appended again: the third tier draws after the first two)
+DRAW.update({"label_prop": _label_prop, "label_prop_grid": _label_prop_grid, "upsample_argmax_hw": _upsample_argmax_hw})
 OPS = tuple(DRAW)
-EVAL_OPS = OPS[len(STEP_OPS):]
+PROP_OPS = OPS[len(STEP_OPS) + len(EVAL_OPS):]
 
 COUNTS = {"linear_f32": 6, "linear_pairs": 8, "linear_planes": 4, "bwd_pairs": 6, "layernorm": 5, "l2norm": 3, "attention": 6, "ce": 3,
           "sinkhorn": 6, "sinkhorn_from_q": 3, "sinkhorn_local": 3, "queue_push": 3,
           "kmeans_assign": 4, "kmeans_accumulate": 4, "col_moments": 3, "upsample_tokens": 3, "upsample_argmax_f32": 3, "upsample_argmax": 3,
-          "confusion_counts": 3, "adamw": 3, "elementwise": 3, "foreground_mask": 4, "pos_embed": 3}
+          "confusion_counts": 3, "adamw": 3, "elementwise": 3, "foreground_mask": 4, "pos_embed": 3,
+          "label_prop": 6, "label_prop_grid": 4, "upsample_argmax_hw": 4}
 
 # The route boundaries, pinned (tests/test_sweep_routes.py names the rule each one reaches)
 PINNED = {
@@ -308,6 +367,53 @@ PINNED = {
         # bicubic, taps clamped at the border: gh != gw, one of them 1, down- and up-sampling, D = 4 (one float4 per token)
         dict(g=14, gh=1, gw=7, D=4), dict(g=14, gh=20, gw=1, D=384), dict(g=14, gh=20, gw=14, D=384), dict(g=28, gh=7, gw=9, D=768),
         dict(g=28, gh=30, gw=40, D=4), dict(g=14, gh=30, gw=40, D=768), dict(g=28, gh=14, gw=14, D=384), dict(g=14, gh=13, gw=15, D=64),
+    ],
+    # ---- third tier (label_prop.hip: lp_route, lp_sims_chunk, lp_chunk and the per-query kernels)
+    "label_prop": [
+        # lp_route, all six kernels either side of each deciding bound.  Contexts of frame t: 1 + min(t - 1, nl).  nl 2 at fs 5: at most 3
+        # contexts (the <3,KT> wave kernels); nl 3 at fs 5: frame 4 has 4 (the clip changes to <8,KT> on its last frame)
+        LP(fs=5, nl=2, r=6, K=64), LP(fs=5, nl=3, r=6, K=65, dup=1), LP(fs=5, nl=2, r=6, K=256, dup=1), LP(fs=5, nl=2, r=6, K=257, dup=1),
+        LP(fs=5, nl=3, r=6, K=256), LP(fs=5, nl=3, r=6, K=257, dup=1), LP(fs=5, nl=3, K=1),
+        # K 512 is the last the wave kernels take (lane + 64 * 7), 513 the first on the workgroup kernel - whatever the window
+        LP(fs=5, nl=3, g=7, K=512, dup=1), LP(fs=5, nl=3, g=7, K=513, dup=1), LP(fs=5, nl=2, g=7, K=512), LP(g=1, K=513, bs=5, fs=4, nl=2),
+        # window 16 (g = 16 under a large radius: min(2 r + 1, g)) on the wave kernel, 17 (radius 8 on g = 17 and g = 20) on the workgroup kernel
+        LP(g=16, r=20, K=7), LP(g=16, r=8, K=7, nl=0), LP(g=17, r=8, K=7, dup=1), LP(g=20, r=8, K=3, fs=2),
+        # every slot of the wave kernel full: 16 x 16 x 8 contexts = 2048 candidates
+        LP(g=16, r=8, nl=7, fs=9, K=3),
+        # n = 4096 is the last grid whose source patch fits 12 bits (wave kernel); g = 65 goes to the workgroup kernel.  At g = 64 three
+        # contexts are 192 MB of similarities per target frame: the real 256 MB cap chunks this clip frame by frame, no variable set
+        LP(g=64, fs=4, nl=2, K=2), LP(g=64, fs=2, nl=0, D=4, K=2, dup=1), LP(g=65, fs=3, K=2),
+        # candidates at the caps.  2048 (32 x 32 x 2): every slot of label_prop_kernel<8> full; 2116 (23 x 23 x 4): the next count any
+        # (window, contexts) reaches above 2048 - label_prop_kernel<16>; 4096 (32 x 32 x 4): every slot of <16> full; 5120: refused
+        LP(g=32, r=16, fs=3, nl=1, K=3), LP(g=32, r=16, fs=4, nl=1, K=3, dup=1), LP(g=23, r=11, fs=5, nl=3, K=3), LP(g=32, r=16, fs=5, nl=3, K=3, dup=1),
+        LP(g=32, r=16, fs=6, nl=4, K=3),
+        # lp_sims_chunk's slot regimes, whole and chunked (cap in MB -> chunk length, lp_chunk): nl 0 (slot 0 only); the queue never fills
+        # (fs < nl + 2), fills on the last frame (fs = nl + 2), is full for several frames (fs > nl + 2); fs = 2.  One target frame of these
+        # shapes is 0.88 - 1.17 MB, so caps of 1 / 3 / 4 MB make chunks of 1 / 2 / 3 frames: starts inside the filling regime, ON
+        # t = nl + 2 (nl 1: T 2 -> 1, 3; nl 3: T 2 -> 1, 3, 5, 7; nl 7: T 2 -> ..., 9, 11) and inside the full regime
+        LP(bs=8, fs=2, nl=0), LP(bs=8, fs=4, nl=0, cap="1/3"), LP(bs=4, fs=2, nl=1), LP(bs=4, fs=3, nl=1, cap="1"), LP(bs=4, fs=5, nl=1, cap="1/3"),
+        LP(bs=2, fs=4, nl=3, cap="1/2"), LP(bs=2, fs=5, nl=3, cap="1/3"), LP(bs=2, fs=8, nl=3, cap="1/3/4", K=21), LP(fs=8, nl=7, cap="3"),
+        LP(fs=9, nl=7, cap="3/4"), LP(fs=12, nl=7, cap="3/4", dup=1), LP(bs=2, fs=8, nl=3, cap="3", K=513, prec="bf16"),
+        # degenerate sizes: one patch (candidates = contexts < topk; bs * n = 3 is not a multiple of the 4 waves of a workgroup); g 2, g 3;
+        # topk 1 and above every total; D 4 (K < 16 in the similarity product), 20 (the general kernel), 64, 384; a ragged batch of 37 clips
+        LP(g=1, bs=3, fs=4, nl=2), LP(g=2, fs=4, nl=2, r=1), LP(g=3, bs=3, fs=4, nl=3, r=1, dup=1), LP(g=7, topk=1), LP(g=7, topk=1000, fs=4, nl=2),
+        LP(g=7, topk=1000, K=513), LP(D=4), LP(D=20, K=21), LP(D=64, fs=4, nl=2), LP(D=384, K=21), LP(bs=37, g=5, fs=4, nl=2, D=20),
+        # precision: the similarities as fp16 pairs' front end hands them over (f16x3) and on bf16 MFMA
+        LP(fs=5, nl=3, r=6, K=21, prec="f16x3"), LP(fs=5, nl=3, r=6, K=21, prec="bf16", dup=1), LP(g=17, r=8, K=7, prec="bf16"),
+        LP(g=23, r=11, fs=5, nl=3, K=3, prec="f16x3"), LP(D=384, K=21, prec="bf16"), LP(bs=37, g=5, fs=4, nl=2, D=20, prec="bf16"),
+    ],
+    "label_prop_grid": [
+        # gh != gw, 1 x n and n x 1; radius 0 (no window) and beyond the grid; nl 0 and 7; topk above the candidates (the `total >= topk`
+        # branch) and below; K 1 and above 256 (a thread owns two channels); 30 x 30 at radius 12 with 8 contexts: 5000 candidates
+        LPG(), LPG(gh=9, gw=5, dup=1), LPG(gh=1, gw=9, r=3), LPG(gh=9, gw=1, r=3, nl=0), LPG(gh=1, gw=1, fs=3, nl=1), LPG(r=0), LPG(gh=7, gw=23, r=0, dup=1),
+        LPG(r=30), LPG(fs=9, nl=7), LPG(fs=3, nl=0, bs=3), LPG(gh=2, gw=3, nl=0, topk=10), LPG(gh=2, gw=3, nl=0, topk=6), LPG(K=1), LPG(K=300, dup=1),
+        LPG(gh=30, gw=30, r=12, fs=9, nl=7, K=3), LPG(gh=14, gw=14, r=6, fs=5, nl=3, K=21, prec="bf16"), LPG(D=4, prec="f16x3"),
+    ],
+    "upsample_argmax_hw": [
+        # output smaller than the grid, equal to it, larger; H or W of 1; K 1, 64, 65; M 1 and above; a duplicated channel (first index wins)
+        dict(M=1, gh=9, gw=5, K=21, H=4, W=3, dup=0), dict(M=3, gh=7, gw=23, K=3, H=7, W=23, dup=1), dict(M=2, gh=5, gw=9, K=64, H=40, W=77, dup=1),
+        dict(M=1, gh=5, gw=9, K=65, H=1, W=30, dup=1), dict(M=2, gh=9, gw=5, K=7, H=30, W=1, dup=0), dict(M=1, gh=1, gw=1, K=1, H=3, W=2, dup=0),
+        dict(M=3, gh=14, gw=1, K=2, H=9, W=9, dup=0), dict(M=1, gh=30, gw=53, K=5, H=480, W=848, dup=0), dict(M=2, gh=6, gw=10, K=200, H=96, W=31, dup=1),
     ],
 }
 

@@ -34,6 +34,11 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert lib.tt_sinkhorn_workspace_bytes(6272, 200) >= 6272 * 200 * 4
     assert lib.tt_ce_workspace_bytes(100) == 400
     assert lib.tt_gemm_tile_choice(25216, 1152, 1) in (0, 1, 2, 3)
+    # ... and so are the route queries: the training protocol's propagation (14 x 14 tokens, 13 x 13 window, K 200) runs the wave kernels -
+    # <3,4> while frame 0 and the queue make at most three contexts, <8,4> from the fourth target frame on -; frame fs is not a target frame
+    assert "tt_label_propagate_route" in declared
+    assert [lib.tt_label_propagate_route(8, 14, 200, 7, 6, t) for t in (1, 2, 3, 4, 7, 8)] == [1, 1, 1, 3, 3, 0]
+    assert lib.tt_label_propagate_workspace_bytes(40000, 3, 1, 16, 3, 1) == 256 * ((40000 * 2 * 4 + 255) // 256) + 2 * 40000 * 3 * 8   # (one frame per chunk: bs * chunk <= 65535)
 
 
 def test_no_cpu_fallback():

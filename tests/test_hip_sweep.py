@@ -8,6 +8,11 @@ the same inputs, fp64 references, bounds and capped excuse rules that tests/test
 the accepted domain of each of those entries at its edge: the largest size computes correctly (a case of the table or a call below), the
 first size beyond is refused by the launcher's own check, with its own message, before anything is launched.
 
+The third tier - temporal label propagation (PROP_OPS: the square entries' six per-query kernels, slot regimes and chunkings, the grid
+entry, its up-sampler) - runs the checks of tests/_sweep_checks_prop.py the same way: one-frame fp64 reference, exact-selection and
+real-valued inputs, the bit-for-bit equalities between the entries; tests/test_sweep_prop_host.py is its host half.  Its domain edges
+follow the second tier's.
+
 ``run_case`` is also what tools/fuzz_ops.py runs on more seeds of the same generator."""
 import json
 import os
@@ -18,8 +23,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _sweep_cases import EVAL_OPS, PAIR_EPILOGUES, case_id, table
+from _sweep_cases import EVAL_OPS, PAIR_EPILOGUES, PROP_OPS, case_id, table
 from _sweep_checks_eval import HipSide, run_eval_case
+from _sweep_checks_prop import PropHip, run_prop_case
 
 pytestmark = pytest.mark.gpu
 TOL_F32 = 2e-5
@@ -322,8 +328,9 @@ CHECK = {"linear_f32": _linear_f32, "linear_pairs": _linear_pairs, "linear_plane
          "sinkhorn_from_q": _sinkhorn_from_q, "sinkhorn_local": _sinkhorn_local, "queue_push": _queue_push}
 
 
-def run_case(op: str, params: dict, worst: dict = None) -> None:
-    """Runs one case of the table on cuda:0; raises AssertionError on a bound it misses.  ``worst``: {"op: what": [max error, bound]}."""
+def run_case(op: str, params: dict, worst: dict = None, monkeypatch=None) -> None:
+    """Runs one case of the table on cuda:0; raises AssertionError on a bound it misses.  ``worst``: {"op: what": [max error, bound]};
+    ``monkeypatch``: pytest's, for the cases that run again under TT_LP_SIMS_CAP_MB (without one the variable is set and restored)."""
     from timetuning_amd import hip_ops as ops
 
     global WORST
@@ -333,6 +340,8 @@ def run_case(op: str, params: dict, worst: dict = None) -> None:
     try:
         if op in EVAL_OPS:
             run_eval_case(HipSide(), op, params, WORST)
+        elif op in PROP_OPS:
+            run_prop_case(PropHip(), op, params, WORST, monkeypatch)
         else:
             CHECK[op](ops, params, _gen(op, params), _note(op))
     finally:
@@ -349,8 +358,8 @@ def _report():
 
 
 @pytest.mark.parametrize("op,params", CASES, ids=[case_id(o, p) for o, p in CASES])
-def test_sweep(op, params):
-    run_case(op, params)
+def test_sweep(op, params, monkeypatch):
+    run_case(op, params, monkeypatch=monkeypatch)
 
 
 # ---- the accepted domains of the second tier's entries, at the edge (include/timetuning_hip.h states them).  Every refusal below is a
@@ -459,3 +468,95 @@ def test_mask_position_and_row_op_limits():
     with _refused("l2norm_fwd: bad arguments"):
         ops.normalize_rows_(_z(2, 1025))
     assert rel_err(ops.normalize_rows_(torch.full((2, 1024), 2.0, device="cuda")), torch.full((2, 1024), 2.0 / 64.0)) < TOL_F32
+
+
+# ---- the accepted domain of the propagation entries, at the edge (include/timetuning_hip.h, k14 and N9).  Every refusal below is a host-side
+# TT_REQUIRE ahead of the first launch (label_prop.hip: lp_run, tt_label_propagate_grid_maps, tt_upsample_argmax_hw); no shape beyond the
+# domain is ever launched.  4096 candidates (correct) against 5120 (refused) are cases of the table above.
+def _one_patch(bs, fs, K, seed=11):
+    """g = 1: every context is the one patch, so every map is the seed - exactly at fs 2 (one kept source of weight 1)."""
+    gen = torch.Generator().manual_seed(seed)
+    xn = F.normalize(torch.randn(fs, bs, 1, 16, generator=gen), dim=-1).cuda()
+    s0 = torch.softmax(2 * torch.randn(bs, 1, K, generator=gen), -1).cuda()
+    return xn, s0
+
+
+def test_label_prop_square_entries_refuse_beyond_their_domain():
+    from timetuning_amd import hip_ops as ops
+
+    xn, s0 = _one_patch(2, 10, 3)
+    x49 = F.normalize(torch.randn(10, 2, 49, 16, generator=torch.Generator().manual_seed(1)), dim=-1).cuda()
+    s49 = torch.softmax(torch.randn(2, 49, 3, generator=torch.Generator().manual_seed(2)), -1).cuda()
+    # n_last_frames 7 is the most (cases above run it); 8 is refused
+    ops.label_propagate_maps(x49, s49, 7, 2, 5, 0.1)
+    for fn in (ops.label_propagate_maps, ops.label_propagate):
+        with _refused(r"n_last_frames must be <= 7"):
+            fn(x49, s49, 8, 2, 5, 0.1)
+        with _refused(r"size_mask_neighborhood must be > 0"):          # the unrestricted variant is the grid entry's
+            fn(x49, s49, 4, 0, 5, 0.1)
+        with _refused(r"feature dim must be a multiple of 4"):           # D = 4 runs in the table; 6 is refused
+            fn(x49[..., :6].contiguous(), s49, 4, 2, 5, 0.1)
+        with _refused(r"topk >= 1"):
+            fn(x49, s49, 4, 2, 0, 0.1)
+    with _refused(r"label_propagate_sims: n_last_frames must be <= 7"):
+        ops.label_propagate_sims(x49, 3, 8)
+    assert ops._lib.load().tt_label_propagate_route(10, 7, 3, 8, 2, 1) == 0 and ops._lib.load().tt_label_propagate_route(10, 7, 3, 4, 0, 1) == 0
+
+
+@pytest.mark.parametrize("K,route,msg", [(513, 5, "65536 clips exceed the 65535 of one launch of the workgroup-per-query kernel"),
+                                         (3, 1, "65536 clips exceed the 65535 problems of one similarity launch")])
+def test_label_prop_takes_65535_clips_and_refuses_more(K, route, msg):
+    """Clips ride on gridDim.y of the workgroup-per-query kernels (K = 513 puts g = 1 there) and, on every route, of the similarity
+    product: 65535 one-patch clips propagate correctly, 65536 are refused by lp_run before anything is launched."""
+    from timetuning_amd import hip_ops as ops
+
+    assert ops._lib.load().tt_label_propagate_route(2, 1, K, 0, 1, 1) == route
+    xn, s0 = _one_patch(65535, 2, K)
+    maps = ops.label_propagate_maps(xn, s0, 0, 1, 5, 0.1)
+    assert torch.equal(maps[0], s0.double())
+    labels, pmap = ops.label_propagate(xn, s0, 0, 1, 5, 0.1, return_pmap=True)
+    assert torch.equal(pmap, maps[0]) and torch.equal(labels, s0.argmax(-1))
+    xn, s0 = _one_patch(65536, 2, K)
+    with _refused(msg):
+        ops.label_propagate_maps(xn, s0, 0, 1, 5, 0.1)
+    with _refused(msg):
+        ops.label_propagate(xn, s0, 0, 1, 5, 0.1)
+
+
+def test_label_prop_shortens_the_chunk_to_the_similarity_launch():
+    """40 000 clips x 2 target frames are 80 000 problems of the slot-0 similarity product, more than one launch carries on gridDim.y: the
+    chunk is shortened to one frame (lp_chunk) and the call runs - the maps of one-patch clips are convex combinations of the seed with
+    itself.  The two-call form, which needs one chunk, declines."""
+    from _sweep_cases import lp_chunk
+    from timetuning_amd import hip_ops as ops
+
+    assert lp_chunk(40000, 3, 1, 1) == 1 and lp_chunk(30000, 3, 1, 1) == 2
+    xn, s0 = _one_patch(40000, 3, 3)
+    maps = ops.label_propagate_maps(xn, s0, 1, 1, 5, 0.1)
+    assert torch.equal(maps[0], s0.double()) and rel_err(maps[1], s0.double()) < 1e-6
+    assert ops.label_propagate_sims(xn, 3, 1) is None
+    gm = ops.label_propagate_grid_maps(xn, s0, (1, 1), 1, 1, 5, 0.1)
+    assert torch.equal(gm[0], s0.double()) and rel_err(gm[1], s0.double()) < 1e-6
+
+
+def test_grid_entry_and_its_upsampler_at_the_edge():
+    from timetuning_amd import hip_ops as ops
+
+    xn, s0 = _one_patch(65535, 2, 3)
+    assert torch.equal(ops.label_propagate_grid_maps(xn, s0, (1, 1), 0, 0, 5, 0.1)[0], s0.double())
+    xn, s0 = _one_patch(65536, 2, 3)
+    with _refused("label_propagate_grid_maps: need fs >= 2 and positive sizes"):
+        ops.label_propagate_grid_maps(xn, s0, (1, 1), 0, 0, 5, 0.1)
+    xn, s0 = _one_patch(2, 10, 3)
+    ops.label_propagate_grid_maps(xn, s0, (1, 1), 7, 0, 5, 0.1)
+    with _refused("label_propagate_grid_maps: n_last_frames must be <= 7"):
+        ops.label_propagate_grid_maps(xn, s0, (1, 1), 8, 0, 5, 0.1)
+    with _refused(r"label_propagate_grid_maps: size_mask_neighborhood must be >= 0"):
+        ops.label_propagate_grid_maps(xn, s0, (1, 1), 4, -1, 5, 0.1)
+    with _refused("label_propagate_grid_maps: feature dim must be a multiple of 4"):
+        ops.label_propagate_grid_maps(xn[..., :6].contiguous(), s0, (1, 1), 4, 1, 5, 0.1)
+    # M rides on gridDim.y: 65535 maps (1 x 1 each, to 2 x 2) are each resampled, 65536 are refused
+    x = torch.randn(65535, 1, 3, generator=torch.Generator().manual_seed(5)).double().cuda()
+    assert torch.equal(ops.upsample_argmax_hw(x, (1, 1), (2, 2)), x.argmax(-1).view(-1, 1, 1).expand(65535, 2, 2))
+    with _refused("upsample_argmax_hw: 65536 maps of 2x2 exceed one launch"):
+        ops.upsample_argmax_hw(_z(65536, 1, 3, dtype=torch.float64), (1, 1), (2, 2))

@@ -9,10 +9,9 @@ import os
 import pytest
 
 from _sweep_cases import EVAL_OPS, case_id, table
-from _sweep_checks_eval import run_eval_case, twin_side
+from _sweep_checks_eval import HOST_WORST as WORST, run_eval_case, twin_side
 
 CASES = [(o, p) for o, p in table() if o in EVAL_OPS]
-WORST: dict = {}
 
 
 @pytest.fixture(scope="module", autouse=True)

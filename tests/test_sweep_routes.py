@@ -8,7 +8,7 @@ import itertools
 
 import pytest
 
-from _sweep_cases import EVAL_OPS, KM_MAXKD, PAIR_EPILOGUES, STEP_OPS, case_id, km_max_k, table
+from _sweep_cases import EVAL_OPS, KM_MAXKD, LP_CAND_CAP, PAIR_EPILOGUES, PROP_OPS, STEP_OPS, case_id, km_max_k, lp_caps, lp_chunk, lp_cmax, table
 from timetuning_amd import _lib, hip_ops
 
 NCU = 256
@@ -220,7 +220,7 @@ def test_second_tier_is_appended_and_complete():
     assert STEP_OPS == ("linear_f32", "linear_pairs", "linear_planes", "bwd_pairs", "layernorm", "l2norm", "attention", "ce", "sinkhorn",
                         "sinkhorn_from_q", "sinkhorn_local", "queue_push")
     ops_in_order = list(dict.fromkeys(o for o, _ in CASES))
-    assert tuple(ops_in_order) == STEP_OPS + EVAL_OPS                    # appended: the first tier's draws - and case ids - are untouched
+    assert tuple(ops_in_order) == STEP_OPS + EVAL_OPS + PROP_OPS         # appended: the first tier's draws - and case ids - are untouched
     ids = [case_id(o, p) for o, p in CASES]
     assert len(set(ids)) == len(ids)
     # (the first and the last case of the first tier, as they were before the second tier existed)
@@ -369,3 +369,134 @@ def test_foreground_mask_and_pos_embed_edges():
     assert any(p["gh"] == 1 for p in pe) and any(p["gw"] == 1 for p in pe) and all((p["gh"], p["gw"]) != (p["g"], p["g"]) for p in pe)
     assert any(p["gh"] < p["g"] and p["gw"] < p["g"] for p in pe) and any(p["gh"] > p["g"] and p["gw"] > p["g"] for p in pe)
     assert any((p["gh"] > p["g"]) != (p["gw"] > p["g"]) for p in pe) and any(p["gh"] != p["gw"] for p in pe)
+
+
+# ---- the third tier: temporal label propagation (label_prop.hip).  tt_label_propagate_route is the function lp_run dispatches on; the
+# rule is restated here independently and compared with it, then the table is held to every kernel, slot regime and chunk position.
+def test_third_tier_is_appended_and_the_first_two_are_what_they_were():
+    import zlib
+
+    assert PROP_OPS == ("label_prop", "label_prop_grid", "upsample_argmax_hw")
+    earlier = [case_id(o, p) for o, p in CASES if o not in PROP_OPS]
+    assert len(earlier) == 290 and zlib.crc32("\n".join(earlier).encode()) == 681109916      # the ids of the first two tiers, unchanged
+    assert earlier[-1].startswith("pos_embed[") and [o for o, _ in CASES][290] == "label_prop"
+
+
+def lp_route_rule(fs, g, K, nl, r, t):
+    """label_prop.hip, lp_run: 0 refused; 1..4 label_prop_wave_kernel<3,4>, <3,8>, <8,4>, <8,8>; 5 / 6 label_prop_kernel<8>, <16>."""
+    if fs < 2 or g < 1 or K < 1 or not 0 <= nl <= 7 or r < 1 or not 1 <= t < fs:
+        return 0
+    win = min(2 * r + 1, g)
+    cand_max = win * win * lp_cmax(fs, nl)                 # of the clip: the workgroup kernels are chosen per call
+    if cand_max > LP_CAND_CAP:
+        return 0
+    if win <= 16 and g * g <= 4096 and K <= 512:           # a 16 x 16 window in 64 lanes x 4 rows; the source patch in 12 bits; lane + 64 * 7
+        c = 1 + len(range(max(1, t - nl), t))              # the contexts of THIS frame: frame 0 and the queue
+        return {(True, True): 1, (True, False): 2, (False, True): 3, (False, False): 4}[(c <= 3, K <= 256)]
+    return 5 if cand_max <= 2048 else 6
+
+
+def test_label_prop_route_export_is_the_restated_rule(lib):
+    seen = set()
+    for fs, g, K, nl, r in itertools.product((1, 2, 3, 4, 5, 6, 9, 10), (0, 1, 2, 7, 14, 16, 17, 23, 32, 33, 64, 65), (0, 1, 64, 256, 257, 512, 513),
+                                             (-1, 0, 1, 2, 3, 4, 7, 8), (0, 1, 6, 7, 8, 11, 16, 40)):
+        for t in range(0, fs + 1):
+            got = lib.tt_label_propagate_route(fs, g, K, nl, r, t)
+            assert got == lp_route_rule(fs, g, K, nl, r, t), (fs, g, K, nl, r, t, got)
+            seen.add(got)
+    assert seen == {0, 1, 2, 3, 4, 5, 6}
+
+
+def _lp_routes(p):
+    return [lp_route_rule(p["fs"], p["g"], p["K"], p["nl"], p["r"], t) for t in range(1, p["fs"])]
+
+
+def _lp_cands(p):
+    win = min(2 * p["r"] + 1, p["g"])
+    return win * win * lp_cmax(p["fs"], p["nl"])
+
+
+def test_label_prop_every_kernel_with_and_without_labels(lib):
+    cases = _of("label_prop")
+    for p in cases:
+        assert _lp_routes(p) == [lib.tt_label_propagate_route(p["fs"], p["g"], p["K"], p["nl"], p["r"], t) for t in range(1, p["fs"])], p
+    # every value of the route query: the refusal and the six kernels; each kernel on the LAST frame (tt_label_propagate requests the labels
+    # there) and on some frame of tt_label_propagate_maps (which requests none) - every case runs both entries
+    assert {rt for p in cases for rt in _lp_routes(p)} == {0, 1, 2, 3, 4, 5, 6}
+    assert {_lp_routes(p)[-1] for p in cases} == {0, 1, 2, 3, 4, 5, 6}
+    assert any(len(set(_lp_routes(p))) > 1 for p in cases)                       # a clip that changes kernel between its own frames
+    refused = [p for p in cases if _lp_routes(p)[0] == 0]
+    assert refused and all(_lp_cands(p) > LP_CAND_CAP and set(_lp_routes(p)) == {0} for p in refused)
+    assert any(_lp_cands(p) == 5120 for p in refused)
+    ok = [p for p in cases if p not in refused]
+    # either side of each deciding bound: K, contexts, window, grid
+    assert {p["K"] for p in ok} >= {1, 64, 65, 256, 257, 512, 513}
+    for K in (512, 513):
+        assert any(p["K"] == K and min(2 * p["r"] + 1, p["g"]) <= 16 and p["g"] <= 64 for p in ok)     # only K moves the call off the wave kernels
+    wave = [p for p in ok if _lp_routes(p)[-1] <= 4]
+    assert {1 + min(p["fs"] - 2, p["nl"]) for p in wave} >= {1, 2, 3, 4, 8}
+    assert {min(2 * p["r"] + 1, p["g"]) for p in ok} >= {1, 2, 3, 16, 17} and any(p["g"] == 16 and p["r"] > 8 for p in ok)
+    assert any(p["g"] == 64 and _lp_routes(p)[-1] <= 4 for p in ok) and any(p["g"] == 65 and _lp_routes(p)[-1] == 5 for p in ok)
+    assert any(_lp_cands(p) == 2048 and _lp_routes(p)[-1] <= 4 and p["nl"] == 7 for p in ok)             # every slot of the wave kernel
+    # candidate counts at the workgroup kernels' caps: 2048 on <8>, the next reachable count and 4096 on <16>
+    reachable = sorted({w * w * c for w in range(1, 65) for c in range(1, 9)})
+    nxt = min(v for v in reachable if v > 2048)
+    assert nxt == 2116
+    assert any(_lp_cands(p) == 2048 and _lp_routes(p)[-1] == 5 for p in ok)
+    assert any(_lp_cands(p) == nxt and _lp_routes(p)[-1] == 6 for p in ok) and any(_lp_cands(p) == 4096 and _lp_routes(p)[-1] == 6 for p in ok)
+    # the first-maximum rule with exactly equal channels on every kernel's label frame, across lanes (K > 1) and slots (K > 64, K > 256)
+    for rt in range(1, 7):
+        assert any(p["dup"] and _lp_routes(p)[-1] == rt for p in ok), rt
+    assert any(p["dup"] and p["K"] > 256 and _lp_routes(p)[-1] in (2, 4) for p in ok) and any(p["dup"] and p["K"] > 256 and _lp_routes(p)[-1] == 5 for p in ok)
+    # degenerate sizes, precisions
+    assert {p["g"] for p in ok} >= {1, 2, 3} and any(p["bs"] * p["g"] ** 2 % 4 for p in wave)
+    assert {p["topk"] for p in ok} >= {1, 5} and any(p["topk"] > _lp_cands(p) for p in wave) and any(p["topk"] > _lp_cands(p) for p in ok if p not in wave)
+    assert any(p["g"] == 1 and lp_cmax(p["fs"], p["nl"]) < p["topk"] for p in ok)
+    assert {p["D"] for p in ok} >= {4, 16, 20, 64, 384} and any(p["bs"] > 32 and p["bs"] % 4 for p in ok)
+    for prec in ("f32", "f16x3", "bf16"):
+        assert {min(_lp_routes(p)[-1], 5) for p in ok if p["prec"] == prec} >= {3, 5}, prec      # wave and workgroup kernels in each precision
+
+
+def test_label_prop_every_slot_regime_and_chunk_position():
+    cases = [p for p in _of("label_prop") if _lp_routes(p)[0] != 0]
+    # lp_sims_chunk: slot 0 holds (t, 0); lag d sits in slot t - d while the queue fills (t <= nl + 1) and in 1 + nl - d afterwards
+    regime = lambda nl, t: "slot0" if nl == 0 or t == 1 else ("filling" if t <= nl + 1 else "full")
+    assert {p["nl"] for p in cases} >= {0, 1, 3, 7} and any(p["fs"] == 2 for p in cases)
+    for nl in (1, 3, 7):      # a queue that never fills, one that fills on the last frame, one that is full for several frames
+        fss = {p["fs"] for p in cases if p["nl"] == nl}
+        assert any(fs < nl + 2 for fs in fss) and nl + 2 in fss and any(fs > nl + 3 for fs in fss), (nl, fss)
+    assert any(p["nl"] == 0 and p["fs"] > 2 for p in cases)
+    # chunk starts: t0 = 1, 1 + T, ... with T = lp_chunk under the case's cap
+    hits = set()
+    for p in cases:
+        n = p["g"] ** 2
+        for cap in lp_caps(p):
+            T = lp_chunk(p["bs"], p["fs"], n, p["nl"], cap)
+            assert T < p["fs"] - 1 or len(lp_caps(p)) > 1, (p, cap, T)             # a cap that cuts nothing is not a chunk case
+            for t0 in range(1 + T, p["fs"], T):
+                hits.add((p["nl"], regime(p["nl"], t0), t0 == p["nl"] + 2, T))
+    for nl in (1, 3, 7):
+        assert any(h[0] == nl and h[1] == "filling" for h in hits) or nl == 1, nl  # (nl 1: the filling regime is t = 2 alone)
+        assert any(h[0] == nl and h[2] for h in hits), nl                          # a chunk that starts ON t = nl + 2
+        assert any(h[0] == nl and h[1] == "full" and not h[2] for h in hits), nl   # ... and one inside the full regime
+    assert any(h[0] == 1 and h[1] == "filling" for h in hits)
+    assert any(h[0] == 0 for h in hits) and {h[3] for h in hits} >= {1, 2, 3}
+    # the real 256 MB cap: a case that is chunked with no variable set
+    real = [p for p in cases if not p["cap"] and lp_chunk(p["bs"], p["fs"], p["g"] ** 2, p["nl"]) < p["fs"] - 1]
+    assert any(p["g"] == 64 and lp_cmax(p["fs"], p["nl"]) == 3 for p in real)
+    assert sum(p["g"] >= 64 for p in cases) <= 3                                   # (the fp64 reference at n >= 4096 takes seconds)
+
+
+def test_grid_entry_and_upsampler_edges():
+    gr = _of("label_prop_grid")
+    assert any(p["gh"] == 1 and p["gw"] > 1 for p in gr) and any(p["gw"] == 1 and p["gh"] > 1 for p in gr) and any(p["gh"] > p["gw"] > 1 for p in gr)
+    assert any(1 < p["gh"] < p["gw"] for p in gr) and any(p["r"] == 0 for p in gr) and any(p["r"] > max(p["gh"], p["gw"]) for p in gr)
+    assert {p["nl"] for p in gr} >= {0, 7} and {p["prec"] for p in gr} == {"f32", "f16x3", "bf16"}
+    total = lambda p: (min(2 * p["r"] + 1, p["gh"]) * min(2 * p["r"] + 1, p["gw"]) if p["r"] else p["gh"] * p["gw"]) * lp_cmax(p["fs"], p["nl"])
+    assert any(total(p) < p["topk"] for p in gr) and any(total(p) == p["topk"] for p in gr) and any(total(p) > LP_CAND_CAP for p in gr)
+    assert any(p["K"] == 1 for p in gr) and any(p["K"] > 256 for p in gr) and any(p["dup"] and p["K"] > 256 for p in gr)
+    hw = _of("upsample_argmax_hw")
+    assert any(p["H"] < p["gh"] and p["W"] < p["gw"] for p in hw) and any((p["H"], p["W"]) == (p["gh"], p["gw"]) for p in hw)
+    assert any(p["H"] > p["gh"] and p["W"] > p["gw"] for p in hw) and any(p["H"] == 1 for p in hw) and any(p["W"] == 1 for p in hw)
+    assert {p["K"] for p in hw} >= {1, 64, 65} and any(p["M"] == 1 for p in hw) and any(p["M"] > 1 for p in hw)
+    assert any(p["dup"] for p in hw) and any(p["H"] * p["W"] > 256 * 256 for p in hw)

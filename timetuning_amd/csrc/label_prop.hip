@@ -346,6 +346,24 @@ static int lp_cmax(int fs, int n_last) {
   return c < 1 ? 1 : c;
 }
 
+// Which per-query kernel target frame t runs (tt_label_propagate_route; lp_run dispatches on this value): 0 = the shape or the frame is
+// refused, 1..4 = label_prop_wave_kernel<3,4>, <3,8>, <8,4>, <8,8>, 5 / 6 = label_prop_kernel<8>, <16>.  The wave kernels take windows of
+// at most 16 x 16 on grids of at most 4096 patches (the source patch is packed into 12 bits) with K <= 512; the choice among them
+// follows the context frames of THAT frame (a clip whose queue is still filling changes kernel between its frames) and K <= 256.  The
+// workgroup kernels are chosen per call, by the most candidates any frame of the clip has.
+static int lp_route(int fs, int g, int K, int n_last, int radius, int t) {
+  if (fs < 2 || g <= 0 || K <= 0 || n_last < 0 || n_last + 1 > LP_MAXC || radius <= 0 || t < 1 || t >= fs) return 0;
+  const int win = (radius < g && 2 * radius + 1 < g) ? 2 * radius + 1 : g;
+  const long long cand_max = (long long)win * win * lp_cmax(fs, n_last);
+  if (cand_max > 256LL * LP_CAND_MAX) return 0;
+  static const bool wave_env = [] { const char* e = getenv("TT_LP_WAVE"); return !e || atoi(e) != 0; }();   // tuning aid
+  if (wave_env && win <= 16 && (long long)g * g <= 4096 && K <= 512) {
+    const int c = 1 + (t - 1 < n_last ? t - 1 : n_last);   // frame 0 and the frames [max(1, t - n_last), t)
+    return (c <= 3 ? 1 : 3) + (K <= 256 ? 0 : 1);
+  }
+  return cand_max <= 256LL * 8 ? 5 : 6;
+}
+
 // target frames whose similarities are held at once (all of them unless that needs more than LP_SIMS_CAP bytes).  256 MB holds every
 // target frame of C2 (44 MB) and all but one of C4's (138 MB at 16 clips x 8 frames); the evaluation protocol's long clips on the
 // 28 x 28 grid are chunked (there a few more similarity launches do not matter - the per-query kernel dominates).  The cost is
@@ -355,6 +373,8 @@ static int lp_chunk(int bs, int fs, int n, int n_last) {
   const size_t per_t = (size_t)bs * lp_cmax(fs, n_last) * n * n * sizeof(float);
   const char* e = getenv("TT_LP_SIMS_CAP_MB");   // test aid: a small cap exercises the chunked path on small inputs
   size_t T = (e ? (size_t)atoll(e) << 20 : LP_SIMS_CAP) / per_t;
+  // (the slot-0 similarity launch carries bs * T problems on gridDim.y: at most 65535 of them)
+  if (bs > 0 && T > (size_t)(65535 / bs)) T = 65535 / bs;
   if (T < 1) T = 1;
   if (T > (size_t)(fs - 1)) T = fs > 1 ? fs - 1 : 1;
   return (int)T;
@@ -404,6 +424,10 @@ extern "C" size_t tt_label_propagate_workspace_bytes(int bs, int fs, int g, int 
   return lp_workspace(lp_chunk(bs, fs, (int)n, n_last_frames), bs, fs, n, K, n_last_frames);
 }
 
+extern "C" int tt_label_propagate_route(int fs, int g, int K, int n_last_frames, int radius, int t) {
+  return lp_route(fs, g, K, n_last_frames, radius, t);
+}
+
 static int lp_run(const char* who, const float* xn, const float* seg0, int64_t* labels, double* pmap_last, double* pmap_all, int bs,
                   int fs, int g, int D, int K, int n_last_frames, int radius, int topk, float temperature, int precision, void* workspace,
                   size_t workspace_bytes, tt_stream_t stream, int phase = 0) {
@@ -421,6 +445,10 @@ static int lp_run(const char* who, const float* xn, const float* seg0, int64_t* 
   TT_REQUIRE(cand_max <= 256LL * LP_CAND_MAX, "%s: window %dx%d with %d context frames exceeds %d candidates per query", who, win, win,
              lp_cmax(fs, n_last_frames), 256 * LP_CAND_MAX);
   TT_REQUIRE(D % 4 == 0, "%s: feature dim must be a multiple of 4", who);
+  // clips ride on gridDim.y of the similarity products (bs * chunk problems, the chunk shortened to fit) and of the workgroup kernels
+  if (lp_route(fs, g, K, n_last_frames, radius, 1) >= 5)
+    TT_REQUIRE(bs <= 65535, "%s: %d clips exceed the 65535 of one launch of the workgroup-per-query kernel", who, bs);
+  TT_REQUIRE(bs <= 65535, "%s: %d clips exceed the 65535 problems of one similarity launch", who, bs);
   hipStream_t s = as_stream(stream);
   const int n = g * g;
   // The chunk length follows the workspace that was actually handed over, not a second reading of the cap (the environment may have
@@ -462,20 +490,15 @@ static int lp_run(const char* who, const float* xn, const float* seg0, int64_t* 
       a.labels = (t == fs - 1) ? labels : nullptr;
       a.c = c; a.cs = cmax; a.bs = bs; a.g = g; a.K = K; a.radius = radius; a.topk = topk; a.temp = temperature;
       const unsigned wgrid = (unsigned)(((long long)bs * n + 3) / 4);
-      static const bool wave_env = [] { const char* e = getenv("TT_LP_WAVE"); return !e || atoi(e) != 0; }();   // tuning aid
-      const bool wave_kernel = wave_env && win <= 16 && n <= 4096 && K <= 512;   // (source patch packed into 12 bits)
-      if (wave_kernel && c <= 3 && K <= 256)
-        hipLaunchKernelGGL((label_prop_wave_kernel<3, 4>), dim3(wgrid), dim3(256), 0, s, a);
-      else if (wave_kernel && c <= 3)
-        hipLaunchKernelGGL((label_prop_wave_kernel<3, 8>), dim3(wgrid), dim3(256), 0, s, a);
-      else if (wave_kernel && K <= 256)
-        hipLaunchKernelGGL((label_prop_wave_kernel<8, 4>), dim3(wgrid), dim3(256), 0, s, a);
-      else if (wave_kernel)
-        hipLaunchKernelGGL((label_prop_wave_kernel<8, 8>), dim3(wgrid), dim3(256), 0, s, a);
-      else if (cand_max <= 256LL * 8)
-        hipLaunchKernelGGL((label_prop_kernel<8>), dim3(n, bs), dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((label_prop_kernel<LP_CAND_MAX>), dim3(n, bs), dim3(256), 0, s, a);
+      switch (lp_route(fs, g, K, n_last_frames, radius, t)) {
+        case 1: hipLaunchKernelGGL((label_prop_wave_kernel<3, 4>), dim3(wgrid), dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((label_prop_wave_kernel<3, 8>), dim3(wgrid), dim3(256), 0, s, a); break;
+        case 3: hipLaunchKernelGGL((label_prop_wave_kernel<8, 4>), dim3(wgrid), dim3(256), 0, s, a); break;
+        case 4: hipLaunchKernelGGL((label_prop_wave_kernel<8, 8>), dim3(wgrid), dim3(256), 0, s, a); break;
+        case 5: hipLaunchKernelGGL((label_prop_kernel<8>), dim3(n, bs), dim3(256), 0, s, a); break;
+        case 6: hipLaunchKernelGGL((label_prop_kernel<LP_CAND_MAX>), dim3(n, bs), dim3(256), 0, s, a); break;
+        default: set_error("%s: no kernel for frame %d", who, t); return TT_EINVAL;   // (unreachable: the checks above are lp_route's)
+      }
       TT_CHECK_LAUNCH(who);
     }
   }
