@@ -607,6 +607,30 @@ int tt_img_color(unsigned char* img, int F, int H, int W, int mode, float factor
 int tt_img_box_blur(const unsigned char* in, unsigned char* out, int F, int H, int W, int direction, int radius, unsigned ww, unsigned fw,
                     tt_stream_t stream);
 
+/* ---- N11: annotation clips through the input pipeline - nearest-neighbour gathering, the only resampling a label map may
+ *      see (video_transformations.py:149-157,189-237,366-419,498-601 and Image.rotate of :551), bit-exact with Pillow.
+ *   Clips are uint8 [F, H, W, C] in device memory with C = 1 (label maps, [F, H, W]) or C = 3 (interleaved RGB frames).
+ *   tt_img_gather_nearest   out[f, y, x, :] = in[f, ytab[y], xtab[x], :].  ytab int32 [OH] / xtab int32 [OW] are device memory
+ *                       and built by the caller (timetuning_amd.video_transformations.nearest_table: crop offset + Pillow's
+ *                       NEAREST resize + a flip as a reversed table); every entry must lie in [0, Hin) / [0, Win) - the
+ *                       kernel does not look (timetuning_amd.hip_ops.img_gather_nearest checks the host copies).
+ *                       Exactly one output: out_u8 [F, OH, OW, C], or out_f32 planar [F, C, OH, OW] = ClipToTensor:
+ *                       C = 3 ((float)v / 255 - mean[c]) / std[c] with the arithmetic of tt_img_resample_v (mean3 / std3 HOST
+ *                       pointers to 3 floats, required), C = 1 (float)v / 255 as one IEEE fp32 division (mean3 / std3 ignored).
+ *                       Domain: C in {1, 3}; 1 <= Hin, Win, OH, OW <= 32767; F >= 1 and F (uint8 output) or F * C (float
+ *                       output) <= 65535.  Buffers may exceed 2^31 bytes (64-bit element offsets).
+ *   tt_img_affine_nearest   Pillow's nearest affine transform with zero fill (Geometry.c affine_fixed; what Image.rotate(angle)
+ *                       runs): out [F, H, W, C], out[f, y, x] = in[f, yin, xin] with xin = (a2 + a1 y + a0 x) >> 16,
+ *                       yin = (a5 + a4 y + a3 x) >> 16 (64-bit, arithmetic shifts) when 0 <= xin < W and 0 <= yin < H, else 0.
+ *                       a6 = {a0 .. a5}: HOST pointer to the six 16.16 fixed-point integers
+ *                       (timetuning_amd.video_transformations.rotate_coeffs).  out must not alias in.
+ *                       Domain: C in {1, 3}; 1 <= H, W <= 16384; 1 <= F <= 65535; the four corners (0 | W, 0 | H) must map
+ *                       strictly inside +-32768 source pixels - beyond that Pillow leaves its fixed-point path.
+ *   Outside its domain a call returns TT_EINVAL and launches nothing. */
+int tt_img_gather_nearest(const unsigned char* in, unsigned char* out_u8, float* out_f32, const int* ytab, const int* xtab, int F, int Hin,
+                          int Win, int C, int OH, int OW, const float* mean3, const float* std3, tt_stream_t stream);
+int tt_img_affine_nearest(const unsigned char* in, unsigned char* out, int F, int H, int W, int C, const int* a6, tt_stream_t stream);
+
 /* ---- N5: linear-probe fine-tuning, linear_finetune.py - a 1x1-conv head on frozen features
  *      (linear_finetune.py:13-31), CrossEntropyLoss(ignore_index=255) at mask resolution and torch.optim.SGD (:66-86).
  *      The reference upsamples the D-channel features to R x R and then applies the conv; both are linear and the bilinear

@@ -8,6 +8,9 @@
 //   gray / enhance            rgb2l, ImageEnhance.{Brightness, Contrast, Color} = Blend.c against black / mean gray / gray
 //   hue                       rgb -> hsv -> H += shift (uint8 wrap) -> rgb, Convert.c's float / double mix
 //   box_blur                  BoxBlur.c's extended box filter (3 passes per direction approximate the Gaussian)
+//   gather_nearest / affine_nearest   (N11) what an annotation clip may see: crop + NEAREST resize + flips as one table gather
+//                             (uint8 or the ClipToTensor float plane), and Geometry.c's nearest affine transform (Image.rotate);
+//                             C = 1 label maps and C = 3 frames, 16-byte pieces per thread
 // All of these are byte work bound by HBM: one thread per output pixel (3 channels), coalesced along the row.
 #include "common.hpp"
 
@@ -210,6 +213,136 @@ __global__ __launch_bounds__(IM_THREADS) void box_blur_kernel(const unsigned cha
   o[2] = (unsigned char)((a2 * ww + (unsigned long long)(pl[2] + pr[2]) * fw + (1ull << 23)) >> 24);
 }
 
+// ---- N11: nearest-neighbour gathering for annotation clips (label maps are never blended) and for the crop / flip steps of frames.
+// Both kernels stream bytes: a thread owns one 16-byte-ALIGNED piece of an output row (found from the row's own address, so rows of
+// any width and any start get wide stores in their interior and byte / scalar stores only at their two ends), gathers its bytes /
+// floats through the tables and stores them with one global_store_dwordx4.  Work item = (row y, piece k) inside one frame (or one
+// frame plane for the float output, blockIdx.y); ytab[y] is the same for a whole row of pieces.  Element offsets are 64-bit.
+template <int C>
+__global__ __launch_bounds__(IM_THREADS) void gather_nearest_u8_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
+                                                                       const int* __restrict__ ytab, const int* __restrict__ xtab, int Hin,
+                                                                       int Win, int OH, int OW, int nseg) {
+  const int item = blockIdx.x * IM_THREADS + threadIdx.x;
+  if (item >= OH * nseg) return;
+  const int y = item / nseg, k = item - y * nseg;
+  const long long f = blockIdx.y, rowbytes = (long long)OW * C;
+  unsigned char* orow = out + (f * OH + y) * rowbytes;
+  const unsigned char* irow = in + (f * Hin + ytab[y]) * (long long)Win * C;
+  const int mis = (int)(reinterpret_cast<uintptr_t>(orow) & 15u);
+  const long long s = (long long)k * 16 - mis;
+  const long long b0 = s < 0 ? 0 : s, b1 = s + 16 < rowbytes ? s + 16 : rowbytes;
+  if (b0 >= b1) return;
+  if (b1 - b0 == 16) {
+    unsigned w[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      unsigned v = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int b = (int)b0 + 4 * q + j, px = b / C, ch = b - px * C;
+        v |= (unsigned)irow[(long long)xtab[px] * C + ch] << (8 * j);
+      }
+      w[q] = v;
+    }
+    *reinterpret_cast<uint4*>(orow + b0) = make_uint4(w[0], w[1], w[2], w[3]);
+  } else {
+    for (int b = (int)b0; b < (int)b1; ++b) {
+      const int px = b / C, ch = b - px * C;
+      orow[b] = irow[(long long)xtab[px] * C + ch];
+    }
+  }
+}
+
+// float32 planar output [F, C, OH, OW]; blockIdx.y = f * C + c.  C == 3: ((float)v / 255 - mean[c]) / std[c], the expression of
+// resample_v_kernel; C == 1: (float)v / 255 (an IEEE division: hipcc's default keeps fp32 division correctly rounded, and nothing in
+// the Makefile's flags relaxes it).
+template <int C>
+__global__ __launch_bounds__(IM_THREADS) void gather_nearest_f32_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
+                                                                        const int* __restrict__ ytab, const int* __restrict__ xtab, int Hin,
+                                                                        int Win, int OH, int OW, int nseg, float m0, float m1, float m2,
+                                                                        float s0, float s1, float s2) {
+  const int item = blockIdx.x * IM_THREADS + threadIdx.x;
+  if (item >= OH * nseg) return;
+  const int y = item / nseg, k = item - y * nseg;
+  const long long fc = blockIdx.y, f = fc / C;
+  const int c = (int)(fc - f * C);
+  float* orow = out + (fc * OH + y) * (long long)OW;
+  const unsigned char* irow = in + (f * Hin + ytab[y]) * (long long)Win * C + c;
+  const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+  const int mis = (int)((reinterpret_cast<uintptr_t>(orow) >> 2) & 3u);
+  const int s = k * 4 - mis;
+  const int x0 = s < 0 ? 0 : s, x1 = s + 4 < OW ? s + 4 : OW;
+  if (x0 >= x1) return;
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int x = x0 + j < x1 ? x0 + j : x1 - 1;
+    const float t = (float)irow[(long long)xtab[x] * C] / 255.0f;
+    v[j] = C == 3 ? (t - mean) / sd : t;
+  }
+  if (x1 - x0 == 4) {
+    *reinterpret_cast<float4*>(orow + x0) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int j = 0; j < x1 - x0; ++j) orow[x0 + j] = v[j];
+  }
+}
+
+constexpr int AF_TILE_SEGS = 4, AF_TILE_ROWS = 16;   // one wave: 4 x 16 pieces
+
+// Pillow's affine_fixed (Geometry.c) with the NEAREST filter and zero fill: 16.16 fixed point, evaluated in closed form in 64 bits
+// (the same integers as Pillow's running sums); out and in are both [F, H, W, C].
+template <int C>
+__global__ __launch_bounds__(IM_THREADS) void affine_nearest_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out, int H,
+                                                                    int W, int nseg, int tiles_x, long long a0, long long a1, long long a2,
+                                                                    long long a3, long long a4, long long a5) {
+  // a wave owns AF_TILE_SEGS pieces of AF_TILE_ROWS rows (64 bytes x 16 rows), not 64 pieces of one row: under a rotation the source
+  // of a long thin strip crosses a cache line every few pixels, the source of a compact tile stays within a few dozen lines
+  const int item = blockIdx.x * IM_THREADS + threadIdx.x;
+  const int tile = item >> 6, lane = item & 63;
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int y = ty * AF_TILE_ROWS + lane / AF_TILE_SEGS, k = tx * AF_TILE_SEGS + lane % AF_TILE_SEGS;
+  if (y >= H || k >= nseg) return;
+  const long long f = blockIdx.y, rowbytes = (long long)W * C;
+  unsigned char* orow = out + (f * H + y) * rowbytes;
+  const unsigned char* frame = in + f * H * rowbytes;
+  const long long xrow = a2 + a1 * y, yrow = a5 + a4 * y;
+  const int mis = (int)(reinterpret_cast<uintptr_t>(orow) & 15u);
+  const long long s = (long long)k * 16 - mis;
+  const long long b0 = s < 0 ? 0 : s, b1 = s + 16 < rowbytes ? s + 16 : rowbytes;
+  if (b0 >= b1) return;
+  // the bytes of a piece are consecutive: walk the pixels with 64-bit adds (the same integers as the products), locate each once
+  int px = (int)b0 / C, ch = (int)b0 - px * C;
+  long long xx = xrow + a0 * px, yy = yrow + a3 * px;
+  auto locate = [&]() -> int {   // element offset inside the frame (H, W <= 16384: fits an int), -1 outside
+    const long long xin = xx >> 16, yin = yy >> 16;
+    return (xin >= 0 && xin < W && yin >= 0 && yin < H) ? ((int)yin * W + (int)xin) * C : -1;
+  };
+  int off = locate();
+  auto next = [&]() -> unsigned {
+    const unsigned v = off >= 0 ? frame[off + ch] : 0u;
+    if (++ch == C) {
+      ch = 0;
+      xx += a0;
+      yy += a3;
+      off = locate();
+    }
+    return v;
+  };
+  if (b1 - b0 == 16) {
+    unsigned w[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      unsigned v = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v |= next() << (8 * j);
+      w[q] = v;
+    }
+    *reinterpret_cast<uint4*>(orow + b0) = make_uint4(w[0], w[1], w[2], w[3]);
+  } else {
+    for (int b = (int)b0; b < (int)b1; ++b) orow[b] = (unsigned char)next();
+  }
+}
+
 }  // namespace tt
 
 using namespace tt;
@@ -266,5 +399,73 @@ extern "C" int tt_img_box_blur(const unsigned char* in, unsigned char* out, int 
   hipLaunchKernelGGL(box_blur_kernel, pix_grid((long long)H * W, F), dim3(IM_THREADS), 0, as_stream(stream), in, out, H, W, direction, radius, ww,
                      fw);
   TT_CHECK_LAUNCH("img_box_blur");
+  return TT_OK;
+}
+
+// ---- N11 launchers.  Everything outside the stated domain is refused here, before any launch.
+constexpr int IM_MAX_SIDE = 32767;      // rows / columns of an input or output of the gather
+constexpr int IM_MAX_GRID_Y = 65535;    // frames (uint8 output) or frame planes F * C (float output): the grid's y extent
+constexpr int IM_AFFINE_MAX_SIDE = 16384;
+
+extern "C" int tt_img_gather_nearest(const unsigned char* in, unsigned char* out_u8, float* out_f32, const int* ytab, const int* xtab, int F,
+                                     int Hin, int Win, int C, int OH, int OW, const float* mean3, const float* std3, tt_stream_t stream) {
+  TT_REQUIRE(in && ytab && xtab && (out_u8 != nullptr) != (out_f32 != nullptr), "img_gather_nearest: exactly one output buffer");
+  TT_REQUIRE(C == 1 || C == 3, "img_gather_nearest: C must be 1 (label maps) or 3 (frames), got %d", C);
+  TT_REQUIRE(F > 0 && Hin > 0 && Win > 0 && OH > 0 && OW > 0, "img_gather_nearest: empty clip or output");
+  TT_REQUIRE(Hin <= IM_MAX_SIDE && Win <= IM_MAX_SIDE && OH <= IM_MAX_SIDE && OW <= IM_MAX_SIDE,
+             "img_gather_nearest: sides up to %d (got %d x %d -> %d x %d)", IM_MAX_SIDE, Hin, Win, OH, OW);
+  TT_REQUIRE((long long)F * (out_f32 ? C : 1) <= IM_MAX_GRID_Y, "img_gather_nearest: %d frames x %d planes exceed the grid limit %d", F,
+             out_f32 ? C : 1, IM_MAX_GRID_Y);
+  TT_REQUIRE(!out_f32 || C == 1 || (mean3 && std3), "img_gather_nearest: the float output of frames needs mean and std (host pointers to 3 floats)");
+  TT_REQUIRE(!out_f32 || (reinterpret_cast<uintptr_t>(out_f32) & 3u) == 0, "img_gather_nearest: the float output must be 4-byte aligned");
+  hipStream_t s = as_stream(stream);
+  if (out_u8) {
+    const int nseg = (int)(((long long)OW * C + 30) / 16);   // 16-byte pieces of a row whose start may sit anywhere in a piece
+    const dim3 grid((unsigned)(((long long)OH * nseg + IM_THREADS - 1) / IM_THREADS), (unsigned)F);
+    if (C == 1)
+      hipLaunchKernelGGL(gather_nearest_u8_kernel<1>, grid, dim3(IM_THREADS), 0, s, in, out_u8, ytab, xtab, Hin, Win, OH, OW, nseg);
+    else
+      hipLaunchKernelGGL(gather_nearest_u8_kernel<3>, grid, dim3(IM_THREADS), 0, s, in, out_u8, ytab, xtab, Hin, Win, OH, OW, nseg);
+  } else {
+    const int nseg = (OW + 6) / 4;
+    const dim3 grid((unsigned)(((long long)OH * nseg + IM_THREADS - 1) / IM_THREADS), (unsigned)(F * C));
+    if (C == 1)
+      hipLaunchKernelGGL(gather_nearest_f32_kernel<1>, grid, dim3(IM_THREADS), 0, s, in, out_f32, ytab, xtab, Hin, Win, OH, OW, nseg, 0.f, 0.f, 0.f,
+                         1.f, 1.f, 1.f);
+    else
+      hipLaunchKernelGGL(gather_nearest_f32_kernel<3>, grid, dim3(IM_THREADS), 0, s, in, out_f32, ytab, xtab, Hin, Win, OH, OW, nseg, mean3[0],
+                         mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  }
+  TT_CHECK_LAUNCH("img_gather_nearest");
+  return TT_OK;
+}
+
+extern "C" int tt_img_affine_nearest(const unsigned char* in, unsigned char* out, int F, int H, int W, int C, const int* a6, tt_stream_t stream) {
+  TT_REQUIRE(in && out && in != out && a6, "img_affine_nearest: bad arguments");
+  TT_REQUIRE(C == 1 || C == 3, "img_affine_nearest: C must be 1 (label maps) or 3 (frames), got %d", C);
+  TT_REQUIRE(F > 0 && H > 0 && W > 0, "img_affine_nearest: empty clip");
+  TT_REQUIRE(H <= IM_AFFINE_MAX_SIDE && W <= IM_AFFINE_MAX_SIDE, "img_affine_nearest: sides up to %d (got %d x %d)", IM_AFFINE_MAX_SIDE, H, W);
+  TT_REQUIRE(F <= IM_MAX_GRID_Y, "img_affine_nearest: %d frames exceed the grid limit %d", F, IM_MAX_GRID_Y);
+  // Pillow takes its fixed-point path only while the four corners map inside +-32768 source pixels (Geometry.c check_fixed); outside,
+  // it switches to floating point, which this kernel does not reproduce
+  const long long lim = 32768LL << 16;
+  for (int cy = 0; cy < 2; ++cy)
+    for (int cx = 0; cx < 2; ++cx) {
+      const long long x = cx ? W : 0, y = cy ? H : 0;
+      const long long xx = (long long)a6[2] + (long long)a6[0] * x + (long long)a6[1] * y;
+      const long long yy = (long long)a6[5] + (long long)a6[3] * x + (long long)a6[4] * y;
+      TT_REQUIRE(xx > -lim && xx < lim && yy > -lim && yy < lim, "img_affine_nearest: the transform leaves Pillow's 16.16 fixed-point range");
+    }
+  const int nseg = (int)(((long long)W * C + 30) / 16);
+  const int tiles_x = (nseg + AF_TILE_SEGS - 1) / AF_TILE_SEGS, tiles_y = (H + AF_TILE_ROWS - 1) / AF_TILE_ROWS;
+  const dim3 grid((unsigned)(((long long)tiles_x * tiles_y * 64 + IM_THREADS - 1) / IM_THREADS), (unsigned)F);
+  hipStream_t s = as_stream(stream);
+  if (C == 1)
+    hipLaunchKernelGGL(affine_nearest_kernel<1>, grid, dim3(IM_THREADS), 0, s, in, out, H, W, nseg, tiles_x, (long long)a6[0], (long long)a6[1],
+                       (long long)a6[2], (long long)a6[3], (long long)a6[4], (long long)a6[5]);
+  else
+    hipLaunchKernelGGL(affine_nearest_kernel<3>, grid, dim3(IM_THREADS), 0, s, in, out, H, W, nseg, tiles_x, (long long)a6[0], (long long)a6[1],
+                       (long long)a6[2], (long long)a6[3], (long long)a6[4], (long long)a6[5]);
+  TT_CHECK_LAUNCH("img_affine_nearest");
   return TT_OK;
 }

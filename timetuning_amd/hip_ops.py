@@ -10,6 +10,7 @@ import ctypes as C
 import os
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -820,6 +821,75 @@ def img_box_blur(frames, direction: int, radius: int, ww: int, fw: int):
     Fr, H, W, _ = frames.shape
     out = torch.empty_like(frames)
     _lib.check(lib.tt_img_box_blur(_p(frames), _p(out), Fr, H, W, int(direction), int(radius), int(ww), int(fw), _stream()), "tt_img_box_blur")
+    return out
+
+
+_DEVICE_TABLES: dict = {}
+
+
+def _index_table_on(tab, limit: int, device, what: str):
+    """A host int32 index table -> its device copy (cached by content), after checking every entry against [0, limit): the gather
+    kernel does not look."""
+    t = np.ascontiguousarray(np.asarray(tab), dtype=np.int32)
+    if t.ndim != 1 or t.size == 0:
+        raise ValueError(f"{what}: a non-empty 1-D index table is needed")
+    if int(t.min()) < 0 or int(t.max()) >= limit:
+        raise ValueError(f"{what}: entries must lie in [0, {limit}), got [{int(t.min())}, {int(t.max())}]")
+    key = (str(device), t.tobytes())
+    hit = _DEVICE_TABLES.get(key)
+    if hit is None:
+        if len(_DEVICE_TABLES) > 4096:
+            _DEVICE_TABLES.clear()
+        hit = _DEVICE_TABLES[key] = torch.from_numpy(t).to(device)
+    return hit
+
+
+def _clip_dims(clip, what: str):
+    _chk(clip, what, torch.uint8)
+    if clip.dim() == 3:
+        return (*clip.shape, 1)
+    if clip.dim() == 4:
+        return tuple(clip.shape)
+    raise ValueError(f"{what}: a uint8 clip [F, H, W] (label maps) or [F, H, W, C] is needed, got {tuple(clip.shape)}")
+
+
+def img_gather_nearest(clip, ytab, xtab, to_tensor=None):
+    """``out[f, y, x] = clip[f, ytab[y], xtab[x]]`` for a uint8 clip [F, H, W] (label maps) or [F, H, W, 3] (frames); ``ytab`` /
+    ``xtab`` are HOST integer tables (checked here).  Returns a uint8 clip of the input's kind, or with ``to_tensor`` the finished
+    ``ClipToTensor``: ``(mean, std)`` for frames -> float32 [F, 3, OH, OW], ``True`` for label maps -> float32 [F, 1, OH, OW] = v / 255."""
+    import ctypes as C
+
+    lib = _lib.load()
+    Fr, H, W, Cn = _clip_dims(clip, "clip")
+    yt, xt = _index_table_on(ytab, H, clip.device, "ytab"), _index_table_on(xtab, W, clip.device, "xtab")
+    OH, OW = yt.numel(), xt.numel()
+    if to_tensor is None:
+        out = torch.empty((Fr, OH, OW) if clip.dim() == 3 else (Fr, OH, OW, Cn), dtype=torch.uint8, device=clip.device)
+        _lib.check(lib.tt_img_gather_nearest(_p(clip), _p(out), None, _p(yt), _p(xt), Fr, H, W, Cn, OH, OW, None, None, _stream()),
+                   "tt_img_gather_nearest")
+        return out
+    out = torch.empty((Fr, Cn, OH, OW), dtype=f32, device=clip.device)
+    m3 = s3 = None
+    if to_tensor is not True:
+        mean, std = to_tensor
+        m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(lib.tt_img_gather_nearest(_p(clip), None, _p(out), _p(yt), _p(xt), Fr, H, W, Cn, OH, OW, m3, s3, _stream()),
+               "tt_img_gather_nearest")
+    return out
+
+
+def img_affine_nearest(clip, coeffs):
+    """Pillow's nearest affine transform with zero fill on a uint8 clip [F, H, W] or [F, H, W, 3]; ``coeffs`` are the six 16.16
+    fixed-point integers (a0 .. a5) of ``video_transformations.rotate_coeffs``."""
+    import ctypes as C
+
+    lib = _lib.load()
+    Fr, H, W, Cn = _clip_dims(clip, "clip")
+    if len(coeffs) != 6:
+        raise ValueError("six fixed-point coefficients are needed")
+    a6 = (C.c_int * 6)(*[int(v) for v in coeffs])
+    out = torch.empty_like(clip)
+    _lib.check(lib.tt_img_affine_nearest(_p(clip), _p(out), Fr, H, W, Cn, a6, _stream()), "tt_img_affine_nearest")
     return out
 
 

@@ -461,7 +461,8 @@ def synthetic_davis_labels(T: int, H: int, W: int, num_objects: int, seed: int):
 
 def build_parser() -> argparse.ArgumentParser:
     """Flag names and defaults of ``mask_propagation.py:849-871`` (``type=bool`` flags keep the any-non-empty-string-is-True
-    quirk).  ``--dataset synthetic``, ``--num_clips`` and ``--davis_metrics`` are additions: the dataset readers are out of scope."""
+    quirk).  ``--dataset synthetic`` / ``synthetic_frames``, ``--raw_size``, ``--num_clips`` and ``--davis_metrics`` are additions: the
+    dataset readers are out of scope."""
     p = argparse.ArgumentParser()
     p.add_argument("--architecture", type=str, default="dino-s16")
     p.add_argument("--model_path", type=str, default="../models/leopart_vits16.ckpt")
@@ -488,6 +489,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_clips", type=int, default=4, help="synthetic data only")
     p.add_argument("--davis_metrics", action="store_true",
                    help="also print DAVIS J / F mean, recall and decay and J&F-Mean per clip and overall (addition)")
+    p.add_argument("--raw_size", type=int, nargs=2, default=(360, 480), metavar=("H", "W"),
+                   help="--dataset synthetic_frames: size of the raw uint8 frames and label maps that go through the reference's "
+                        "Resize -> RandomCrop -> ClipToTensor pair transform; multiples of 8 (addition)")
     p.add_argument("--frame_size", type=int, nargs=2, default=None, metavar=("H", "W"),
                    help="synthetic H x W clips propagated on their native token grid (H / P, W / P) and scored at H x W; multiples of "
                         "the patch size P (addition)")
@@ -524,6 +528,31 @@ def synthetic_tracking_clip(fs: int, resolution: int, seed: int, objects: int = 
     return torch.from_numpy(np.stack(frames).astype(np.float32)), torch.from_numpy(np.stack(masks))
 
 
+def synthetic_frame_clip(fs: int, height: int, width: int, seed: int, objects: int = 2):
+    """``synthetic_tracking_clip`` as a decoder would hand it over: raw frames uint8 [fs, H, W, 3] (the unit-normal textures mapped to
+    127 + 50 x, clipped) and label maps uint8 [fs, H, W] (0 = background, objects 1..).  H and W are multiples of the 8 x 8 texture cell."""
+    if height <= 0 or width <= 0 or height % 8 or width % 8:
+        raise ValueError(f"raw size {height} x {width}: both sides must be positive multiples of 8")
+    clip, masks = synthetic_tracking_clip(fs, height, seed, objects, width=width)
+    frames = (127.0 + 50.0 * clip).clamp_(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+    return frames, masks.to(torch.uint8)
+
+
+def synthetic_frames_clip(args, index: int, device):
+    """Clip ``index`` of ``--dataset synthetic_frames``: raw frames and label maps through ``propagation_transforms`` (the pair
+    transform of ``mask_propagation.py:779``, seeded per clip) and ``read_batch``'s uint8 conversion, as the reference's loader
+    delivers them: (clip float32 [fs, 3, R, R], masks int64 [fs, R, R]) on ``device``."""
+    import random
+
+    from . import video_transformations as VT
+
+    H, W = (int(v) for v in args.raw_size)
+    frames, labels = synthetic_frame_clip(args.num_frames, H, W, seed=index + 1)
+    random.seed(index + 1)
+    data, ann = VT.propagation_transforms(args.input_resolution)(frames.to(device), labels.to(device))
+    return data, VT.annotations_to_uint8(ann[None])[0].long()
+
+
 def clip_size(args, patch_size: int) -> Tuple[int, int]:
     """(H, W) of the evaluation clips: ``--frame_size H W`` (each a multiple of the patch size, else ValueError) or the square
     ``--input_resolution``."""
@@ -540,15 +569,21 @@ _FLOW_FRAME_MULTIPLE = 8
 
 
 def mask_propagation(args) -> float:
-    """The evaluation loop of ``mask_propagation.py:757-846`` on synthetic clips; returns the mean J over clips.  With
+    """The evaluation loop of ``mask_propagation.py:757-846`` on synthetic clips; returns the mean J over clips.  ``--dataset
+    synthetic`` renders normalised clips at the model's size; ``--dataset synthetic_frames`` renders raw uint8 frames with label maps at
+    ``--raw_size`` and takes them through the reference's pair transform first (``synthetic_frames_clip``).  With
     ``--davis_metrics`` it also prints the DAVIS statistics (``db_statistics`` over each object's frames) per clip and over all
     objects of all clips; the return value is the same.  ``--use_optical_flow`` runs the optical-flow baseline
     (``propagate_clip_optical_flow``) on the same clips, with the same scoring, and builds no backbone.  Both branches score predicted
     frame j against annotated frame j; the reference compares ``predictions[:, 1:]`` with ``annotations[:, 1:]``, one frame off."""
-    if args.dataset != "synthetic":
-        raise NotImplementedError("dataset readers (data_loader.py) are out of scope for this build; run with --dataset synthetic")
+    if args.dataset not in ("synthetic", "synthetic_frames"):
+        raise NotImplementedError("dataset readers (data_loader.py) are out of scope for this build; run with --dataset synthetic "
+                                  "or synthetic_frames")
     use_flow = bool(args.use_optical_flow)
     native = getattr(args, "frame_size", None) is not None
+    raw_frames = args.dataset == "synthetic_frames"
+    if raw_frames and native:
+        raise ValueError("--dataset synthetic_frames crops to --input_resolution as the reference's loader does; --frame_size does not apply")
     device = torch.device("cuda", 0)
     if use_flow:
         H, W = clip_size(args, _FLOW_FRAME_MULTIPLE)
@@ -563,7 +598,9 @@ def mask_propagation(args) -> float:
     scores = []
     davis = []   # per object: (J_M, J_R, J_D, F_M, F_R, F_D)
     for i in range(args.num_clips):
-        if native:
+        if raw_frames:
+            clip, masks = synthetic_frames_clip(args, i, device)
+        elif native:
             clip, masks = synthetic_tracking_clip(args.num_frames, H, seed=i + 1, width=W)
         else:
             clip, masks = synthetic_tracking_clip(args.num_frames, args.input_resolution, seed=i + 1)

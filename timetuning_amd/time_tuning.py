@@ -1066,6 +1066,34 @@ class SyntheticEvalClips:
         return iter(self.batches)
 
 
+class SyntheticEvalFrameClips:
+    """``SyntheticEvalClips`` from the decoder's side: raw uint8 frames ``[fs, H, W, 3]`` with uint8 label maps ``[fs, H, W]`` at
+    ``raw_size`` go through ``evaluation_transforms(resolution)`` (the pair transform of ``evaluation.py:533``) and ``read_batch``'s uint8
+    conversion; batches ``(data [bs,1,fs,3,R,R] float32, annotations [bs,1,fs,R,R] uint8)`` as ``Evaluator.evaluate`` takes them."""
+
+    def __init__(self, num_clips, num_frames, resolution, batch_size, device, raw_size=(360, 480)):
+        from . import mask_propagation as MP
+        from . import video_transformations as VT
+
+        transform = VT.evaluation_transforms(resolution)
+        H, W = raw_size
+        self.batches = []
+        for b0 in range(0, num_clips, batch_size):
+            data, ann = [], []
+            for i in range(b0, min(num_clips, b0 + batch_size)):
+                frames, labels = MP.synthetic_frame_clip(num_frames, H, W, seed=900 + i)
+                d, a = transform(frames.to(device), labels.to(device))
+                data.append(d)
+                ann.append(a)
+            self.batches.append((torch.stack(data).unsqueeze(1), VT.annotations_to_uint8(torch.stack(ann)).unsqueeze(1)))
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __iter__(self):
+        return iter(self.batches)
+
+
 def seed_everything(seed: int = 1) -> None:
     """The reference seeds python / numpy / torch with 1 at import time (time_tuning.py:66-69): prototype initialisation and
     the queue permutations (``torch.randperm``, :259) are reproducible from run to run."""
