@@ -135,6 +135,47 @@ def test_planes_route_decisions_without_a_gpu():
     assert route(3, 25216, 1152, 200) == 0                       # K not a multiple of two K-tiles
 
 
+def _knob_table():
+    """(name, default) of every tuning knob, as csrc/core.cpp documents them; the enum of csrc/common.hpp must have as many entries."""
+    core = open(os.path.join(REPO, "timetuning_amd", "csrc", "core.cpp")).read()
+    names = re.findall(r'"(TT_[A-Z0-9_]+)"', re.search(r"kKnobNames\[KNOB_COUNT\] = \{(.*?)\};", core, flags=re.S).group(1))
+    defaults = [int(v) for v in re.search(r"kKnobDefaults\[KNOB_COUNT\] = \{(.*?)\};", core, flags=re.S).group(1).split(",")]
+    common = open(os.path.join(REPO, "timetuning_amd", "csrc", "common.hpp")).read()
+    enum = re.findall(r"\bKNOB_[A-Z0-9_]+", re.search(r"enum \{ (KNOB_.*?KNOB_COUNT) \};", common).group(1))
+    assert enum[-1] == "KNOB_COUNT" and ["TT_" + e[5:] for e in enum[:-1]] == names and len(defaults) == len(names)
+    return list(zip(names, defaults))
+
+
+def test_tuning_knob_setter_knows_every_documented_knob_and_no_retired_one():
+    """tt_set_tuning_knob takes every knob of the table in core.cpp (names, defaults and the enum of common.hpp are three parallel lists) and
+    setting a knob back to its default restores the default dispatch - seen through the route queries for the knobs that have one, among
+    them the entries that follow the two retired names in the table.  A retired knob is an error, not a silent no-op: a tool that still
+    passes TT_Q8_STREAM (the round-4 pair kernel) or TT_PAIRS_NBUF (a forced ring depth) must hear about it."""
+    lib = _lib.load()
+    table = _knob_table()
+    assert len(table) == 17 and len(set(n for n, _ in table)) == 17
+    pairs = lambda M, N, K: lib.tt_linear_fwd_pairs_route(M, N, K, 0, 1, 0, 1, 0, 0)
+    planes = lambda: lib.tt_linear_fwd_planes_route(1, 25216, 768, 3072, 0, 1, 1, 1, 0, 0)
+    # knob -> (a non-default value, the route query it moves, its answer at the default, its answer at that value); no device: 256 CUs
+    seen = {"TT_PLANES_VARIANT": (10, planes, 8, 0),                                # any non-zero value: the general kernel
+            "TT_PAIRS_NO8": (1, lambda: pairs(25216, 384, 384), 8, 0),
+            "TT_Q8_MIN_TILES": (96, lambda: pairs(6272, 512, 1024), 0, 8),          # 100 tiles of 256 x 128
+            "TT_Q4_SMALL": (1, lambda: pairs(6304, 384, 384), 0, 8)}                # 75 tiles: the four-wave kernel takes them under the knob
+    try:
+        for name, default in table:
+            assert lib.tt_set_tuning_knob(name.encode(), default) == 0, name
+        for name, (value, query, at_default, at_value) in seen.items():
+            assert query() == at_default, name
+            assert lib.tt_set_tuning_knob(name.encode(), value) == 0 and query() == at_value, name
+            assert lib.tt_set_tuning_knob(name.encode(), dict(table)[name]) == 0 and query() == at_default, name
+        for retired in ("TT_Q8_STREAM", "TT_PAIRS_NBUF"):
+            assert lib.tt_set_tuning_knob(retired.encode(), 1) == -1                 # TT_EINVAL
+            assert "unknown knob" in lib.tt_last_error().decode() and retired in lib.tt_last_error().decode()
+    finally:
+        for name, default in table:
+            lib.tt_set_tuning_knob(name.encode(), default)
+
+
 def test_queue_fullness_is_tracked_on_the_host():
     """Own pushes are counted on the host; a write from outside (copy_, set_queue) is detected by the storage / version signature and
     answered by the reference's own check of the last row (time_tuning.py:207)."""

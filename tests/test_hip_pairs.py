@@ -334,8 +334,9 @@ def test_hip_pair_ops_equal_their_cpu_twins():
 
 
 def test_pairs8_load_part_orders_give_the_same_bits():
-    """TT_Q8_ORDER only moves a wave's DMA instructions relative to its fragment reads inside a phase of gemm_pairs8_kernel: every order
-    must leave the same bits (a hazard in the counted-vmcnt schedule would show here or as a run-to-run difference)."""
+    """TT_Q8_ORDER reaches the persistent pair kernel as Q8Args::order_mode and must never change what it computes (the kernel that ships
+    has one order of its DMA sites and fragment reads; the value only tells a stamp build to print): every value must leave the same bits
+    (a hazard in the counted-vmcnt schedule would show here or as a run-to-run difference)."""
     from timetuning_amd import hip_ops as ops
 
     M, N, K = 25216, 384, 384

@@ -95,8 +95,8 @@ __device__ __forceinline__ void wait_vmcnt() {
 // PAIR (round 4): the operands are fp16 PAIRS (common.hpp split_pair; gemm_pairs8.hip) - P = 1, BK = 64: a "row" of 64 16-bit elements is
 // one pair group [hi x 32][lo x 32] of a 32-deep K-tile, g.K counts 16-bit elements (2 x the reduction length), and a term costs three
 // v_mfma_f32_32x32x16_f16 into two accumulator sets (hi hi | hi lo + lo hi, folded with 2^-11 in the epilogue).  The general-shape
-// kernel of the "f16x3" mode: everything the persistent gemm_pairs8_kernel does not take (any M, N % 64 == 0, the projection head,
-// pre-activation outputs, gelu' products, split-K).
+// kernel of the "f16x3" mode: everything the persistent gemm_pairs8s_kernel does not take (any M, N % 64 == 0, grids too small for a
+// persistent launch, split-K).
 template <int P, int BK, int WM, int WN, int NBUF, int GM = 2, int GN = 2, int LD = 0, bool PAIR = false>
 __global__ __launch_bounds__(64 * GM * GN * (1 + LD)) void gemm_planes_kernel(PlaneArgs g) {
   static_assert(!PAIR || (P == 1 && BK == 64), "pair operands: one 128-byte row per 32-deep K-tile");
@@ -922,7 +922,10 @@ static int linear_planes_impl(const void* x_planes, long long x_plane_stride, co
   PlaneArgs g{static_cast<const __bf16*>(x_planes), static_cast<const __bf16*>(w_planes), x_plane_stride, w_plane_stride, M, N, K, bias, residual, y,
               pre_out, static_cast<__bf16*>(y_planes), y_plane_stride, y_nplanes, act, gelu_pre, splits, split_stride, nullptr};
   hipStream_t s = as_stream(stream);
-  const int variant = tuning_knob(KNOB_PLANES_VARIANT);   // tuning aid (tt_set_tuning_knob: A/B in one process)
+  // tuning aid (tt_set_tuning_knob: A/B in one process): 0 the default dispatch; any other value skips the persistent kernel and the
+  // 8-wave tiles below - the general kernel at 128 x 128 / 64-row tiles (the tile experiments of rounds 2 and 3 that the values 1 - 9
+  // once selected: profiles/r02_gemm_planes_variants.txt, r03_p8_variants.txt)
+  const int variant = tuning_knob(KNOB_PLANES_VARIANT);
   // whole-tile forward products on a grid that fills the chip: the persistent 8-phase kernel (gemm_planes8.hip)
   if (variant == 0 && !pre_out && !gelu_pre && splits == 1) {
     const int rc = planes8_try(x_planes, x_plane_stride, w_planes, w_plane_stride, planes, bias, residual, y, y_planes, y_plane_stride, y_nplanes, M, N,
@@ -937,15 +940,6 @@ static int linear_planes_impl(const void* x_planes, long long x_plane_stride, co
   switch (planes) {
     case 1:
       if (big) {
-        if (variant == 1) return launch_planes<1, 64, 2, 2, 2>(g, s);
-        if (variant == 2) return launch_planes<1, 32, 2, 2, 3>(g, s);
-        if (variant == 3) return launch_planes<1, 64, 2, 2, 3>(g, s);
-        if (variant == 4 && N % 256 == 0) return launch_planes<1, 32, 4, 2, 3, 2, 4>(g, s);   // 256 x 256, 8 waves of 128 x 64
-        if (variant == 5 && N % 256 == 0) return launch_planes<1, 64, 4, 2, 2, 2, 4>(g, s);   // same, 128-byte rows, 2 slabs
-        if (variant == 6) return launch_planes<1, 32, 2, 2, 4, 4, 2>(g, s);                    // 256 x 128, 8 waves of 64 x 64
-        if (variant == 7) return launch_planes<1, 64, 2, 2, 3, 4, 2>(g, s);
-        if (variant == 8) return launch_planes<1, 32, 2, 2, 4, 2, 2, 1>(g, s);                 // 128 x 128, 4 compute + 4 loader waves
-        if (variant == 9) return launch_planes<1, 64, 2, 2, 2, 2, 2, 1>(g, s);
         // default: 256 x 256 (8 waves) when that still makes >= 3 tiles per CU (ViT-B/16 qkv / fc1: 131 / 208 us against 150 / 213
         // for 128 x 128, profiles/r02_gemm_planes_variants.txt), else 128 x 128 with a 4-slab ring
         if (variant == 0 && N % 256 == 0 && (long long)((M + 255) / 256) * (N / 256) >= 3 * 256) return launch_planes<1, 64, 4, 2, 2, 2, 4>(g, s);
@@ -959,22 +953,12 @@ static int linear_planes_impl(const void* x_planes, long long x_plane_stride, co
       return launch_planes<2, 32, 1, 1>(g, s);
     default:
       if (big) {
-        if (variant == 1) return launch_planes<3, 16, 2, 2, 2>(g, s);
-        if (variant == 2) return launch_planes<3, 16, 2, 2, 4>(g, s);
-        if (variant == 3) return launch_planes<3, 32, 2, 2, 2>(g, s);
-        if (variant == 6) return launch_planes<3, 32, 2, 2, 2, 4, 2>(g, s);                    // 256 x 128, 8 waves, 64-byte rows
-        if (variant == 7) return launch_planes<3, 16, 2, 2, 2, 4, 2>(g, s);
-        if (variant == 8) return launch_planes<3, 16, 2, 2, 3, 2, 2, 1>(g, s);
-        if (variant == 9) return launch_planes<3, 32, 2, 2, 2, 2, 2, 1>(g, s);
         // default: 256 x 128 (8 waves, 64-byte rows) when that still makes >= 3 tiles per CU (ViT-S/16 qkv / fc1: 160 / 230 us against
         // 185 / 247), else 128 x 128
         if (variant == 0 && (long long)((M + 255) / 256) * (N / 128) >= 3 * 256) return launch_planes<3, 32, 2, 2, 2, 4, 2>(g, s);
         return launch_planes<3, 16, 2, 2, 3>(g, s);
       }
-      if (wide) {
-        if (variant == 1) return launch_planes<3, 16, 1, 2, 2>(g, s);
-        return launch_planes<3, 32, 1, 2, 2>(g, s);
-      }
+      if (wide) return launch_planes<3, 32, 1, 2, 2>(g, s);
       return launch_planes<3, 16, 1, 1>(g, s);
   }
 }
@@ -1027,21 +1011,16 @@ static int linear_pairs_impl(const void* x_pairs, const void* w_pairs, const flo
   const long long t128 = (long long)((M + 127) / 128) * (N / 128);
   const bool big = (N % 128 == 0) && t128 * splits >= 3 * 256;
   const bool wide = (N % 128 == 0) && (long long)((M + 63) / 64) * (N / 128) * splits >= 2 * 256;
-  // Ring depth (round 5; knob TT_PAIRS_NBUF: 0 = this rule, 2 .. 6 = forced).  These are the launches that do not fill the chip, and in a
+  // Ring depth (the sweep of 2 .. 6 slabs: profiles/r06_step_knob_sweeps.txt).  These are the launches that do not fill the chip, and in a
   // step their operands are cold (HBM / MALL, not L2): a workgroup's K loop is a chain of LDS-DMA latencies - one per 32-deep K-tile with a
   // double buffer, a half / a third of one with two / three K-tiles in flight.  Three slabs everywhere (C2 -0.8 %); four on the 64 x 64
   // tile while the grid is under two workgroups per CU, where the 64 KB cost no residency (C1 2.39 -> 2.09 ms; at 594 tiles - the
   // 6304-row launches of C2 - four measured slower than two).  With hot operands (tools/ab_pairs.py) the depth changes nothing.
-  const int knob = tuning_knob(KNOB_PAIRS_NBUF);
   const long long t64 = (long long)((M + 63) / 64) * (N / 64) * splits;
-  const int nbuf = knob ? knob : (!big && !wide && t64 <= 2LL * device_cu_count() ? 4 : 3);
-  if (big) return nbuf >= 3 ? launch_planes<1, 64, 2, 2, 3, 2, 2, 0, true>(g, s) : launch_planes<1, 64, 2, 2, 2, 2, 2, 0, true>(g, s);
-  if (wide) return nbuf >= 3 ? launch_planes<1, 64, 1, 2, 3, 2, 2, 0, true>(g, s) : launch_planes<1, 64, 1, 2, 2, 2, 2, 0, true>(g, s);
-  if (nbuf >= 6) return launch_planes<1, 64, 1, 1, 6, 2, 2, 0, true>(g, s);
-  if (nbuf == 5) return launch_planes<1, 64, 1, 1, 5, 2, 2, 0, true>(g, s);
-  if (nbuf == 4) return launch_planes<1, 64, 1, 1, 4, 2, 2, 0, true>(g, s);
-  if (nbuf == 3) return launch_planes<1, 64, 1, 1, 3, 2, 2, 0, true>(g, s);
-  return launch_planes<1, 64, 1, 1, 2, 2, 2, 0, true>(g, s);
+  if (big) return launch_planes<1, 64, 2, 2, 3, 2, 2, 0, true>(g, s);
+  if (wide) return launch_planes<1, 64, 1, 2, 3, 2, 2, 0, true>(g, s);
+  if (t64 <= 2LL * device_cu_count()) return launch_planes<1, 64, 1, 1, 4, 2, 2, 0, true>(g, s);
+  return launch_planes<1, 64, 1, 1, 3, 2, 2, 0, true>(g, s);
 }
 
 extern "C" int tt_linear_fwd_pairs_route(int M, int N, int K, int act, int has_bias, int has_residual, int has_y, int has_y_pairs,

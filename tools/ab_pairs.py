@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of tt_linear_fwd_pairs between library builds in one process (tools/build_variant.sh) on the ViT-S/16 and ViT-B/16 block shapes;
 outputs compared bit for bit.  usage: ab_pairs.py libA.so libB.so ...
-An entry may carry tuning knobs, set before each of its launches: `label=path.so:TT_Q8_STREAM=0,TT_Q8_KSPLIT=1` (A/B of two dispatch settings
+An entry may carry tuning knobs, set before each of its launches: `label=path.so:TT_Q8_MIN_TILES=96,TT_Q8_KSPLIT=1` (A/B of two dispatch settings
 of ONE library: the same path may appear twice)."""
 import ctypes as C, os, statistics, sys, torch
 import sys as _sys, os as _os; _sys.path.insert(0, _os.path.dirname(_os.path.abspath(__file__)))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times tt_linear_fwd_planes on the block shapes of C2 (ViT-S/16, planes 3) and C4 (ViT-B/16, planes 1).
-TT_PLANES_VARIANT=<n> selects a tuning variant of the dispatcher (gemm_planes.hip); one process per variant."""
+TT_PLANES_VARIANT=0 is the default dispatch, any other value the general kernel only (gemm_planes.hip); one process per value."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

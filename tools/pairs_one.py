@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One kernel of the "f16x3" mode, a few launches, for the rocprofv3 --pmc passes (tools/pmc_pairs.sh).
-  pairs_one.py gemm M N K epi      epi: f32 | res | pairs | gelu        (gemm_pairs8_kernel where the shape allows)
+  pairs_one.py gemm M N K epi      epi: f32 | res | pairs | gelu        (gemm_pairs8s_kernel where the shape allows)
   pairs_one.py attn F N H          attention_fwd_pairs_kernel (N <= 256) / attention_fwd_pairs_flash_kernel
   pairs_one.py tn M N K            gemm_pairs_tn_kernel: dW [N, K] from row pairs dy [M, N], x [M, K]"""
 import sys

@@ -24,9 +24,9 @@ print(f"{'kernel':90s} {'launches':>8s} {'read MB':>9s} {'write MB':>9s}")
 for tot, k, n, fb, wb in rows[:14]:
     print(f"{k[:90]:90s} {n:8d} {fb/1e6:9.1f} {wb/1e6:9.1f}")
 if len(sys.argv) > 3:
-    # the dominant kernel of the step (bench.py's roofline kernel, keyed by label): round 4 - gemm_pairs8_kernel (all epilogue instantiations
+    # the dominant kernel of the step (bench.py's roofline kernel, keyed by label): rounds 4 on - the persistent pair kernel (all epilogue instantiations
     # together, as the bench line books them); earlier rounds - the gemm_nt_fast instantiation with the most launches
-    pairs = [r for r in rows if "gemm_pairs8" in r[1]]   # gemm_pairs8s_kernel (round 5) / gemm_pairs8_kernel
+    pairs = [r for r in rows if "gemm_pairs8" in r[1]]   # gemm_pairs8s_kernel (round 4 profiles: its predecessor, same prefix)
     head = sys.argv[4] if len(sys.argv) > 4 else "unknown"
     if pairs:
         n = sum(r[2] for r in pairs)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where gemm_pairs8's time goes: interleaved timing of its crippled instantiations (tools/build_variant.sh q8ablate gemm_pairs8.hip
+"""Where gemm_pairs8s_kernel's time goes: interleaved timing of its crippled instantiations (tools/build_variant.sh q8ablate gemm_pairs8.hip
 -DTT_Q8_ABLATE; TT_Q8_DBG bit mask: 1 no MFMAs, 2 no LDS-DMA, 8 no epilogue) on the ViT-S/16 / ViT-B/16 block shapes and on a shape with
 an exact tile count per CU."""
 import ctypes as C, os, statistics, sys, torch
@@ -17,7 +17,7 @@ lib.tt_split_pairs.restype = C.c_int
 lib.tt_split_pairs.argtypes = [vp, vp, ll, vp, vp]
 st = torch.cuda.current_stream().cuda_stream
 NAMES = {0: "full", 1: "noMFMA", 2: "noDMA", 8: "noEpi", 9: "noEpi+noMFMA", 10: "noEpi+noDMA", 3: "noMFMA+noDMA", 11: "reads+barriers only"}
-if "hot" in sys.argv:   # round 6: + the hot-operand instantiations of gemm_pairs8s_kernel (every item streams operand tile (0, 0))
+if "hot" in sys.argv:   # round 6: + the hot-operand instantiations (every item streams operand tile (0, 0))
     sys.argv.remove("hot")
     NAMES.update({4: "hot", 12: "hot+noEpi", 13: "hot+noEpi+noMFMA"})
 def split(x):
@@ -28,15 +28,7 @@ def split(x):
 cases = [(16384, 1024, 384, 0, 0, 0, "ideal 2 tiles/CU K384 f32out"), (16384, 1024, 1536, 0, 0, 1, "ideal 2 tiles/CU K1536 f32+res"),
          (25216, 1152, 384, 0, 0, 0, "qkv"), (25216, 384, 384, 0, 0, 1, "proj"), (25216, 1536, 384, 1, 1, 0, "fc1"), (25216, 384, 1536, 0, 0, 1, "fc2"),
          (25216, 2304, 768, 0, 0, 0, "B qkv"), (25216, 768, 3072, 0, 0, 1, "B fc2")]
-# first argument `stream=0|1`: which persistent kernel (TT_Q8_STREAM: 1 = gemm_pairs8s_kernel, round 5; 0 = gemm_pairs8_kernel)
-args = sys.argv[1:]
-if args and args[0].startswith("stream="):
-    lib.tt_set_tuning_knob.restype = C.c_int
-    lib.tt_set_tuning_knob.argtypes = [C.c_char_p, C.c_int]
-    assert lib.tt_set_tuning_knob(b"TT_Q8_STREAM", int(args[0][7:])) == 0
-    print(f"== TT_Q8_STREAM = {args[0][7:]}", flush=True)
-    args = args[1:]
-only = args
+only = sys.argv[1:]
 for M, N, K, act, po, res, name in cases:
     if only and name not in only: continue
     x = split(torch.randn(M, K, device="cuda")); w = split(torch.randn(N, K, device="cuda") * 0.05)
