@@ -37,9 +37,13 @@ typedef void* tt_stream_t;
 
 const char* tt_last_error(void);
 int tt_abi_version(void);   /* 8 = this header (7: before `precision` became an argument - tt_set_gemm_precision, a process-wide switch, is gone; 6: before the caller-owned K-split workspace and the range flag; 5: before the transpose-free weight gradient, the batched operand refresh and the distributed Sinkhorn steps; 4: before the fp16-pair entry points; 3: before tt_vit_params.patch_wp; 2: before the coarse entry points) */
-/* Tuning knobs of the dispatchers (names and defaults: the table kKnobNames / kKnobDefaults in csrc/core.cpp) are read ONCE from the
+/* Tuning knobs of the dispatchers (names and defaults: the one list TT_KNOB_LIST in csrc/common.hpp) are read ONCE from the
  * environment; this setter changes one afterwards - for the A/B tools and tests only.  An unknown name is TT_EINVAL. */
 int tt_set_tuning_knob(const char* name, int value);
+/* Row `index` of that list: fills the non-null outputs with the knob's environment name (a static string), its default and its current
+ * value.  TT_EINVAL for an index outside the list - so a caller enumerates from 0 until it is refused; that refusal is no failure and
+ * leaves tt_last_error as it was. */
+int tt_tuning_knob_info(int index, const char** name, int* default_value, int* value);
 /* Fills name (<= cap bytes) with the gcnArchName of the current device; returns CU count or <0. */
 int tt_device_info(char* name, int cap);
 

@@ -29,7 +29,6 @@ The grid entry agrees with the square entry within the one-frame bound wherever 
 from __future__ import annotations
 
 import contextlib
-import os
 
 import numpy as np
 import torch
@@ -52,26 +51,9 @@ def map_bound(m: int) -> float:
     return TOL_MAP + max(m - 1, 0) * EPS32
 
 
-@contextlib.contextmanager
-def sims_cap(mb, monkeypatch=None):
-    """TT_LP_SIMS_CAP_MB for the calls inside (``monkeypatch``: pytest's, where there is one)."""
-    name = "TT_LP_SIMS_CAP_MB"
-    if monkeypatch is not None:
-        monkeypatch.setenv(name, str(mb))
-        try:
-            yield
-        finally:
-            monkeypatch.delenv(name)
-        return
-    old = os.environ.get(name)
-    os.environ[name] = str(mb)
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ[name]
-        else:
-            os.environ[name] = old
+def sims_cap(side, mb):
+    """The knob TT_LP_SIMS_CAP_MB for the HIP side's calls inside (the twins hold every frame's similarities at once: nothing to cap)."""
+    return side.ops.tuning_knob("TT_LP_SIMS_CAP_MB", mb) if side.name == "hip" else contextlib.nullcontext()
 
 
 # ---- the two sides ---------------------------------------------------------------------------------------------------------------------------
@@ -297,7 +279,7 @@ def lp_refusal(p):
     return None
 
 
-def check_label_prop(side, p, rng, note, monkeypatch=None):
+def check_label_prop(side, p, rng, note):
     bs, fs, g, D, K, nl, r, topk, prec, dup = (p[k] for k in ("bs", "fs", "g", "D", "K", "nl", "r", "topk", "prec", "dup"))
     n = g * g
     routes = [side.route(fs, g, K, nl, r, t) for t in range(1, fs)]
@@ -328,7 +310,7 @@ def check_label_prop(side, p, rng, note, monkeypatch=None):
             assert np.array_equal(two[0], labels) and np.array_equal(two[1], pmap), (fam, "two-call form differs")
         # every chunking equals the whole run
         for cap in lp_caps(p):
-            with sims_cap(cap, monkeypatch):
+            with sims_cap(side, cap):
                 assert np.array_equal(side.lp_maps(xn, seed, nl, r, topk, prec), maps), (fam, "chunked run differs", cap, lp_chunk(bs, fs, n, nl, cap))
                 if side.name == "hip" and lp_chunk(bs, fs, n, nl, cap) < fs - 1:
                     assert side.lp_labels(xn, seed, nl, r, topk, prec, two_call=True) is None
@@ -340,7 +322,7 @@ def check_label_prop(side, p, rng, note, monkeypatch=None):
             judge_maps(gm, xn, seed, (g, g), nl, r, topk, note, "grid entry on the square grid,", False, pair, False)
 
 
-def check_label_prop_grid(side, p, rng, note, monkeypatch=None):
+def check_label_prop_grid(side, p, rng, note):
     bs, fs, gh, gw, D, K, nl, r, topk, prec, dup = (p[k] for k in ("bs", "fs", "gh", "gw", "D", "K", "nl", "r", "topk", "prec", "dup"))
     n = gh * gw
     seed, pair = seeds(rng, bs, n, K, dup)
@@ -354,7 +336,7 @@ def check_label_prop_grid(side, p, rng, note, monkeypatch=None):
 
 # ---- the up-sampler ------------------------------------------------------------------------------------------------------------------------------
 
-def check_upsample_argmax_hw(side, p, rng, note, monkeypatch=None):
+def check_upsample_argmax_hw(side, p, rng, note):
     M, gh, gw, K, H, W, dup = (p[k] for k in ("M", "gh", "gw", "K", "H", "W", "dup"))
     maps = rng.random((M, gh * gw, K))
     pair = None
@@ -384,5 +366,5 @@ def check_upsample_argmax_hw(side, p, rng, note, monkeypatch=None):
 CHECK = {"label_prop": check_label_prop, "label_prop_grid": check_label_prop_grid, "upsample_argmax_hw": check_upsample_argmax_hw}
 
 
-def run_prop_case(side, op: str, params: dict, worst: dict, monkeypatch=None) -> None:
-    CHECK[op](side, params, case_rng(op, params), make_note(worst, op), monkeypatch)
+def run_prop_case(side, op: str, params: dict, worst: dict) -> None:
+    CHECK[op](side, params, case_rng(op, params), make_note(worst, op))

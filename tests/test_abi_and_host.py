@@ -136,24 +136,28 @@ def test_planes_route_decisions_without_a_gpu():
 
 
 def _knob_table():
-    """(name, default) of every tuning knob, as csrc/core.cpp documents them; the enum of csrc/common.hpp must have as many entries."""
-    core = open(os.path.join(REPO, "timetuning_amd", "csrc", "core.cpp")).read()
-    names = re.findall(r'"(TT_[A-Z0-9_]+)"', re.search(r"kKnobNames\[KNOB_COUNT\] = \{(.*?)\};", core, flags=re.S).group(1))
-    defaults = [int(v) for v in re.search(r"kKnobDefaults\[KNOB_COUNT\] = \{(.*?)\};", core, flags=re.S).group(1).split(",")]
-    common = open(os.path.join(REPO, "timetuning_amd", "csrc", "common.hpp")).read()
-    enum = re.findall(r"\bKNOB_[A-Z0-9_]+", re.search(r"enum \{ (KNOB_.*?KNOB_COUNT) \};", common).group(1))
-    assert enum[-1] == "KNOB_COUNT" and ["TT_" + e[5:] for e in enum[:-1]] == names and len(defaults) == len(names)
-    return list(zip(names, defaults))
+    """(name, default) of every tuning knob, enumerated through tt_tuning_knob_info (the library generates its enum, names and defaults
+    from the one list in csrc/common.hpp); the index past the end is TT_EINVAL."""
+    import ctypes as C
+
+    lib, table = _lib.load(), []
+    name, default, value = C.c_char_p(), C.c_int(), C.c_int()
+    while lib.tt_tuning_knob_info(len(table), C.byref(name), C.byref(default), C.byref(value)) == 0:
+        table.append((name.value.decode(), default.value))
+        assert len(table) < 1000
+    assert lib.tt_tuning_knob_info(-1, None, None, None) == -1 and lib.tt_tuning_knob_info(len(table), None, None, None) == -1
+    assert lib.tt_tuning_knob_info(0, None, None, None) == 0      # null outputs are skipped
+    return table
 
 
 def test_tuning_knob_setter_knows_every_documented_knob_and_no_retired_one():
-    """tt_set_tuning_knob takes every knob of the table in core.cpp (names, defaults and the enum of common.hpp are three parallel lists) and
-    setting a knob back to its default restores the default dispatch - seen through the route queries for the knobs that have one, among
-    them the entries that follow the two retired names in the table.  A retired knob is an error, not a silent no-op: a tool that still
-    passes TT_Q8_STREAM (the round-4 pair kernel) or TT_PAIRS_NBUF (a forced ring depth) must hear about it."""
+    """tt_set_tuning_knob takes every knob of the library's list (tt_tuning_knob_info) and setting a knob back to its default restores the
+    default dispatch - seen through the route queries for the knobs that have one, among them the entries that follow the two retired names
+    in the table.  A retired knob is an error, not a silent no-op: a tool that still passes TT_Q8_STREAM (the round-4 pair kernel) or
+    TT_PAIRS_NBUF (a forced ring depth) must hear about it."""
     lib = _lib.load()
     table = _knob_table()
-    assert len(table) == 17 and len(set(n for n, _ in table)) == 17
+    assert len(table) == 32 and len(set(n for n, _ in table)) == 32
     pairs = lambda M, N, K: lib.tt_linear_fwd_pairs_route(M, N, K, 0, 1, 0, 1, 0, 0)
     planes = lambda: lib.tt_linear_fwd_planes_route(1, 25216, 768, 3072, 0, 1, 1, 1, 0, 0)
     # knob -> (a non-default value, the route query it moves, its answer at the default, its answer at that value); no device: 256 CUs
@@ -174,6 +178,59 @@ def test_tuning_knob_setter_knows_every_documented_knob_and_no_retired_one():
     finally:
         for name, default in table:
             lib.tt_set_tuning_knob(name.encode(), default)
+
+
+def test_tuning_knob_context_manager_restores_what_it_found():
+    """hip_ops.tuning_knobs() is the same table with the current values; hip_ops.tuning_knob puts back the value it found, so blocks nest."""
+    from timetuning_amd import hip_ops
+
+    assert {n: d for n, (d, _) in hip_ops.tuning_knobs().items()} == dict(_knob_table())
+    value = lambda: hip_ops.tuning_knobs()["TT_SPLIT_MINK"]
+    assert value() == (256, 256)
+    with hip_ops.tuning_knob("TT_SPLIT_MINK", 128):
+        assert value() == (256, 128)
+        with hip_ops.tuning_knob("TT_SPLIT_MINK", 64):
+            assert value() == (256, 64)
+        assert value() == (256, 128)
+    assert value() == (256, 256)
+    with pytest.raises(_lib.HipLibraryError, match="TT_Q8_STREAM"):
+        with hip_ops.tuning_knob("TT_Q8_STREAM", 1):
+            pass
+    hip_ops.tuning_knobs()                       # the refusal that ends an enumeration is no failure: the last error stays
+    assert "TT_Q8_STREAM" in _lib.load().tt_last_error().decode()
+
+
+def test_moved_tuning_aids_act_through_the_setter_on_the_host():
+    """The aids that used to be function-local statics read from the environment at the first launch now move the host-visible
+    decisions inside one process.  The expected answers were measured on the parent build with the variable in the environment of a
+    fresh process (no device: the 256-CU fallback); every check also sees the default answer return after its block."""
+    from timetuning_amd.hip_ops import tuning_knob
+
+    lib = _lib.load()
+    tile = lib.tt_gemm_tile_choice
+    for t in range(4):
+        with tuning_knob("TT_FORCE_TILE", t):
+            assert tile(25216, 1152, 1) == t
+        assert tile(25216, 1152, 1) == 0
+    assert tile(6272, 200, 1) == 3                       # 196 tiles of 128 x 64: the small-grid rule picks 64 x 64
+    with tuning_knob("TT_TILE_RULE", 0):
+        assert tile(6272, 200, 1) == 2                   # the plain rule
+    assert tile(6272, 200, 1) == 3
+    routes = lambda: [lib.tt_label_propagate_route(8, 14, 200, 7, 6, t) for t in (1, 2, 3, 4, 7, 8)]
+    assert routes() == [1, 1, 1, 3, 3, 0]
+    with tuning_knob("TT_LP_WAVE", 0):
+        assert routes() == [5, 5, 5, 5, 5, 0]            # the workgroup kernel; frame fs is still no target frame
+    assert routes() == [1, 1, 1, 3, 3, 0]
+    lp_ws = lambda: lib.tt_label_propagate_workspace_bytes(196, 8, 4, 16, 7, 1)
+    assert lp_ws() == 4_039_168 == 7 * 401_408 + 1_229_312       # seven target frames per chunk: 401 408 B of similarities each + the maps
+    with tuning_knob("TT_LP_SIMS_CAP_MB", 1):
+        assert lp_ws() == 2_032_128 == 2 * 401_408 + 1_229_312   # 1 MB holds two
+    assert lp_ws() == 4_039_168
+    bwd_ws = lambda: [lib.tt_linear_bwd_weight_workspace_bytes(*s) for s in ((6304, 384, 1536), (2048, 64, 64))]
+    assert bwd_ws() == [19_169_280, 133_120]
+    with tuning_knob("TT_SPLIT_TARGET", 4096), tuning_knob("TT_SPLIT_MINK", 128):
+        assert bwd_ws() == [69_488_640, 266_240]
+    assert bwd_ws() == [19_169_280, 133_120]
 
 
 def test_queue_fullness_is_tracked_on_the_host():

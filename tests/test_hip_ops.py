@@ -207,6 +207,37 @@ def test_linear_bwd_fused_equals_the_two_products(ops, M, N, K, gelu):
     assert rel_err(db.cpu(), dy.double().sum(0)) < 2e-5
 
 
+@pytest.mark.parametrize("M", [256, 130])          # every tile whole / a partial last row tile
+def test_forced_tiles_change_no_result(ops, M):
+    """TT_FORCE_TILE (a tuning aid, through the setter): every tile of the lean forward kernel gives the product test_linear_fwd checks."""
+    N, K = 256, 64
+    x, w, b, r = rnd("ftx", M, K), rnd("ftw", N, K, std=0.05), rnd("ftb", N), rnd("ftr", M, N)
+    ref = F.linear(x.double(), w.double(), b.double()) + r.double()
+    lib = ops._lib.load()
+    for tile in range(4):
+        with ops.tuning_knob("TT_FORCE_TILE", tile):
+            assert lib.tt_linear_fwd_route(M, N, K) == 256 | tile
+            y = ops.linear_fwd(dev(x), dev(w), dev(b), residual=dev(r))
+        assert rel_err(y.cpu(), ref) < TOL, tile
+    assert ops.tuning_knobs()["TT_FORCE_TILE"] == (-1, -1)
+
+
+@pytest.mark.parametrize("M,N,K,split", [(6304, 384, 1536, True), (788, 256, 512, False)])
+def test_unfused_linear_bwd_equals_the_fused_one(ops, M, N, K, split):
+    """TT_BWD_NO_FUSE = 1 (a tuning aid, through the setter) sends tt_linear_bwd down its two-launch path: bit for bit what the default call
+    gives.  The knob can only matter where the default call fuses, i.e. where the weight gradient is split along M (at least two [N, K]
+    slices in the workspace): (6304, 384, 1536) is such a shape - eight slices -, (788, 256, 512) is not (fewer than 1024 rows: no split,
+    two launches either way), and is kept as the shape the two-products test states the equality for."""
+    ws = ops._lib.load().tt_linear_bwd_weight_workspace_bytes(M, N, K)
+    assert (ws >= 2 * N * K * 4) == split, ws
+    tag = f"nf{M}"
+    dy, w, x, pre = (dev(t) for t in (rnd(tag + "dy", M, N), rnd(tag + "w", N, K, std=0.05), rnd(tag + "x", M, K), rnd(tag + "pre", M, K)))
+    fused = ops.linear_bwd(dy, w, x, gelu_pre=pre)
+    with ops.tuning_knob("TT_BWD_NO_FUSE", 1):
+        unfused = ops.linear_bwd(dy, w, x, gelu_pre=pre)
+    assert all(torch.equal(a, b) for a, b in zip(fused, unfused))
+
+
 def test_my_utils_sinkhorn_signature(golden):
     """``my_utils.sinkhorn(Q, nmb_iters, world_size)`` as the reference calls it (Q = exp(scores / eps).T, my_utils.py:246-274)."""
     from timetuning_amd.my_utils import sinkhorn
@@ -328,18 +359,14 @@ def test_sinkhorn_one_launch_equals_the_launch_per_iteration_path(ops, B, K, ite
     x = F.normalize(rnd(f"sk1.x{B}.{K}", B, 48), dim=1)
     p = F.normalize(rnd(f"sk1.p{K}", K, 48), dim=1)
     scores = dev((x @ p.t()).contiguous())
-    from timetuning_amd import hip_ops
     q0 = ops.sinkhorn(scores, iters)                     # the product path: one launch per iteration
-    try:
-        hip_ops.set_tuning_knob("TT_SK_PERSIST", 1)      # (measured slower than it: kept behind the knob, see sinkhorn.hip)
+    with ops.tuning_knob("TT_SK_PERSIST", 1):            # (measured slower than it: kept behind the knob, see sinkhorn.hip)
         q1 = ops.sinkhorn(scores, iters)
         for _ in range(3):
             assert torch.equal(ops.sinkhorn(scores, iters), q1)
         r0, n = B // 3, B // 4
         qw = ops.sinkhorn(scores, iters, row0=r0, rows_out=n)
         assert torch.equal(qw, q1[r0:r0 + n])
-    finally:
-        hip_ops.set_tuning_knob("TT_SK_PERSIST", 0)
     assert rel_err(q1.cpu(), q0.cpu()) < 2e-6 and rel_l2(q1.cpu(), q0.cpu()) < 1e-6
     if B <= 8320:
         ref = O.sinkhorn(torch.exp((x @ p.t()).double() / 0.05).t(), iters)
@@ -378,7 +405,7 @@ def test_label_propagation_batch(ops):
         assert (labels[b].cpu().numpy() != ref.argmax(1)).mean() <= 0.01
 
 
-def test_label_propagation_in_two_calls(ops, monkeypatch):
+def test_label_propagation_in_two_calls(ops):
     """tt_label_propagate_sims + tt_label_propagate_from_sims (the training step runs the first on a side stream, beside the Sinkhorn
     solve that produces the seed) launch what tt_label_propagate launches: labels and map bit for bit the one-call form's, also when
     the similarities were computed on another stream; when the similarities do not fit one chunk the first half declines (None)."""
@@ -409,9 +436,8 @@ def test_label_propagation_in_two_calls(ops, monkeypatch):
             ops.set_gemm_precision("f16x3")
     # more than one chunk: 24 x 3 clips x 3 target frames x 196^2 x 4 B = 33 MB of similarities against a 4 MB cap
     xn_w = xn.repeat(1, 24, 1, 1).contiguous()
-    monkeypatch.setenv("TT_LP_SIMS_CAP_MB", "4")
-    assert ops.label_propagate_sims(xn_w, K) is None
-    monkeypatch.delenv("TT_LP_SIMS_CAP_MB")
+    with ops.tuning_knob("TT_LP_SIMS_CAP_MB", 4):
+        assert ops.label_propagate_sims(xn_w, K) is None
     assert ops.label_propagate_sims(xn_w, K) is not None
 
 
@@ -632,7 +658,7 @@ def test_label_propagation_with_exact_ties(ops):
     assert rel_err(pmap[0].cpu(), want) < 1e-5
 
 
-def test_label_propagation_chunked_similarities(ops, monkeypatch):
+def test_label_propagation_chunked_similarities(ops):
     """The target x context similarities are computed up front for as many target frames as fit a workspace cap: a 10-frame clip
     with 3 context frames (both slot regimes: queue filling, queue full) run whole and in chunks of 1 / 2 / 4 target frames must
     give the same maps bit for bit, and those must equal the oracle's."""
@@ -656,6 +682,6 @@ def test_label_propagation_chunked_similarities(ops, monkeypatch):
     base = ops.label_propagate_maps(xn_w, q0_w, nlast, 2, 3, 0.1)
     assert torch.equal(base[:, :bs], whole)
     for cap_mb in (1, 4, 8):                                    # 1 (floor), 2 and 4 target frames per chunk
-        monkeypatch.setenv("TT_LP_SIMS_CAP_MB", str(cap_mb))
-        assert torch.equal(ops.label_propagate_maps(xn_w, q0_w, nlast, 2, 3, 0.1), base), cap_mb
-    monkeypatch.delenv("TT_LP_SIMS_CAP_MB")
+        with ops.tuning_knob("TT_LP_SIMS_CAP_MB", cap_mb):
+            assert torch.equal(ops.label_propagate_maps(xn_w, q0_w, nlast, 2, 3, 0.1), base), cap_mb
+    assert ops.tuning_knobs()["TT_LP_SIMS_CAP_MB"] == (256, 256)

@@ -137,15 +137,11 @@ def test_four_wave_pair_gemm_experiment(M, N, K):
         out["bg_pre"], out["bg_p"] = o["pre"], o["pairs"]
         return out
 
-    ops.set_tuning_knob("TT_Q8_KSPLIT", 0)          # (the 8-wave kernel's K-split changes an accumulation order: off for the bit comparison)
-    try:
+    with ops.tuning_knob("TT_Q8_KSPLIT", 0):        # (the 8-wave kernel's K-split changes an accumulation order: off for the bit comparison)
         base = run_all()
-        ops.set_tuning_knob("TT_Q4", 1)
-        q4 = run_all()
-        again = run_all()
-    finally:
-        ops.set_tuning_knob("TT_Q4", 0)
-        ops.set_tuning_knob("TT_Q8_KSPLIT", 1)
+        with ops.tuning_knob("TT_Q4", 1):
+            q4 = run_all()
+            again = run_all()
     for k_ in q4:
         assert torch.equal(q4[k_], again[k_]), k_
         assert torch.equal(q4[k_], base[k_]), k_
@@ -166,11 +162,8 @@ def test_four_wave_pair_gemm_experiment(M, N, K):
 def test_attention_pairs(Fr, N, H, flash):
     from timetuning_amd import hip_ops as ops
 
-    ops.set_tuning_knob("TT_ATTN_PAIRS_FLASH", flash)
-    try:
+    with ops.tuning_knob("TT_ATTN_PAIRS_FLASH", flash):
         _attention_pairs_case(ops, Fr, N, H)
-    finally:
-        ops.set_tuning_knob("TT_ATTN_PAIRS_FLASH", 0)
 
 
 def _attention_pairs_case(ops, Fr, N, H):
@@ -190,11 +183,8 @@ def _attention_pairs_case(ops, Fr, N, H):
     only_pairs = ops.attention_fwd_pairs(qkvp, H)[0]
     assert torch.equal(only_pairs, op)
     if N <= 256:   # one workgroup per item (the round-4 launch shape of the same kernel): the same bits
-        ops.set_tuning_knob("TT_ATTN_PAIRS_PERSIST", 0)
-        try:
+        with ops.tuning_knob("TT_ATTN_PAIRS_PERSIST", 0):
             assert torch.equal(ops.attention_fwd_pairs(qkvp, H)[0], op)
-        finally:
-            ops.set_tuning_knob("TT_ATTN_PAIRS_PERSIST", 1)
 
 
 @pytest.mark.parametrize("tn", [True, False])
@@ -343,12 +333,9 @@ def test_pairs8_load_part_orders_give_the_same_bits():
     xp, wp = ops.split_pairs(rnd("ord.x", M, K).cuda()), ops.split_pairs(rnd("ord.w", N, K, scale=0.05).cuda())
     b = rnd("ord.b", N).cuda()
     outs = []
-    try:
-        for order in (3, 0, 1, 2):
-            ops.set_tuning_knob("TT_Q8_ORDER", order)
+    for order in (3, 0, 1, 2):
+        with ops.tuning_knob("TT_Q8_ORDER", order):
             outs.append(ops.linear_fwd_pairs(xp, wp, b, act=1, out_f32=False, out_pairs=True)["pairs"].clone())
-    finally:
-        ops.set_tuning_knob("TT_Q8_ORDER", 3)
     assert all(torch.equal(o, outs[0]) for o in outs[1:])
 
 
@@ -400,13 +387,10 @@ def test_ksplit_partial_exchange_soak():
     for it in range(20):
         for c, f in zip(cases, first):
             assert torch.equal(run(c), f), f"launch {it}: result differs from the first one"
-    ops.set_tuning_knob("TT_Q8_KSPLIT", 0)
-    try:
+    with ops.tuning_knob("TT_Q8_KSPLIT", 0):
         for c, f in zip(cases[:2], first[:2]):
             ref = run(c)
             assert (ref - f).abs().max() <= 2e-6 * ref.abs().max()
-    finally:
-        ops.set_tuning_knob("TT_Q8_KSPLIT", 1)
     torch.cuda.synchronize()
 
 

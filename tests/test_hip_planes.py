@@ -148,7 +148,7 @@ P8_SHAPES = {   # tile counts (256-row x 256 / 128-column tiles): what the work 
 
 @pytest.mark.parametrize("planes", [1, 3])
 @pytest.mark.parametrize("case", list(P8_SHAPES))
-def test_linear_planes8_every_epilogue(planes, case, monkeypatch):
+def test_linear_planes8_every_epilogue(planes, case):
     """The persistent kernel on every tile-count regime of its work decomposition x every compiled epilogue (fp32, fp32 + residual in
     place, bf16 / 3-plane output with and without GELU): (1) the route query says it runs, (2) fp64 products of the same plane operands
     on a row sample that includes the first rows, the LAST rows (ragged tail, half tiles) and random ones, (3) the WHOLE output against
@@ -181,12 +181,9 @@ def test_linear_planes8_every_epilogue(planes, case, monkeypatch):
         new = run()
         again = run()
         assert torch.equal(new, again), (case, e)
-        try:
-            ops.set_tuning_knob("TT_PLANES_VARIANT", 10)   # (the library reads its knobs once; tests flip them through the setter)
+        with ops.tuning_knob("TT_PLANES_VARIANT", 10):     # (the library reads its knobs once; tests flip them through the setter)
             assert lib.tt_linear_fwd_planes_route(planes, M, N, K, e["act"], 1, int(e["res"]), int(e["po"] == 0), e["po"], 0) == 0
             old = run()
-        finally:
-            ops.set_tuning_knob("TT_PLANES_VARIANT", 0)
         want = torch.nn.functional.gelu(ref) if e["act"] else ref
         if e["res"]:
             want = want + r.double()[idx]
@@ -248,8 +245,8 @@ def test_patch_embed_on_bf16_operands(Fr, D, route):
 
 
 @pytest.mark.parametrize("planes", [1, 3])
-def test_planes8_load_part_orders_give_the_same_bits(planes, monkeypatch):
-    """TT_P8_ORDER (a tuning knob: ops.set_tuning_knob) only moves a wave's DMA instructions relative to its fragment reads inside a phase (gemm_planes8.hip `reads_first`):
+def test_planes8_load_part_orders_give_the_same_bits(planes):
+    """TT_P8_ORDER (a tuning knob: ops.tuning_knob) only moves a wave's DMA instructions relative to its fragment reads inside a phase (gemm_planes8.hip `reads_first`):
     every order must leave the same bits; the default (3) is checked against fp64 by test_linear_planes8_every_epilogue."""
     from timetuning_amd import hip_ops as ops
 
@@ -258,12 +255,9 @@ def test_planes8_load_part_orders_give_the_same_bits(planes, monkeypatch):
     xp, wp = ops.split_planes(rnd("ord.x", M, K).cuda(), planes), ops.split_planes(rnd("ord.w", N, K, scale=0.05).cuda(), planes)
     b = rnd("ord.b", N).cuda()
     outs = []
-    try:
-        for order in (3, 0, 1, 2):
-            ops.set_tuning_knob("TT_P8_ORDER", order)
+    for order in (3, 0, 1, 2):
+        with ops.tuning_knob("TT_P8_ORDER", order):
             outs.append(ops.linear_fwd_planes(xp, wp, b, act=1, out_f32=False, out_planes=planes)["planes"].clone())
-    finally:
-        ops.set_tuning_knob("TT_P8_ORDER", 3)
     assert all(torch.equal(o, outs[0]) for o in outs[1:])
 
 

@@ -229,11 +229,8 @@ def _attention(ops, p, rnd, note):
             note("pair dqkv l2 / f32 kernel's", rel_l2(dq_p, qd.grad * gs) / max(e32, 1e-30), 2.0, strict=True)
     # the pair forward: resident (N <= 256) or KV-tiled (beyond, or forced)
     qkvp = ops.split_pairs(qkv.view(Fr * N, 3 * D)).view(Fr, N, 6 * D)
-    ops.set_tuning_knob("TT_ATTN_PAIRS_FLASH", p["flash"])
-    try:
+    with ops.tuning_knob("TT_ATTN_PAIRS_FLASH", p["flash"]):
         op_, of_, lsep = ops.attention_fwd_pairs(qkvp, H, out_pairs=True, out_f32=True, save_lse=True)
-    finally:
-        ops.set_tuning_knob("TT_ATTN_PAIRS_FLASH", 0)
     note("pair out max", rel_err(of_, ref), 3e-6)                     # tools/fuzz_ops.py's bound
     note("pair out l2", rel_l2(of_, ref), TOL_L2)
     note("pair out (pairs) max", rel_err(ops.join_pairs(op_.view(Fr * N, -1)).view(Fr, N, D), ref), 3e-6)
@@ -278,14 +275,11 @@ def _sinkhorn(ops, p, rnd, note):
     if not p["persist"]:
         return
     lib = ops._lib.load()
-    ops.set_tuning_knob("TT_SK_PERSIST", 1)
-    try:
+    with ops.tuning_knob("TT_SK_PERSIST", 1):
         G = lib.tt_sinkhorn_persistent_grid(B, K)
         q1 = ops.sinkhorn(scores, it, row0=r0, rows_out=n)
         for _ in range(2):
             assert torch.equal(ops.sinkhorn(scores, it, row0=r0, rows_out=n), q1)
-    finally:
-        ops.set_tuning_knob("TT_SK_PERSIST", 0)
     if G == 0:   # too big for the one-launch solve: the knob leaves the call on the launch-per-iteration kernels, bit for bit
         assert torch.equal(q1, q0)
         return
@@ -328,9 +322,8 @@ CHECK = {"linear_f32": _linear_f32, "linear_pairs": _linear_pairs, "linear_plane
          "sinkhorn_from_q": _sinkhorn_from_q, "sinkhorn_local": _sinkhorn_local, "queue_push": _queue_push}
 
 
-def run_case(op: str, params: dict, worst: dict = None, monkeypatch=None) -> None:
-    """Runs one case of the table on cuda:0; raises AssertionError on a bound it misses.  ``worst``: {"op: what": [max error, bound]};
-    ``monkeypatch``: pytest's, for the cases that run again under TT_LP_SIMS_CAP_MB (without one the variable is set and restored)."""
+def run_case(op: str, params: dict, worst: dict = None) -> None:
+    """Runs one case of the table on cuda:0; raises AssertionError on a bound it misses.  ``worst``: {"op: what": [max error, bound]}."""
     from timetuning_amd import hip_ops as ops
 
     global WORST
@@ -341,7 +334,7 @@ def run_case(op: str, params: dict, worst: dict = None, monkeypatch=None) -> Non
         if op in EVAL_OPS:
             run_eval_case(HipSide(), op, params, WORST)
         elif op in PROP_OPS:
-            run_prop_case(PropHip(), op, params, WORST, monkeypatch)
+            run_prop_case(PropHip(), op, params, WORST)
         else:
             CHECK[op](ops, params, _gen(op, params), _note(op))
     finally:
@@ -358,8 +351,8 @@ def _report():
 
 
 @pytest.mark.parametrize("op,params", CASES, ids=[case_id(o, p) for o, p in CASES])
-def test_sweep(op, params, monkeypatch):
-    run_case(op, params, monkeypatch=monkeypatch)
+def test_sweep(op, params):
+    run_case(op, params)
 
 
 # ---- the accepted domains of the second tier's entries, at the edge (include/timetuning_hip.h states them).  Every refusal below is a

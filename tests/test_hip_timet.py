@@ -590,37 +590,36 @@ def test_two_streams_equal_one_stream(cfg):
     x = torch.from_numpy(synth.make_clips(bs, fs, 224, seed=12)).cuda()
     try:
         for ksplit, exact in ((0, True), (1, False)):
-            hip_ops.set_tuning_knob("TT_Q8_KSPLIT", ksplit)
-            runs = []
-            labels = []
-            for two in (False, True):
-                engine.TWO_STREAMS = two
-                m, o = make(cfg, 8)
-                torch.manual_seed(5)
-                losses = []
-                for i in range(3):
-                    pin = labels[i] if (two and not exact) else None
-                    loss = m.get_loss(x, target_labels=pin)
-                    if not two:
-                        labels.append(m.last_aux["labels"].clone())
-                    elif pin is not None:
-                        assert (m.last_aux["labels"] != pin).float().mean().item() <= 1e-3
-                    m.train_update(o, loss, i + 1 if queue else 0)
-                    losses.append(loss.item())
-                runs.append((m, losses, {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}))
-            (m1, l1, g1), (m2, l2, g2) = runs
-            if exact:
-                assert l1 == l2, (cfg, l1, l2)
-                assert all(torch.equal(g1[n], g2[n]) for n in g1)
-                p1, p2 = dict(m1.named_parameters()), dict(m2.named_parameters())
-                assert all(torch.equal(p1[n], p2[n]) for n in p1)
-            else:
-                assert max(abs(a - b) for a, b in zip(l1, l2)) < 2e-5, (l1, l2)
-                worst = max(rel_l2(g2[n], g1[n]) for n in g1)
-                assert worst < 2e-6, worst
+            with hip_ops.tuning_knob("TT_Q8_KSPLIT", ksplit):
+                runs = []
+                labels = []
+                for two in (False, True):
+                    engine.TWO_STREAMS = two
+                    m, o = make(cfg, 8)
+                    torch.manual_seed(5)
+                    losses = []
+                    for i in range(3):
+                        pin = labels[i] if (two and not exact) else None
+                        loss = m.get_loss(x, target_labels=pin)
+                        if not two:
+                            labels.append(m.last_aux["labels"].clone())
+                        elif pin is not None:
+                            assert (m.last_aux["labels"] != pin).float().mean().item() <= 1e-3
+                        m.train_update(o, loss, i + 1 if queue else 0)
+                        losses.append(loss.item())
+                    runs.append((m, losses, {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}))
+                (m1, l1, g1), (m2, l2, g2) = runs
+                if exact:
+                    assert l1 == l2, (cfg, l1, l2)
+                    assert all(torch.equal(g1[n], g2[n]) for n in g1)
+                    p1, p2 = dict(m1.named_parameters()), dict(m2.named_parameters())
+                    assert all(torch.equal(p1[n], p2[n]) for n in p1)
+                else:
+                    assert max(abs(a - b) for a, b in zip(l1, l2)) < 2e-5, (l1, l2)
+                    worst = max(rel_l2(g2[n], g1[n]) for n in g1)
+                    assert worst < 2e-6, worst
     finally:
         engine.TWO_STREAMS = keep
-        hip_ops.set_tuning_knob("TT_Q8_KSPLIT", 1)
         hip_ops.set_gemm_precision("f32")
 
 

@@ -25,5 +25,5 @@ def _report():
 
 
 @pytest.mark.parametrize("op,params", CASES, ids=[case_id(o, p) for o, p in CASES])
-def test_sweep_prop_on_the_twin(op, params, monkeypatch):
-    run_prop_case(prop_twin(), op, params, WORST, monkeypatch)
+def test_sweep_prop_on_the_twin(op, params):
+    run_prop_case(prop_twin(), op, params, WORST)

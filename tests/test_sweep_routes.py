@@ -206,12 +206,10 @@ def test_sinkhorn_workspace_places_the_granules_on_an_8_byte_boundary(lib, B, K)
 
 def test_sinkhorn_persistent_grid_follows_the_knob(lib):
     assert lib.tt_sinkhorn_persistent_grid(777, 333) == 0            # the knob is off by default
-    hip_ops.set_tuning_knob("TT_SK_PERSIST", 1)
-    try:
+    with hip_ops.tuning_knob("TT_SK_PERSIST", 1):
         for B, K in [(777, 333), (50176, 200), (6272, 200), (33, 511), (1705, 1)]:
             assert lib.tt_sinkhorn_persistent_grid(B, K) == skp_grid(B, K), (B, K)
-    finally:
-        hip_ops.set_tuning_knob("TT_SK_PERSIST", 0)
+    assert lib.tt_sinkhorn_persistent_grid(777, 333) == 0
 
 
 # ---- the second tier: the evaluator, optimizer and mask kernels.  Their launchers branch without a host query, so each rule is restated

@@ -50,6 +50,7 @@ SIGNATURES = {
     "tt_last_error": (C.c_char_p, []),
     "tt_abi_version": (c_i, []),
     "tt_set_tuning_knob": (c_i, [C.c_char_p, c_i]),
+    "tt_tuning_knob_info": (c_i, [c_i, C.POINTER(C.c_char_p), C.POINTER(c_i), C.POINTER(c_i)]),
     "tt_device_info": (c_i, [C.c_char_p, c_i]),
     "tt_linear_ksplit_workspace_bytes": (c_sz, []),
     "tt_linear_ksplit_workspace_init": (c_i, [c_vp, c_sz, c_vp]),

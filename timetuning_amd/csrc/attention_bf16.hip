@@ -194,8 +194,7 @@ extern "C" int tt_attention_fwd_bf16(const void* qkv, void* out, int F, int N, i
   __bf16* o = static_cast<__bf16*>(out);
 #ifdef TT_ABF_ABLATE
   {
-    const char* e = getenv("TT_ABF_DBG");
-    const int dbg = e ? atoi(e) : 0;
+    const int dbg = tuning_knob(KNOB_ABF_DBG);
     TT_REQUIRE(N <= 224, "ablation build: N <= 224");
 #define ABF(D) case D: hipLaunchKernelGGL((attention_fwd_bf16_kernel<7, D>), dim3(F * H), dim3(256), 0, s, q, o, N, H, scale); break;
     switch (dbg) { ABF(0) ABF(1) ABF(2) ABF(4) ABF(8) ABF(16) ABF(22) ABF(9) ABF(31) ABF(30) default: TT_REQUIRE(false, "TT_ABF_DBG"); }

@@ -35,8 +35,45 @@ inline hipStream_t as_stream(tt_stream_t s) { return reinterpret_cast<hipStream_
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int device_cu_count();   // core.cpp: multiprocessors of the CURRENT device (looked up once per device id)
-// core.cpp: tuning knobs, read once from the environment (TT_<NAME>) and settable through tt_set_tuning_knob (A/B tools, tests)
-enum { KNOB_PLANES_VARIANT = 0, KNOB_P8_ORDER, KNOB_P8_NO_HALF, KNOB_P8_CLOCK_PRINT, KNOB_Q8_ORDER, KNOB_PAIRS_NO8, KNOB_PAIRS8_NO_KEPT, KNOB_Q8_KSPLIT, KNOB_ATTN_PAIRS_FLASH, KNOB_TN_WGS, KNOB_TN_XCD, KNOB_Q8_MIN_TILES, KNOB_SK_PERSIST, KNOB_ATTN_PAIRS_PERSIST, KNOB_Q4, KNOB_Q4_SMALL, KNOB_SPLIT_ROWS, KNOB_COUNT };
+// Tuning knobs (core.cpp): read once from the environment and settable through tt_set_tuning_knob (A/B tools, tests).  THE list: one row
+// X(identifier, "environment name", default) per knob - the KNOB_* enum here, the names and defaults in core.cpp and what
+// tt_tuning_knob_info enumerates all come from it.  Unset = the default, set but empty = 1, anything else atoi.
+#define TT_KNOB_LIST(X)                                                                                                               \
+  X(PLANES_VARIANT, "TT_PLANES_VARIANT", 0)       /* gemm_planes.hip: != 0 the general kernel only */                                  \
+  X(P8_ORDER, "TT_P8_ORDER", 3)                   /* gemm_planes8.hip: tile order */                                                   \
+  X(P8_NO_HALF, "TT_P8_NO_HALF", 0)               /* gemm_planes8.hip / gemm_pairs8.hip: no half-tile tail */                          \
+  X(P8_CLOCK_PRINT, "TT_P8_CLOCK_PRINT", 0)       /* gemm_planes8.hip, the clock-stamp build only */                                   \
+  X(Q8_ORDER, "TT_Q8_ORDER", 3)                   /* gemm_pairs8.hip: tile order */                                                    \
+  X(PAIRS_NO8, "TT_PAIRS_NO8", 0)                 /* gemm_planes.hip: the general pair kernel everywhere */                            \
+  X(PAIRS8_NO_KEPT, "TT_PAIRS8_NO_KEPT", 0)       /* gemm_pairs8.hip: A/B of the kept-frame routes */                                  \
+  X(Q8_KSPLIT, "TT_Q8_KSPLIT", 1)                 /* gemm_pairs8.hip / gemm_planes8.hip: K-split of the left-over tiles */             \
+  X(ATTN_PAIRS_FLASH, "TT_ATTN_PAIRS_FLASH", 0)   /* attention_pairs.hip: the KV-tiled kernel at every N */                            \
+  X(TN_WGS, "TT_TN_WGS", 0)                       /* gemm_pairs_tn.hip: workgroups (0 = 1.5 per CU) */                                 \
+  X(TN_XCD, "TT_TN_XCD", 1)                       /* gemm_pairs_tn.hip: whole splits per XCD */                                        \
+  X(Q8_MIN_TILES, "TT_Q8_MIN_TILES", 128)         /* gemm_pairs8.hip */                                                                \
+  X(SK_PERSIST, "TT_SK_PERSIST", 0)               /* sinkhorn.hip: the one-launch solve */                                             \
+  X(ATTN_PAIRS_PERSIST, "TT_ATTN_PAIRS_PERSIST", 1) /* attention_pairs.hip: one workgroup per CU */                                    \
+  X(Q4, "TT_Q4", 0)                               /* gemm_pairs8.hip: gemm_pairs4_kernel (an experiment) */                            \
+  X(Q4_SMALL, "TT_Q4_SMALL", 0)                   /* gemm_pairs8.hip */                                                                \
+  X(SPLIT_ROWS, "TT_SPLIT_ROWS", 1)               /* gemm_planes.hip: the streaming row-pair split */                                  \
+  X(SK_WGS, "TT_SK_WGS", 0)                       /* sinkhorn.hip sk_wgs: workgroup cap (0 = sk_default_cap) */                        \
+  X(SKP_ROWS, "TT_SKP_ROWS", 0)                   /* sinkhorn.hip: rows per workgroup of the one-launch solve (0 = the LDS capacity) */ \
+  X(FORCE_TILE, "TT_FORCE_TILE", -1)              /* gemm_f32.hip gemm_tile_choice: 0..3 forces that tile */                           \
+  X(TILE_RULE, "TT_TILE_RULE", 1)                 /* gemm_f32.hip gemm_tile_choice: 0 = the plain rule */                              \
+  X(SPLIT_TARGET, "TT_SPLIT_TARGET", 0)           /* gemm_f32.hip gemm_splitk_choice: workgroups aimed at (0 = 1024) */                \
+  X(SPLIT_MINK, "TT_SPLIT_MINK", 256)             /* gemm_f32.hip gemm_splitk_choice: least K per slice */                             \
+  X(BWD_NO_FUSE, "TT_BWD_NO_FUSE", 0)             /* gemm_f32.hip tt_linear_bwd: the two products as two launches */                   \
+  X(PATCH_LEAN, "TT_PATCH_LEAN", 1)               /* gemm_f32.hip tt_patch_embed_gemm: 0 = the general kernel */                       \
+  X(GEMM_DYNLDS, "TT_GEMM_DYNLDS", 0)             /* gemm_nt_fast.hip: bytes of unused dynamic LDS per launch */                       \
+  X(GEMM_SMALL_GRID, "TT_GEMM_SMALL_GRID", 320)   /* gemm_nt_fast.hip: deep slabs up to this many tiles */                             \
+  X(LP_WAVE, "TT_LP_WAVE", 1)                     /* label_prop.hip lp_route: 0 = the workgroup kernels only */                        \
+  X(LP_SIMS_CAP_MB, "TT_LP_SIMS_CAP_MB", 256)     /* label_prop.hip lp_chunk: MB of similarities held at once */                       \
+  X(Q8_DBG, "TT_Q8_DBG", 0)                       /* gemm_pairs8.hip, the TT_Q8_ABLATE build only */                                   \
+  X(P8_DBG, "TT_P8_DBG", 0)                       /* gemm_planes8.hip, the TT_P8_ABLATE build only */                                  \
+  X(ABF_DBG, "TT_ABF_DBG", 0)                     /* attention_bf16.hip, the TT_ABF_ABLATE build only */
+#define TT_KNOB_ENUM(id, name, def) KNOB_##id,
+enum { TT_KNOB_LIST(TT_KNOB_ENUM) KNOB_COUNT };
+#undef TT_KNOB_ENUM
 int tuning_knob(int which);
 
 // The K-split workspace of the persistent GEMMs (gemm_pairs8.hip / gemm_planes8.hip: fp32 partials of the left-over tiles + one arrival

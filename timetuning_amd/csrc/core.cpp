@@ -40,12 +40,15 @@ bool ksplit_ws_carve(void* ws, size_t bytes, KsplitWs* out) {
   return true;
 }
 
-// ---- tuning knobs: read ONCE from the environment into atomics - a launch path never calls getenv (not safe against a
+// ---- tuning knobs: read ONCE from the environment into atomics - a launch path never reads the environment (not safe against a
 // concurrent setenv from another Python thread, and a knob must not flip under a production run) - with an explicit setter for the A/B
-// tools and tests that compare settings inside one process.
-static const char* const kKnobNames[KNOB_COUNT] = {"TT_PLANES_VARIANT", "TT_P8_ORDER", "TT_P8_NO_HALF", "TT_P8_CLOCK_PRINT",
-                                                   "TT_Q8_ORDER",       "TT_PAIRS_NO8", "TT_PAIRS8_NO_KEPT", "TT_Q8_KSPLIT", "TT_ATTN_PAIRS_FLASH", "TT_TN_WGS", "TT_TN_XCD", "TT_Q8_MIN_TILES", "TT_SK_PERSIST", "TT_ATTN_PAIRS_PERSIST", "TT_Q4", "TT_Q4_SMALL", "TT_SPLIT_ROWS"};
-static const int kKnobDefaults[KNOB_COUNT] = {0, 3, 0, 0, 3, 0, 0, 1, 0, 0, 1, 128, 0, 1, 0, 0, 1};
+// tools and tests that compare settings inside one process.  Names and defaults come from TT_KNOB_LIST (common.hpp).
+#define TT_KNOB_NAME(id, name, def) name,
+#define TT_KNOB_DEFAULT(id, name, def) def,
+static const char* const kKnobNames[KNOB_COUNT] = {TT_KNOB_LIST(TT_KNOB_NAME)};
+static const int kKnobDefaults[KNOB_COUNT] = {TT_KNOB_LIST(TT_KNOB_DEFAULT)};
+#undef TT_KNOB_NAME
+#undef TT_KNOB_DEFAULT
 static std::atomic<int> g_knobs[KNOB_COUNT];
 static std::once_flag g_knobs_once;
 static void knobs_init() {
@@ -69,6 +72,14 @@ extern "C" int tt_set_tuning_knob(const char* name, int value) {
     }
   tt::set_error("set_tuning_knob: unknown knob '%s'", name ? name : "(null)");
   return TT_EINVAL;
+}
+
+extern "C" int tt_tuning_knob_info(int index, const char** name, int* default_value, int* value) {
+  if (index < 0 || index >= tt::KNOB_COUNT) return TT_EINVAL;   // (how an enumeration ends: the last-error string is left alone)
+  if (name) *name = tt::kKnobNames[index];
+  if (default_value) *default_value = tt::kKnobDefaults[index];
+  if (value) *value = tt::tuning_knob(index);
+  return TT_OK;
 }
 
 extern "C" const char* tt_last_error(void) { return tt::g_err; }

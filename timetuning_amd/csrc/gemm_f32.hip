@@ -24,7 +24,6 @@
 // outputs are too small to fill 256 CUs: partial tiles go to a workspace and a second kernel folds them in a fixed
 // order (deterministic, no atomics).
 #include "common.hpp"
-#include <cstdlib>
 
 namespace tt {
 
@@ -408,7 +407,7 @@ int launch_splitk_reduce_colfold(const float* partial, float* out, long long n, 
 }
 
 int gemm_tile_choice(int M, int N, int batch) {
-  static const int forced = [] { const char* e = getenv("TT_FORCE_TILE"); return e ? atoi(e) : -1; }();  // tuning aid
+  const int forced = tuning_knob(KNOB_FORCE_TILE);   // tuning aid
   if (forced >= 0 && forced <= 3) return forced;
   struct Cfg { int wm, wn; double pen; };
   // (128 x 64 beats 64 x 128 at equal tile counts on every ViT-S/16 block shape - 813.6 vs 836.3 us per block of 128 frames,
@@ -426,8 +425,7 @@ int gemm_tile_choice(int M, int N, int batch) {
   // the smallest tile then halves / quarters that loop at the same residency (round 6, in the step: the prototype-score products -
   // 6272 x 200 x 256, 196 tiles of 128 x 64 - and their gradients: C2 -0.25 %, C2 in f32 -0.7 %; below 128 tiles - C1's launches -
   // it measured no better: left alone; TT_TILE_RULE=0 restores the plain rule; profiles/r06_step_knob_sweeps.txt).
-  static const bool small_rule = [] { const char* e = getenv("TT_TILE_RULE"); return e ? atoi(e) != 0 : true; }();
-  if (small_rule) {
+  if (tuning_knob(KNOB_TILE_RULE) != 0) {
     const long long bm = 64 * cfgs[best].wm, bn = 64 * cfgs[best].wn;
     const long long t = ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * (long long)batch;
     if (t >= 128 && t < 256) best = 3;
@@ -478,8 +476,7 @@ int gemm_splitk_choice(int M, int N, int K, int* tile_out) {
   const long long tiles = (long long)((M + 63) / 64) * ((N + 63) / 64);
   if (tile_out) *tile_out = tile;
   if (tiles >= 768 || K < 1024) return 1;
-  static const int target_env = [] { const char* e = getenv("TT_SPLIT_TARGET"); return e ? atoi(e) : 0; }();  // tuning aids
-  static const int mink = [] { const char* e = getenv("TT_SPLIT_MINK"); return e ? atoi(e) : 256; }();
+  const int target_env = tuning_knob(KNOB_SPLIT_TARGET), mink = tuning_knob(KNOB_SPLIT_MINK);   // tuning aids
   const int target = target_env ? target_env : 1024;
   int s = (int)((target + tiles - 1) / tiles);
   const int smax = K / mink;                         // keep >= mink of K per slice
@@ -668,7 +665,7 @@ extern "C" int tt_linear_bwd(const float* dy, const float* w, const float* x, co
   TT_REQUIRE(dy && w && x && dx && dw && M > 0 && N > 0 && K > 0, "linear_bwd: null operand / bad shape");
   // ONE launch when the weight gradient is split along M (its plan: gemm_splitk_choice) and both lean kernels take the shapes
   const int s = (((long long)N * K) % 4 == 0) ? tt::gemm_splitk_choice(N, K, M, nullptr) : 1;
-  static const bool no_fuse = getenv("TT_BWD_NO_FUSE") != nullptr;   // tuning aid
+  const bool no_fuse = tt::tuning_knob(tt::KNOB_BWD_NO_FUSE) != 0;   // tuning aid
   if (s > 1 && !no_fuse && workspace && workspace_bytes >= tt_linear_bwd_weight_workspace_bytes(M, N, K)) {
     const int kchunk = ((M + s - 1) / s + tt::kBK - 1) / tt::kBK * tt::kBK;
     float* part = static_cast<float*>(workspace);
@@ -705,8 +702,7 @@ int try_launch_patch_embed_fast(const float* img, const int* frame_map, const fl
 extern "C" int tt_patch_embed_gemm(const float* img, const int32_t* frame_map, const float* w, const float* bias,
                                    const float* pos, float* tokens, int F, int C, int H, int W, int P, int D,
                                    tt_stream_t stream) {
-  static const bool lean = [] { const char* e = getenv("TT_PATCH_LEAN"); return !e || atoi(e) != 0; }();   // tuning aid
-  if (lean) {
+  if (tt::tuning_knob(tt::KNOB_PATCH_LEAN) != 0) {   // tuning aid
     const int rc = tt::try_launch_patch_embed_fast(img, frame_map, w, bias, pos, tokens, F, C, H, W, P, D, tt::as_stream(stream));
     if (rc <= 0) return rc;
   }

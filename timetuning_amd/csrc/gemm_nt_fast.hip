@@ -39,7 +39,6 @@
 //     against 6, and with 5-6 short-lived workgroups per CU the hardware's own dispatch already overlaps one workgroup's prologue
 //     and epilogue with the others' main loops.
 #include "common.hpp"
-#include <cstdlib>
 
 namespace tt {
 
@@ -264,8 +263,7 @@ template <int WM, int WN>
 static int launch_fast(const FastArgs& g, hipStream_t s) {
   const int tiles = ((g.M + 64 * WM - 1) / (64 * WM)) * (g.N / (64 * WN));
   // tuning aid: TT_GEMM_DYNLDS=<bytes> adds unused dynamic LDS to every launch, which caps the workgroups per CU
-  static const int dyn_lds = [] { const char* e = getenv("TT_GEMM_DYNLDS"); return e ? atoi(e) : 0; }();
-  static const int small_grid = [] { const char* e = getenv("TT_GEMM_SMALL_GRID"); return e ? atoi(e) : 320; }();  // tuning aid
+  const int dyn_lds = tuning_knob(KNOB_GEMM_DYNLDS), small_grid = tuning_knob(KNOB_GEMM_SMALL_GRID);   // (the latter a tuning aid too)
   if (tiles <= small_grid && g.K % 64 == 0) {   // latency-bound grid: deep slabs
     hipLaunchKernelGGL((gemm_nt_fast_kernel<WM, WN, 64>), dim3(tiles), dim3(256), dyn_lds, s, g);
     TT_CHECK_LAUNCH("gemm_nt_fast");

@@ -52,7 +52,6 @@
 //
 // gemm_pairs4_kernel (round 6, an experiment behind the knob TT_Q4) is the same product in four-wave workgroups on 128 x 128 tiles.
 #include "common.hpp"
-#include <cstdlib>
 
 namespace tt {
 
@@ -1135,8 +1134,7 @@ int pairs8_try(const void* x_pairs, const void* w_pairs, const float* bias, cons
            pl.ks_S, pl.ks_R, out_scale, ks_ws, ks_cnt, range_flag, amax_out};
 #ifdef TT_Q8_ABLATE   // timing-study build only (tools/q8_ablate.py): TT_Q8_DBG selects a crippled instantiation
   {
-    const char* e = getenv("TT_Q8_DBG");
-    const int dbg = e ? atoi(e) : 0;
+    const int dbg = tuning_knob(KNOB_Q8_DBG);
 #define Q8S_DBG_CASE(EV)                                   \
   if (epi == EV) {                                         \
     if (dbg == 1) return launch_pairs8s<EV, 1>(g, s);      \

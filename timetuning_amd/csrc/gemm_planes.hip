@@ -36,7 +36,6 @@
 // Epilogue through LDS (8 columns per thread): bias, GELU (erf to 1.5e-7, common.hpp gelu_fast_f), residual, and any of: fp32 y, fp32 pre-activation, bf16 planes
 // of y (so the consumer finds its operand pre-split).
 #include "common.hpp"
-#include <cstdlib>
 
 namespace tt {
 

@@ -47,7 +47,6 @@
 // consumed at once, an IEEE division inside the GELU (__frcp_rn) and a vmcnt(0) behind the stores, all CUs in lockstep - was
 // 17-43 % of the launches.
 #include "common.hpp"
-#include <cstdlib>
 
 namespace tt {
 
@@ -895,8 +894,7 @@ int planes8_try(const void* x_planes, long long x_plane_stride, const void* w_pl
            ks_S, ks_S >= 2 ? (int)(ntiles - (long long)n_full * ncu) : 0, ks_ws, ks_cnt};
 #ifdef TT_P8_ABLATE   // timing-study build only (tools/build_variant.sh -DTT_P8_ABLATE): TT_P8_DBG selects a crippled instantiation
   {
-    const char* e = getenv("TT_P8_DBG");
-    const int dbg = e ? atoi(e) : 0;
+    const int dbg = tuning_knob(KNOB_P8_DBG);
 #define P8_DBG_CASE(PV, EV)                                       \
   if (planes == PV && epi == EV) {                                \
     if (dbg == 1) return launch_planes8<PV, EV, 1>(g, s);         \

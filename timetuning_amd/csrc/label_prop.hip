@@ -5,7 +5,7 @@
 // label maps by it - on the host, one sample at a time.  Here, per target frame t:
 //   1. cosine similarities target x context: batched fp32 MFMA GEMM over (clip, context frame)   [gemm_f32.hip].  They depend
 //      on the features only, not on the propagated maps, so they are computed UP FRONT for a whole chunk of target frames
-//      (as many as fit LP_SIMS_CAP bytes of workspace): one launch for the pairs (t, frame 0) of all t, and one or two per
+//      (as many as fit TT_LP_SIMS_CAP_MB of workspace): one launch for the pairs (t, frame 0) of all t, and one or two per
 //      lag d for the pairs (t, t - d) - 3 launches instead of 6 at fs = 4, 7 instead of 28 at fs = 8, each with a batch large
 //      enough to fill the chip (a 196 x 196 x D product per clip is 16 tiles).
 //   2. one workgroup per (clip, query patch): window gather -> exp(sim / 0.1) -> exact k-th largest with
@@ -18,7 +18,6 @@
 // with the same similarity GEMMs (lp_sims_chunk) and a per-query kernel that streams its candidates from the similarity rows, so
 // neither the window (radius 0: the whole grid) nor the number of context frames is bounded by registers or LDS.
 #include "common.hpp"
-#include <cstdlib>
 
 namespace tt {
 
@@ -356,23 +355,20 @@ static int lp_route(int fs, int g, int K, int n_last, int radius, int t) {
   const int win = (radius < g && 2 * radius + 1 < g) ? 2 * radius + 1 : g;
   const long long cand_max = (long long)win * win * lp_cmax(fs, n_last);
   if (cand_max > 256LL * LP_CAND_MAX) return 0;
-  static const bool wave_env = [] { const char* e = getenv("TT_LP_WAVE"); return !e || atoi(e) != 0; }();   // tuning aid
-  if (wave_env && win <= 16 && (long long)g * g <= 4096 && K <= 512) {
+  if (tuning_knob(KNOB_LP_WAVE) != 0 && win <= 16 && (long long)g * g <= 4096 && K <= 512) {   // (the knob: a tuning aid)
     const int c = 1 + (t - 1 < n_last ? t - 1 : n_last);   // frame 0 and the frames [max(1, t - n_last), t)
     return (c <= 3 ? 1 : 3) + (K <= 256 ? 0 : 1);
   }
   return cand_max <= 256LL * 8 ? 5 : 6;
 }
 
-// target frames whose similarities are held at once (all of them unless that needs more than LP_SIMS_CAP bytes).  256 MB holds every
-// target frame of C2 (44 MB) and all but one of C4's (138 MB at 16 clips x 8 frames); the evaluation protocol's long clips on the
-// 28 x 28 grid are chunked (there a few more similarity launches do not matter - the per-query kernel dominates).  The cost is
+// target frames whose similarities are held at once (all of them unless that needs more than the knob TT_LP_SIMS_CAP_MB allows).  The
+// default 256 MB holds every target frame of C2 (44 MB) and all but one of C4's (138 MB at 16 clips x 8 frames); the evaluation protocol's
+// long clips on the 28 x 28 grid are chunked (there a few more similarity launches do not matter - the per-query kernel dominates).  The cost is
 // workspace the caller allocates: see INTEGRATION.md "Workspaces".
-constexpr size_t LP_SIMS_CAP = 256ull << 20;
 static int lp_chunk(int bs, int fs, int n, int n_last) {
   const size_t per_t = (size_t)bs * lp_cmax(fs, n_last) * n * n * sizeof(float);
-  const char* e = getenv("TT_LP_SIMS_CAP_MB");   // test aid: a small cap exercises the chunked path on small inputs
-  size_t T = (e ? (size_t)atoll(e) << 20 : LP_SIMS_CAP) / per_t;
+  size_t T = ((size_t)tuning_knob(KNOB_LP_SIMS_CAP_MB) << 20) / per_t;   // (a small cap exercises the chunked path on small inputs)
   // (the slot-0 similarity launch carries bs * T problems on gridDim.y: at most 65535 of them)
   if (bs > 0 && T > (size_t)(65535 / bs)) T = 65535 / bs;
   if (T < 1) T = 1;

@@ -22,7 +22,6 @@
 // 287 us instead of 89 us per 10-iteration solve at B = 6272 and growing with the workgroup count; the fences write back /
 // invalidate L2 around the 5 MB of E every launch.  The redundant fold of at most 96 x K floats is the cheaper evil.)
 #include "common.hpp"
-#include <cstdlib>
 
 namespace tt {
 
@@ -53,7 +52,7 @@ constexpr int SK_WAVES = SK_THREADS / 64;
 
 static int sk_wgs(int B) {
   int w = (B + 2 * SK_WAVES - 1) / (2 * SK_WAVES);  // >= 2 rows per wave
-  static const int cap_env = [] { const char* e = getenv("TT_SK_WGS"); return e ? atoi(e) : 0; }();  // tuning aid
+  const int cap_env = tuning_knob(KNOB_SK_WGS);   // tuning aid
   const int cap = (cap_env > 0 && cap_env <= SK_MAXWG) ? cap_env : sk_default_cap(B);
   return w > cap ? cap : (w < 1 ? 1 : w);
 }
@@ -488,7 +487,7 @@ extern "C" int tt_sinkhorn_persistent_grid(int B_total, int K) {
   if (B_total <= 0 || K <= 0 || K > 64 * SK_KPL || tuning_knob(KNOB_SK_PERSIST) == 0) return 0;
   const int ncu = device_cu_count();
   const int cap = skp_lds_rows(K);
-  static const int rows_env = [] { const char* e = getenv("TT_SKP_ROWS"); return e ? atoi(e) : 0; }();   // tuning aid
+  const int rows_env = tuning_knob(KNOB_SKP_ROWS);   // tuning aid
   int rows = rows_env > 0 ? rows_env : cap;
   if (rows > cap) rows = cap;
   const int G = rows > 0 ? (B_total + rows - 1) / rows : ncu + 1;

@@ -6,6 +6,7 @@ the library is unavailable - there is no eager fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional, Sequence
@@ -126,6 +127,27 @@ def set_gemm_precision(mode: str) -> None:
 def set_tuning_knob(name: str, value: int) -> None:
     """A dispatcher tuning knob (``TT_<NAME>``; the library reads them once from the environment): A/B tools and tests only."""
     _lib.check(_lib.load().tt_set_tuning_knob(name.encode(), int(value)), "tt_set_tuning_knob")
+
+
+def tuning_knobs() -> dict:
+    """``{name: (default, value)}`` of every tuning knob, in the order of the library's list (tt_tuning_knob_info; the index past its end
+    is refused without touching the last-error string)."""
+    lib, table = _lib.load(), {}
+    name, default, value = C.c_char_p(), C.c_int(), C.c_int()
+    while lib.tt_tuning_knob_info(len(table), C.byref(name), C.byref(default), C.byref(value)) == 0:
+        table[name.value.decode()] = (default.value, value.value)
+    return table
+
+
+@contextlib.contextmanager
+def tuning_knob(name: str, value: int):
+    """Sets a tuning knob for the ``with`` block and restores the value it FOUND (not the default: nested blocks unwind correctly)."""
+    found = tuning_knobs().get(name)
+    set_tuning_knob(name, value)          # (an unknown name raises here)
+    try:
+        yield
+    finally:
+        set_tuning_knob(name, found[1])
 
 
 def get_gemm_precision() -> str:

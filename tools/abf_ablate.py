@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Where attention_fwd_bf16's time goes: interleaved timing of its crippled instantiations (tools/build_variant.sh abfablate
-attention_bf16.hip -DTT_ABF_ABLATE; TT_ABF_DBG bit mask: 1 no MFMAs, 2 no K/V LDS-DMA, 4 no Q loads, 8 no exponentials, 16 no stores)
+attention_bf16.hip -DTT_ABF_ABLATE; knob TT_ABF_DBG, a bit mask: 1 no MFMAs, 2 no K/V LDS-DMA, 4 no Q loads, 8 no exponentials, 16 no stores)
 on BASELINE C4's layer (128 frames x 12 heads x 197 tokens)."""
 import ctypes as C, os, statistics, sys, torch
 vp, i32 = C.c_void_p, C.c_int
 lib = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin", "libabfablate.so"))
+def knob(name, value):   # the library reads its tuning knobs once: flip them through its setter
+    lib.tt_set_tuning_knob.argtypes = [C.c_char_p, C.c_int]
+    assert lib.tt_set_tuning_knob(name.encode(), int(value)) == 0
 lib.tt_attention_fwd_bf16.restype = C.c_int
 lib.tt_attention_fwd_bf16.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp]
 st = torch.cuda.current_stream().cuda_stream
@@ -16,7 +19,7 @@ out = torch.empty(F, N, H * 64, device="cuda", dtype=torch.bfloat16)
 ts = {d: [] for d in NAMES}
 for rd in range(8):
     for d in NAMES:
-        os.environ["TT_ABF_DBG"] = str(d)
+        knob("TT_ABF_DBG", d)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(10):

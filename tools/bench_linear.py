@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times tt_linear_fwd (fp32) on the ViT-S/16 block shapes of C2 and checks it against fp64.  Env switches of the library
-(TT_GEMM_DMA=<ring depth>, TT_FORCE_TILE) select variants; one process per variant."""
+(TT_FORCE_TILE, ...) select variants; one process per variant."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where gemm_planes8's time goes: interleaved timing of its crippled instantiations (tools/build_variant.sh p8ablate gemm_planes8.hip
--DTT_P8_ABLATE; TT_P8_DBG bit mask: 1 no MFMAs, 2 no LDS-DMA, 4 no fragment reads, 8 no epilogue, 16 epilogue without global traffic)
+-DTT_P8_ABLATE; knob TT_P8_DBG, a bit mask: 1 no MFMAs, 2 no LDS-DMA, 4 no fragment reads, 8 no epilogue, 16 epilogue without global traffic)
 on shapes with an exact tile count per CU (16384 x 2048) and on the ViT-B/16 / ViT-S/16 block shapes."""
 import ctypes as C, os, statistics, sys, torch
 import sys as _sys, os as _os; _sys.path.insert(0, _os.path.dirname(_os.path.abspath(__file__)))
@@ -11,6 +11,9 @@ def _ks(lib, st):
     return _KS[id(lib)]
 vp, ll, i32 = C.c_void_p, C.c_longlong, C.c_int
 lib = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin", "libp8ablate.so"))
+def knob(name, value):   # the library reads its tuning knobs once: flip them through its setter
+    lib.tt_set_tuning_knob.argtypes = [C.c_char_p, C.c_int]
+    assert lib.tt_set_tuning_knob(name.encode(), int(value)) == 0
 lib.tt_linear_fwd_planes.restype = C.c_int
 lib.tt_linear_fwd_planes.argtypes = [vp, ll, vp, ll, i32, vp, vp, vp, vp, vp, ll, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]   # ABI 7: + K-split workspace
 lib.tt_split_planes.restype = C.c_int
@@ -35,7 +38,7 @@ for P, M, N, K, act, po, res, name in cases:
     ts = {d: [] for d in NAMES}
     for rd in range(8):
         for d in NAMES:
-            os.environ["TT_P8_DBG"] = str(d)
+            knob("TT_P8_DBG", d)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(10):

@@ -27,7 +27,7 @@ for P, M, N, K, po in ((1, 25216, 2304, 768, 1), (3, 25216, 1152, 384, 0)):
     y = torch.empty(M, N, device="cuda") if not po else None
     yp = torch.empty(po, M, N, device="cuda", dtype=torch.bfloat16) if po else None
     for dbg, name in ((0, "full"), (14, "MFMA only (pseudo-random register operands)"), (9, "skeleton (no MFMA, no epilogue)"), (8, "no epilogue"), (10, "no epilogue, no DMA (MFMA + LDS reads of the random data the full variant left in LDS)"), (12, "no epilogue, no LDS reads (MFMA on pseudo-random registers + DMA)")):
-        os.environ["TT_P8_DBG"] = str(dbg)
+        knob("TT_P8_DBG", dbg)
         print(f"== P={P} {name}", flush=True)
         def go():
             lib.tt_linear_fwd_planes(x.data_ptr(), M * K, w.data_ptr(), N * K, P, b.data_ptr(), None, y.data_ptr() if y is not None else None, None,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where gemm_pairs8s_kernel's time goes: interleaved timing of its crippled instantiations (tools/build_variant.sh q8ablate gemm_pairs8.hip
--DTT_Q8_ABLATE; TT_Q8_DBG bit mask: 1 no MFMAs, 2 no LDS-DMA, 8 no epilogue) on the ViT-S/16 / ViT-B/16 block shapes and on a shape with
+-DTT_Q8_ABLATE; knob TT_Q8_DBG, a bit mask: 1 no MFMAs, 2 no LDS-DMA, 8 no epilogue) on the ViT-S/16 / ViT-B/16 block shapes and on a shape with
 an exact tile count per CU."""
 import ctypes as C, os, statistics, sys, torch
 import sys as _sys, os as _os; _sys.path.insert(0, _os.path.dirname(_os.path.abspath(__file__)))
@@ -11,6 +11,9 @@ def _ks(lib, st):
     return _KS[id(lib)]
 vp, ll, i32 = C.c_void_p, C.c_longlong, C.c_int
 lib = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin", "libq8ablate.so"))
+def knob(name, value):   # the library reads its tuning knobs once: flip them through its setter
+    lib.tt_set_tuning_knob.argtypes = [C.c_char_p, C.c_int]
+    assert lib.tt_set_tuning_knob(name.encode(), int(value)) == 0
 lib.tt_linear_fwd_pairs.restype = C.c_int
 lib.tt_linear_fwd_pairs.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, C.c_size_t, vp, vp]   # ABI 7: + K-split workspace, range flag
 lib.tt_split_pairs.restype = C.c_int
@@ -38,7 +41,7 @@ for M, N, K, act, po, res, name in cases:
     ts = {d: [] for d in NAMES}
     for rd in range(8):
         for d in NAMES:
-            os.environ["TT_Q8_DBG"] = str(d)
+            knob("TT_Q8_DBG", d)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(10):
