@@ -588,6 +588,28 @@ size_t tt_kmeans_accumulate_workspace_bytes(long long P, int d, int k);
 int tt_kmeans_accumulate(const float* x, const int32_t* labels, double* sums, long long* counts, long long P, int d, int k,
                          void* workspace, size_t workspace_bytes, tt_stream_t stream);
 
+/* ---- N12: k-means beyond the LDS limit - the same two passes for centroid sets tt_kmeans_shape_ok refuses, which
+ *      the reference's over-clustering needs: faiss.Kmeans(50, 500) at clustering.py:39-41,55-57,69-71 (cluster_features, the three
+ *      protocols; evaluation.py:431-441 with many_to_one) and faiss.Kmeans(256, num_classes) at clustering.py:108-110 (proto_clustering).
+ *   The centroids (the sums) pass through LDS in tiles of tile_k rows; the arithmetic per output number is that of the resident
+ *   entries, so wherever both take a shape the outputs are equal bit for bit, whatever tile_k is.
+ *   tt_kmeans_tiled_shape_ok      1 for 1 <= d <= 1024, k >= 1, k * d < 2^31, else 0.
+ *   tt_kmeans_tile_centroids      the default tile at d: the most rows of d floats that fill at most 64 KB (0 outside 1 <= d <= 1024).
+ *   tt_kmeans_assign_tiled        tt_kmeans_assign (clustering.py:39-41,55-57,69-71,108-110: index.search(x, 1) and the assignment of every
+ *                                 Lloyd iteration of train): first minimum, also across tile boundaries; dist2 optional.
+ *   tt_kmeans_accumulate_tiled    tt_kmeans_accumulate (the same sites: the centroid update of every Lloyd iteration of train);
+ *                                 labels outside [0, k) are skipped.  No atomics; the workspace is that of tt_kmeans_accumulate,
+ *                                 one fp64 partial per (workgroup, cluster, column) - 8 k (d + 1) bytes per 128 points, at most 4096 times.
+ *   tile_k: 0 = the default, or any value in 1 ... tt_kmeans_tile_centroids(d); a larger one is refused (TT_EINVAL, the message
+ *   names both numbers), as is a shape beyond tt_kmeans_tiled_shape_ok.  Nothing is launched on a refusal.  Any P > 0. */
+int tt_kmeans_tiled_shape_ok(int d, int k);   /* 1 when the two tiled entries take (d, k): what clustering.py:39-41,55-57,69-71,108-110 may ask */
+int tt_kmeans_tile_centroids(int d);          /* the default and largest tile_k at d; pure host function, like the shape rule */
+int tt_kmeans_assign_tiled(const float* x, const float* centroids, int32_t* labels, float* dist2, long long P, int d, int k, int tile_k,
+                           tt_stream_t stream);
+size_t tt_kmeans_accumulate_tiled_workspace_bytes(long long P, int d, int k, int tile_k);
+int tt_kmeans_accumulate_tiled(const float* x, const int32_t* labels, double* sums, long long* counts, long long P, int d, int k,
+                               int tile_k, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+
 /* ---- N3: the clip input pipeline - the pixel work of video_transformations.py as wired at
  *      time_tuning.py:588-593, bit-exact with Pillow (which the reference calls per frame on the host).
  *   Frames are interleaved uint8 RGB [F, H, W, 3] in device memory.

@@ -158,6 +158,11 @@ SIGNATURES = {
     "tt_kmeans_shape_ok": (c_i, [c_i, c_i]),
     "tt_kmeans_assign_route": (c_i, [c_i]),
     "tt_kmeans_accumulate": (c_i, [c_vp, c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_vp, c_sz, c_vp]),
+    "tt_kmeans_tiled_shape_ok": (c_i, [c_i, c_i]),
+    "tt_kmeans_tile_centroids": (c_i, [c_i]),
+    "tt_kmeans_assign_tiled": (c_i, [c_vp, c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_i, c_vp]),
+    "tt_kmeans_accumulate_tiled_workspace_bytes": (c_sz, [c_ll, c_i, c_i, c_i]),
+    "tt_kmeans_accumulate_tiled": (c_i, [c_vp, c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
     "tt_label_propagate_sims": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
     "tt_label_propagate_from_sims": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_vp, c_sz, c_vp]),
     "tt_label_propagate_maps": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp, c_sz, c_vp]),

@@ -124,7 +124,27 @@ class Kmeans:
             raise RuntimeError(f"Number of training points ({n}) should be at least as large as number of clusters ({k})")
         if n > k * self.max_points_per_centroid:  # subsample_training_set
             x = x[self._perm(n, self.seed)[: k * self.max_points_per_centroid].to(x.device)].contiguous()
-        return self._lloyd(x, init_indices)
+        return self._fit(x, init_indices)
+
+    # -- the two kernel pairs ----------------------------------------------------------------------------------------------------------
+    # ``kmeans_assign`` / ``kmeans_accumulate`` hold all centroids in LDS and take what ``kmeans_shape_ok`` says (k * d <= 16384: k <= 327
+    # at the 50 PCA columns of cluster_features); ``kmeans_assign_tiled`` / ``kmeans_accumulate_tiled`` pass them through LDS in tiles and
+    # take any k.  Where both run they return the same bits, so the route does not show in a result; a shape the resident pair takes
+    # stays on it.
+
+    def _kernels(self, d: int):
+        """(assign, accumulate) for self.k centroids of d columns; a shape neither pair takes is refused here, before any launch."""
+        if ops.kmeans_shape_ok(d, self.k):
+            return ops.kmeans_assign, ops.kmeans_accumulate
+        if not ops.kmeans_tiled_shape_ok(d, self.k):
+            raise ops._lib.HipLibraryError(f"Kmeans: k = {self.k} centroids of d = {d} columns are beyond what the tiled k-means kernels "
+                                           "take (1 <= d <= 1024, k >= 1, k * d < 2^31)")
+        return ops.kmeans_assign_tiled, ops.kmeans_accumulate_tiled
+
+    def _fit(self, x: torch.Tensor, init_indices=None) -> float:
+        if ops.kmeans_shape_ok(x.shape[1], self.k):
+            return self._lloyd(x, init_indices)
+        return self._iterate(x, init_indices, *self._kernels(x.shape[1]))
 
     def _lloyd(self, x: torch.Tensor, init_indices=None) -> float:
         """The redos of Lloyd iterations on the (subsampled) training points x [n, d]."""
@@ -133,6 +153,12 @@ class Kmeans:
         if not ops.kmeans_shape_ok(d, k):   # refused here, not after the first assignment: both kernels share this rule
             raise ops._lib.HipLibraryError(f"Kmeans: k = {k} centroids of d = {d} columns are beyond what the k-means kernels hold in LDS "
                                        "(k * d <= 16384; at d = 64, k <= 252)")
+        return self._iterate(x, init_indices, ops.kmeans_assign, ops.kmeans_accumulate)
+
+    def _iterate(self, x: torch.Tensor, init_indices, assign, accumulate) -> float:
+        """The Lloyd loop both drivers share; ``assign`` / ``accumulate`` are the kernel pair."""
+        n, d = x.shape
+        k = self.k
         best_obj, best = float("inf"), None
         self.obj = []
         for redo in range(self.nredo):
@@ -143,9 +169,9 @@ class Kmeans:
             cent = x[idx.to(x.device)].clone()
             obj = float("inf")
             for _ in range(self.niter):
-                labels, dist2 = ops.kmeans_assign(x, cent, return_dist=True)
+                labels, dist2 = assign(x, cent, return_dist=True)
                 obj = float(dist2.double().sum())
-                sums, counts = ops.kmeans_accumulate(x, labels, k)
+                sums, counts = accumulate(x, labels, k)
                 counts_h = counts.cpu().numpy().copy()
                 nonempty = counts > 0
                 cent = torch.where(nonempty.unsqueeze(1), (sums / counts.clamp(min=1).unsqueeze(1)).float(), cent)
@@ -162,7 +188,7 @@ class Kmeans:
         x = torch.as_tensor(x, dtype=torch.float32)
         if not x.is_cuda:
             x = x.cuda()
-        labels, dist2 = ops.kmeans_assign(x.contiguous(), self._centroids_dev, return_dist=True)
+        labels, dist2 = self._kernels(x.shape[1])[0](x.contiguous(), self._centroids_dev, return_dist=True)
         return dist2, labels.long()
 
     # -- points that are the nearest upsampling of token grids ---------------------------------------------------------------------
@@ -192,7 +218,7 @@ class Kmeans:
         p = self._perm(n, self.seed)[: k * self.max_points_per_centroid] if n > k * self.max_points_per_centroid else torch.arange(n)
         rows = self._virtual_rows(p, M, g, R).to(tokens.device)
         x = tokens.reshape(M * n_tok, d)[rows].cuda().contiguous()
-        return self._lloyd(x, init_indices)
+        return self._fit(x, init_indices)
 
     def assign_upsampled(self, tokens: torch.Tensor, resolution: int) -> torch.Tensor:
         """Labels int64 [M, R*R] of the nearest upsampling of tokens [M, g*g, d]: one assignment per token, then the labels are
@@ -202,7 +228,7 @@ class Kmeans:
             tokens = tokens.cuda()
         M, n_tok, d = tokens.shape
         g = int(round(n_tok ** 0.5))
-        labels = ops.kmeans_assign(tokens.reshape(M * n_tok, d).contiguous(), self._centroids_dev)
+        labels = self._kernels(d)[0](tokens.reshape(M * n_tok, d).contiguous(), self._centroids_dev)
         iy, ix = nearest_index_table(g, resolution, device=tokens.device)
         return ops.nearest_upsample_labels(labels.view(M, n_tok), iy, ix)
 

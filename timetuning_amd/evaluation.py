@@ -4,8 +4,14 @@ the wandb plumbing are out of scope; the loader is any iterable of ``(data, anno
 
 ``use_mask=True`` evaluates masked features as the reference does (``evaluation.py:411-424,461-462``): with ``fg_masks`` given to the
 constructor (the foreground masks of cluster_based_foreground_extraction, [N, R', R']) the dataset-wise features are multiplied by
-the masks' nearest downsampling to the token grid; otherwise by the attention foreground (``models.apply_attention_mask``)."""
+the masks' nearest downsampling to the token grid; otherwise by the attention foreground (``models.apply_attention_mask``).
+
+``build_parser`` / ``main`` are the command line of ``evaluation.py:490-566`` (``python -m timetuning_amd.evaluation``): the reference's
+flags and defaults on a synthetic loader.  Any ``--num_clusters`` runs: ``clustering.Kmeans`` takes the tiled k-means kernels beyond what
+the LDS-resident ones hold, so the over-clustering protocol (``--num_clusters 500 --many_to_one True``) is one invocation."""
 from __future__ import annotations
+
+import argparse
 
 import torch
 import torch.nn.functional as F
@@ -129,3 +135,66 @@ class Evaluator:
             maps = self._cluster(features, g, eval_resolution, evaluation_protocol, num_clusters, annotations if use_annotations else None)
             scores.append(evaluate_localizations(self.PredsEval, annotations, maps, evaluation_protocol, None, many_to_one, precision_based))
         return sum(scores) / len(scores)
+
+
+# ------------------------------------------------------------------------------------------------
+# command line (evaluation.py:490-566)
+# ------------------------------------------------------------------------------------------------
+
+def build_parser() -> argparse.ArgumentParser:
+    """Flag names, types and defaults of ``evaluation.py:544-566``.  The ``type=bool`` flags treat ANY non-empty string as True, as in
+    the reference (and in ``time_tuning.build_parser``): ``--many_to_one False`` turns many-to-one matching ON.  ``--dataset_path``,
+    ``--destination_path``, ``--num_workers`` and ``--logging_directory`` are parsed and unused (the dataset readers and the video
+    logging are out of scope).  Added: ``--dataset synthetic`` and ``--eval_clips``; an EMPTY ``--model_path`` selects synthetic weights."""
+    p = argparse.ArgumentParser()
+    p.add_argument("--architecture", type=str, default="dino-s16", help="which back-bone architecture do you want to use?")
+    p.add_argument("--model_path", type=str, default="/home/ssalehi/video/vos_pretrained/cyclic_swav/src/leopart_vits16.ckpt")
+    p.add_argument("--dataset", type=str, default="davis_val")
+    p.add_argument("--dataset_path", type=str, default="../data")
+    p.add_argument("--destination_path", type=str, default="ytvos")
+    p.add_argument("--evaluation_protocol", type=str, default="frame-wise")
+    p.add_argument("--logging_directory", type=str, default="visualizations")
+    p.add_argument("--batch_size", type=int, default=16)
+    p.add_argument("--num_workers", type=int, default=3)
+    p.add_argument("--num_clusters", type=int, default=10)
+    p.add_argument("--input_resolution", type=int, default=224)
+    p.add_argument("--many_to_one", type=bool, default=False)
+    p.add_argument("--num_frames", type=int, default=4)
+    p.add_argument("--precision_based", type=bool, default=False)
+    p.add_argument("--uvos", type=int, default=False)
+    p.add_argument("--use_teacher", type=bool, default=False)
+    p.add_argument("--EMA_decay", type=float, default=0.999)
+    p.add_argument("--eval_clips", type=int, default=8, help="synthetic evaluation set size")
+    return p
+
+
+def main(argv=None, vit_cfg=None) -> float:
+    """``evaluation.py:490-540``: a FeatureExtractor with the [1024, 1024, 512, 256] head inside ``TimeT(fe, 200)``, optionally with its
+    EMA teacher, evaluated by k-means over the headless features; returns (and prints, as the reference) the dataset score.
+    ``vit_cfg`` (not a flag) replaces the architecture's transformer sizes - a testing aid, as in ``FeatureExtractor``."""
+    from .time_tuning import SyntheticEvalClips, TimeT
+
+    args = build_parser().parse_args(argv)
+    if args.dataset != "synthetic":
+        raise NotImplementedError("the dataset readers (data_loader.py: directory scanning, JPEG decoding) are out of scope for this "
+                                  "build; run with --dataset synthetic")
+    num_epochs, num_itr = 50, 1000                                                     # :491,513
+    device = torch.device("cuda", 0)
+    fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], vit_cfg=vit_cfg, return_attention=False)  # :520
+    model = TimeT(fe, 200)
+    if args.use_teacher:
+        model.init_momentum_teacher()
+        model.set_momentum_teacher_schedular_params(args.EMA_decay, 1.0, num_epochs, num_itr)
+    model = model.to(device)
+    loader = SyntheticEvalClips(args.eval_clips, args.num_frames, args.input_resolution, args.batch_size, device)
+    eval_resolution = 112 if args.evaluation_protocol == "dataset-wise" else args.input_resolution   # :536
+    evaluator = Evaluator(model, loader, 10, device, clustering_algorithm="k-means", uvos_flag=bool(args.uvos), involve_bg=True)  # :364,539
+    score = float(evaluator.evaluate(many_to_one=args.many_to_one, evaluation_protocol=args.evaluation_protocol,
+                                     eval_resolution=eval_resolution, num_clusters=args.num_clusters, use_annotations=False,
+                                     use_mask=False, precision_based=args.precision_based))
+    print(f"Dataset score is {score}")
+    return score
+
+
+if __name__ == "__main__":
+    main()

@@ -991,6 +991,44 @@ def kmeans_accumulate(x, labels, k: int):
     return sums, counts
 
 
+def kmeans_tiled_shape_ok(d: int, k: int) -> bool:
+    """Whether ``kmeans_assign_tiled`` and ``kmeans_accumulate_tiled`` take k centroids of d columns (tt_kmeans_tiled_shape_ok)."""
+    return bool(_lib.load().tt_kmeans_tiled_shape_ok(int(d), int(k)))
+
+
+def kmeans_tile_centroids(d: int) -> int:
+    """The default (and largest) ``tile_k`` at d columns: the centroid rows that fill at most 64 KB of LDS."""
+    return int(_lib.load().tt_kmeans_tile_centroids(int(d)))
+
+
+def kmeans_assign_tiled(x, centroids, return_dist=False, tile_k: int = 0):
+    """``kmeans_assign`` for centroids that do not fit in LDS: they pass through it ``tile_k`` rows at a time (0 = the default tile).
+    Same layouts and dtypes, and the same bits wherever ``kmeans_assign`` runs."""
+    lib = _lib.load()
+    _chk(x, "x"); _chk(centroids, "centroids")
+    P, d = x.shape
+    k = centroids.shape[0]
+    labels = torch.empty(P, dtype=torch.int32, device=x.device)
+    dist2 = torch.empty(P, dtype=f32, device=x.device) if return_dist else None
+    _lib.check(lib.tt_kmeans_assign_tiled(_p(x), _p(centroids), _p(labels), _p(dist2), P, d, k, int(tile_k), _stream()), "tt_kmeans_assign_tiled")
+    return (labels, dist2) if return_dist else labels
+
+
+def kmeans_accumulate_tiled(x, labels, k: int, tile_k: int = 0):
+    """``kmeans_accumulate`` for k * d beyond the LDS: sums [k, d] (fp64) and counts [k] (int64), one tile of ``tile_k`` clusters at a
+    time (0 = the default tile).  The same bits wherever ``kmeans_accumulate`` runs."""
+    lib = _lib.load()
+    _chk(x, "x"); _chk(labels, "labels", torch.int32)
+    P, d = x.shape
+    sums = torch.empty((k, d), dtype=torch.float64, device=x.device)
+    counts = torch.empty(k, dtype=torch.int64, device=x.device)
+    nb = lib.tt_kmeans_accumulate_tiled_workspace_bytes(P, d, k, int(tile_k))
+    ws = _ws(nb, x.device)
+    _lib.check(lib.tt_kmeans_accumulate_tiled(_p(x), _p(labels), _p(sums), _p(counts), P, d, k, int(tile_k), _p(ws), nb, _stream()),
+               "tt_kmeans_accumulate_tiled")
+    return sums, counts
+
+
 def ce_loss_fwd_bwd(scores, labels, temperature=0.1, need_grad=True, row_weight=None):
     """mean CE of scores/temperature vs labels (per-row weights = the --use_mask loss mask); returns (loss[1], dscores or None)."""
     lib = _lib.load()
