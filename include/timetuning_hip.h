@@ -610,7 +610,45 @@ size_t tt_kmeans_accumulate_tiled_workspace_bytes(long long P, int d, int k, int
 int tt_kmeans_accumulate_tiled(const float* x, const int32_t* labels, double* sums, long long* counts, long long P, int d, int k,
                                int tile_k, void* workspace, size_t workspace_bytes, tt_stream_t stream);
 
-/* ---- N3: the clip input pipeline - the pixel work of video_transformations.py as wired at
+/* ---- N13: the whole Lloyd loop of B k-means problems in one launch - what the frame-wise and sample-wise protocols of
+ *      cluster_features ask per frame / per clip: faiss.Kmeans(50, k, niter=50, nredo=5).train(x) at clustering.py:39-41,55-57
+ *      (Clustering::train as configured there, after its subsample) and the index.search(x, 1) that follows it.
+ *   tt_kmeans_fit_batched      x [B, n, d] (B problems of equal shape), init int32 [nredo, k] (rows of a problem's points that seed
+ *                              redo r, shared by all problems; init_host is a HOST copy of it, checked before the launch) ->
+ *                              centroids [B, nredo, k, d], obj fp64 [B, nredo], status int32 [B, nredo].  One workgroup per
+ *                              (problem, redo) runs niter iterations; no workgroup waits on another.  Per output number the
+ *                              arithmetic is that of the loop over tt_kmeans_assign / tt_kmeans_accumulate:
+ *                                assignment    per centroid j in order s = 0.f, over the columns in order df = x - c, s += df * df;
+ *                                              first minimum by strict <, from best = INFINITY, besti = 0;
+ *                                accumulation  tt_kmeans_accumulate's sums: clamp(ceil(n / 128), 1, 4096) blocks of consecutive points,
+ *                                              fp32 per (cluster, column) from 0.f in point order inside a block, the partials widened
+ *                                              to fp64 and added in block order; integer counts;
+ *                                update        c = (float)(sum / (double)count) where count > 0, the old centroid otherwise;
+ *                                objective     obj[b][r] is the LAST iteration's fp64 sum of the points' best distances (to the
+ *                                              centroids before the last update), summed in an order fixed by n alone;
+ *                                empty cluster an iteration whose counts hold a zero ends that (problem, redo): status = the 1-based
+ *                                              iteration, its centroids and obj are unspecified.  Otherwise status = 0.  faiss'
+ *                                              split is not done here: the caller reruns such a problem on the loop.
+ *   tt_kmeans_assign_batched   x [B, N, d], centroids [B, k, d] -> labels int32 [B, N] (+ dist2 [B, N], optional): tt_kmeans_assign
+ *                              per problem, bit for bit; the problems ride on gridDim.y, 65535 per launch, any B >= 1.
+ *   tt_kmeans_fit_shape_ok     1 for 1 <= d <= 64 (the point's row in registers), 1 <= k <= n <= 2^20 and 16 k d + 4 k bytes within
+ *                              128 KB of LDS (fp64 sums, centroids, one block's fp32 sums, counts): k <= 127 at d = 64, k <= 163 at
+ *                              d = 50; every 1 <= d, k <= 64 with k <= n <= 256 k is inside.  Else 0.
+ *   tt_kmeans_fit_workspace_bytes   the labels of every (problem, redo), 4 B nredo n bytes; 0 for a refused shape.
+ *   tt_kmeans_assign_batched takes the (d, k) of tt_kmeans_shape_ok.  Refused with TT_EINVAL and a message naming the numbers, nothing
+ *   launched: null pointers, B outside 1 ... 65535 (fit), niter < 1, nredo < 1, n < k, an init index outside [0, n), a shape beyond
+ *   the rule, a workspace that is too small. */
+int tt_kmeans_fit_shape_ok(long long n, int d, int k);   /* pure host function, like tt_kmeans_shape_ok */
+size_t tt_kmeans_fit_lds_bytes(long long n, int d, int k);   /* the LDS a fit workgroup asks for: as many blocks' fp32 sums side by side
+                                                                as fit 72 KB (two workgroups per CU), at least one; 0 = refused */
+size_t tt_kmeans_fit_workspace_bytes(int B, int nredo, long long n, int d, int k);
+int tt_kmeans_fit_batched(const float* x, const int32_t* init, const int32_t* init_host, float* centroids, double* obj, int32_t* status,
+                          int B, long long n, int d, int k, int nredo, int niter, void* workspace, size_t workspace_bytes,
+                          tt_stream_t stream);
+int tt_kmeans_assign_batched(const float* x, const float* centroids, int32_t* labels, float* dist2, int B, long long N, int d, int k,
+                             tt_stream_t stream);
+
+/* ---- N3(SURVEY.md 8(f)): the clip input pipeline - the pixel work of video_transformations.py as wired at
  *      time_tuning.py:588-593, bit-exact with Pillow (which the reference calls per frame on the host).
  *   Frames are interleaved uint8 RGB [F, H, W, 3] in device memory.
  *   tt_img_resample_h   horizontal pass of Image.resize(BILINEAR) (Resample.c) over the crop rows y0..y0+h, columns starting

@@ -233,6 +233,72 @@ class Kmeans:
         return ops.nearest_upsample_labels(labels.view(M, n_tok), iy, ix)
 
 
+class KmeansBatch:
+    """``Kmeans(d, k, ...)`` for B problems of equal shape at once: ``train(points [B, n, d])`` runs every problem's redos and Lloyd
+    iterations in ONE launch (``ops.kmeans_fit_batched``) and reads the objectives and the empty-cluster flags back once.  Per problem
+    the subsample, the seeds and the arithmetic are those of ``Kmeans.train``, so the centroids are the same bits - with one
+    reservation: the per-redo objective is the kernel's own fixed-order fp64 sum, not torch's reduction (they agree to about
+    n * 2^-53 relative), so the redo kept can differ where two DISTINCT objectives lie that close.  A problem in which any redo met an
+    empty cluster is rerun whole on the loop (``Kmeans._fit``), which knows faiss' split; ``fallback`` says which."""
+
+    def __init__(self, d: int, k: int, niter: int = 50, nredo: int = 5, seed: int = 1, max_points_per_centroid: int = 256):
+        self.d, self.k, self.niter, self.nredo, self.seed = d, k, niter, nredo, seed
+        self.max_points_per_centroid = max_points_per_centroid
+        self.centroids: Optional[torch.Tensor] = None   # [B, k, d] on the device
+        self.obj: list = []                             # per problem, the per-redo objectives (as Kmeans.obj)
+        self.fallback: list = []                        # per problem, whether the loop replaced the kernel's result
+        self.status: Optional[np.ndarray] = None        # [B, nredo]: 0, or the iteration at which the kernel met an empty cluster
+
+    def train(self, points, init_indices=None) -> list:
+        """points [B, n, d].  ``init_indices`` [nredo, k] optionally fixes the initial centroids of every problem (testing aid).
+        Returns the best objective of each problem."""
+        x = torch.as_tensor(points, dtype=torch.float32)
+        if not x.is_cuda:
+            x = x.cuda()
+        B, n, d = x.shape
+        k = self.k
+        if n < k:
+            raise RuntimeError(f"Number of training points ({n}) should be at least as large as number of clusters ({k})")
+        if n > k * self.max_points_per_centroid:  # subsample_training_set: the draw depends on n alone, so all problems share it
+            x = x[:, Kmeans._perm(n, self.seed)[: k * self.max_points_per_centroid].to(x.device)]
+        x = x.contiguous()
+        n = x.shape[1]
+        if init_indices is not None:
+            init = torch.stack([torch.as_tensor(init_indices[r], dtype=torch.int64) for r in range(self.nredo)])
+        else:
+            init = torch.stack([Kmeans._perm(n, self.seed + 1 + r * 15486557)[:k] for r in range(self.nredo)])
+        cent, obj, status = ops.kmeans_fit_batched(x, init.to(torch.int32), self.niter)
+        host = torch.cat([obj, status.to(torch.float64)], dim=1).cpu().numpy()   # the one read-back
+        obj_h, status_h = host[:, : self.nredo], host[:, self.nredo:]
+        self.status = status_h.astype(np.int32)
+        self.obj, self.fallback, best_obj, pick = [], [], [], []
+        for b in range(B):
+            self.fallback.append(bool((status_h[b] != 0).any()))
+            best, best_r = float("inf"), 0
+            for r in range(self.nredo):   # the loop's ``obj < best_obj``: the first redo with the strictly smallest objective
+                if float(obj_h[b, r]) < best:
+                    best, best_r = float(obj_h[b, r]), r
+            self.obj.append([float(o) for o in obj_h[b]])
+            best_obj.append(best)
+            pick.append(best_r)
+        self.centroids = cent[torch.arange(B, device=cent.device), torch.as_tensor(pick, device=cent.device)].contiguous()
+        for b in range(B):
+            if self.fallback[b]:   # the unchanged loop on the very subsample and seeds
+                km = Kmeans(d, k, niter=self.niter, nredo=self.nredo, seed=self.seed, max_points_per_centroid=self.max_points_per_centroid)
+                best_obj[b] = km._fit(x[b], init)
+                self.centroids[b] = km._centroids_dev
+                self.obj[b] = list(km.obj)
+        return best_obj
+
+    def assign(self, points):
+        """points [B, N, d] -> (dist2 [B, N], labels int64 [B, N]) against each problem's own centroids."""
+        x = torch.as_tensor(points, dtype=torch.float32)
+        if not x.is_cuda:
+            x = x.cuda()
+        labels, dist2 = ops.kmeans_assign_batched(x.contiguous(), self.centroids, return_dist=True)
+        return dist2, labels.long()
+
+
 def nearest_index_table(g: int, R: int, device=None):
     """Row / column source indices of ``F.interpolate(mode="nearest")`` from g x g to R x R, read off torch itself (an index grid
     interpolated on the host): int32 numpy arrays (iy, ix), or int32 tensors on ``device``."""
@@ -256,6 +322,28 @@ def _kmeans_maps(points: torch.Tensor, num_clusters: int) -> torch.Tensor:
     return km.assign(points)[1]
 
 
+def _kmeans_maps_grouped(points: torch.Tensor, ks) -> torch.Tensor:
+    """``_kmeans_maps`` of every problem of points [B, N, d], problem b with ks[b] clusters -> labels int64 [B, N].  The problems of one
+    k run as one ``KmeansBatch`` where the fused fit takes their (subsampled) shape, and one after the other on the loop otherwise;
+    both return the same bits (the reservation on nearly equal objectives: ``KmeansBatch``)."""
+    B, N, d = points.shape
+    out = torch.empty((B, N), dtype=torch.int64, device=points.device)
+    for k in sorted(set(ks)):
+        idx = [b for b in range(B) if ks[b] == k]
+        if ops.kmeans_fit_shape_ok(min(N, 256 * k), d, k):
+            group = points if len(idx) == B else points[torch.as_tensor(idx, device=points.device)]
+            kb = KmeansBatch(d, k, niter=50, nredo=5, seed=1)
+            kb.train(group)
+            labels = kb.assign(group)[1]
+            if len(idx) == B:
+                return labels
+            out[torch.as_tensor(idx, device=points.device)] = labels
+        else:
+            for b in idx:
+                out[b] = _kmeans_maps(points[b], k)
+    return out
+
+
 def cluster_features(features, num_clusters, feature_resolution, input_resolution, evaluation_protocol, annotations=None):
     """``clustering.cluster_features``: features [bs, fs, num_patches, dim] -> cluster maps [bs, fs, R, R] int16."""
     bs, fs, num_patches, dim = features.shape
@@ -264,19 +352,12 @@ def cluster_features(features, num_clusters, feature_resolution, input_resolutio
     feats = feats.view(bs * fs, num_patches, dim)
     R = input_resolution
     up = ops.upsample_bilinear_tokens(feats, R).view(bs, fs, R * R, dim)      # what the reference builds frame by frame
-    if evaluation_protocol == "frame-wise":
-        maps = []
-        for i in range(bs):
-            for j in range(fs):
-                k = torch.unique(annotations[i, j]).shape[0] if annotations is not None else num_clusters
-                maps.append(_kmeans_maps(up[i, j], k).view(1, 1, R, R))
-        out = torch.cat(maps, dim=0).view(bs, fs, R, R)
-    elif evaluation_protocol == "sample-wise":
-        maps = []
-        for i in range(bs):
-            k = torch.unique(annotations[i]).shape[0] if annotations is not None else num_clusters
-            maps.append(_kmeans_maps(up[i].reshape(fs * R * R, dim), k).view(1, fs, R, R))
-        out = torch.cat(maps, dim=0)
+    if evaluation_protocol == "frame-wise":   # one k-means per frame
+        ks = [torch.unique(annotations[i, j]).shape[0] if annotations is not None else num_clusters for i in range(bs) for j in range(fs)]
+        out = _kmeans_maps_grouped(up.view(bs * fs, R * R, dim), ks).view(bs, fs, R, R)
+    elif evaluation_protocol == "sample-wise":   # one per clip
+        ks = [torch.unique(annotations[i]).shape[0] if annotations is not None else num_clusters for i in range(bs)]
+        out = _kmeans_maps_grouped(up.view(bs, fs * R * R, dim), ks).view(bs, fs, R, R)
     elif evaluation_protocol == "dataset-wise":
         k = torch.unique(annotations).shape[0] if annotations is not None else num_clusters
         out = _kmeans_maps(up.reshape(bs * fs * R * R, dim), k).view(bs, fs, R, R)

@@ -1029,6 +1029,50 @@ def kmeans_accumulate_tiled(x, labels, k: int, tile_k: int = 0):
     return sums, counts
 
 
+def kmeans_fit_shape_ok(n: int, d: int, k: int) -> bool:
+    """Whether ``kmeans_fit_batched`` takes problems of n points, d columns and k clusters (tt_kmeans_fit_shape_ok)."""
+    return bool(_lib.load().tt_kmeans_fit_shape_ok(int(n), int(d), int(k)))
+
+
+def kmeans_fit_batched(x, init, niter: int):
+    """The Lloyd loops of B problems in one launch: x [B, n, d], init int32 [nredo, k] on the HOST (rows of each problem's points that
+    seed redo r) -> centroids [B, nredo, k, d], obj fp64 [B, nredo], status int32 [B, nredo] (0, or the 1-based iteration at which an
+    empty cluster ended that redo: its centroids and objective are then unspecified).  Everything stays on the device."""
+    lib = _lib.load()
+    _chk(x, "x")
+    B, n, d = x.shape
+    init_h = torch.as_tensor(init, dtype=torch.int32).cpu().contiguous()
+    if init_h.dim() != 2:
+        raise ValueError(f"init: expected [nredo, k], got {tuple(init_h.shape)}")
+    nredo, k = init_h.shape
+    init_d = init_h.to(x.device)
+    cent = torch.empty((B, nredo, k, d), dtype=f32, device=x.device)
+    obj = torch.empty((B, nredo), dtype=torch.float64, device=x.device)
+    status = torch.empty((B, nredo), dtype=torch.int32, device=x.device)
+    step = max(1, min(B, 65535))   # problems of one launch (they ride on gridDim.y)
+    nb = lib.tt_kmeans_fit_workspace_bytes(step, nredo, n, d, k)
+    ws = _ws(nb, x.device)
+    for b0 in range(0, B, step):
+        b1 = min(b0 + step, B)
+        _lib.check(lib.tt_kmeans_fit_batched(_p(x[b0:b1]), _p(init_d), _p(init_h), _p(cent[b0:b1]), _p(obj[b0:b1]), _p(status[b0:b1]), b1 - b0, n, d, k,
+                                             nredo, int(niter), _p(ws), nb, _stream()), "tt_kmeans_fit_batched")
+    return cent, obj, status
+
+
+def kmeans_assign_batched(x, centroids, return_dist=False):
+    """x [B, N, d], centroids [B, k, d] -> labels int32 [B, N] (+ squared distances): ``kmeans_assign`` per problem, in one launch."""
+    lib = _lib.load()
+    _chk(x, "x"); _chk(centroids, "centroids")
+    B, N, d = x.shape
+    if centroids.shape[0] != B or centroids.shape[2] != d:
+        raise ValueError(f"centroids: expected [{B}, k, {d}], got {tuple(centroids.shape)}")
+    k = centroids.shape[1]
+    labels = torch.empty((B, N), dtype=torch.int32, device=x.device)
+    dist2 = torch.empty((B, N), dtype=f32, device=x.device) if return_dist else None
+    _lib.check(lib.tt_kmeans_assign_batched(_p(x), _p(centroids), _p(labels), _p(dist2), B, N, d, k, _stream()), "tt_kmeans_assign_batched")
+    return (labels, dist2) if return_dist else labels
+
+
 def ce_loss_fwd_bwd(scores, labels, temperature=0.1, need_grad=True, row_weight=None):
     """mean CE of scores/temperature vs labels (per-row weights = the --use_mask loss mask); returns (loss[1], dscores or None)."""
     lib = _lib.load()
