@@ -560,6 +560,13 @@ int tt_foreground_mask_from_probs(const float* cls_probs, float* mask_out, float
  *   tt_upsample_argmax_f32      fp32 twin of tt_upsample_argmax for proto_clustering's prototype scores (clustering.py:101-104).
  *   tt_kmeans_assign            labels[p] = argmin_j |x_p - c_j|^2 (first minimum) over centroids [k, d]; dist2 optional.
  *   tt_kmeans_accumulate        sums[k, d] (fp64) and counts[k] of the points per label, deterministic (no atomics).
+ *   THE K-MEANS CONTRACT, shared by every k-means entry here, in N12 and in N13 (one statement in the code as well: csrc/kmeans.hpp), so
+ *   that wherever two of them take a shape their outputs are equal bit for bit:
+ *     distance      per centroid j one fp32 accumulator: s = 0.f, then over the columns in increasing order df = x - c, s += df * df
+ *                   (contracted to one fma);
+ *     assignment    the FIRST minimum: from best = INFINITY, besti = 0, updated by a strict s < best in increasing j;
+ *     accumulation  the points are cut into clamp(ceil(P / 128), 1, 4096) blocks of consecutive points; per (cluster, column) fp32 from
+ *                   0.f in point order inside a block, the partials widened to fp64 and added in block order; integer counts.
  *   Accepted domains (each refusal is a TT_EINVAL with the entry's own message; nothing is launched):
  *     tt_col_moments              0 < cols <= 1024; any rows > 0 (1024 workgroups from 262 144 rows on).  The sums are taken about
  *                                 the column's first row, so a small variance beside a large mean survives.
@@ -591,8 +598,8 @@ int tt_kmeans_accumulate(const float* x, const int32_t* labels, double* sums, lo
 /* ---- N12: k-means beyond the LDS limit - the same two passes for centroid sets tt_kmeans_shape_ok refuses, which
  *      the reference's over-clustering needs: faiss.Kmeans(50, 500) at clustering.py:39-41,55-57,69-71 (cluster_features, the three
  *      protocols; evaluation.py:431-441 with many_to_one) and faiss.Kmeans(256, num_classes) at clustering.py:108-110 (proto_clustering).
- *   The centroids (the sums) pass through LDS in tiles of tile_k rows; the arithmetic per output number is that of the resident
- *   entries, so wherever both take a shape the outputs are equal bit for bit, whatever tile_k is.
+ *   The centroids (the sums) pass through LDS in tiles of tile_k rows; the arithmetic per output number is the k-means contract (N2
+ *   above), so wherever both pairs take a shape the outputs are equal bit for bit, whatever tile_k is.
  *   tt_kmeans_tiled_shape_ok      1 for 1 <= d <= 1024, k >= 1, k * d < 2^31, else 0.
  *   tt_kmeans_tile_centroids      the default tile at d: the most rows of d floats that fill at most 64 KB (0 outside 1 <= d <= 1024).
  *   tt_kmeans_assign_tiled        tt_kmeans_assign (clustering.py:39-41,55-57,69-71,108-110: index.search(x, 1) and the assignment of every
@@ -618,11 +625,7 @@ int tt_kmeans_accumulate_tiled(const float* x, const int32_t* labels, double* su
  *                              centroids [B, nredo, k, d], obj fp64 [B, nredo], status int32 [B, nredo].  One workgroup per
  *                              (problem, redo) runs niter iterations; no workgroup waits on another.  Per output number the
  *                              arithmetic is that of the loop over tt_kmeans_assign / tt_kmeans_accumulate:
- *                                assignment    per centroid j in order s = 0.f, over the columns in order df = x - c, s += df * df;
- *                                              first minimum by strict <, from best = INFINITY, besti = 0;
- *                                accumulation  tt_kmeans_accumulate's sums: clamp(ceil(n / 128), 1, 4096) blocks of consecutive points,
- *                                              fp32 per (cluster, column) from 0.f in point order inside a block, the partials widened
- *                                              to fp64 and added in block order; integer counts;
+ *                                assignment, accumulation   the k-means contract (N2 above);
  *                                update        c = (float)(sum / (double)count) where count > 0, the old centroid otherwise;
  *                                objective     obj[b][r] is the LAST iteration's fp64 sum of the points' best distances (to the
  *                                              centroids before the last update), summed in an order fixed by n alone;
@@ -630,7 +633,8 @@ int tt_kmeans_accumulate_tiled(const float* x, const int32_t* labels, double* su
  *                                              iteration, its centroids and obj are unspecified.  Otherwise status = 0.  faiss'
  *                                              split is not done here: the caller reruns such a problem on the loop.
  *   tt_kmeans_assign_batched   x [B, N, d], centroids [B, k, d] -> labels int32 [B, N] (+ dist2 [B, N], optional): tt_kmeans_assign
- *                              per problem, bit for bit; the problems ride on gridDim.y, 65535 per launch, any B >= 1.
+ *                              per problem, bit for bit (tt_kmeans_assign IS this kernel at one problem); the problems ride on
+ *                              gridDim.y, 65535 per launch, any B >= 1.
  *   tt_kmeans_fit_shape_ok     1 for 1 <= d <= 64 (the point's row in registers), 1 <= k <= n <= 2^20 and 16 k d + 4 k bytes within
  *                              128 KB of LDS (fp64 sums, centroids, one block's fp32 sums, counts): k <= 127 at d = 64, k <= 163 at
  *                              d = 50; every 1 <= d, k <= 64 with k <= n <= 256 k is inside.  Else 0.

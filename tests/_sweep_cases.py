@@ -94,11 +94,11 @@ def _queue_push(rng):
 
 
 # ---- second tier: the evaluator, optimizer and mask kernels (checks: tests/_sweep_checks_eval.py, on the C twin and on the HIP library)
-KM_MAXKD = 16384          # cluster.hip: k * d floats of centroids in LDS
+KM_MAXKD = 16384          # kmeans.hpp: k * d floats of centroids in LDS
 
 
 def km_max_k(d: int) -> int:
-    """cluster.hip, km_shape_ok: the largest k both k-means entries take at d (k * d <= KM_MAXKD; at d <= 64 the point tile shares the LDS)."""
+    """kmeans.hpp, km_shape_ok: the largest k both k-means entries take at d (k * d <= KM_MAXKD; at d <= 64 the point tile shares the LDS)."""
     k = KM_MAXKD // d
     if d <= 64:
         k = min(k, (128 * 1024 // 4 - 256 * (d | 1)) // d)
@@ -286,7 +286,7 @@ PINNED = {
     "sinkhorn_from_q": [dict(B=777, K=333, iters=5, transposed=0), dict(B=2049, K=256, iters=0, transposed=1), dict(B=65, K=511, iters=1, transposed=1)],
     "sinkhorn_local": [dict(B=777, K=333, iters=5), dict(B=2049, K=257, iters=0), dict(B=31, K=64, iters=1)],
     "queue_push": [dict(Q=40, D=32, m=1), dict(Q=40, D=32, m=40), dict(Q=1, D=128, m=1)],
-    # ---- second tier (cluster.hip, label_prop.hip, rowops.hip, attn_mask.hip)
+    # ---- second tier (cluster.hip, kmeans.hip, label_prop.hip, rowops.hip, attn_mask.hip)
     "kmeans_assign": [
         # tt_kmeans_assign's dispatch: d <= 16 (16 registers), d <= 64 (64 registers), wider rows read in place - either side of each edge
         dict(P=300, d=1, k=7, dup=0), dict(P=5000, d=16, k=100, dup=0), dict(P=5000, d=17, k=100, dup=0), dict(P=20000, d=64, k=200, dup=0),
@@ -300,7 +300,7 @@ PINNED = {
         dict(P=3000, d=16, k=1024, dup=0), dict(P=3000, d=64, k=252, dup=0), dict(P=3000, d=128, k=128, dup=0),
     ],
     "kmeans_accumulate": [
-        # accumulate_blocks: ceil(P / 128) workgroups up to 4096 - beyond P = 524 288 a workgroup sums MORE than 128 points (129 here, and the
+        # km_accumulate_blocks: ceil(P / 128) workgroups up to 4096 - beyond P = 524 288 a workgroup sums MORE than 128 points (129 here, and the
         # last 31 workgroups get none; 147 at 600 000); under the cap every workgroup has points
         dict(P=524289, d=8, k=5, mode="rand"), dict(P=600000, d=3, k=7, mode="skip"), dict(P=1100000, d=8, k=5, mode="rand"),
         dict(P=524288, d=2, k=3, mode="rand"), dict(P=7001, d=50, k=21, mode="rand"), dict(P=1, d=1, k=1, mode="rand"),

@@ -156,6 +156,28 @@ def test_batched_assignment_equals_one_call_per_problem(ops, d, k):
     assert torch.equal(ops.kmeans_assign_batched(x, c), labels)
 
 
+@pytest.mark.parametrize("dup", [False, True])
+@pytest.mark.parametrize("d,k", [(16, 1024), (64, 252), (128, 128)])   # the largest k the resident rule takes on each of the three routes
+def test_batched_assignment_equals_the_tiled_kernel(ops, d, k, dup):
+    """``tt_kmeans_assign`` is the batched kernel at one problem, so the test above holds the offsets only; the arithmetic is held here
+    against another kernel body, the tiled assignment with a tile of 7 centroids.  ``dup``: centroid 3 is point 0 itself and is
+    repeated as centroid k - 1, in another tile - both kernels must keep the first of the two equal (zero) distances."""
+    N = 700
+    x = synth.normal(f"kf.t.x.{d}", (B, N, d))
+    c = synth.normal(f"kf.t.c.{d}.{k}", (B, k, d)) * 0.5
+    if dup:
+        c[:, 3] = x[:, 0]
+        c[:, k - 1] = c[:, 3]
+    x, c = dev(x), dev(c)
+    assert ops.kmeans_shape_ok(d, k) and not ops.kmeans_shape_ok(d, k + 1)
+    labels, dist2 = ops.kmeans_assign_batched(x, c, return_dist=True)
+    for b in range(B):
+        tl, td2 = ops.kmeans_assign_tiled(x[b], c[b], return_dist=True, tile_k=7)
+        assert torch.equal(labels[b], tl) and torch.equal(dist2[b], td2), b
+        if dup:
+            assert int(labels[b, 0]) == 3 and float(dist2[b, 0]) == 0.0, b
+
+
 # ---- 5. cluster_features ------------------------------------------------------------------------------------------------------------------
 
 def _planted():

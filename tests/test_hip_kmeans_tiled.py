@@ -1,5 +1,5 @@
-"""GPU checks of N12, k-means beyond the LDS limit (kmeans_tiled.hip): the tiled assignment and accumulation are held BIT FOR BIT to the
-LDS-resident pair of cluster.hip wherever both run, and - beyond what the resident pair takes - to combinations of resident calls on
+"""GPU checks of N12, k-means beyond the LDS limit (kmeans.hip): the tiled assignment and accumulation are held BIT FOR BIT to the
+LDS-resident pair of the same file wherever both run, and - beyond what the resident pair takes - to combinations of resident calls on
 centroid chunks that fit (no tolerance either) and to fp64 NumPy at the bounds of tests/test_hip_evaluator.py::test_kmeans_kernels.
 Then the router in ``clustering.Kmeans``, ``cluster_features`` / ``proto_clustering`` at cluster counts the resident kernels refuse, and
 the evaluation command line."""

@@ -112,6 +112,17 @@ def test_assign_batched_refusals(lib):
         assert ("beyond what kmeans_assign takes" in refused[1]) == (not lib.tt_kmeans_shape_ok(d, k)), (d, k, refused)
 
 
+def test_assign_batched_takes_exactly_the_resident_rule(lib):
+    """One centroid beyond the largest k ``tt_kmeans_shape_ok`` accepts at d is refused by the batched entry, by argument (TT_EINVAL, not a
+    failed launch) and naming k and d.  The refusing side only: an accepted shape would launch on the dummy pointers."""
+    for d in list(range(1, 130)) + [256, 384, 1024]:
+        kmax = max(k for k in range(1, 16384 // d + 2) if lib.tt_kmeans_shape_ok(d, k))
+        assert lib.tt_kmeans_shape_ok(d, kmax) and not lib.tt_kmeans_shape_ok(d, kmax + 1), (d, kmax)
+        rc = lib.tt_kmeans_assign_batched(16, 16, 16, None, 3, 10, d, kmax + 1, None)
+        msg = lib.tt_last_error().decode()
+        assert rc == TT_EINVAL and f"k = {kmax + 1}, d = {d}" in msg and "beyond what kmeans_assign takes" in msg, (d, kmax, rc, msg)
+
+
 # ---- KmeansBatch, with a NumPy stand-in for the fused kernel ------------------------------------------------------------------------------
 
 OBJ = np.array([[5.0, 3.0, 3.0], [4.0, 1.0, 2.0], [2.0, 2.0, 9.0]])

@@ -226,7 +226,7 @@ def test_second_tier_is_appended_and_complete():
     assert len(first) == 130 and first[0] == "linear_f32[M=1,N=64,K=20,act=0,res=0]" and first[-4] == "queue_push[Q=1,D=128,m=1]"
 
 
-def km_assign_kernel(d):                     # cluster.hip, tt_kmeans_assign: kmeans_assign_kernel<16>, <64>, <0>
+def km_assign_kernel(d):                     # kmeans.hip, tt_kmeans_assign: kmeans_assign_kernel<16>, <64>, <0>
     return 16 if d <= 16 else (64 if d <= 64 else 0)
 
 
@@ -235,7 +235,7 @@ def km_assign_strides(P):                    # tt_kmeans_assign: ceil(P / 256) w
 
 
 def test_kmeans_shape_rule_is_one_rule(lib):
-    # cluster.hip, km_shape_ok: k * d <= KM_MAXKD, and at d <= 64 the tile of 256 points shares the 128 KB of LDS
+    # kmeans.hpp, km_shape_ok: k * d <= KM_MAXKD, and at d <= 64 the tile of 256 points shares the 128 KB of LDS
     for d in list(range(1, 130)) + [255, 256, 257, 384, 1024, 16384, 16385]:
         kmax = km_max_k(d)
         assert (kmax == 0 or lib.tt_kmeans_shape_ok(d, kmax)) and not lib.tt_kmeans_shape_ok(d, kmax + 1), d
@@ -267,7 +267,7 @@ def test_kmeans_assign_every_kernel_and_the_stride_loop(lib):
     assert any(p["k"] * p["d"] == KM_MAXKD for p in cases)
 
 
-def km_accumulate_grid(P):                   # cluster.hip, accumulate_blocks: (workgroups, points per workgroup, workgroups with no points)
+def km_accumulate_grid(P):                   # kmeans.hpp, km_accumulate_blocks: (workgroups, points per workgroup, workgroups with no points)
     b = min(4096, max(1, (P + 127) // 128))
     ppb = (P + b - 1) // b
     return b, ppb, b - (P + ppb - 1) // ppb

@@ -63,6 +63,25 @@ def normalize_and_transform(feats: torch.Tensor, pca_dim: int) -> torch.Tensor:
 # k-means  (faiss.Kmeans as the reference configures it)
 # ------------------------------------------------------------------------------------------------
 
+def _check_n(n: int, k: int) -> None:
+    if n < k:
+        raise RuntimeError(f"Number of training points ({n}) should be at least as large as number of clusters ({k})")
+
+
+def _subsample_rows(n: int, k: int, seed: int, max_points_per_centroid: int) -> Optional[torch.Tensor]:
+    """faiss subsample_training_set: the rows kept of n training points (host int64), or None where all of them are.  The draw depends
+    on (n, seed) alone."""
+    return Kmeans._perm(n, seed)[: k * max_points_per_centroid] if n > k * max_points_per_centroid else None
+
+
+def _redo_seeds(n: int, k: int, seed: int, nredo: int, init_indices=None) -> torch.Tensor:
+    """int64 [nredo, k]: the rows of the n (subsampled) points that seed each redo - faiss' draw, or the first nredo rows of
+    ``init_indices`` where given (all of one length: they are stacked before the first redo)."""
+    if init_indices is not None:
+        return torch.stack([torch.as_tensor(init_indices[r], dtype=torch.int64) for r in range(nredo)])
+    return torch.stack([Kmeans._perm(n, seed + 1 + r * 15486557)[:k] for r in range(nredo)])
+
+
 class Kmeans:
     """``faiss.Kmeans(d, k, niter=50, nredo=5, seed=1, verbose=False, gpu=False, spherical=False)`` surface: ``train(x)``,
     ``centroids`` ([k, d] numpy, as faiss exposes them), ``assign(x) -> (dist2, labels)`` in place of ``index.search(x, 1)``."""
@@ -118,12 +137,11 @@ class Kmeans:
         if not x.is_cuda:
             x = x.cuda()
         x = x.contiguous()
-        n, d = x.shape
-        k = self.k
-        if n < k:
-            raise RuntimeError(f"Number of training points ({n}) should be at least as large as number of clusters ({k})")
-        if n > k * self.max_points_per_centroid:  # subsample_training_set
-            x = x[self._perm(n, self.seed)[: k * self.max_points_per_centroid].to(x.device)].contiguous()
+        n = x.shape[0]
+        _check_n(n, self.k)
+        rows = _subsample_rows(n, self.k, self.seed, self.max_points_per_centroid)
+        if rows is not None:
+            x = x[rows.to(x.device)].contiguous()
         return self._fit(x, init_indices)
 
     # -- the two kernel pairs ----------------------------------------------------------------------------------------------------------
@@ -142,14 +160,11 @@ class Kmeans:
         return ops.kmeans_assign_tiled, ops.kmeans_accumulate_tiled
 
     def _fit(self, x: torch.Tensor, init_indices=None) -> float:
-        if ops.kmeans_shape_ok(x.shape[1], self.k):
-            return self._lloyd(x, init_indices)
         return self._iterate(x, init_indices, *self._kernels(x.shape[1]))
 
     def _lloyd(self, x: torch.Tensor, init_indices=None) -> float:
-        """The redos of Lloyd iterations on the (subsampled) training points x [n, d]."""
-        n, d = x.shape
-        k = self.k
+        """The redos of Lloyd iterations on the (subsampled) training points x [n, d], on the resident pair only."""
+        d, k = x.shape[1], self.k
         if not ops.kmeans_shape_ok(d, k):   # refused here, not after the first assignment: both kernels share this rule
             raise ops._lib.HipLibraryError(f"Kmeans: k = {k} centroids of d = {d} columns are beyond what the k-means kernels hold in LDS "
                                        "(k * d <= 16384; at d = 64, k <= 252)")
@@ -161,11 +176,7 @@ class Kmeans:
         k = self.k
         best_obj, best = float("inf"), None
         self.obj = []
-        for redo in range(self.nredo):
-            if init_indices is not None:
-                idx = torch.as_tensor(init_indices[redo], dtype=torch.int64)
-            else:
-                idx = self._perm(n, self.seed + 1 + redo * 15486557)[:k]
+        for idx in _redo_seeds(n, k, self.seed, self.nredo, init_indices):
             cent = x[idx.to(x.device)].clone()
             obj = float("inf")
             for _ in range(self.niter):
@@ -212,11 +223,10 @@ class Kmeans:
         if g * g != n_tok:
             raise ValueError(f"train_upsampled: {n_tok} tokens are not a square grid")
         R = int(resolution)
-        n, k = M * R * R, self.k
-        if n < k:
-            raise RuntimeError(f"Number of training points ({n}) should be at least as large as number of clusters ({k})")
-        p = self._perm(n, self.seed)[: k * self.max_points_per_centroid] if n > k * self.max_points_per_centroid else torch.arange(n)
-        rows = self._virtual_rows(p, M, g, R).to(tokens.device)
+        n = M * R * R
+        _check_n(n, self.k)
+        p = _subsample_rows(n, self.k, self.seed, self.max_points_per_centroid)
+        rows = self._virtual_rows(torch.arange(n) if p is None else p, M, g, R).to(tokens.device)
         x = tokens.reshape(M * n_tok, d)[rows].cuda().contiguous()
         return self._fit(x, init_indices)
 
@@ -257,16 +267,12 @@ class KmeansBatch:
             x = x.cuda()
         B, n, d = x.shape
         k = self.k
-        if n < k:
-            raise RuntimeError(f"Number of training points ({n}) should be at least as large as number of clusters ({k})")
-        if n > k * self.max_points_per_centroid:  # subsample_training_set: the draw depends on n alone, so all problems share it
-            x = x[:, Kmeans._perm(n, self.seed)[: k * self.max_points_per_centroid].to(x.device)]
+        _check_n(n, k)
+        rows = _subsample_rows(n, k, self.seed, self.max_points_per_centroid)   # shared by all problems
+        if rows is not None:
+            x = x[:, rows.to(x.device)]
         x = x.contiguous()
-        n = x.shape[1]
-        if init_indices is not None:
-            init = torch.stack([torch.as_tensor(init_indices[r], dtype=torch.int64) for r in range(self.nredo)])
-        else:
-            init = torch.stack([Kmeans._perm(n, self.seed + 1 + r * 15486557)[:k] for r in range(self.nredo)])
+        init = _redo_seeds(x.shape[1], k, self.seed, self.nredo, init_indices)
         cent, obj, status = ops.kmeans_fit_batched(x, init.to(torch.int32), self.niter)
         host = torch.cat([obj, status.to(torch.float64)], dim=1).cpu().numpy()   # the one read-back
         obj_h, status_h = host[:, : self.nredo], host[:, self.nredo:]

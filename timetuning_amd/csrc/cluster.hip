@@ -1,13 +1,10 @@
 // Evaluator clustering: the GPU side of clustering.cluster_features / proto_clustering
-// (clustering.py:20-117), my_utils.normalize_and_transform (my_utils.py:19-37) and the k-means the reference delegates to
-// faiss (faiss.Kmeans(d, k, niter=50, nredo=5, seed=1), clustering.py:39-41,55-57,69-71,108-110).
+// (clustering.py:20-117) and my_utils.normalize_and_transform (my_utils.py:19-37) around the k-means, which has its own file (kmeans.hip).
 //
 // The reference moves every feature map to the host, upsamples it in fp64 with ATen, and runs faiss' CPU Lloyd iterations
-// while the other ranks wait at a barrier (time_tuning.py:634-648).  Here the dense passes stay on the device:
+// while the other ranks wait at a barrier (time_tuning.py:634-648).  Here the dense passes stay on the device (with kmeans.hip's):
 //   column moments (StandardScaler)         one two-stage fp64 reduction over the rows
 //   bilinear upsampling of token maps       [M, g*g, C] -> [M, R*R, C], fp64 arithmetic like the reference's DoubleTensor pass
-//   k-means assignment                      one thread per point, centroids in LDS: an HBM-bound scan (200 B / point at d = 50)
-//   k-means accumulation                    per-workgroup partial sums in LDS, then a fixed-order fold: deterministic, no atomics
 // The tiny dense algebra between them (50 x 384 PCA basis from a 384 x 384 eigen-problem, k x d centroid bookkeeping, the
 // Hungarian matching of a k x k score matrix) stays on the host.
 #include "common.hpp"
@@ -16,20 +13,7 @@ namespace tt {
 
 constexpr int CL_THREADS = 256;
 constexpr int CL_MAXD = 1024;     // feature columns for the moments
-constexpr int KM_MAXKD = 16384;   // k * d floats of centroids held in LDS (64 KB; k = 300 at d = 50 for the CBFE over-clustering)
-constexpr size_t KM_MAX_LDS = 128 * 1024;   // dynamic LDS a k-means workgroup may ask for (the attribute raised below)
 constexpr int UP_MAXM = 65535;    // maps of one up-sampling launch (they ride on gridDim.y)
-
-// The (d, k) BOTH k-means entries take - clustering.Kmeans calls one after the other, so they share the rule (tt_kmeans_shape_ok):
-//   k * d <= KM_MAXKD floats of centroids (the assignment's LDS copy; the accumulation's sums, plus k counts: at most 128 KB at d = 1);
-//   d <= 64: the assignment's tile of 256 points (row stride d | 1) shares the LDS - k * d + 256 (d | 1) floats <= 128 KB.  That binds
-//   at d = 64 only: the tile takes 65 KB, which leaves 63 KB of centroids, k <= 252.
-// tt_kmeans_assign's kernel by d: 16 / 64 = the point's row in that many registers (tile in LDS), 0 = wider rows read in place
-static int km_assign_route(int d) { return d <= 16 ? 16 : (d <= 64 ? 64 : 0); }
-static size_t km_assign_lds(int d, int k) {
-  return sizeof(float) * ((size_t)k * d + (km_assign_route(d) ? (size_t)CL_THREADS * (d | 1) : 0));
-}
-static bool km_shape_ok(int d, int k) { return d > 0 && k > 0 && (long long)k * d <= KM_MAXKD && km_assign_lds(d, k) <= KM_MAX_LDS; }
 
 // ---- column moments: partial[b][0][c] = sum_r v, partial[b][1][c] = sum_r v^2 over the block's rows (fp64), v = x[r][c] - x[0][c].
 // The sums are taken about the column's first row: E[v^2] - E[v]^2 on the raw values subtracts two numbers of size mean^2 and loses a
@@ -121,104 +105,6 @@ __global__ __launch_bounds__(CL_THREADS) void upsample_argmax_f32_kernel(const f
   out[(size_t)m * R * R + pix] = besti;
 }
 
-// ---- k-means assignment: label = argmin_j |x - c_j|^2 (first minimum), optional squared distance.
-// A workgroup owns 256 consecutive points: their rows are fetched as one contiguous, fully coalesced block into LDS (row
-// stride d | 1, odd, so that the per-thread row reads below are bank-conflict-free), each thread then keeps ITS point in
-// registers (d <= 64) and walks the centroids, which every lane reads from LDS at the same address (broadcast).
-template <int DREG>
-__global__ __launch_bounds__(CL_THREADS) void kmeans_assign_kernel(const float* __restrict__ x, const float* __restrict__ cent,
-                                                                   int32_t* __restrict__ labels, float* __restrict__ dist2, long long P, int d,
-                                                                   int k) {
-  extern __shared__ float sm[];
-  float* cs = sm;                 // [k][d]
-  float* xs = sm + k * d;         // [256][ds]
-  const int ds = d | 1;
-  for (int i = threadIdx.x; i < k * d; i += CL_THREADS) cs[i] = cent[i];
-  for (long long p0 = (long long)blockIdx.x * CL_THREADS; p0 < P; p0 += (long long)gridDim.x * CL_THREADS) {
-    __syncthreads();
-    if (DREG > 0) {
-      const long long cnt = (P - p0 < CL_THREADS ? P - p0 : CL_THREADS) * d;
-      for (long long i = threadIdx.x; i < cnt; i += CL_THREADS) xs[(i / d) * ds + (i % d)] = x[p0 * d + i];
-      __syncthreads();
-    }
-    const long long p = p0 + threadIdx.x;
-    if (p >= P) continue;
-    const float* xp = DREG > 0 ? xs + threadIdx.x * ds : x + p * d;   // wide rows (d > 64) are read in place
-    float best = INFINITY;
-    int besti = 0;
-    if (DREG > 0) {
-      float xr[DREG > 0 ? DREG : 1];
-#pragma unroll
-      for (int t = 0; t < DREG; ++t) xr[t] = t < d ? xp[t] : 0.f;
-      for (int j = 0; j < k; ++j) {
-        const float* c = cs + j * d;
-        float s = 0.f;
-#pragma unroll
-        for (int t = 0; t < DREG; ++t)
-          if (t < d) {
-            const float df = xr[t] - c[t];
-            s += df * df;
-          }
-        if (s < best) {
-          best = s;
-          besti = j;
-        }
-      }
-    } else {
-      for (int j = 0; j < k; ++j) {
-        const float* c = cs + j * d;
-        float s = 0.f;
-        for (int t = 0; t < d; ++t) {
-          const float df = xp[t] - c[t];
-          s += df * df;
-        }
-        if (s < best) {
-          best = s;
-          besti = j;
-        }
-      }
-    }
-    labels[p] = besti;
-    if (dist2) dist2[p] = best;
-  }
-}
-
-// ---- k-means accumulation: per-block sums[k][d] (fp32 in LDS over the block's pts_per_block points, then fp64 partials)
-__global__ __launch_bounds__(CL_THREADS) void kmeans_accumulate_stage1(const float* __restrict__ x, const int32_t* __restrict__ labels,
-                                                                       double* __restrict__ part_sums, long long* __restrict__ part_cnt,
-                                                                       long long P, int d, int k, long long pts_per_block) {
-  extern __shared__ float acc[];  // [k][d] sums, then [k] counts
-  float* cnt = acc + k * d;
-  for (int i = threadIdx.x; i < k * d + k; i += CL_THREADS) acc[i] = 0.f;
-  __syncthreads();
-  const long long p0 = (long long)blockIdx.x * pts_per_block;
-  const long long p1 = p0 + pts_per_block < P ? p0 + pts_per_block : P;
-  // thread t owns feature columns t, t + 256, ... and walks the block's points in order: no atomics, fixed summation order
-  for (int t = threadIdx.x; t < d; t += CL_THREADS)
-    for (long long p = p0; p < p1; ++p) acc[labels[p] * d + t] += x[p * d + t];
-  if (threadIdx.x == 0)
-    for (long long p = p0; p < p1; ++p) cnt[labels[p]] += 1.f;
-  __syncthreads();
-  for (int i = threadIdx.x; i < k * d; i += CL_THREADS) part_sums[(long long)blockIdx.x * k * d + i] = (double)acc[i];
-  for (int i = threadIdx.x; i < k; i += CL_THREADS) part_cnt[(long long)blockIdx.x * k + i] = (long long)cnt[i];
-}
-
-__global__ __launch_bounds__(CL_THREADS) void kmeans_accumulate_stage2(const double* __restrict__ part_sums, const long long* __restrict__ part_cnt,
-                                                                       double* __restrict__ sums, long long* __restrict__ counts, int kd, int k,
-                                                                       int blocks) {
-  const int i = blockIdx.x * CL_THREADS + threadIdx.x;
-  if (i < kd) {
-    double s = 0.0;
-    for (int b = 0; b < blocks; ++b) s += part_sums[(long long)b * kd + i];
-    sums[i] = s;
-  }
-  if (i < k) {
-    long long c = 0;
-    for (int b = 0; b < blocks; ++b) c += part_cnt[(long long)b * k + i];
-    counts[i] = c;
-  }
-}
-
 // x[r][c] = x[r][c] * scale[c] + shift[c]  (StandardScaler.transform, my_utils.py:29-30)
 __global__ __launch_bounds__(CL_THREADS) void affine_cols_kernel(float* __restrict__ x, const float* __restrict__ scale,
                                                                  const float* __restrict__ shift, long long total, int cols) {
@@ -232,12 +118,6 @@ __global__ __launch_bounds__(CL_THREADS) void affine_cols_kernel(float* __restri
 static int moments_blocks(long long rows) {
   long long b = (rows + 255) / 256;
   return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
-}
-static int accumulate_blocks(long long P) {
-  // 128 points per block keep the fp32 LDS sums short - up to 4096 blocks: beyond P = 524 288 a block takes ceil(P / 4096) points
-  // (269 at the 1.1 M points of the CBFE over-clustering; the sums stay within the fp32 class there: the sweep holds them to 1e-5)
-  long long b = (P + 127) / 128;
-  return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
 }
 
 }  // namespace tt
@@ -278,64 +158,6 @@ extern "C" int tt_upsample_argmax_f32(const float* maps, int64_t* labels_out, in
   hipLaunchKernelGGL(upsample_argmax_f32_kernel, dim3((R * R + CL_THREADS - 1) / CL_THREADS, M), dim3(CL_THREADS), 0, as_stream(stream), maps,
                      labels_out, g, K, R);
   TT_CHECK_LAUNCH("upsample_argmax_f32");
-  return TT_OK;
-}
-
-extern "C" int tt_kmeans_assign(const float* x, const float* centroids, int32_t* labels, float* dist2, long long P, int d, int k,
-                                tt_stream_t stream) {
-  TT_REQUIRE(x && centroids && labels && P > 0 && d > 0 && k > 0, "kmeans_assign: bad arguments");
-  TT_REQUIRE((long long)k * d <= KM_MAXKD, "kmeans_assign: k * d = %lld exceeds %d", (long long)k * d, KM_MAXKD);
-  const size_t lds = km_assign_lds(d, k);
-  TT_REQUIRE(km_shape_ok(d, k), "kmeans_assign: k = %d, d = %d need %zu bytes of LDS (at most %zu)", k, d, lds, KM_MAX_LDS);
-  static const bool lds_attr_set = [] {  // the centroids and the d <= 64 tile's points, 128 KB together (km_shape_ok)
-    bool ok = true;
-    for (const void* f : {reinterpret_cast<const void*>(&kmeans_assign_kernel<16>), reinterpret_cast<const void*>(&kmeans_assign_kernel<64>),
-                          reinterpret_cast<const void*>(&kmeans_assign_kernel<0>)})
-      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_MAX_LDS) == hipSuccess;
-    return ok;
-  }();
-  TT_REQUIRE(lds_attr_set, "kmeans_assign: could not raise the dynamic LDS limit");
-  long long blocks = (P + CL_THREADS - 1) / CL_THREADS;
-  blocks = blocks > 4096 ? 4096 : blocks;
-  hipStream_t s = as_stream(stream);
-  const int route = km_assign_route(d);
-  if (route == 16)
-    hipLaunchKernelGGL((kmeans_assign_kernel<16>), dim3((unsigned)blocks), dim3(CL_THREADS), lds, s, x, centroids, labels, dist2, P, d, k);
-  else if (route == 64)
-    hipLaunchKernelGGL((kmeans_assign_kernel<64>), dim3((unsigned)blocks), dim3(CL_THREADS), lds, s, x, centroids, labels, dist2, P, d, k);
-  else
-    hipLaunchKernelGGL((kmeans_assign_kernel<0>), dim3((unsigned)blocks), dim3(CL_THREADS), lds, s, x, centroids, labels, dist2, P, d, k);
-  TT_CHECK_LAUNCH("kmeans_assign");
-  return TT_OK;
-}
-
-extern "C" int tt_kmeans_shape_ok(int d, int k) { return km_shape_ok(d, k) ? 1 : 0; }
-extern "C" int tt_kmeans_assign_route(int d) { return km_assign_route(d); }
-
-extern "C" size_t tt_kmeans_accumulate_workspace_bytes(long long P, int d, int k) {
-  return (size_t)accumulate_blocks(P) * ((size_t)k * d * sizeof(double) + (size_t)k * sizeof(long long));
-}
-
-extern "C" int tt_kmeans_accumulate(const float* x, const int32_t* labels, double* sums, long long* counts, long long P, int d, int k,
-                                    void* workspace, size_t workspace_bytes, tt_stream_t stream) {
-  TT_REQUIRE(x && labels && sums && counts && workspace && P > 0 && d > 0 && k > 0, "kmeans_accumulate: bad arguments");
-  TT_REQUIRE((long long)k * d <= KM_MAXKD, "kmeans_accumulate: k * d = %lld exceeds %d", (long long)k * d, KM_MAXKD);
-  TT_REQUIRE(km_shape_ok(d, k), "kmeans_accumulate: k = %d, d = %d is beyond what kmeans_assign takes (%zu bytes of LDS, at most %zu)", k, d,
-             km_assign_lds(d, k), KM_MAX_LDS);
-  TT_REQUIRE(workspace_bytes >= tt_kmeans_accumulate_workspace_bytes(P, d, k), "kmeans_accumulate: workspace too small");
-  static const bool lds_attr_set = hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_accumulate_stage1),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)KM_MAX_LDS) == hipSuccess;
-  TT_REQUIRE(lds_attr_set, "kmeans_accumulate: could not raise the dynamic LDS limit");
-  hipStream_t s = as_stream(stream);
-  const int blocks = accumulate_blocks(P);
-  const long long ppb = (P + blocks - 1) / blocks;
-  double* part_sums = static_cast<double*>(workspace);
-  long long* part_cnt = reinterpret_cast<long long*>(part_sums + (size_t)blocks * k * d);
-  hipLaunchKernelGGL(kmeans_accumulate_stage1, dim3(blocks), dim3(CL_THREADS), sizeof(float) * (k * d + k), s, x, labels, part_sums, part_cnt, P, d,
-                     k, ppb);
-  hipLaunchKernelGGL(kmeans_accumulate_stage2, dim3((k * d + CL_THREADS - 1) / CL_THREADS), dim3(CL_THREADS), 0, s, part_sums, part_cnt, sums,
-                     counts, k * d, k, blocks);
-  TT_CHECK_LAUNCH("kmeans_accumulate");
   return TT_OK;
 }
 

@@ -5,89 +5,34 @@
 //   kmeans_fit_kernel            workgroup (redo, problem) keeps its centroids, the fp32 block sums, the fp64 sums and the counts in
 //                                LDS and walks niter iterations of assignment / accumulation / update.  No workgroup waits on
 //                                another: there is no flag, counter or barrier between workgroups.
-//   kmeans_assign_batched_kernel tt_kmeans_assign with the problem on gridDim.y (the final index.search(x, 1) of every problem).
-// The arithmetic per output number is that of cluster.hip's pair (the contract is spelled out at tt_kmeans_fit_batched in the
-// header), so a fit that meets no empty cluster returns the bits of the loop; one that does is flagged and left to the loop.
-#include "common.hpp"
+// The final index.search(x, 1) of every problem is tt_kmeans_assign_batched (kmeans.hip).
+// The arithmetic per output number is that of kmeans.hip's resident pair - km_nearest and km_accumulate_blocks are kmeans.hpp's, the
+// contract is spelled out in the header - so a fit that meets no empty cluster returns the bits of the loop; one that does is flagged
+// and left to the loop.
+#include "kmeans.hpp"
 
 namespace tt {
 
 constexpr int KF_THREADS = 512;              // one workgroup per (problem, redo); two of them fit a CU
 constexpr int KF_WAVES = KF_THREADS / 64;
-constexpr int KF_MAXD = 64;                  // the point's row lives in registers (cluster.hip's routes 16 and 64)
+constexpr int KF_MAXD = 64;                  // the point's row lives in registers (km_assign_route's 16 and 64)
 constexpr long long KF_MAXN = 1 << 20;       // points of one problem (the subsample of a fit: at most 256 k)
-constexpr size_t KF_MAX_LDS = 128 * 1024;    // what a fit workgroup may ask for (the limit cluster.hip's kernels raise to as well)
 constexpr size_t KF_PREF_LDS = 72 * 1024;    // what it asks for when more blocks per pass are on offer: two workgroups per 160 KB CU
-constexpr int KF_MAX_GRID_Y = 65535;
-
-// cluster.hip's rules, restated (the batched assignment takes what tt_kmeans_shape_ok takes; the partition of the accumulation is
-// accumulate_blocks, or the sums' bits differ)
-constexpr int KF_ASSIGN_THREADS = 256;
-constexpr int KF_KM_MAXKD = 16384;
-static int kf_assign_route(int d) { return d <= 16 ? 16 : (d <= 64 ? 64 : 0); }
-static size_t kf_assign_lds(int d, int k) {
-  return sizeof(float) * ((size_t)k * d + (kf_assign_route(d) ? (size_t)KF_ASSIGN_THREADS * (d | 1) : 0));
-}
-static bool kf_km_shape_ok(int d, int k) { return d > 0 && k > 0 && (long long)k * d <= KF_KM_MAXKD && kf_assign_lds(d, k) <= KF_MAX_LDS; }
-static int kf_accumulate_blocks(long long P) {
-  long long b = (P + 127) / 128;
-  return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
-}
 
 // LDS of a fit workgroup that holds g blocks' fp32 sums at once: fp64 sums [k][d], centroids [k][d], g x fp32 sums [k][d], counts [k].
 // The rule (tt_kmeans_fit_shape_ok): 1 <= d <= 64, 1 <= k <= n <= 2^20, and that budget at g = 1 within 128 KB - 16 k d + 4 k bytes,
 // k * d <= 8160 or so: k <= 127 at d = 64, k <= 163 at d = 50.  Everything inside 1 <= d, k <= 64 fits with g >= 5.
 static size_t kf_fit_lds(int d, int k, int g) { return (size_t)k * d * (sizeof(double) + sizeof(float) * (1 + (size_t)g)) + sizeof(int) * (size_t)k; }
 static bool kf_fit_shape_ok(long long n, int d, int k) {
-  return d >= 1 && d <= KF_MAXD && k >= 1 && n >= k && n <= KF_MAXN && kf_fit_lds(d, k, 1) <= KF_MAX_LDS;
+  return d >= 1 && d <= KF_MAXD && k >= 1 && n >= k && n <= KF_MAXN && kf_fit_lds(d, k, 1) <= KM_MAX_LDS;
 }
 // blocks whose fp32 sums a pass holds side by side: as many as fit the preferred budget, at least one, at most all of them
 static int kf_fit_group(long long n, int d, int k) {
-  const int blocks = kf_accumulate_blocks(n);
+  const int blocks = km_accumulate_blocks(n);
   const size_t fixed = kf_fit_lds(d, k, 0), per = sizeof(float) * (size_t)k * d;
   long long g = fixed < KF_PREF_LDS ? (long long)((KF_PREF_LDS - fixed) / per) : 0;
   g = g < 1 ? 1 : g;
   return (int)(g > blocks ? blocks : g);
-}
-
-// The nearest centroid of one point: kmeans_assign_kernel's inner loops, statement for statement (the same flags contract
-// s += df * df to the same fma).  DREG > 0: the row is in xr; DREG == 0: it is read in place from xp.
-template <int DREG>
-__device__ __forceinline__ void kf_nearest(const float* xr, const float* __restrict__ xp, const float* cs, int d, int k, float& best_out,
-                                           int& besti_out) {
-  float best = INFINITY;
-  int besti = 0;
-  if (DREG > 0) {
-    for (int j = 0; j < k; ++j) {
-      const float* c = cs + j * d;
-      float s = 0.f;
-#pragma unroll
-      for (int t = 0; t < DREG; ++t)
-        if (t < d) {
-          const float df = xr[t] - c[t];
-          s += df * df;
-        }
-      if (s < best) {
-        best = s;
-        besti = j;
-      }
-    }
-  } else {
-    for (int j = 0; j < k; ++j) {
-      const float* c = cs + j * d;
-      float s = 0.f;
-      for (int t = 0; t < d; ++t) {
-        const float df = xp[t] - c[t];
-        s += df * df;
-      }
-      if (s < best) {
-        best = s;
-        besti = j;
-      }
-    }
-  }
-  best_out = best;
-  besti_out = besti;
 }
 
 // ---- the fused fit.  grid (nredo, B), KF_THREADS threads.  Per iteration:
@@ -153,7 +98,7 @@ __global__ __launch_bounds__(KF_THREADS) void kmeans_fit_kernel(const float* __r
       }
       float best;
       int besti;
-      kf_nearest<DREG>(xr, xp, cs, d, k, best, besti);
+      km_nearest<DREG>(xr, xp, cs, d, k, best, besti);
       labels[p] = besti;
       atomicAdd(&cnt[besti], 1);
       if (last) o += (double)best;
@@ -225,50 +170,6 @@ __global__ __launch_bounds__(KF_THREADS) void kmeans_fit_kernel(const float* __r
   }
 }
 
-// ---- tt_kmeans_assign with the problem on gridDim.y: kmeans_assign_kernel (cluster.hip) on problem y0 + blockIdx.y
-template <int DREG>
-__global__ __launch_bounds__(KF_ASSIGN_THREADS) void kmeans_assign_batched_kernel(const float* __restrict__ x, const float* __restrict__ cent,
-                                                                                  int32_t* __restrict__ labels, float* __restrict__ dist2,
-                                                                                  long long P, int d, int k, int y0) {
-  extern __shared__ float sm[];
-  float* cs = sm;                 // [k][d]
-  float* xs = sm + k * d;         // [256][ds]
-  const int ds = d | 1;
-  const size_t b = (size_t)y0 + blockIdx.y;
-  x += b * (size_t)P * d;
-  cent += b * (size_t)k * d;
-  labels += b * (size_t)P;
-  if (dist2) dist2 += b * (size_t)P;
-  for (int i = threadIdx.x; i < k * d; i += KF_ASSIGN_THREADS) cs[i] = cent[i];
-  for (long long p0 = (long long)blockIdx.x * KF_ASSIGN_THREADS; p0 < P; p0 += (long long)gridDim.x * KF_ASSIGN_THREADS) {
-    __syncthreads();
-    if (DREG > 0) {
-      const long long cnt = (P - p0 < KF_ASSIGN_THREADS ? P - p0 : KF_ASSIGN_THREADS) * d;
-      for (long long i = threadIdx.x; i < cnt; i += KF_ASSIGN_THREADS) xs[(i / d) * ds + (i % d)] = x[p0 * d + i];
-      __syncthreads();
-    }
-    const long long p = p0 + threadIdx.x;
-    if (p >= P) continue;
-    const float* xp = DREG > 0 ? xs + threadIdx.x * ds : x + p * d;   // wide rows (d > 64) are read in place
-    float xr[DREG > 0 ? DREG : 1];
-    if (DREG > 0) {
-#pragma unroll
-      for (int t = 0; t < DREG; ++t) xr[t] = t < d ? xp[t] : 0.f;
-    }
-    float best;
-    int besti;
-    kf_nearest<DREG>(xr, xp, cs, d, k, best, besti);
-    labels[p] = besti;
-    if (dist2) dist2[p] = best;
-  }
-}
-
-template <int DREG, int VEC>
-static bool kf_raise_fit_lds() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_fit_kernel<DREG, VEC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)KF_MAX_LDS) == hipSuccess;
-}
-
 }  // namespace tt
 
 using namespace tt;
@@ -290,21 +191,21 @@ extern "C" int tt_kmeans_fit_batched(const float* x, const int32_t* init, const 
                                      int32_t* status, int B, long long n, int d, int k, int nredo, int niter, void* workspace,
                                      size_t workspace_bytes, tt_stream_t stream) {
   TT_REQUIRE(x && init && init_host && centroids && obj && status && workspace, "kmeans_fit_batched: null pointer");
-  TT_REQUIRE(B >= 1 && B <= KF_MAX_GRID_Y, "kmeans_fit_batched: B = %d problems: need 1 ... %d per call", B, KF_MAX_GRID_Y);
-  TT_REQUIRE(niter >= 1 && nredo >= 1 && nredo <= KF_MAX_GRID_Y, "kmeans_fit_batched: niter = %d, nredo = %d: need niter >= 1, 1 <= nredo <= %d",
-             niter, nredo, KF_MAX_GRID_Y);
+  TT_REQUIRE(B >= 1 && B <= KM_MAX_GRID_Y, "kmeans_fit_batched: B = %d problems: need 1 ... %d per call", B, KM_MAX_GRID_Y);
+  TT_REQUIRE(niter >= 1 && nredo >= 1 && nredo <= KM_MAX_GRID_Y, "kmeans_fit_batched: niter = %d, nredo = %d: need niter >= 1, 1 <= nredo <= %d",
+             niter, nredo, KM_MAX_GRID_Y);
   TT_REQUIRE(n >= k, "kmeans_fit_batched: n = %lld points are fewer than k = %d clusters", n, k);
   TT_REQUIRE(kf_fit_shape_ok(n, d, k),
              "kmeans_fit_batched: n = %lld, d = %d, k = %d: need 1 <= d <= %d, 1 <= k <= n <= %lld and 16 k d + 4 k = %zu bytes of LDS within %zu",
-             n, d, k, KF_MAXD, KF_MAXN, kf_fit_lds(d > 0 ? d : 0, k > 0 ? k : 0, 1), KF_MAX_LDS);
+             n, d, k, KF_MAXD, KF_MAXN, kf_fit_lds(d > 0 ? d : 0, k > 0 ? k : 0, 1), KM_MAX_LDS);
   for (long long i = 0; i < (long long)nredo * k; ++i)
     TT_REQUIRE(init_host[i] >= 0 && init_host[i] < n, "kmeans_fit_batched: init[%lld][%lld] = %d is outside [0, %lld)", i / k, i % k, init_host[i], n);
   const size_t need = tt_kmeans_fit_workspace_bytes(B, nredo, n, d, k);
   TT_REQUIRE(workspace_bytes >= need, "kmeans_fit_batched: workspace of %zu bytes is too small (%zu needed)", workspace_bytes, need);
-  static const bool lds_attr_set = kf_raise_fit_lds<16, 1>() && kf_raise_fit_lds<16, 2>() && kf_raise_fit_lds<16, 4>() && kf_raise_fit_lds<64, 1>() &&
-                                   kf_raise_fit_lds<64, 2>() && kf_raise_fit_lds<64, 4>();
+  static const bool lds_attr_set = km_raise_lds({KM_KERNEL(kmeans_fit_kernel<16, 1>), KM_KERNEL(kmeans_fit_kernel<16, 2>), KM_KERNEL(kmeans_fit_kernel<16, 4>),
+                                                 KM_KERNEL(kmeans_fit_kernel<64, 1>), KM_KERNEL(kmeans_fit_kernel<64, 2>), KM_KERNEL(kmeans_fit_kernel<64, 4>)});
   TT_REQUIRE(lds_attr_set, "kmeans_fit_batched: could not raise the dynamic LDS limit");
-  const int blocks = kf_accumulate_blocks(n);
+  const int blocks = km_accumulate_blocks(n);
   const int ppb = (int)((n + blocks - 1) / blocks);
   const int group = kf_fit_group(n, d, k);
   const size_t lds = kf_fit_lds(d, k, group);
@@ -314,44 +215,12 @@ extern "C" int tt_kmeans_fit_batched(const float* x, const int32_t* init, const 
   const dim3 grid(nredo, B), block(KF_THREADS);
 #define KF_LAUNCH(DREG, VEC) \
   hipLaunchKernelGGL((kmeans_fit_kernel<DREG, VEC>), grid, block, lds, s, x, init, centroids, obj, status, labels, (int)n, d, k, niter, blocks, ppb, group)
-  if (d <= 16) {
+  if (km_assign_route(d) == 16) {
     if (vec == 4) KF_LAUNCH(16, 4); else if (vec == 2) KF_LAUNCH(16, 2); else KF_LAUNCH(16, 1);
   } else {
     if (vec == 4) KF_LAUNCH(64, 4); else if (vec == 2) KF_LAUNCH(64, 2); else KF_LAUNCH(64, 1);
   }
 #undef KF_LAUNCH
   TT_CHECK_LAUNCH("kmeans_fit_batched");
-  return TT_OK;
-}
-
-extern "C" int tt_kmeans_assign_batched(const float* x, const float* centroids, int32_t* labels, float* dist2, int B, long long N, int d, int k,
-                                        tt_stream_t stream) {
-  TT_REQUIRE(x && centroids && labels, "kmeans_assign_batched: null pointer");
-  TT_REQUIRE(kf_km_shape_ok(d, k), "kmeans_assign_batched: k = %d, d = %d is beyond what kmeans_assign takes (k * d <= %d, %zu bytes of LDS within %zu)",
-             k, d, KF_KM_MAXKD, d > 0 && k > 0 ? kf_assign_lds(d, k) : (size_t)0, KF_MAX_LDS);
-  TT_REQUIRE(B >= 1 && N >= 1, "kmeans_assign_batched: B = %d problems of N = %lld points: need both >= 1", B, N);
-  static const bool lds_attr_set = [] {
-    bool ok = true;
-    for (const void* f : {reinterpret_cast<const void*>(&kmeans_assign_batched_kernel<16>), reinterpret_cast<const void*>(&kmeans_assign_batched_kernel<64>),
-                          reinterpret_cast<const void*>(&kmeans_assign_batched_kernel<0>)})
-      ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KF_MAX_LDS) == hipSuccess;
-    return ok;
-  }();
-  TT_REQUIRE(lds_attr_set, "kmeans_assign_batched: could not raise the dynamic LDS limit");
-  const size_t lds = kf_assign_lds(d, k);
-  long long blocks = (N + KF_ASSIGN_THREADS - 1) / KF_ASSIGN_THREADS;
-  blocks = blocks > 4096 ? 4096 : blocks;
-  hipStream_t s = as_stream(stream);
-  const int route = kf_assign_route(d);
-  for (int y0 = 0; y0 < B; y0 += KF_MAX_GRID_Y) {   // the problems ride on gridDim.y, at most 65535 per launch
-    const dim3 grid((unsigned)blocks, (unsigned)(B - y0 < KF_MAX_GRID_Y ? B - y0 : KF_MAX_GRID_Y));
-    if (route == 16)
-      hipLaunchKernelGGL((kmeans_assign_batched_kernel<16>), grid, dim3(KF_ASSIGN_THREADS), lds, s, x, centroids, labels, dist2, N, d, k, y0);
-    else if (route == 64)
-      hipLaunchKernelGGL((kmeans_assign_batched_kernel<64>), grid, dim3(KF_ASSIGN_THREADS), lds, s, x, centroids, labels, dist2, N, d, k, y0);
-    else
-      hipLaunchKernelGGL((kmeans_assign_batched_kernel<0>), grid, dim3(KF_ASSIGN_THREADS), lds, s, x, centroids, labels, dist2, N, d, k, y0);
-  }
-  TT_CHECK_LAUNCH("kmeans_assign_batched");
   return TT_OK;
 }

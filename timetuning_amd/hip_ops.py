@@ -966,29 +966,39 @@ def kmeans_shape_ok(d: int, k: int) -> bool:
     return bool(_lib.load().tt_kmeans_shape_ok(int(d), int(k)))
 
 
-def kmeans_assign(x, centroids, return_dist=False):
-    """x [P, d], centroids [k, d] -> labels int32 [P] (+ squared distances)."""
+def _kmeans_assign(entry: str, x, centroids, return_dist, *tile):
+    """labels / dist2 of ``x`` and the call of the assignment entry ``entry`` (``tile``: the tiled entry's tile_k)."""
     lib = _lib.load()
     _chk(x, "x"); _chk(centroids, "centroids")
     P, d = x.shape
     k = centroids.shape[0]
     labels = torch.empty(P, dtype=torch.int32, device=x.device)
     dist2 = torch.empty(P, dtype=f32, device=x.device) if return_dist else None
-    _lib.check(lib.tt_kmeans_assign(_p(x), _p(centroids), _p(labels), _p(dist2), P, d, k, _stream()), "tt_kmeans_assign")
+    _lib.check(getattr(lib, entry)(_p(x), _p(centroids), _p(labels), _p(dist2), P, d, k, *tile, _stream()), entry)
     return (labels, dist2) if return_dist else labels
 
 
-def kmeans_accumulate(x, labels, k: int):
-    """Sums [k, d] (fp64) and counts [k] (int64) of the points of each label."""
+def _kmeans_accumulate(entry: str, x, labels, k: int, *tile):
+    """sums / counts, the workspace and the call of the accumulation entry ``entry`` (``tile``: the tiled entry's tile_k)."""
     lib = _lib.load()
     _chk(x, "x"); _chk(labels, "labels", torch.int32)
     P, d = x.shape
     sums = torch.empty((k, d), dtype=torch.float64, device=x.device)
     counts = torch.empty(k, dtype=torch.int64, device=x.device)
-    nb = lib.tt_kmeans_accumulate_workspace_bytes(P, d, k)
+    nb = getattr(lib, entry + "_workspace_bytes")(P, d, k, *tile)
     ws = _ws(nb, x.device)
-    _lib.check(lib.tt_kmeans_accumulate(_p(x), _p(labels), _p(sums), _p(counts), P, d, k, _p(ws), nb, _stream()), "tt_kmeans_accumulate")
+    _lib.check(getattr(lib, entry)(_p(x), _p(labels), _p(sums), _p(counts), P, d, k, *tile, _p(ws), nb, _stream()), entry)
     return sums, counts
+
+
+def kmeans_assign(x, centroids, return_dist=False):
+    """x [P, d], centroids [k, d] -> labels int32 [P] (+ squared distances)."""
+    return _kmeans_assign("tt_kmeans_assign", x, centroids, return_dist)
+
+
+def kmeans_accumulate(x, labels, k: int):
+    """Sums [k, d] (fp64) and counts [k] (int64) of the points of each label."""
+    return _kmeans_accumulate("tt_kmeans_accumulate", x, labels, k)
 
 
 def kmeans_tiled_shape_ok(d: int, k: int) -> bool:
@@ -1004,29 +1014,13 @@ def kmeans_tile_centroids(d: int) -> int:
 def kmeans_assign_tiled(x, centroids, return_dist=False, tile_k: int = 0):
     """``kmeans_assign`` for centroids that do not fit in LDS: they pass through it ``tile_k`` rows at a time (0 = the default tile).
     Same layouts and dtypes, and the same bits wherever ``kmeans_assign`` runs."""
-    lib = _lib.load()
-    _chk(x, "x"); _chk(centroids, "centroids")
-    P, d = x.shape
-    k = centroids.shape[0]
-    labels = torch.empty(P, dtype=torch.int32, device=x.device)
-    dist2 = torch.empty(P, dtype=f32, device=x.device) if return_dist else None
-    _lib.check(lib.tt_kmeans_assign_tiled(_p(x), _p(centroids), _p(labels), _p(dist2), P, d, k, int(tile_k), _stream()), "tt_kmeans_assign_tiled")
-    return (labels, dist2) if return_dist else labels
+    return _kmeans_assign("tt_kmeans_assign_tiled", x, centroids, return_dist, int(tile_k))
 
 
 def kmeans_accumulate_tiled(x, labels, k: int, tile_k: int = 0):
     """``kmeans_accumulate`` for k * d beyond the LDS: sums [k, d] (fp64) and counts [k] (int64), one tile of ``tile_k`` clusters at a
     time (0 = the default tile).  The same bits wherever ``kmeans_accumulate`` runs."""
-    lib = _lib.load()
-    _chk(x, "x"); _chk(labels, "labels", torch.int32)
-    P, d = x.shape
-    sums = torch.empty((k, d), dtype=torch.float64, device=x.device)
-    counts = torch.empty(k, dtype=torch.int64, device=x.device)
-    nb = lib.tt_kmeans_accumulate_tiled_workspace_bytes(P, d, k, int(tile_k))
-    ws = _ws(nb, x.device)
-    _lib.check(lib.tt_kmeans_accumulate_tiled(_p(x), _p(labels), _p(sums), _p(counts), P, d, k, int(tile_k), _p(ws), nb, _stream()),
-               "tt_kmeans_accumulate_tiled")
-    return sums, counts
+    return _kmeans_accumulate("tt_kmeans_accumulate_tiled", x, labels, k, int(tile_k))
 
 
 def kmeans_fit_shape_ok(n: int, d: int, k: int) -> bool:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the tiled k-means kernels (N12, kmeans_tiled.hip) against the LDS-resident ones (cluster.hip) on one GPU, with HIP events
+"""Times the tiled k-means kernels (N12) against the LDS-resident ones (both in kmeans.hip) on one GPU, with HIP events
 after warm-up, the two kernels of a comparison alternating inside one timed series.
 
 1. A shape both take - the CBFE over-clustering, P = 1 100 000 points, d = 50, k = 300: tt_kmeans_assign against
