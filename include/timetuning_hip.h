@@ -437,6 +437,27 @@ int tt_upsample_argmax(const double* maps, int64_t* labels_out, int M, int g, in
 int tt_confusion_counts(const int64_t* pred, const int64_t* gt, long long n, int C, unsigned long long* counts,
                         tt_stream_t stream);
 
+/* ---- N15: segmented confusion counts - the matrices of every PredsmIoU.compute of one evaluate_localizations call (evaluation.py:250-310:
+ *      per frame :266-275, per clip :276-289, per dataset :290-307 with Pascal's ignore label :304-305) and the per-frame counts behind
+ *      PredsmIoU.compute_propagation_score (metrics.py:271-346, called by evaluation.py:228-246), in one launch.
+ *   tt_confusion_counts_segments  pred [S, n] (pred_dtype: TT_LABELS_I16 = int16, what cluster_features returns, or TT_LABELS_I64 = int64,
+ *                                 what proto_clustering returns), gt [S, n] int64 -> counts uint64 [S, Cg, Cp]:
+ *                                   counts[s][g][p] += 1 for every element of segment s with 0 <= g < Cg, 0 <= p < Cp and, where
+ *                                   has_ignore != 0, g != ignore_gt; every other element is skipped.
+ *                                 tt_confusion_counts made rectangular, with an ignore value and a segment axis.  The entry zeroes counts.
+ *                                 Integer atomics only: the result depends on neither order nor grid.  The segments ride on gridDim.y,
+ *                                 65535 per launch, any S >= 1; pred and gt need only the alignment of their elements (16-byte loads are
+ *                                 used where the addresses allow).  Element offsets are 64-bit.
+ *   tt_confusion_segments_route   host only: 0 = (Cg, Cp) refused, 1 = a u32 histogram per workgroup in LDS (Cg * Cp <= 16384 cells, 64 KB:
+ *                                 the over-clustering shape 21 x 500 among them), 2 = 64-bit global atomics (beyond, Cg, Cp <= 4096).
+ *   Refused with TT_EINVAL and a message naming the numbers, nothing launched: null pointers, an unknown dtype code, S < 1, n < 1, Cg or Cp
+ *   outside [1, 4096], S * Cg * Cp > 2^32 cells (32 GB of counts: the bound this entry addresses), S * n > 2^59, a misaligned pointer. */
+#define TT_LABELS_I16 0
+#define TT_LABELS_I64 1
+int tt_confusion_segments_route(int Cg, int Cp);
+int tt_confusion_counts_segments(const void* pred, int pred_dtype, const int64_t* gt, int S, long long n, int Cg, int Cp, long long ignore_gt,
+                                 int has_ignore, unsigned long long* counts, tt_stream_t stream);
+
 /* ---- N9: the evaluation propagation on RECTANGULAR token grids (frames at native size, e.g. 480 x 848 -> 30 x 53 tokens at patch 16)
  *   tt_label_propagate_grid_maps  tt_label_propagate_maps on a gh x gw grid (n = gh * gw, row-major tokens): xn [fs, bs, n, D], seg0
  *                                 [bs, n, K], pmap_all [fs-1, bs, n, K] fp64.  The window is restrict_neighborhood(gh, gw, radius)

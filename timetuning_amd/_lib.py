@@ -173,6 +173,8 @@ SIGNATURES = {
     "tt_label_propagate_maps": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp, c_sz, c_vp]),
     "tt_upsample_argmax": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
     "tt_confusion_counts": (c_i, [c_vp, c_vp, c_ll, c_i, c_vp, c_vp]),
+    "tt_confusion_segments_route": (c_i, [c_i, c_i]),
+    "tt_confusion_counts_segments": (c_i, [c_vp, c_i, c_vp, c_i, c_ll, c_i, c_i, c_ll, c_i, c_vp, c_vp]),
     "tt_label_propagate_grid_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
     "tt_label_propagate_grid_maps": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp, c_sz, c_vp]),
     "tt_upsample_argmax_hw": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp]),

@@ -1,6 +1,8 @@
 """Evaluator with the reference's surface (``evaluation.py:250-310,312-486``): features without head -> clustering ->
 matched mIoU, for the three protocols (frame-wise / sample-wise / dataset-wise).  Dataset readers, video / GIF logging and
 the wandb plumbing are out of scope; the loader is any iterable of ``(data, annotations[, label])`` batches.
+``evaluate_localizations`` scores a whole batch from one segmented confusion-count launch (``PredsmIoU.compute_segments``);
+``evaluate_propagation`` is the reference's (``evaluation.py:228-246``).
 
 ``use_mask=True`` evaluates masked features as the reference does (``evaluation.py:411-424,461-462``): with ``fg_masks`` given to the
 constructor (the foreground masks of cluster_based_foreground_extraction, [N, R', R']) the dataset-wise features are multiplied by
@@ -13,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -22,32 +25,39 @@ from .metrics import PredsmIoU
 from .models import FeatureExtractor, apply_attention_mask
 
 
+def evaluate_propagation(PredsEval, gts, preds):
+    """gts / preds [bs, fs, h, w] -> the mean, over every object of every clip, of ``PredsmIoU.compute_propagation_score``
+    (``evaluation.py:228-246``).  As in the reference the clip's frames are stored with ``update(preds, gts)`` - the arguments of
+    ``update(gt, pred)`` swapped - so the objects the score iterates over are the non-zero values of the PREDICTIONS and a frame "holds"
+    an object when its prediction does.  That quirk is kept: the scores are the reference's."""
+    bs, fs = preds.shape[:2]
+    scores = []
+    for i in range(bs):
+        PredsEval.reset()
+        for j in range(fs):
+            PredsEval.update(preds[i, j].flatten(), gts[i, j].flatten())
+        scores += PredsEval.compute_propagation_score(is_global_zero=True)
+    return np.array(scores).mean()
+
+
 def evaluate_localizations(PredsEval, gts, preds, evaluation_protocol, logging_directory=None, many_to_one=False, precision_based=False):
-    """gts / preds [bs, fs, R, R] -> mean score (``evaluation.py:250-310``)."""
+    """gts / preds [bs, fs, R, R] -> mean score (``evaluation.py:250-310``).  Every ``PredsmIoU.compute`` of the reference's loops - one
+    per frame (frame-wise), per clip (sample-wise) or for everything but Pascal VOC's ignore label 255 (dataset-wise, :304-305) - is one
+    segment of a single ``PredsmIoU.compute_segments`` call: one counting launch and one read-back per protocol call."""
     if logging_directory is not None:
         raise NotImplementedError("video logging of the matched maps is not part of this build")
-    scores = []
+    bs, fs = preds.shape[:2]
     if evaluation_protocol == "frame-wise":
-        for i, datum in enumerate(preds):
-            for j, frame in enumerate(datum):
-                PredsEval.update(gts[i, j].flatten(), frame.flatten())
-                scores.append(PredsEval.compute(True, many_to_one, precision_based=precision_based)[0])
-                PredsEval.reset()
+        segments, ignore_gt = bs * fs, None
     elif evaluation_protocol == "sample-wise":
-        for i, datum in enumerate(preds):
-            for j, frame in enumerate(datum):
-                PredsEval.update(gts[i, j].flatten(), frame.flatten())
-            scores.append(PredsEval.compute(True, many_to_one, precision_based=precision_based)[0])
-            PredsEval.reset()
+        segments, ignore_gt = bs, None
     elif evaluation_protocol == "dataset-wise":
-        for i, datum in enumerate(preds):
-            for j, frame in enumerate(datum):
-                valid = gts[i, j] != 255   # Pascal VOC's ignore label (:304-305)
-                PredsEval.update(gts[i, j][valid].flatten(), frame[valid].flatten())
-        scores.append(PredsEval.compute(True, many_to_one, precision_based=precision_based)[0])
-        PredsEval.reset()
+        segments, ignore_gt = 1, 255
     else:
         raise ValueError(f"unknown evaluation protocol {evaluation_protocol!r}")
+    results = PredsEval.compute_segments(gts.reshape(segments, -1), preds.reshape(segments, -1), many_to_one, precision_based, ignore_gt)
+    PredsEval.reset()
+    scores = [r[0] for r in results]
     return sum(scores) / len(scores)
 
 

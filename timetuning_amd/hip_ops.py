@@ -790,6 +790,26 @@ def confusion_counts(pred, gt, num_classes: int):
     return counts
 
 
+_LABEL_CODES = {torch.int16: 0, torch.int64: 1}   # TT_LABELS_I16 / TT_LABELS_I64
+
+
+def confusion_counts_segments(pred, gt, num_gt: int, num_pred: int, ignore_gt: Optional[int] = None):
+    """pred [S, n] int16 or int64, gt [S, n] int64 -> counts[s, gt, pred] int64 [S, num_gt, num_pred], one launch for all S segments:
+    every element of segment s with 0 <= gt < num_gt, 0 <= pred < num_pred and gt != ignore_gt counts once, all others are skipped."""
+    lib = _lib.load()
+    if pred.dtype not in _LABEL_CODES:
+        raise TypeError(f"pred: expected torch.int16 or torch.int64, got {pred.dtype}")
+    _chk(pred, "pred", pred.dtype); _chk(gt, "gt", torch.int64)
+    if pred.dim() != 2 or pred.shape != gt.shape:
+        raise ValueError(f"pred and gt: expected two [S, n] tensors of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    S, n = pred.shape
+    counts = torch.empty((S, int(num_gt), int(num_pred)), dtype=torch.int64, device=pred.device)
+    _lib.check(lib.tt_confusion_counts_segments(_p(pred), _LABEL_CODES[pred.dtype], _p(gt), S, n, int(num_gt), int(num_pred),
+                                                0 if ignore_gt is None else int(ignore_gt), 0 if ignore_gt is None else 1, _p(counts),
+                                                _stream()), "tt_confusion_counts_segments")
+    return counts
+
+
 # ---- clip input pipeline (uint8 frames [F, H, W, 3]) ------------------------------------------------------------------
 
 def img_resample_h(frames, coeffs, bounds, y0: int, x0: int, h: int):

@@ -5,6 +5,10 @@ The reference concatenates every prediction / ground-truth pixel on the host and
 (ground-truth class, predicted class) pair (``compute_score_matrix``, joblib-parallel).  Every quantity it derives - the
 score matrix, the matching, tp / fp / fn after remapping - is a function of the confusion matrix alone, so here one GPU
 pass (``tt_confusion_counts``) builds that matrix and the rest is exact integer bookkeeping on a few hundred numbers.
+
+``compute_segments`` scores MANY independent (gt, pred) pairs - the frames or clips of one ``evaluate_localizations`` call - from one
+launch (``tt_confusion_counts_segments``) and one read-back; ``compute_propagation_score`` (``metrics.py:271-346``) reads the per-frame
+true / false positives and false negatives of every object off the same per-frame matrices.
 """
 from __future__ import annotations
 
@@ -50,6 +54,72 @@ class PredsmIoU(torch.nn.Module):
         pred, conf, gt_unique, pred_unique = self._confusion()
         self.num_pred_classes, self.num_gt_classes = len(pred_unique), len(gt_unique)
         return self.compute_miou_from_confusion(conf, gt_unique, pred_unique, pred, many_to_one, precision_based, linear_probe)
+
+    def compute_segments(self, gt: torch.Tensor, pred: torch.Tensor, many_to_one: bool = False, precision_based: bool = False,
+                         ignore_gt=None) -> list:
+        """``compute`` of S independent segments at once: gt, pred [S, n] -> a list of S ``compute`` tuples (score, tp, fp, fn, None,
+        matched background share), WITHOUT the reordered map.  ``ignore_gt``: elements whose ground truth has this value are left out
+        (Pascal VOC's 255).  One read-back of the two maxima sizes the matrices (any upper bound gives the same scores: the class sets are
+        the non-empty rows and columns, as in ``_confusion``), one ``confusion_counts_segments`` call counts and one ``.cpu()`` brings
+        every matrix to the host; what was stored with ``update`` is neither used nor changed."""
+        gt = gt.long().cuda().contiguous()
+        pred = (pred if pred.dtype in (torch.int16, torch.int64) else pred.long()).cuda().contiguous()
+        if gt.dim() != 2 or gt.shape != pred.shape:
+            raise ValueError(f"compute_segments: expected gt and pred of one shape [S, n], got {tuple(gt.shape)} and {tuple(pred.shape)}")
+        counted_gt = gt if ignore_gt is None else torch.where(gt == ignore_gt, -1, gt)
+        gt_max, pred_max = torch.stack([counted_gt.max(), pred.max().long()]).tolist()
+        counts = ops.confusion_counts_segments(pred, gt, max(gt_max, 0) + 1, max(pred_max, 0) + 1, ignore_gt).cpu().numpy()
+        results = []
+        for s, full in enumerate(counts):                            # [gt value, pred value] of segment s
+            gt_unique = np.nonzero(full.sum(1))[0]
+            pred_unique = np.nonzero(full.sum(0))[0]
+            if len(gt_unique) == 0:
+                raise ValueError(f"compute_segments: segment {s} has no element to score")
+            self.num_pred_classes, self.num_gt_classes = len(pred_unique), len(gt_unique)
+            results.append(self.compute_miou_from_confusion(full[np.ix_(gt_unique, pred_unique)], gt_unique, pred_unique, None, many_to_one,
+                                                            precision_based))
+        return results
+
+    def compute_propagation_score(self, is_global_zero: bool):
+        """``metrics.py:271-296``: the per-object scores of ONE clip whose frames were stored with ``update``, one per call and all of
+        one size (the reference stacks them)."""
+        if not is_global_zero:
+            return None
+        return self.compute_propagation_iou(torch.stack(self.gt), torch.stack(self.pred))
+
+    def compute_propagation_iou(self, gt, pred) -> List[float]:
+        """``metrics.py:297-346`` on gt, pred [frames, ...]: no matching - for every non-zero value v of gt, in ascending order, tp, fp
+        and fn of (gt == v) against (pred == v) ACCUMULATE over the frames, every frame adds the Jaccard index of the sums so far, and the
+        total is divided by the number of frames whose gt holds v.  Per frame, tp is the diagonal cell of that frame's confusion matrix,
+        tp + fn its row sum and tp + fp its column sum: one segmented call, one read-back.  Labels must be non-negative (the kernel skips
+        negative ones, which the reference would count among the false positives and negatives)."""
+        gt, pred = torch.as_tensor(gt), torch.as_tensor(pred)
+        if gt.shape != pred.shape or gt.dim() < 1:
+            raise ValueError(f"compute_propagation_iou: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} need one shape [frames, ...]")
+        frames = gt.shape[0]
+        gt = gt.reshape(frames, -1).long().cuda().contiguous()
+        pred = pred.reshape(frames, -1)
+        pred = (pred if pred.dtype in (torch.int16, torch.int64) else pred.long()).cuda().contiguous()
+        gt_max, pred_max, gt_min, pred_min = torch.stack([gt.max(), pred.max().long(), gt.min(), pred.min().long()]).tolist()
+        if min(gt_min, pred_min) < 0:
+            raise ValueError(f"compute_propagation_iou: negative labels (gt from {gt_min}, pred from {pred_min})")
+        C = max(gt_max, pred_max) + 1
+        counts = ops.confusion_counts_segments(pred, gt, C, C).cpu().numpy()             # [frame, gt value, pred value]
+        in_gt, in_pred = counts.sum(2), counts.sum(1)                                   # [frame, value]
+        self.num_pred_classes, self.num_gt_classes = int((in_pred.sum(0) > 0).sum()), int((in_gt.sum(0) > 0).sum())
+        jac = []
+        for v in np.nonzero(in_gt.sum(0))[0]:
+            if v == 0:
+                continue
+            tp = fp = fn = 0
+            score = 0
+            for f in range(frames):
+                tp += int(counts[f, v, v])
+                fp += int(in_pred[f, v] - counts[f, v, v])
+                fn += int(in_gt[f, v] - counts[f, v, v])
+                score += float(tp) / max(float(tp + fp + fn), 1e-8)
+            jac.append(score / int((in_gt[:, v] > 0).sum()))
+        return jac
 
     @staticmethod
     def score_matrix(conf: np.ndarray, precision_based: bool = False) -> np.ndarray:
