@@ -37,7 +37,10 @@ TWINS = ["sinkhorn", "ce_loss_fwd_bwd", "img_resample_h", "img_resample_v", "img
          "linear_bwd_weight_pairs_tn_workspace_bytes", "split_pairs_dual_multi",
          "split_pairs_dual_parts", "linear_bwd_weight_pairs_tn_bias", "amax_slot_bytes",
          "patch_embed_fwd_pairs", "patch_embed_pairs_workspace_bytes",
-         "sinkhorn_local_workspace_bytes", "sinkhorn_local_begin", "sinkhorn_local_step", "sinkhorn_local_end"]
+         "sinkhorn_local_workspace_bytes", "sinkhorn_local_begin", "sinkhorn_local_step", "sinkhorn_local_end",
+         # the linear probe (the sweep's fourth tier)
+         "probe_logits", "probe_upsample_ce", "probe_upsample_ce_workspace_bytes", "bilinear_adjoint_tokens", "probe_wgrad",
+         "probe_wgrad_workspace_bytes", "sgd_step"]
 _lib = None
 
 

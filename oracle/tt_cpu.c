@@ -1717,3 +1717,172 @@ int tt_cpu_label_propagate_grid_maps(const float* xn, const float* seg0, double*
   if (radius < 0) return -1;
   return lp_cpu(xn, seg0, NULL, NULL, pmap_all, bs, fs, gh, gw, D, K, n_last_frames, radius, topk, temperature);
 }
+
+/* ======================================================================================================================
+ * N5: the linear probe (linear_finetune.py:13-31,66-86), written from the contract in include/timetuning_hip.h: fp32 values,
+ * sums in index order (blocked where the contract splits rows), the bilinear rule of tt_cpu_upsample_bilinear_tokens with the
+ * weight rounded to fp32.  The accepted domain is the header's; anything else is -1 (TT_EINVAL).  Workspaces are ignored.
+ * ==================================================================================================================== */
+static int probe_dims_ok(int D, int C) { return D > 0 && D % 4 == 0 && D <= 1024 && C >= 1 && C <= 256; }
+static int probe_grid_ok(int B, int g, int C, int R) { return B >= 1 && B <= 65535 && g >= 1 && g <= 64 && C >= 1 && C <= 256 && R >= 1 && R <= 1024; }
+static int on_16_bytes(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+/* logits = feats W^T + b (linear_finetune.py:30): per output a sum over D in runs of 16 columns, the runs then added in order */
+int tt_cpu_probe_logits(const float* feats, const float* weight, const float* bias, float* logits, long long rows, int D, int C,
+                        tt_stream_t stream) {
+  (void)stream;
+  if (!feats || !weight || !logits || rows <= 0 || !probe_dims_ok(D, C) || !on_16_bytes(feats) || !on_16_bytes(weight)) return -1;
+  for (long long r = 0; r < rows; ++r)
+    for (int c = 0; c < C; ++c) {
+      const float *x = feats + r * D, *w = weight + (size_t)c * D;
+      float total = 0.f;
+      for (int k0 = 0; k0 < D; k0 += 16) {
+        float run = 0.f;
+        for (int k = k0; k < D && k < k0 + 16; ++k) run += x[k] * w[k];
+        total += run;
+      }
+      logits[r * C + c] = total + (bias ? bias[c] : 0.f);
+    }
+  return 0;
+}
+
+/* the source rows / columns and the weight of the second one for output position `dst` (ATen area_pixel_compute_source_index,
+ * align_corners = False): coordinate in double, weight rounded to float */
+static void probe_src(int dst, int n_in, int n_out, int* i0, int* i1, float* l1) {
+  double s = ((double)n_in / (double)n_out) * (dst + 0.5) - 0.5;
+  if (s < 0) s = 0;
+  *i0 = (int)s;
+  *i1 = *i0 + (*i0 < n_in - 1);
+  *l1 = (float)(s - *i0);
+}
+
+size_t tt_cpu_probe_upsample_ce_workspace_bytes(int B, int g) { (void)B; (void)g; return 0; }
+
+/* interpolate -> CrossEntropyLoss(ignore_index=255) -> backward (linear_finetune.py:26-30,81-84), pixel by pixel: the four taps of a
+ * VALID pixel give its logits, its loss term and softmax - one-hot, which is scattered back onto the four taps; pixels labelled 255
+ * contribute nothing, other labels outside [0, C) are counted */
+int tt_cpu_probe_upsample_ce(const float* logits_low, const int64_t* labels, float* dlogits_low, float* loss_out, long long* counts_out, int B,
+                             int g, int C, int R, void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+  (void)workspace; (void)workspace_bytes; (void)stream;
+  if (!logits_low || !labels || !dlogits_low || !loss_out || !counts_out || !probe_grid_ok(B, g, C, R)) return -1;
+  const size_t n = (size_t)B * g * g * C;
+  memset(dlogits_low, 0, n * sizeof(float));
+  float z[256];
+  double loss = 0.0;
+  long long valid = 0, invalid = 0;
+  for (int b = 0; b < B; ++b) {
+    const float* low = logits_low + (size_t)b * g * g * C;
+    float* dlow = dlogits_low + (size_t)b * g * g * C;
+    for (int oy = 0; oy < R; ++oy) {
+      int y0, y1; float ly;
+      probe_src(oy, g, R, &y0, &y1, &ly);
+      for (int ox = 0; ox < R; ++ox) {
+        const int64_t y = labels[((size_t)b * R + oy) * R + ox];
+        if (y == 255) continue;
+        if (y < 0 || y >= C) { ++invalid; continue; }
+        int x0, x1; float lx;
+        probe_src(ox, g, R, &x0, &x1, &lx);
+        const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
+        const size_t t00 = (size_t)(y0 * g + x0) * C, t01 = (size_t)(y0 * g + x1) * C, t10 = (size_t)(y1 * g + x0) * C, t11 = (size_t)(y1 * g + x1) * C;
+        float top = -INFINITY;
+        for (int c = 0; c < C; ++c) {
+          z[c] = (w00 * low[t00 + c] + w01 * low[t01 + c]) + (w10 * low[t10 + c] + w11 * low[t11 + c]);
+          if (z[c] > top) top = z[c];
+        }
+        float sum = 0.f;
+        for (int c = 0; c < C; ++c) sum += expf(z[c] - top);
+        loss += (double)(logf(sum) + (top - z[y]));
+        ++valid;
+        for (int c = 0; c < C; ++c) {
+          const float d = expf(z[c] - top) / sum - (c == y ? 1.f : 0.f);
+          dlow[t00 + c] += w00 * d; dlow[t01 + c] += w01 * d; dlow[t10 + c] += w10 * d; dlow[t11 + c] += w11 * d;
+        }
+      }
+    }
+  }
+  const float inv = valid > 0 ? (float)(1.0 / (double)valid) : 0.f;
+  for (size_t e = 0; e < n; ++e) dlogits_low[e] *= inv;
+  loss_out[0] = (float)(loss / (double)valid);     /* 0 / 0 = NaN without a valid pixel, as torch */
+  counts_out[0] = valid; counts_out[1] = invalid;
+  return 0;
+}
+
+/* the adjoint of tt_cpu_upsample_bilinear_tokens (autograd of linear_finetune.py:26-27): every mask pixel's value goes to its four
+ * source tokens with the weights the upsampling read them with */
+int tt_cpu_bilinear_adjoint_tokens(const float* d_hi, float* d_low, int B, int g, int C, int R, tt_stream_t stream) {
+  (void)stream;
+  if (!d_hi || !d_low || !probe_grid_ok(B, g, C, R)) return -1;
+  memset(d_low, 0, (size_t)B * g * g * C * sizeof(float));
+  for (int b = 0; b < B; ++b)
+    for (int oy = 0; oy < R; ++oy) {
+      int y0, y1; float ly;
+      probe_src(oy, g, R, &y0, &y1, &ly);
+      for (int ox = 0; ox < R; ++ox) {
+        int x0, x1; float lx;
+        probe_src(ox, g, R, &x0, &x1, &lx);
+        const float* v = d_hi + (((size_t)b * R + oy) * R + ox) * C;
+        float* lowb = d_low + (size_t)b * g * g * C;
+        for (int c = 0; c < C; ++c) {
+          lowb[(size_t)(y0 * g + x0) * C + c] += (1.f - ly) * (1.f - lx) * v[c];
+          lowb[(size_t)(y0 * g + x1) * C + c] += (1.f - ly) * lx * v[c];
+          lowb[(size_t)(y1 * g + x0) * C + c] += ly * (1.f - lx) * v[c];
+          lowb[(size_t)(y1 * g + x1) * C + c] += ly * lx * v[c];
+        }
+      }
+    }
+  return 0;
+}
+
+size_t tt_cpu_probe_wgrad_workspace_bytes(long long rows, int D, int C) { (void)rows; (void)D; (void)C; return 0; }
+
+/* dw = dlogits^T feats, db = column sums of dlogits, times *scale_device (linear_finetune.py:84 through autograd).  "Split rows,
+ * fixed fold order": runs of 256 rows are summed in fp32 and the runs added in order */
+int tt_cpu_probe_wgrad(const float* dlogits, const float* feats, const float* scale_device, float* dw, float* db, long long rows, int D, int C,
+                       void* workspace, size_t workspace_bytes, tt_stream_t stream) {
+  (void)workspace; (void)workspace_bytes; (void)stream;
+  if (!dlogits || !feats || !dw || rows <= 0 || !probe_dims_ok(D, C) || !on_16_bytes(feats)) return -1;
+  const size_t n = (size_t)C * D;
+  float* run = (float*)malloc((n + C) * sizeof(float));
+  float* tot = (float*)calloc(n + C, sizeof(float));
+  if (!run || !tot) { free(run); free(tot); return -3; }
+  for (long long r0 = 0; r0 < rows; r0 += 256) {
+    memset(run, 0, (n + C) * sizeof(float));
+    for (long long r = r0; r < rows && r < r0 + 256; ++r)
+      for (int c = 0; c < C; ++c) {
+        const float a = dlogits[r * C + c];
+        const float* x = feats + r * D;
+        float* o = run + (size_t)c * D;
+        for (int d = 0; d < D; ++d) o[d] += a * x[d];
+        run[n + c] += a;
+      }
+    for (size_t e = 0; e < n + C; ++e) tot[e] += run[e];
+  }
+  const float m = scale_device ? *scale_device : 1.f;
+  for (size_t e = 0; e < n; ++e) dw[e] = tot[e] * m;
+  if (db)
+    for (int c = 0; c < C; ++c) db[c] = tot[n + c] * m;
+  free(run); free(tot);
+  return 0;
+}
+
+/* torch.optim.SGD, dampening 0, no Nesterov (linear_finetune.py:66,85): d = g + wd p; with momentum, buf = d on a tensor's first
+ * step and momentum buf + d afterwards, d = buf; p -= lr d */
+int tt_cpu_sgd_step(const tt_cpu_adamw_tensor* tensors, int count, float momentum, int first_step, tt_stream_t stream) {
+  (void)stream;
+  if (!tensors || count < 1 || count > 40) return -1;
+  for (int t = 0; t < count; ++t)
+    if (!tensors[t].p || !tensors[t].g || tensors[t].n <= 0 || (momentum != 0.f && !tensors[t].m)) return -1;
+  for (int t = 0; t < count; ++t) {
+    const tt_cpu_adamw_tensor a = tensors[t];
+    for (long long i = 0; i < a.n; ++i) {
+      float d = a.g[i];
+      if (a.weight_decay != 0.f) d += a.weight_decay * a.p[i];
+      if (momentum != 0.f) {
+        if (!first_step) d += momentum * a.m[i];
+        a.m[i] = d;
+      }
+      a.p[i] -= a.lr * d;
+    }
+  }
+  return 0;
+}

@@ -212,6 +212,129 @@ def _upsample_argmax_hw(rng):
                 W=int(rng.integers(1, 4 * gw + 2)), dup=_b(rng, 0.3))
 
 
+# ---- fourth tier: the linear probe and the clip input pipeline (checks: tests/_sweep_checks_head.py, on the C twin and on the HIP library)
+PROBE_MAXD, PROBE_MAXC, PROBE_MAXG, PROBE_MAXR = 1024, 256, 64, 1024          # linear_probe.hip: LP_MAXD, LP_MAXC, LP_MAXG, LP_MAXR
+WGRAD_LONG_RUN = 512      # rows one workgroup of tt_probe_wgrad sums in fp32 from which the regime rule sets the bound (tests/_sweep_checks_head.py)
+ADJOINT_LONG_RUN = 1024   # mask pixels one token of tt_bilinear_adjoint_tokens gathers in fp32, (2 R / g)^2, from which the regime rule applies
+GRAY_SUM_CAP = 256 * 2048  # image_ops.hip, tt_img_color: at most 256 workgroups of 256 threads x 8 pixels - beyond, gray_sum_kernel strides
+IMG_MODES = ("gray", "brightness", "contrast", "saturation", "hue")
+
+
+def gather_tp_log2(C: int) -> int:
+    """linear_probe.hip, gather_tp_log2: lanes per pixel (log2) so that a lane owns at most 8 classes."""
+    l = 0
+    while (C + (1 << l) - 1) >> l > 8:
+        l += 1
+    return l
+
+
+def probe_logits_kernel(C: int) -> tuple:
+    """linear_probe.hip, tt_probe_logits: the (CT, RPT) instantiation for ct = ceil(C / 64) - and 16 * RPT rows per workgroup."""
+    ct = (C + 63) // 64
+    return (1, 4) if ct == 1 else ((2, 2) if ct == 2 else (4, 2))
+
+
+def wgrad_split(rows: int, D: int, C: int) -> tuple:
+    """linear_probe.hip, wgrad_split -> (splits, rows per split, what capped the split count: "one", "chunks" or "tiles")."""
+    tiles = ((D + 63) // 64) * ((C + 63) // 64)
+    chunks = (rows + 31) // 32
+    cap = (1024 + tiles - 1) // tiles
+    ns = max(1, min(cap, chunks))
+    rps = ((rows + ns - 1) // ns + 31) // 32 * 32
+    return (rows + rps - 1) // rps, rps, "one" if chunks == 1 else ("chunks" if chunks <= cap else "tiles")
+
+
+def adjoint_run(g: int, R: int) -> float:
+    """Mask pixels that read one low-res token: about 2 R / g along each axis (every token is the first or the second tap of R / g pixels)."""
+    return (2.0 * R / g) ** 2
+
+
+def sgd_lengths(T: int, big: int) -> list:
+    """Lengths 1, 255, 257, big, 1, ... (one tensor: big), as the adamw cases: a length-1 tensor shares the grid of the longest."""
+    cyc = (1, 255, 257, big)
+    return [cyc[i % 4] for i in range(T)] if T > 1 else [big]
+
+
+def PL(rows, D, C, bias) -> dict:
+    return dict(rows=rows, D=D, C=C, bias=bias)
+
+
+def CE(B, g, R, C, ignored=0.3, kind="normal") -> dict:
+    return dict(B=B, g=g, R=R, C=C, ignored=ignored, kind=kind)
+
+
+def ADJ(B, g, R, C) -> dict:
+    return dict(B=B, g=g, R=R, C=C)
+
+
+def WG(rows, D, C, scale, need_bias) -> dict:
+    return dict(rows=rows, D=D, C=C, scale=scale, need_bias=need_bias)
+
+
+def SGD(T, big, steps=3, momentum=0.9, wd=1e-4) -> dict:
+    return dict(T=T, big=big, steps=steps, momentum=momentum, wd=wd)
+
+
+def RS(F, h, w, oh, ow, crop="", flip=0, to_tensor=0) -> dict:
+    """crop: "y0/x0/h/w" inside the h x w frame, "" = the whole frame; a flip needs the float output."""
+    assert not flip or to_tensor
+    return dict(F=F, h=h, w=w, crop=crop, oh=oh, ow=ow, flip=flip, to_tensor=to_tensor)
+
+
+def COL(F, H, W, mode, factor) -> dict:
+    return dict(F=F, H=H, W=W, mode=mode, factor=factor)
+
+
+def BL(F, H, W, radius) -> dict:
+    return dict(F=F, H=H, W=W, radius=radius)
+
+
+def _probe_logits(rng):
+    return PL(int(rng.integers(1, 1200)), _ch(rng, (4, 32, 36, 64, 100, 384, 768, 1024)), int(rng.integers(1, 257)), _b(rng))
+
+
+def _probe_geometry(rng):
+    g = int(rng.integers(1, 29))
+    return int(rng.integers(1, 4)), g, int(rng.integers(1, 5 * g + 2)), _ch(rng, (1, 2, 5, 8, 9, 21, 33, 64, 65, 150, 256))
+
+
+def _probe_upsample_ce(rng):
+    B, g, R, C = _probe_geometry(rng)
+    return CE(B, g, R, C, _ch(rng, (0.0, 0.3, 0.3, "rows")), _ch(rng, ("normal", "normal", "large", "const")))
+
+
+def _bilinear_adjoint(rng):
+    return ADJ(*_probe_geometry(rng))
+
+
+def _probe_wgrad(rng):
+    return WG(int(rng.integers(1, 3000)), _ch(rng, (4, 60, 64, 68, 384, 1024)), int(rng.integers(1, 257)), _ch(rng, (0, 0.5)), _b(rng))
+
+
+def _sgd(rng):
+    return SGD(int(rng.integers(1, 100)), int(rng.integers(1, 400000)), 3, _ch(rng, (0.0, 0.9)), _ch(rng, (0.0, 1e-4)))
+
+
+def _img_resize(rng):
+    h, w = int(rng.integers(1, 41)), int(rng.integers(1, 41))
+    crop = ""
+    if rng.random() < 0.5:
+        ch, cw = int(rng.integers(1, h + 1)), int(rng.integers(1, w + 1))
+        crop = f"{int(rng.integers(0, h - ch + 1))}/{int(rng.integers(0, w - cw + 1))}/{ch}/{cw}"
+    tt = _b(rng)
+    return RS(int(rng.integers(1, 5)), h, w, int(rng.integers(1, 41)), int(rng.integers(1, 41)), crop, _b(rng) if tt else 0, tt)
+
+
+def _img_color(rng):
+    mode = _ch(rng, IMG_MODES)
+    factor = _ch(rng, (-0.5, -0.07, 0.13, 0.5)) if mode == "hue" else _ch(rng, (0.0, 0.2, 0.9999, 1.0, 1.3, 1.8))
+    return COL(int(rng.integers(1, 5)), int(rng.integers(1, 70)), int(rng.integers(1, 70)), mode, factor)
+
+
+def _img_blur(rng):
+    return BL(int(rng.integers(1, 4)), int(rng.integers(1, 40)), int(rng.integers(1, 40)), _ch(rng, (0.1, 0.37, 0.9, 1.3, 2.0)))
+
+
 DRAW = {"linear_f32": _linear_f32, "linear_pairs": _linear_pairs, "linear_planes": _linear_planes, "bwd_pairs": _bwd_pairs,
         "layernorm": _layernorm, "l2norm": _l2norm, "attention": _attention, "ce": _ce, "sinkhorn": _sinkhorn,
         "sinkhorn_from_q": _sinkhorn_from_q, "sinkhorn_local": _sinkhorn_local, "queue_push": _queue_push}
@@ -224,14 +347,20 @@ DRAW.update({"kmeans_assign": _kmeans_assign, "kmeans_accumulate": _kmeans_accum
 EVAL_OPS = tuple(DRAW)[len(STEP_OPS):]
 # (appended again: the third tier draws after the first two)
 DRAW.update({"label_prop": _label_prop, "label_prop_grid": _label_prop_grid, "upsample_argmax_hw": _upsample_argmax_hw})
+PROP_OPS = tuple(DRAW)[len(STEP_OPS) + len(EVAL_OPS):]
+# (and again: the fourth tier draws after the first three)
+DRAW.update({"probe_logits": _probe_logits, "probe_upsample_ce": _probe_upsample_ce, "bilinear_adjoint": _bilinear_adjoint,
+             "probe_wgrad": _probe_wgrad, "sgd": _sgd, "img_resize": _img_resize, "img_color": _img_color, "img_blur": _img_blur})
 OPS = tuple(DRAW)
-PROP_OPS = OPS[len(STEP_OPS) + len(EVAL_OPS):]
+HEAD_OPS = OPS[len(STEP_OPS) + len(EVAL_OPS) + len(PROP_OPS):]
 
 COUNTS = {"linear_f32": 6, "linear_pairs": 8, "linear_planes": 4, "bwd_pairs": 6, "layernorm": 5, "l2norm": 3, "attention": 6, "ce": 3,
           "sinkhorn": 6, "sinkhorn_from_q": 3, "sinkhorn_local": 3, "queue_push": 3,
           "kmeans_assign": 4, "kmeans_accumulate": 4, "col_moments": 3, "upsample_tokens": 3, "upsample_argmax_f32": 3, "upsample_argmax": 3,
           "confusion_counts": 3, "adamw": 3, "elementwise": 3, "foreground_mask": 4, "pos_embed": 3,
-          "label_prop": 6, "label_prop_grid": 4, "upsample_argmax_hw": 4}
+          "label_prop": 6, "label_prop_grid": 4, "upsample_argmax_hw": 4,
+          "probe_logits": 4, "probe_upsample_ce": 4, "bilinear_adjoint": 3, "probe_wgrad": 4, "sgd": 3, "img_resize": 4, "img_color": 4,
+          "img_blur": 3}
 
 # The route boundaries, pinned (tests/test_sweep_routes.py names the rule each one reaches)
 PINNED = {
@@ -414,6 +543,74 @@ PINNED = {
         dict(M=1, gh=9, gw=5, K=21, H=4, W=3, dup=0), dict(M=3, gh=7, gw=23, K=3, H=7, W=23, dup=1), dict(M=2, gh=5, gw=9, K=64, H=40, W=77, dup=1),
         dict(M=1, gh=5, gw=9, K=65, H=1, W=30, dup=1), dict(M=2, gh=9, gw=5, K=7, H=30, W=1, dup=0), dict(M=1, gh=1, gw=1, K=1, H=3, W=2, dup=0),
         dict(M=3, gh=14, gw=1, K=2, H=9, W=9, dup=0), dict(M=1, gh=30, gw=53, K=5, H=480, W=848, dup=0), dict(M=2, gh=6, gw=10, K=200, H=96, W=31, dup=1),
+    ],
+    # ---- fourth tier (linear_probe.hip, image_ops.hip)
+    "probe_logits": [
+        # probe_logits_kernel<1,4> (C <= 64: 64 rows per workgroup), <2,2> (C <= 128: 32 rows) and <4,2> (ct = 3 and 4: 32 rows), the last
+        # workgroup of each one short of whole, whole, one over and alone; D below, at and off the 32-column stage; bias present and NULL
+        PL(1, 4, 1, 0), PL(63, 32, 63, 1), PL(64, 36, 64, 0), PL(65, 384, 64, 1), PL(1001, 1024, 1, 1),
+        PL(31, 36, 65, 1), PL(32, 384, 128, 0), PL(33, 4, 128, 1), PL(1001, 32, 65, 0), PL(64, 1024, 128, 1),
+        PL(31, 4, 129, 0), PL(32, 36, 192, 1), PL(33, 384, 192, 0), PL(1001, 32, 129, 1),
+        PL(31, 384, 193, 1), PL(32, 1024, 256, 0), PL(33, 36, 256, 1), PL(65, 4, 193, 0), PL(1001, 384, 256, 1), PL(63, 32, 256, 0), PL(1, 1024, 256, 1),
+    ],
+    "probe_upsample_ce": [
+        # geometry: down-sampling (R < g: low-res rows and columns that no pixel reads), R = g, R just above g, one token, one pixel,
+        # the largest mask at 2 classes, the LDS maximum (64 x 64 x 256 accumulators, R 1024) with 1 % of the pixels valid
+        CE(2, 28, 14, 5), CE(1, 28, 9, 21, 0.0), CE(2, 64, 1, 5, 0.0), CE(1, 5, 4, 9, 0.3, "large"), CE(2, 14, 14, 21), CE(1, 28, 29, 5, 0.0),
+        CE(3, 1, 1, 5, 0.0), CE(2, 1, 7, 17), CE(1, 64, 1024, 2), CE(1, 64, 1024, 256, 0.99),
+        # lanes per pixel 1, 2, 4, 8, 16, 32 either side of each edge (gather_tp_log2), every kind of logits and share of ignored pixels
+        CE(2, 7, 20, 1, 0.3), CE(1, 7, 20, 1, 0.0, "const"), CE(2, 7, 20, 8, 0.0, "large"), CE(2, 7, 20, 9, "rows"), CE(3, 7, 20, 16, 0.3, "const"),
+        CE(2, 7, 20, 17, 0.0, "const"), CE(2, 7, 20, 32, 0.3, "large"), CE(2, 7, 20, 33, "rows", "const"), CE(2, 7, 20, 64, 0.0, "const"), CE(2, 7, 20, 65, 0.3),
+        CE(2, 7, 20, 128, "rows", "large"), CE(2, 7, 20, 129, 0.0, "const"), CE(2, 7, 20, 256, 0.3), CE(1, 7, 20, 256, 0.0, "large"),
+        # nothing valid (NaN loss, zero gradient); whole mask rows ignored (workgroups that own no valid pixel); more than one pixel chunk
+        # with a ragged last one (R 300 at 256 pixels per chunk, 100 at 64); three images
+        CE(2, 7, 20, 5, 1.0), CE(1, 14, 14, 256, 1.0, "large"), CE(2, 14, 56, 21, "rows"), CE(1, 14, 300, 5), CE(3, 28, 100, 21),
+        CE(1, 14, 150, 12, 0.0), CE(1, 7, 50, 40),          # ... R 150 at 128 pixels per chunk, 50 at 32
+    ],
+    "bilinear_adjoint": [
+        # the same geometry and class counts; the big masks at small C only (d_hi is B * R * R * C floats); 64 x 64 x 256 accumulators
+        ADJ(2, 28, 14, 5), ADJ(1, 28, 9, 21), ADJ(2, 64, 1, 5), ADJ(1, 5, 4, 9), ADJ(2, 14, 14, 21), ADJ(1, 28, 29, 5), ADJ(3, 1, 1, 5),
+        ADJ(2, 1, 7, 17), ADJ(1, 64, 1024, 2), ADJ(1, 64, 64, 256), ADJ(1, 14, 300, 5), ADJ(3, 28, 100, 21), ADJ(1, 14, 150, 12), ADJ(1, 7, 50, 40),
+        ADJ(2, 7, 20, 1), ADJ(2, 7, 20, 8), ADJ(2, 7, 20, 9), ADJ(2, 7, 20, 16), ADJ(2, 7, 20, 17), ADJ(2, 7, 20, 32), ADJ(2, 7, 20, 33),
+        ADJ(2, 7, 20, 64), ADJ(2, 7, 20, 65), ADJ(2, 7, 20, 128), ADJ(2, 7, 20, 129), ADJ(2, 7, 20, 256),
+    ],
+    "probe_wgrad": [
+        # wgrad_split: one split (rows <= 32); 33 rows (two splits, the last of one row); splits capped by the 32-row chunks; capped by
+        # 1024 / tiles (47 040 rows of the probe's own shape: 164 splits of 288, the last of 96; 64 tiles: 10 splits of 64, the last of 24;
+        # 16 splits of 512: the longest fp32 runs here); C and D off the 64-wide tiles; scale and db each present and NULL
+        WG(1, 4, 1, 0.5, 1), WG(32, 60, 63, 0, 0), WG(17, 68, 65, 0.5, 1), WG(33, 4, 256, 0.5, 1), WG(1000, 60, 63, 0.5, 0),
+        WG(100, 68, 65, 0, 1), WG(47040, 384, 21, 0.5, 1), WG(600, 1024, 256, 0, 1), WG(8192, 1024, 256, 0.5, 1), WG(2049, 1024, 1, 0, 0),
+    ],
+    "sgd": [
+        # tables of 1, 40 (TT_MAX_TENSORS) and - through the wrapper's chunks - 41 and 85 tensors; lengths 1, 255, 257 and `big` round-robin
+        # (a one-element tensor beside one above 1024 x 256 elements: the grid-stride loop); momentum and weight decay each on and off
+        SGD(1, 300001), SGD(1, 1, 3, 0.0, 0.0), SGD(40, 262145, 3, 0.9, 0.0), SGD(41, 300001, 3, 0.0, 1e-4), SGD(85, 262145), SGD(4, 262144, 3, 0.0, 0.0),
+        SGD(40, 1000, 1),
+    ],
+    "img_resize": [
+        # one-pixel sides; 1 -> N and N -> 1 (a thousand taps per output pixel); an axis that keeps its size, each way and both; crops that
+        # end on the right and bottom border, one-pixel crops; the flip at odd and even widths; 300 tiny frames; uint8 and float outputs
+        RS(1, 1, 1, 5, 3), RS(2, 7, 1, 3, 4, to_tensor=1), RS(2, 1, 9, 4, 2, flip=1, to_tensor=1), RS(1, 1000, 3, 1, 3), RS(1, 3, 1000, 3, 1, to_tensor=1),
+        RS(2, 9, 7, 9, 4), RS(2, 9, 7, 5, 7, flip=1, to_tensor=1), RS(1, 6, 5, 6, 5, flip=1, to_tensor=1), RS(1, 6, 5, 6, 5),
+        RS(2, 20, 30, 8, 8, "5/11/15/19", to_tensor=1), RS(2, 20, 30, 4, 5, "19/29/1/1"), RS(1, 20, 30, 3, 3, "0/0/1/1", flip=1, to_tensor=1),
+        RS(2, 20, 30, 5, 19, "3/11/10/19"), RS(1, 20, 30, 15, 19, "5/11/15/19"), RS(2, 20, 30, 15, 7, "5/0/15/30", to_tensor=1),
+        RS(1, 12, 12, 8, 8, flip=1, to_tensor=1), RS(300, 3, 4, 2, 5, flip=1, to_tensor=1), RS(300, 2, 2, 3, 3, "1/1/1/1"), RS(1, 1000, 1, 1, 1),
+    ],
+    "img_color": [
+        # every mode on one pixel; the contrast mean above gray_sum_kernel's cap of 524 288 pixels (its grid-stride loop) and exactly at it;
+        # five frames of differing brightness (one mean each); factors 0, 0.9999, 1 and 1.8; hue shifts at both ends; the last frame of
+        # every clip of two or more is exact grays
+        COL(1, 1, 1, "gray", 1.0), COL(1, 1, 1, "brightness", 1.8), COL(1, 1, 1, "contrast", 0.0), COL(1, 1, 1, "saturation", 0.9999), COL(1, 1, 1, "hue", 0.5),
+        COL(1, 600, 1024, "contrast", 1.8), COL(2, 512, 1024, "contrast", 0.9999), COL(5, 33, 47, "contrast", 0.0), COL(5, 33, 47, "contrast", 1.8),
+        COL(3, 40, 31, "contrast", 1.0), COL(2, 40, 31, "brightness", 0.0), COL(2, 40, 31, "brightness", 0.9999), COL(2, 40, 31, "saturation", 1.8),
+        COL(2, 40, 31, "saturation", 0.0), COL(2, 40, 31, "saturation", 1.0), COL(3, 40, 31, "hue", -0.5), COL(3, 40, 31, "hue", 0.5),
+        COL(2, 17, 1, "hue", 0.13), COL(300, 3, 2, "gray", 1.0), COL(300, 2, 3, "contrast", 1.8),
+    ],
+    "img_blur": [
+        # lines of 1, 2 and 3 pixels at radius 2.0 (box radius 1 and the far taps at +-2: at or beyond the line), each direction; 1 x 53
+        # and 37 x 1; the smallest and the largest radius of the training transform
+        BL(2, 5, 1, 2.0), BL(2, 1, 5, 2.0), BL(1, 2, 7, 2.0), BL(1, 7, 2, 2.0), BL(1, 3, 3, 2.0), BL(1, 1, 1, 2.0), BL(2, 1, 53, 2.0), BL(2, 37, 1, 2.0),
+        BL(1, 1, 53, 0.1), BL(1, 37, 1, 0.1), BL(300, 3, 2, 2.0), BL(2, 37, 53, 0.1),
     ],
 }
 

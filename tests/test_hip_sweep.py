@@ -13,6 +13,10 @@ entry, its up-sampler) - runs the checks of tests/_sweep_checks_prop.py the same
 real-valued inputs, the bit-for-bit equalities between the entries; tests/test_sweep_prop_host.py is its host half.  Its domain edges
 follow the second tier's.
 
+The fourth tier - the linear probe's kernels and the clip input pipeline (HEAD_OPS) - runs the checks of tests/_sweep_checks_head.py: fp64
+references at the existing linear-probe bounds, bit equality with the Pillow-pinned image oracle; tests/test_sweep_head_host.py is its host
+half, and the probe's domain edges follow the second tier's.
+
 ``run_case`` is also what tools/fuzz_ops.py runs on more seeds of the same generator."""
 import json
 import os
@@ -23,8 +27,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _sweep_cases import EVAL_OPS, PAIR_EPILOGUES, PROP_OPS, case_id, table
+from _sweep_cases import EVAL_OPS, HEAD_OPS, PAIR_EPILOGUES, PROP_OPS, case_id, table
 from _sweep_checks_eval import HipSide, run_eval_case
+from _sweep_checks_head import HeadHip, run_head_case
 from _sweep_checks_prop import PropHip, run_prop_case
 
 pytestmark = pytest.mark.gpu
@@ -335,6 +340,8 @@ def run_case(op: str, params: dict, worst: dict = None) -> None:
             run_eval_case(HipSide(), op, params, WORST)
         elif op in PROP_OPS:
             run_prop_case(PropHip(), op, params, WORST)
+        elif op in HEAD_OPS:
+            run_head_case(HeadHip(), op, params, WORST)
         else:
             CHECK[op](ops, params, _gen(op, params), _note(op))
     finally:
@@ -461,6 +468,102 @@ def test_mask_position_and_row_op_limits():
     with _refused("l2norm_fwd: bad arguments"):
         ops.normalize_rows_(_z(2, 1025))
     assert rel_err(ops.normalize_rows_(torch.full((2, 1024), 2.0, device="cuda")), torch.full((2, 1024), 2.0 / 64.0)) < TOL_F32
+
+
+# ---- the accepted domain of the linear probe's entries, at the edge (include/timetuning_hip.h, N5; linear_probe.hip: probe_shape_error,
+# probe_grid_error).  The largest accepted size computes correctly - here or as a case of the table above - and the first one beyond is
+# refused by the launcher's own message: every refusal is a host-side TT_REQUIRE ahead of the first launch.
+def _probe_ce_raw(B, g, Cc, R, ws_bytes=None):
+    """tt_probe_upsample_ce on zero logits and labels 0, through the C entry: -> (rc, loss, dlow, counts)"""
+    from timetuning_amd import _lib
+
+    lib = _lib.load()
+    low, y = _z(B, g * g, Cc), _z(B, R, R, dtype=torch.int64)
+    dlow, loss, counts = torch.full_like(low, 7.0), _z(1), _z(2, dtype=torch.int64)
+    nb = lib.tt_probe_upsample_ce_workspace_bytes(B, g) if ws_bytes is None else ws_bytes
+    ws = _z(max(nb, 8), dtype=torch.uint8)
+    rc = lib.tt_probe_upsample_ce(low.data_ptr(), y.data_ptr(), dlow.data_ptr(), loss.data_ptr(), counts.data_ptr(), B, g, Cc, R, ws.data_ptr(), nb,
+                                  torch.cuda.current_stream().cuda_stream)
+    return rc, loss, dlow, counts
+
+
+@pytest.mark.parametrize("what,ok,bad,msg", [("g", 64, 65, r"need 1 <= g <= 64 \(got 65\)"), ("R", 1024, 1025, r"need 1 <= R <= 1024 \(got 1025\)"),
+                                             ("C", 256, 257, r"need 1 <= classes <= 256 \(got 257\)"),
+                                             ("B", 65535, 65536, r"need 1 <= B <= 65535 \(got 65536\)")])
+def test_probe_grid_entries_at_the_edge(what, ok, bad, msg):
+    """g, R, C and B of tt_probe_upsample_ce and tt_bilinear_adjoint_tokens.  Equal logits under labels 0 give loss = log C and, summed over
+    the tokens, the gradient 1 / C - [c == 0] per class (the bilinear weights of every mask pixel sum to 1); a mask of ones gives the
+    adjoint R * R per image and class - B = 65535 at g = R = C = 1 included."""
+    from timetuning_amd import _lib, hip_ops as ops
+
+    def dims(v):
+        d = dict(g=dict(B=1, g=64, C=3, R=4), R=dict(B=1, g=64, C=2, R=1024), C=dict(B=1, g=2, C=256, R=4), B=dict(B=65535, g=1, C=1, R=1))[what]
+        d[what] = v
+        return d["B"], d["g"], d["C"], d["R"]
+
+    B, g, Cc, R = dims(ok)
+    rc, loss, dlow, counts = _probe_ce_raw(B, g, Cc, R)
+    assert rc == 0 and counts.tolist() == [B * R * R, 0]
+    assert abs(loss.item() - np.log(Cc)) <= 1e-5 * max(np.log(Cc), 1.0)
+    want = torch.full((Cc,), 1.0 / Cc, dtype=torch.float64)
+    want[0] -= 1.0
+    assert float((dlow.double().sum((0, 1)).cpu() - want).abs().max()) <= 1e-5 * max(float(want.abs().max()), 1.0 / Cc)
+    d_low = ops.bilinear_adjoint_tokens(torch.ones(B, R * R, Cc, device="cuda"), g)
+    assert rel_err(d_low.double().sum(1), torch.full((B, Cc), float(R * R), dtype=torch.float64)) < 1e-6
+    if R % g == 0:      # whole ratios: every token is read with a total weight of (R / g)^2, border tokens included
+        assert rel_err(d_low, torch.full((B, g * g, Cc), (R / g) ** 2)) < 1e-6
+    B, g, Cc, R = dims(bad)
+    with _refused("linear probe: " + msg):
+        _lib.check(_probe_ce_raw(B, g, Cc, R)[0], "tt_probe_upsample_ce")
+    with _refused("linear probe: " + msg):
+        ops.bilinear_adjoint_tokens(_z(B, R * R, Cc), g)
+
+
+def test_probe_matrix_entries_at_the_edge():
+    from timetuning_amd import _lib, hip_ops as ops
+
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    # D = 1024 and C = 256 compute (cases above); D = 1028, D = 6 and C = 257 are refused by both matrix entries
+    for D, Cc, msg in ((1028, 4, r"need D % 4 == 0 and 0 < D <= 1024 \(got 1028\)"), (6, 4, r"need D % 4 == 0 and 0 < D <= 1024 \(got 6\)"),
+                       (8, 257, r"need 1 <= classes <= 256 \(got 257\)")):
+        with _refused("linear probe: " + msg):
+            ops.probe_logits(_z(3, D), _z(Cc, D))
+        with _refused("linear probe: " + msg):
+            ops.probe_wgrad(_z(3, Cc), _z(3, D))
+    x = torch.ones(5, 1024, device="cuda")
+    assert torch.equal(ops.probe_logits(x, torch.ones(256, 1024, device="cuda")), torch.full((5, 256), 1024.0, device="cuda"))
+    dw, db = ops.probe_wgrad(torch.ones(5, 256, device="cuda"), x)
+    assert torch.equal(dw, torch.full((256, 1024), 5.0, device="cuda")) and torch.equal(db, torch.full((256,), 5.0, device="cuda"))
+    # feats one float off a 16-byte boundary
+    off = _z(3 * 8 + 4)[1:25].view(3, 8)
+    assert off.data_ptr() % 16 == 4
+    with _refused("probe_logits: feats and weight must be 16-byte aligned"):
+        ops.probe_logits(off, _z(2, 8))
+    with _refused("probe_wgrad: feats and workspace must be 16-byte aligned"):
+        ops.probe_wgrad(_z(3, 2), off)
+    # a workspace one byte short
+    dl, xs, dws = _z(100, 4), _z(100, 8), _z(4, 8)
+    nb = lib.tt_probe_wgrad_workspace_bytes(100, 8, 4)
+    ws = _z(nb, dtype=torch.uint8)
+    assert nb > 0 and lib.tt_probe_wgrad(dl.data_ptr(), xs.data_ptr(), None, dws.data_ptr(), None, 100, 8, 4, ws.data_ptr(), nb, st) == 0
+    with _refused("probe_wgrad: workspace too small"):
+        _lib.check(lib.tt_probe_wgrad(dl.data_ptr(), xs.data_ptr(), None, dws.data_ptr(), None, 100, 8, 4, ws.data_ptr(), nb - 1, st), "tt_probe_wgrad")
+    with _refused("probe_upsample_ce: workspace too small"):
+        _lib.check(_probe_ce_raw(2, 3, 4, 5, ws_bytes=lib.tt_probe_upsample_ce_workspace_bytes(2, 3) - 1)[0], "tt_probe_upsample_ce")
+    # TT_MAX_TENSORS = 40 per table: 40 update every tensor, 41 in one call are refused at the C entry
+    ps = [torch.ones(4, device="cuda") for _ in range(41)]
+    grad = torch.ones(4, device="cuda")
+    tab = (_lib.AdamwTensor * 41)()
+    for j, q in enumerate(ps):
+        tab[j] = _lib.AdamwTensor(q.data_ptr(), grad.data_ptr(), None, None, 4, 0.5, 0.0)
+    with _refused(r"sgd_step: need 1\.\.40 tensors"):
+        _lib.check(lib.tt_sgd_step(tab, 41, 0.0, 1, st), "tt_sgd_step")
+    assert all(torch.equal(q, torch.ones(4, device="cuda")) for q in ps)             # nothing was launched
+    _lib.check(lib.tt_sgd_step(tab, 40, 0.0, 1, st), "tt_sgd_step")
+    assert all(torch.equal(q, torch.full((4,), 0.5, device="cuda")) for q in ps[:40]) and torch.equal(ps[40], torch.ones(4, device="cuda"))
+    with _refused("sgd_step: tensor 0 has no momentum buffer"):
+        _lib.check(lib.tt_sgd_step(tab, 1, 0.9, 1, st), "tt_sgd_step")
 
 
 # ---- the accepted domain of the propagation entries, at the edge (include/timetuning_hip.h, k14 and N9).  Every refusal below is a host-side

@@ -8,7 +8,9 @@ import itertools
 
 import pytest
 
-from _sweep_cases import EVAL_OPS, KM_MAXKD, LP_CAND_CAP, PAIR_EPILOGUES, PROP_OPS, STEP_OPS, case_id, km_max_k, lp_caps, lp_chunk, lp_cmax, table
+from _sweep_cases import (ADJOINT_LONG_RUN, EVAL_OPS, GRAY_SUM_CAP, HEAD_OPS, IMG_MODES, KM_MAXKD, LP_CAND_CAP, OPS, PAIR_EPILOGUES, PROP_OPS, STEP_OPS,
+                          WGRAD_LONG_RUN, adjoint_run, case_id, gather_tp_log2, km_max_k, lp_caps, lp_chunk, lp_cmax, probe_logits_kernel, sgd_lengths,
+                          table, wgrad_split)
 from timetuning_amd import _lib, hip_ops
 
 NCU = 256
@@ -218,7 +220,7 @@ def test_second_tier_is_appended_and_complete():
     assert STEP_OPS == ("linear_f32", "linear_pairs", "linear_planes", "bwd_pairs", "layernorm", "l2norm", "attention", "ce", "sinkhorn",
                         "sinkhorn_from_q", "sinkhorn_local", "queue_push")
     ops_in_order = list(dict.fromkeys(o for o, _ in CASES))
-    assert tuple(ops_in_order) == STEP_OPS + EVAL_OPS + PROP_OPS         # appended: the first tier's draws - and case ids - are untouched
+    assert tuple(ops_in_order) == STEP_OPS + EVAL_OPS + PROP_OPS + HEAD_OPS == OPS   # appended: the first tier's draws - and case ids - are untouched
     ids = [case_id(o, p) for o, p in CASES]
     assert len(set(ids)) == len(ids)
     # (the first and the last case of the first tier, as they were before the second tier existed)
@@ -375,7 +377,7 @@ def test_third_tier_is_appended_and_the_first_two_are_what_they_were():
     import zlib
 
     assert PROP_OPS == ("label_prop", "label_prop_grid", "upsample_argmax_hw")
-    earlier = [case_id(o, p) for o, p in CASES if o not in PROP_OPS]
+    earlier = [case_id(o, p) for o, p in CASES if o in STEP_OPS + EVAL_OPS]
     assert len(earlier) == 290 and zlib.crc32("\n".join(earlier).encode()) == 681109916      # the ids of the first two tiers, unchanged
     assert earlier[-1].startswith("pos_embed[") and [o for o, _ in CASES][290] == "label_prop"
 
@@ -498,3 +500,135 @@ def test_grid_entry_and_upsampler_edges():
     assert any(p["H"] > p["gh"] and p["W"] > p["gw"] for p in hw) and any(p["H"] == 1 for p in hw) and any(p["W"] == 1 for p in hw)
     assert {p["K"] for p in hw} >= {1, 64, 65} and any(p["M"] == 1 for p in hw) and any(p["M"] > 1 for p in hw)
     assert any(p["dup"] for p in hw) and any(p["H"] * p["W"] > 256 * 256 for p in hw)
+
+
+# ---- the fourth tier: the linear probe (linear_probe.hip) and the clip input pipeline (image_ops.hip).  None of their launchers has a host
+# query: each rule is restated in tests/_sweep_cases.py with the function it comes from, and the table is held to every branch here.
+def test_fourth_tier_is_appended_and_the_first_three_are_what_they_were():
+    import zlib
+
+    assert HEAD_OPS == ("probe_logits", "probe_upsample_ce", "bilinear_adjoint", "probe_wgrad", "sgd", "img_resize", "img_color", "img_blur")
+    earlier = [case_id(o, p) for o, p in CASES if o not in HEAD_OPS]
+    assert len(earlier) == 383 and zlib.crc32("\n".join(earlier).encode()) == 1936048768      # the ids of the first three tiers, unchanged
+    assert earlier[-1].startswith("upsample_argmax_hw[") and [o for o, _ in CASES][383] == "probe_logits"
+    # every op of the table has a check on the side it runs on (tools/fuzz_ops.py draws from OPS and runs tests/test_hip_sweep.py::run_case)
+    from _sweep_checks_eval import CHECK as EVAL_CHECK
+    from _sweep_checks_head import CHECK as HEAD_CHECK
+    from _sweep_checks_prop import CHECK as PROP_CHECK
+
+    assert set(HEAD_CHECK) == set(HEAD_OPS) and set(EVAL_CHECK) == set(EVAL_OPS) and set(PROP_CHECK) == set(PROP_OPS)
+
+
+def test_probe_logits_every_kernel_whole_and_ragged():
+    cases = _of("probe_logits")
+    assert [probe_logits_kernel(C) for C in (1, 64, 65, 128, 129, 192, 193, 256)] == [(1, 4)] * 2 + [(2, 2)] * 2 + [(4, 2)] * 4
+    for ct in (1, 2, 3, 4):      # tt_probe_logits: ct = ceil(C / 64) picks the kernel, 16 * RPT rows per workgroup; <4,2> also serves ct = 3
+        sel = [p for p in cases if (p["C"] + 63) // 64 == ct]
+        rpb = 16 * probe_logits_kernel(64 * ct)[1]
+        assert rpb == (64 if ct == 1 else 32)
+        rows = {p["rows"] for p in sel}
+        assert {rpb - 1, rpb, rpb + 1} <= rows and any(r > 8 * rpb and r % rpb for r in rows), ct      # the last workgroup short, whole, one row
+        assert {p["bias"] for p in sel} == {0, 1} and any(p["D"] % 32 for p in sel) and any(p["D"] % 32 == 0 for p in sel), ct
+    assert {p["rows"] for p in cases} >= {1, 31, 32, 33, 63, 64, 65, 1001}
+    assert {p["C"] for p in cases} >= {1, 63, 64, 65, 128, 129, 192, 193, 256} and {p["D"] for p in cases} >= {4, 32, 36, 384, 1024}
+
+
+def _gather_geometry(cases, op):
+    gr = {(p["g"], p["R"]) for p in cases}
+    assert gr >= {(28, 14), (28, 9), (64, 1), (5, 4), (14, 14), (28, 29), (1, 1), (1, 7), (64, 1024)}, op
+    # lanes per pixel 1 .. 32, either side of each edge; pixel chunks P = 256 >> tp_log2: R below P, above it and no multiple of it
+    assert [gather_tp_log2(C) for C in (1, 8, 9, 16, 17, 32, 33, 64, 65, 128, 129, 256)] == [0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5]
+    assert {p["C"] for p in cases if (p["g"], p["R"]) == (7, 20)} >= {1, 8, 9, 16, 17, 32, 33, 64, 65, 128, 129, 256}, op
+    for l in range(6):
+        P = 256 >> l
+        assert any(gather_tp_log2(p["C"]) == l and p["R"] > P and p["R"] % P for p in cases), (op, l)
+    assert any(p["B"] == 3 for p in cases) and any(p["g"] * p["C"] == 64 * 256 for p in cases), op      # gridDim.y; the LDS accumulators' maximum
+
+
+def test_probe_upsample_ce_every_geometry_lane_count_and_label_kind():
+    cases = _of("probe_upsample_ce")
+    _gather_geometry(cases, "probe_upsample_ce")
+    assert any((p["g"], p["R"], p["C"], p["B"]) == (64, 1024, 256, 1) and p["ignored"] == 0.99 for p in cases)      # gather_lds_bytes at its maximum
+    assert any((p["g"], p["R"], p["C"]) == (64, 1024, 2) for p in cases)
+    assert {p["kind"] for p in cases} == {"normal", "large", "const"} and {p["ignored"] for p in cases} >= {0.0, 0.3, 1.0, "rows"}
+    for kind in ("large", "const"):
+        assert len({gather_tp_log2(p["C"]) for p in cases if p["kind"] == kind and p["C"] > 1}) >= 4, kind
+    assert any(p["C"] == 1 and p["kind"] == k for p in cases for k in ("normal",)) and any(p["C"] == 1 and p["kind"] == "const" for p in cases)
+    assert any(p["C"] == 256 and p["ignored"] == 0.3 for p in cases)      # 255 among the labels of a 256-class head: ignored, and counted labels
+    assert any(p["ignored"] == "rows" and p["R"] >= 4 * p["g"] for p in cases)      # low-res rows whose every mask row is ignored
+
+
+def test_bilinear_adjoint_every_geometry_and_lane_count():
+    cases = _of("bilinear_adjoint")
+    _gather_geometry(cases, "bilinear_adjoint")
+    assert all(p["B"] * p["R"] ** 2 * p["C"] <= 1 << 22 for p in cases)      # d_hi stays small: the big masks at small C only
+    assert any(adjoint_run(p["g"], p["R"]) >= ADJOINT_LONG_RUN for p in cases) and sum(adjoint_run(p["g"], p["R"]) >= ADJOINT_LONG_RUN for p in cases) <= 3
+
+
+def test_probe_wgrad_every_split_regime():
+    cases = _of("probe_wgrad")
+    # linear_probe.hip, wgrad_split (restated in tests/_sweep_cases.py): ns = min(ceil(1024 / tiles), ceil(rows / 32)), at least 1;
+    # rows per split = ceil(rows / ns) rounded up to 32; splits = ceil(rows / rows per split)
+    assert wgrad_split(47040, 384, 21) == (164, 288, "tiles") and wgrad_split(33, 4, 256) == (2, 32, "chunks") and wgrad_split(32, 60, 63) == (1, 32, "one")
+    assert wgrad_split(600, 1024, 256) == (10, 64, "tiles") and wgrad_split(8192, 1024, 256) == (16, 512, "tiles")
+    seen = {}
+    for p in cases:
+        ns, rps, why = wgrad_split(p["rows"], p["D"], p["C"])
+        assert ns >= 1 and (ns - 1) * rps < p["rows"] <= ns * rps and rps % 32 == 0, p      # every split has rows; none is left over
+        seen.setdefault(why, []).append((p, ns, rps))
+    assert set(seen) == {"one", "chunks", "tiles"}
+    assert all(ns == 1 for _, ns, _ in seen["one"]) and any(p["rows"] == 32 for p, _, _ in seen["one"]) and any(p["rows"] == 1 for p, _, _ in seen["one"])
+    for why in ("chunks", "tiles"):      # a short last split and a whole one... in each capped regime a last split shorter than the others
+        assert any(p["rows"] % rps for p, _, rps in seen[why]), why
+    assert any(p["rows"] % rps == 0 and ns > 1 for p, ns, rps in seen["tiles"])
+    assert any(p["rows"] == 33 for p, _, _ in seen["chunks"]) and any((p["rows"], p["D"], p["C"]) == (47040, 384, 21) for p, _, _ in seen["tiles"])
+    tiles = lambda p: ((p["D"] + 63) // 64) * ((p["C"] + 63) // 64)
+    assert any(tiles(p) == 64 for p, _, _ in seen["tiles"]) and any(tiles(p) == 1 for p in cases)
+    assert any(rps >= WGRAD_LONG_RUN for _, _, rps in seen["tiles"]) and sum(wgrad_split(p["rows"], p["D"], p["C"])[1] >= WGRAD_LONG_RUN for p in cases) <= 2
+    assert {p["C"] for p in cases} >= {1, 63, 65, 256} and {p["D"] for p in cases} >= {4, 60, 68, 1024}
+    assert {(bool(p["scale"]), p["need_bias"]) for p in cases} == {(False, 0), (False, 1), (True, 0), (True, 1)}
+
+
+def test_sgd_tables_chunks_and_grids():
+    cases = _of("sgd")
+    assert {p["T"] for p in cases} >= {1, 40, 41, 85} and {min(2, (p["T"] - 1) // 40) for p in cases} == {0, 1, 2}      # hip_ops.sgd_step_: chunks of 40
+    assert {(bool(p["momentum"]), bool(p["wd"])) for p in cases} == {(False, False), (False, True), (True, False), (True, True)}
+    assert any(p["steps"] == 3 for p in cases) and all(p["steps"] >= 1 for p in cases)
+    # linear_probe.hip, tt_sgd_step: the grid is sized by the LONGEST tensor, at most 1024 workgroups of 256; a length-1 tensor rides along
+    grid = lambda p: (max(sgd_lengths(p["T"], p["big"])) + 255) // 256
+    assert any(grid(p) > 1024 and sgd_lengths(p["T"], p["big"])[0] == 1 for p in cases) and any(grid(p) == 1024 for p in cases)
+    assert any(grid(p) < 1024 for p in cases) and any(grid(p) == 1 for p in cases)
+    assert {p["big"] for p in cases} >= {262145, 300001} and any({1, 255, 257} <= set(sgd_lengths(p["T"], p["big"])) for p in cases)
+
+
+def test_clip_pipeline_edges():
+    rs = _of("img_resize")
+    dims = lambda p: tuple(int(v) for v in p["crop"].split("/")) if p["crop"] else (0, 0, p["h"], p["w"])
+    shapes = {(dims(p)[2], dims(p)[3], p["oh"], p["ow"]) for p in rs}
+    assert shapes >= {(1, 1, 5, 3), (7, 1, 3, 4), (1, 9, 4, 2), (1000, 3, 1, 3), (3, 1000, 3, 1)}
+    # timetuning_amd.video_transformations.resized_crop: the horizontal pass is skipped at OW = w, the vertical one at OH = h on uint8 output
+    for tt in (0, 1):
+        sel = [p for p in rs if p["to_tensor"] == tt]
+        assert any(dims(p)[3] == p["ow"] and dims(p)[2] != p["oh"] for p in sel) and any(dims(p)[2] == p["oh"] and dims(p)[3] != p["ow"] for p in sel), tt
+        assert any(dims(p)[2:] == (p["oh"], p["ow"]) for p in sel) and any(p["crop"] for p in sel) and any(p["F"] == 300 for p in sel), tt
+    crops = [p for p in rs if p["crop"]]
+    assert any(dims(p)[0] + dims(p)[2] == p["h"] and dims(p)[1] + dims(p)[3] == p["w"] and dims(p)[0] and dims(p)[1] for p in crops)
+    assert any(dims(p)[2:] == (1, 1) and dims(p)[:2] == (p["h"] - 1, p["w"] - 1) for p in crops) and any(dims(p) == (0, 0, 1, 1) for p in crops)
+    assert any(p["crop"] and dims(p)[3] == p["ow"] and (dims(p)[1] or dims(p)[3] != p["w"]) for p in crops)      # the column slice instead of a pass
+    assert {p["ow"] % 2 for p in rs if p["flip"]} == {0, 1} and all(p["to_tensor"] for p in rs if p["flip"])
+    col = _of("img_color")
+    assert {p["mode"] for p in col if p["H"] * p["W"] == 1} == set(IMG_MODES)
+    # image_ops.hip, tt_img_color: gray_sum_kernel on min(256, ceil(npix / 2048)) workgroups - the grid-stride loop runs above 524 288 pixels
+    con = [p for p in col if p["mode"] == "contrast"]
+    assert GRAY_SUM_CAP == 524288 and any(p["H"] * p["W"] == GRAY_SUM_CAP for p in con) and any(p["H"] * p["W"] > GRAY_SUM_CAP for p in con)
+    assert any(p["H"] * p["W"] == 600 * 1024 for p in con) and any(p["F"] == 5 for p in con) and any(p["F"] > 256 for p in con)
+    for mode in ("brightness", "contrast", "saturation"):
+        assert {p["factor"] for p in col if p["mode"] == mode} >= ({0.0, 0.9999, 1.0, 1.8} if mode != "brightness" else {0.0, 0.9999, 1.8}), mode
+    assert {p["factor"] for p in col if p["mode"] == "hue"} >= {-0.5, 0.5} and any(p["mode"] == "hue" and p["F"] >= 2 for p in col)      # (a gray frame)
+    bl = _of("img_blur")
+    from timetuning_amd.video_transformations import gaussian_box_params
+
+    assert gaussian_box_params(2.0)[0] == 1 and gaussian_box_params(0.1)[0] == 0      # box radius 1: the far taps sit at +-2
+    for side in ("H", "W"):
+        assert {p[side] for p in bl if p["radius"] == 2.0} >= {1, 2, 3}, side
+    assert {(p["H"], p["W"]) for p in bl} >= {(1, 53), (37, 1)} and {p["radius"] for p in bl} >= {0.1, 2.0} and any(p["F"] > 256 for p in bl)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Randomised shape fuzz of the HIP ops against torch fp64 / the oracle (development aid; run on the GPU box).
 Each round draws one case per op from the generator of the suite's sweep (tests/_sweep_cases.py) and checks it with the sweep's own
-checks and bounds (tests/test_hip_sweep.py::run_case): more seeds of that sweep, all three tiers - the kernels of the training step, the
-evaluator / optimizer / mask kernels (tests/_sweep_checks_eval.py) and label propagation on square and rectangular grids with its
-up-sampler (tests/_sweep_checks_prop.py: one-frame fp64 reference).  Then the ops the sweep does not cover.
+checks and bounds (tests/test_hip_sweep.py::run_case): more seeds of that sweep, all four tiers - the kernels of the training step, the
+evaluator / optimizer / mask kernels (tests/_sweep_checks_eval.py), label propagation on square and rectangular grids with its
+up-sampler (tests/_sweep_checks_prop.py: one-frame fp64 reference) and the linear probe with the clip input pipeline
+(tests/_sweep_checks_head.py).  Then the ops the sweep does not cover.
 usage: fuzz_ops.py [rounds=40] [seed=0]"""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
