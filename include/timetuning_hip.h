@@ -458,6 +458,48 @@ int tt_confusion_segments_route(int Cg, int Cp);
 int tt_confusion_counts_segments(const void* pred, int pred_dtype, const int64_t* gt, int S, long long n, int Cg, int Cp, long long ignore_gt,
                                  int has_ignore, unsigned long long* counts, tt_stream_t stream);
 
+/* ---- N17: overlay rendering and the prototype histogram - the qualitative side (time_tuning.py:305-457, evaluation.py:255-300).
+ *   tt_overlay_grid   renders ALL F frames of a batch in one launch as out uint8 [F, 3, H + 2 pad, n W + (n + 1) pad]:
+ *                     torchvision.utils.make_grid's layout for n tiles in one row (pad value 0, tile t at column t (W + pad) + pad, row
+ *                     pad), which the reference fills on the host frame by frame (time_tuning.py:332-341 make_overlayed_grid, :305-319
+ *                     localize_objects; evaluation.py:271-272,288,293 through my_utils.localize_objects, my_utils.py:41-65).
+ *                       TT_OVERLAY_PHOTO   n = 2: [base | blend(base, colour(A))], frames float32 [F, 3, H, W];
+ *                                          base_c = (uint8) clamp(trunc((x_c * std_c + mean_c) * 255), 0, 255), NaN -> 0 - three rounded
+ *                                          fp32 operations, my_utils.denormalize (my_utils.py:68-70) and (img * 255).type(torch.uint8).
+ *                                          mean3 / std3: HOST pointers to 3 floats, NULL = 0 / 1 (frames already in [0, 1]).
+ *                       TT_OVERLAY_LABELS  n = 3: [colour(B) | colour(A) | blend(colour(B), colour(A))], B the ground truth, A the
+ *                                          prediction; frames is not read.
+ *                     colour(v) = palette[idx mod P] (palette uint8 [P, 3]; a true modulo, negative indices wrap) with
+ *                     idx = lut[f * lut_stride + v] for labels_a where lut (int32) is given - lut_stride 0 = one table of lut_len entries
+ *                     for all frames, else lut_stride >= lut_len; a v outside [0, lut_len) gives idx 0 - and idx = v otherwise.  The
+ *                     LUT is a matching's pred value -> gt value table: labels_b, the ground truth, is never mapped.
+ *                     blend = (uint8) trunc(fl(fl(a (1 - alpha)) + fl(b alpha))), three rounded fp32 operations without contraction:
+ *                     draw_segmentation_masks' img * (1 - alpha) + colour * alpha and .to(uint8) with every pixel masked.  alpha is a
+ *                     double: (float)alpha and (float)(1.0 - alpha) are what the kernel multiplies by, as torch rounds a Python scalar.
+ *                     labels_a / labels_b [F, Hl, Wl] of label_dtype TT_LABELS_U8 / _I16 / _I64; where (Hl, Wl) != (H, W) they are read
+ *                     through the DEVICE tables ytab int32 [H] (entries in [0, Hl)) and xtab int32 [W] (in [0, Wl)), which the kernel
+ *                     does not check (timetuning_amd.hip_ops.overlay_grid checks the host copies); both NULL = maps of the frames' size.
+ *                     A thread owns one 16-byte-aligned piece of an output row (tt_img_gather_nearest's idiom) and writes the padding
+ *                     too; offsets are 64-bit; no LDS, no atomics, no workspace.
+ *                     Refused with TT_EINVAL, nothing launched: null out / labels_a / palette (frames in the photo mode, labels_b in the
+ *                     labels mode), an unknown mode or dtype code, F, H, W, Hl, Wl <= 0, P <= 0, pad < 0, one table without the other or
+ *                     none with (Hl, Wl) != (H, W), a lut with lut_len <= 0 or 0 < lut_stride < lut_len, alpha outside [0, 1], an output
+ *                     row (or row count) of more than 2^31 - 1 bytes, a misaligned frames / labels pointer.
+ *   tt_upsample_argmax_hist_f32   maps [M, g * g, K] fp32 -> counts[k] += the number of the M * R * R output pixels whose bilinear arg-max
+ *                     is k: the histogram of tt_upsample_argmax_f32's labels without the labels (time_tuning.py:354-375
+ *                     get_similarity_histogram: proto_clustering's [N, 224, 224] map on the host, then torch.histc).  Per pixel the
+ *                     statement of tt_upsample_argmax_f32 (same fp32 expressions, first maximum).  counts uint64 [K] is ADDED to: the
+ *                     caller zeroes it, and a loop over batches adds up.  A u32 histogram per workgroup in LDS, 64-bit integer atomics
+ *                     for its non-zero bins: exact, independent of order and grid.  Refused with TT_EINVAL: null pointers, M, g, K, R
+ *                     <= 0, K > 16384 (the LDS limit of tt_confusion_counts_segments), M > 65535, g or R > 32768, counts misaligned. */
+#define TT_LABELS_U8 2        /* with TT_LABELS_I16 / TT_LABELS_I64 above; tt_overlay_grid only */
+#define TT_OVERLAY_PHOTO 0
+#define TT_OVERLAY_LABELS 1
+int tt_overlay_grid(unsigned char* out, int mode, const float* frames, const float* mean3, const float* std3, const void* labels_a,
+                    const void* labels_b, int label_dtype, int Hl, int Wl, const int* ytab, const int* xtab, const int* lut, int lut_len,
+                    int lut_stride, const unsigned char* palette, int P, double alpha, int F, int H, int W, int pad, tt_stream_t stream);
+int tt_upsample_argmax_hist_f32(const float* maps, unsigned long long* counts, int M, int g, int K, int R, tt_stream_t stream);
+
 /* ---- N9: the evaluation propagation on RECTANGULAR token grids (frames at native size, e.g. 480 x 848 -> 30 x 53 tokens at patch 16)
  *   tt_label_propagate_grid_maps  tt_label_propagate_maps on a gh x gw grid (n = gh * gw, row-major tokens): xn [fs, bs, n, D], seg0
  *                                 [bs, n, K], pmap_all [fs-1, bs, n, K] fp64.  The window is restrict_neighborhood(gh, gw, radius)

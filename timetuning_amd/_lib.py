@@ -175,6 +175,9 @@ SIGNATURES = {
     "tt_confusion_counts": (c_i, [c_vp, c_vp, c_ll, c_i, c_vp, c_vp]),
     "tt_confusion_segments_route": (c_i, [c_i, c_i]),
     "tt_confusion_counts_segments": (c_i, [c_vp, c_i, c_vp, c_i, c_ll, c_i, c_i, c_ll, c_i, c_vp, c_vp]),
+    "tt_overlay_grid": (c_i, [c_vp, c_i, c_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_i, c_i, c_vp,
+                              c_i, c_d, c_i, c_i, c_i, c_i, c_vp]),
+    "tt_upsample_argmax_hist_f32": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
     "tt_label_propagate_grid_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
     "tt_label_propagate_grid_maps": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp, c_sz, c_vp]),
     "tt_upsample_argmax_hw": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp]),

@@ -373,14 +373,20 @@ def cluster_features(features, num_clusters, feature_resolution, input_resolutio
 
 
 @torch.no_grad()
+def proto_scores(x, prototypes):
+    """The cosine scores ``proto_clustering`` up-samples: x [samples, num_patch, dim], prototypes [k, dim] -> fp32 [samples, num_patch, k]."""
+    sample_num, num_patches, dim = x.shape
+    xn = ops.l2norm_fwd(x.reshape(sample_num * num_patches, dim).contiguous().float())
+    pn = ops.l2norm_fwd(prototypes.detach().contiguous().float())
+    return ops.linear_fwd(xn, pn).view(sample_num, num_patches, -1)
+
+
+@torch.no_grad()
 def proto_clustering(x, prototypes, input_size=14, output_size=224, num_classes=None):
     """``clustering.proto_clustering``: x [samples, num_patch, dim], prototypes [k, dim] -> assignments [samples, R, R]
     (upsampled cosine scores, arg-max; with ``num_classes`` the prototypes are first merged by k-means)."""
     sample_num, num_patches, dim = x.shape
-    xn = ops.l2norm_fwd(x.reshape(sample_num * num_patches, dim).contiguous().float())
-    pn = ops.l2norm_fwd(prototypes.detach().contiguous().float())
-    scores = ops.linear_fwd(xn, pn).view(sample_num, num_patches, -1)
-    assign = ops.upsample_argmax_f32(scores, output_size)
+    assign = ops.upsample_argmax_f32(proto_scores(x, prototypes), output_size)
     if num_classes is not None:
         km = Kmeans(prototypes.shape[1], num_classes, niter=50, nredo=5, seed=1)
         km.train(prototypes.detach().float())

@@ -1,6 +1,7 @@
 """Evaluator with the reference's surface (``evaluation.py:250-310,312-486``): features without head -> clustering ->
-matched mIoU, for the three protocols (frame-wise / sample-wise / dataset-wise).  Dataset readers, video / GIF logging and
-the wandb plumbing are out of scope; the loader is any iterable of ``(data, annotations[, label])`` batches.
+matched mIoU, for the three protocols (frame-wise / sample-wise / dataset-wise), with the GIF logs of the matched maps
+(``evaluation.py:255-300``) on ``visualization``'s render launch.  Dataset readers and the wandb plumbing are out of scope; the
+loader is any iterable of ``(data, annotations[, label])`` batches.
 ``evaluate_localizations`` scores a whole batch from one segmented confusion-count launch (``PredsmIoU.compute_segments``);
 ``evaluate_propagation`` is the reference's (``evaluation.py:228-246``).
 
@@ -14,6 +15,7 @@ the LDS-resident ones hold, so the over-clustering protocol (``--num_clusters 50
 from __future__ import annotations
 
 import argparse
+import os
 
 import numpy as np
 import torch
@@ -40,12 +42,19 @@ def evaluate_propagation(PredsEval, gts, preds):
     return np.array(scores).mean()
 
 
-def evaluate_localizations(PredsEval, gts, preds, evaluation_protocol, logging_directory=None, many_to_one=False, precision_based=False):
+def evaluate_localizations(PredsEval, gts, preds, evaluation_protocol, logging_directory=None, many_to_one=False, precision_based=False,
+                           first_clip=0):
     """gts / preds [bs, fs, R, R] -> mean score (``evaluation.py:250-310``).  Every ``PredsmIoU.compute`` of the reference's loops - one
     per frame (frame-wise), per clip (sample-wise) or for everything but Pascal VOC's ignore label 255 (dataset-wise, :304-305) - is one
-    segment of a single ``PredsmIoU.compute_segments`` call: one counting launch and one read-back per protocol call."""
-    if logging_directory is not None:
-        raise NotImplementedError("video logging of the matched maps is not part of this build")
+    segment of a single ``PredsmIoU.compute_segments`` call: one counting launch and one read-back per protocol call.
+
+    ``logging_directory`` (``evaluation.py:255-300``): frame-wise and sample-wise write two GIFs per clip into
+    ``{logging_directory}/{protocol}/`` under the reference's names - "Reordered" shows the predictions through the matching (per frame
+    for frame-wise, per clip for sample-wise), "Inorder" as they are - at 80 ms per frame; dataset-wise writes nothing, as in the
+    reference.  A frame is ``visualization.label_panels``' ``[ground truth | prediction | both]`` (the reference's matplotlib figure
+    is not restated); all frames of the call are rendered by one launch per GIF kind.  The score is the one returned without a
+    directory.  ``first_clip`` numbers the clips from there and keeps the GIFs already in the directory (0 clears them, as
+    ``my_utils.make_working_directory`` does)."""
     bs, fs = preds.shape[:2]
     if evaluation_protocol == "frame-wise":
         segments, ignore_gt = bs * fs, None
@@ -55,20 +64,55 @@ def evaluate_localizations(PredsEval, gts, preds, evaluation_protocol, logging_d
         segments, ignore_gt = 1, 255
     else:
         raise ValueError(f"unknown evaluation protocol {evaluation_protocol!r}")
-    results = PredsEval.compute_segments(gts.reshape(segments, -1), preds.reshape(segments, -1), many_to_one, precision_based, ignore_gt)
+    log = logging_directory is not None and evaluation_protocol != "dataset-wise"
+    results = PredsEval.compute_segments(gts.reshape(segments, -1), preds.reshape(segments, -1), many_to_one, precision_based, ignore_gt,
+                                         with_mapping=log)
     PredsEval.reset()
     scores = [r[0] for r in results]
+    if log:
+        _log_matched_maps(gts, preds, results, evaluation_protocol, logging_directory, first_clip)
     return sum(scores) / len(scores)
+
+
+def _log_matched_maps(gts, preds, results, evaluation_protocol, logging_directory, first_clip):
+    """The GIFs of ``evaluation.py:255-300`` for one scored batch; ``results`` are ``compute_segments(..., with_mapping=True)``'s."""
+    from . import visualization as V
+
+    bs, fs, h, w = preds.shape
+    sub_directory = logging_directory + "/" + evaluation_protocol
+    if first_clip == 0:
+        V.make_working_directory(sub_directory)
+    else:
+        os.makedirs(sub_directory, exist_ok=True)
+    per_clip = len(results) // bs                                  # fs segments per clip (frame-wise) or one (sample-wise)
+    length = max(int(r[4].numel()) for r in results)
+    lut = torch.zeros((len(results), length), dtype=torch.int64)  # rows padded with 0, the value of an unmapped prediction
+    for s, r in enumerate(results):
+        lut[s, : r[4].numel()] = r[4]
+    lut = lut.repeat_interleave(fs // per_clip, dim=0)              # one row per frame
+    g, p = gts.reshape(bs * fs, h, w), preds.reshape(bs * fs, h, w)
+    reordered = V.grids_to_frames(V.label_panels(g, p, lut))
+    inorder = V.grids_to_frames(V.label_panels(g, p))
+    sep = ":" if evaluation_protocol == "frame-wise" else "-"      # evaluation.py:277-278 against :299-300
+    for i in range(bs):
+        clip_score = [r[0] for r in results[i * per_clip:(i + 1) * per_clip]]
+        stem = f"Score{sep}{sum(clip_score) / len(clip_score)}_Evaluation_{evaluation_protocol}_"
+        V.convert_list_to_video(reordered[i * fs:(i + 1) * fs], f"{stem}Reordered_{first_clip + i}", speed=80, directory=sub_directory + "/")
+        V.convert_list_to_video(inorder[i * fs:(i + 1) * fs], f"{stem}Inorder_{first_clip + i}", speed=80, directory=sub_directory + "/")
 
 
 class Evaluator:
     """``Evaluator(model, data_loader, num_prototypes, device, logger, clustering_algorithm)`` (``evaluation.py:312-371``) reduced
     to what ``evaluate`` needs.  ``fg_masks`` ([N, R', R'] or [N, 1, R', R'], one per frame of the loader in order): the reference's
-    foreground masks for ``evaluate(use_mask=True)`` (``evaluation.py:325,340``)."""
+    foreground masks for ``evaluate(use_mask=True)`` (``evaluation.py:325,340``).  ``logging_directory`` (None = no GIFs) is handed to
+    ``evaluate_localizations`` for the frame-wise and sample-wise protocols; the clips are numbered over the WHOLE loader.  The reference
+    restarts ``i`` at every batch (``evaluation.py:261,280``) and clears the directory per call (:259), so there only the last batch's
+    GIFs survive; here the directory is cleared at the loader's first batch."""
 
     def __init__(self, model, data_loader, num_prototypes=21, device="cuda", logger=None, clustering_algorithm="k-means", uvos_flag=False,
-                 involve_bg=False, fg_masks=None):
+                 involve_bg=False, fg_masks=None, logging_directory=None):
         self.model, self.data_loader, self.device = model, data_loader, device
+        self.logging_directory = logging_directory
         self.clustering_algorithm = clustering_algorithm
         self.uvos_flag = uvos_flag
         self.PredsEval = PredsmIoU(num_prototypes, num_prototypes, involve_bg=involve_bg)
@@ -135,7 +179,7 @@ class Evaluator:
             annotations = F.interpolate(annotations.double(), size=(eval_resolution, eval_resolution), mode="nearest").long().to(self.device)
             maps = self._cluster(features, g, eval_resolution, evaluation_protocol, num_clusters, annotations if use_annotations else None)
             return evaluate_localizations(self.PredsEval, annotations, maps, evaluation_protocol, None, many_to_one, precision_based)
-        scores = []
+        scores, first_clip = [], 0
         for batch in self.data_loader:
             data, annotations = batch[0].squeeze(1), batch[1].squeeze(1).long()
             features, g = self._attention_masked(data) if use_mask else self._features(data)
@@ -143,7 +187,9 @@ class Evaluator:
                 annotations = (annotations > 0).long()
             annotations = F.interpolate(annotations.double(), size=(eval_resolution, eval_resolution), mode="nearest").long().to(self.device)
             maps = self._cluster(features, g, eval_resolution, evaluation_protocol, num_clusters, annotations if use_annotations else None)
-            scores.append(evaluate_localizations(self.PredsEval, annotations, maps, evaluation_protocol, None, many_to_one, precision_based))
+            scores.append(evaluate_localizations(self.PredsEval, annotations, maps, evaluation_protocol, self.logging_directory, many_to_one,
+                                                 precision_based, first_clip=first_clip))
+            first_clip += data.shape[0]
         return sum(scores) / len(scores)
 
 
@@ -154,8 +200,10 @@ class Evaluator:
 def build_parser() -> argparse.ArgumentParser:
     """Flag names, types and defaults of ``evaluation.py:544-566``.  The ``type=bool`` flags treat ANY non-empty string as True, as in
     the reference (and in ``time_tuning.build_parser``): ``--many_to_one False`` turns many-to-one matching ON.  ``--dataset_path``,
-    ``--destination_path``, ``--num_workers`` and ``--logging_directory`` are parsed and unused (the dataset readers and the video
-    logging are out of scope).  Added: ``--dataset synthetic`` and ``--eval_clips``; an EMPTY ``--model_path`` selects synthetic weights."""
+    ``--destination_path`` and ``--num_workers`` are parsed and unused (the dataset readers are out of scope).  Added: ``--dataset
+    synthetic`` and ``--eval_clips``; an EMPTY ``--model_path`` selects synthetic weights; ``--log_videos`` (off by default: an evaluation
+    writes no file unless asked) makes ``--logging_directory`` live - the frame-wise and sample-wise protocols then write the GIFs of the
+    matched maps there (``evaluate_localizations``)."""
     p = argparse.ArgumentParser()
     p.add_argument("--architecture", type=str, default="dino-s16", help="which back-bone architecture do you want to use?")
     p.add_argument("--model_path", type=str, default="/home/ssalehi/video/vos_pretrained/cyclic_swav/src/leopart_vits16.ckpt")
@@ -175,6 +223,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--use_teacher", type=bool, default=False)
     p.add_argument("--EMA_decay", type=float, default=0.999)
     p.add_argument("--eval_clips", type=int, default=8, help="synthetic evaluation set size")
+    p.add_argument("--log_videos", action="store_true", help="write the matched-map GIFs into --logging_directory (frame-wise / sample-wise)")
     return p
 
 
@@ -198,7 +247,12 @@ def main(argv=None, vit_cfg=None) -> float:
     model = model.to(device)
     loader = SyntheticEvalClips(args.eval_clips, args.num_frames, args.input_resolution, args.batch_size, device)
     eval_resolution = 112 if args.evaluation_protocol == "dataset-wise" else args.input_resolution   # :536
-    evaluator = Evaluator(model, loader, 10, device, clustering_algorithm="k-means", uvos_flag=bool(args.uvos), involve_bg=True)  # :364,539
+    logging_directory = None
+    if args.log_videos:
+        logging_directory = args.logging_directory
+        os.makedirs(logging_directory, exist_ok=True)
+    evaluator = Evaluator(model, loader, 10, device, clustering_algorithm="k-means", uvos_flag=bool(args.uvos), involve_bg=True,
+                          logging_directory=logging_directory)                                                        # :364,539
     score = float(evaluator.evaluate(many_to_one=args.many_to_one, evaluation_protocol=args.evaluation_protocol,
                                      eval_resolution=eval_resolution, num_clusters=args.num_clusters, use_annotations=False,
                                      use_mask=False, precision_based=args.precision_based))

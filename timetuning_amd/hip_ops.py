@@ -981,6 +981,109 @@ def upsample_argmax_f32(maps, resolution: int):
     return out
 
 
+def upsample_argmax_hist(maps, resolution: int, counts=None):
+    """maps [M, n, K] fp32 -> int64 [K]: how many of the M * R * R pixels ``upsample_argmax_f32(maps, R)`` labels k, without the
+    labels (one launch, integer atomics: exact).  ``counts`` (int64 [K] on the device) is ADDED to and returned; None starts from zero."""
+    lib = _lib.load()
+    _chk(maps, "maps")
+    M, n, K = maps.shape
+    g = int(round(n ** 0.5))
+    if g * g != n:
+        raise ValueError(f"maps: {n} tokens are not a square grid")
+    if counts is None:
+        counts = torch.zeros(K, dtype=torch.int64, device=maps.device)
+    _chk(counts, "counts", torch.int64)
+    if tuple(counts.shape) != (K,):
+        raise ValueError(f"counts: expected int64 [{K}], got {tuple(counts.shape)}")
+    _lib.check(lib.tt_upsample_argmax_hist_f32(_p(maps), _p(counts), M, g, K, int(resolution), _stream()), "tt_upsample_argmax_hist_f32")
+    return counts
+
+
+# ---- overlay rendering (N17) ---------------------------------------------------------------------------------------------
+
+OVERLAY_PHOTO, OVERLAY_LABELS = 0, 1                                       # TT_OVERLAY_PHOTO / TT_OVERLAY_LABELS
+_OVERLAY_LABEL_CODES = {torch.int16: 0, torch.int64: 1, torch.uint8: 2}    # TT_LABELS_I16 / _I64 / _U8
+
+
+def overlay_grid(mode: int, labels_a, palette, frames=None, labels_b=None, size=None, ytab=None, xtab=None, lut=None, alpha: float = 0.5,
+                 pad: int = 2, mean=None, std=None):
+    """One launch renders every frame of a batch as uint8 [F, 3, H + 2 pad, n W + (n + 1) pad] (``make_grid``'s layout, pad value 0).
+
+    ``OVERLAY_PHOTO``  (n = 2): ``[base | blend(base, colour(labels_a))]`` with ``frames`` float32 [F, 3, H, W] and
+    ``base = uint8(clamp(trunc((x * std + mean) * 255), 0, 255))`` (``mean`` / ``std``: 3 numbers each, None = 0 / 1).
+    ``OVERLAY_LABELS`` (n = 3): ``[colour(labels_b) | colour(labels_a) | blend(colour(labels_b), colour(labels_a))]``, (H, W) = ``size``
+    or the maps' own.
+
+    ``labels_*`` [F, Hl, Wl] uint8 / int16 / int64 (one dtype); where (Hl, Wl) != (H, W) the HOST index tables ``ytab`` [H] / ``xtab`` [W]
+    say which map row / column a pixel reads (checked here).  ``palette`` uint8 [P, 3]; ``colour(v) = palette[idx mod P]`` with
+    ``idx = lut[v]`` (``lut`` [L]) or ``lut[f, v]`` ([F, L]) for ``labels_a`` where a LUT is given (a v outside [0, L) gives 0), else
+    ``idx = v``; ``labels_b``, the ground truth, is never mapped.
+    ``blend = uint8(a * (1 - alpha) + b * alpha)`` in three rounded fp32 operations."""
+    import ctypes as C
+
+    lib = _lib.load()
+    if labels_a.dtype not in _OVERLAY_LABEL_CODES:
+        raise TypeError(f"labels_a: expected torch.uint8, torch.int16 or torch.int64, got {labels_a.dtype}")
+    _chk(labels_a, "labels_a", labels_a.dtype)
+    if labels_a.dim() != 3:
+        raise ValueError(f"labels_a: expected [F, Hl, Wl], got {tuple(labels_a.shape)}")
+    Fr, Hl, Wl = labels_a.shape
+    dev = labels_a.device
+    if labels_b is not None:
+        _chk(labels_b, "labels_b", labels_a.dtype)
+        if labels_b.shape != labels_a.shape:
+            raise ValueError(f"labels_b {tuple(labels_b.shape)} and labels_a {tuple(labels_a.shape)} need one shape")
+    if mode == OVERLAY_PHOTO:
+        if frames is None:
+            raise ValueError("overlay_grid: the photo mode needs the frames")
+        _chk(frames, "frames")
+        if frames.dim() != 4 or frames.shape[0] != Fr or frames.shape[1] != 3:
+            raise ValueError(f"frames: expected [{Fr}, 3, H, W], got {tuple(frames.shape)}")
+        H, W = frames.shape[2:]
+    elif mode == OVERLAY_LABELS:
+        if labels_b is None:
+            raise ValueError("overlay_grid: the labels mode needs labels_b (the ground truth)")
+        H, W = (Hl, Wl) if size is None else (int(size[0]), int(size[1]))
+        frames = None
+    else:
+        raise ValueError(f"overlay_grid: unknown mode {mode!r}")
+    if H <= 0 or W <= 0 or Fr <= 0:
+        raise ValueError(f"overlay_grid: {Fr} frames of {H} x {W}")
+    yt = xt = None
+    if (ytab is None) != (xtab is None):
+        raise ValueError("overlay_grid: ytab and xtab come together")
+    if ytab is not None:
+        yt, xt = _index_table_on(ytab, Hl, dev, "ytab"), _index_table_on(xtab, Wl, dev, "xtab")
+        if yt.numel() != H or xt.numel() != W:
+            raise ValueError(f"overlay_grid: tables of {yt.numel()} rows and {xt.numel()} columns for frames of {H} x {W}")
+    elif (Hl, Wl) != (H, W):
+        raise ValueError(f"overlay_grid: label maps of {Hl} x {Wl} under frames of {H} x {W} need ytab and xtab")
+    pal = torch.as_tensor(palette)
+    if pal.dtype != torch.uint8 or pal.dim() != 2 or pal.shape[1] != 3 or pal.shape[0] < 1:
+        raise ValueError(f"palette: expected uint8 [P, 3], got {pal.dtype} {tuple(pal.shape)}")
+    pal = pal.to(dev).contiguous()
+    lut_t, lut_len, lut_stride = None, 0, 0
+    if lut is not None:
+        lut_t = torch.as_tensor(lut)
+        if lut_t.dim() not in (1, 2) or lut_t.shape[-1] < 1 or (lut_t.dim() == 2 and lut_t.shape[0] != Fr) or lut_t.is_floating_point():
+            raise ValueError(f"lut: expected integers [L] or [{Fr}, L], got {lut_t.dtype} {tuple(lut_t.shape)}")
+        lut_t = lut_t.to(device=dev, dtype=torch.int32).contiguous()
+        lut_len = int(lut_t.shape[-1])
+        lut_stride = lut_len if lut_t.dim() == 2 else 0
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"overlay_grid: alpha = {alpha} outside [0, 1]")
+    if pad < 0:
+        raise ValueError(f"overlay_grid: pad = {pad}")
+    n = 2 if mode == OVERLAY_PHOTO else 3
+    out = torch.empty((Fr, 3, H + 2 * pad, n * W + (n + 1) * pad), dtype=torch.uint8, device=dev)
+    m3 = None if mean is None else (C.c_float * 3)(*[float(v) for v in mean])
+    s3 = None if std is None else (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(lib.tt_overlay_grid(_p(out), int(mode), _p(frames), m3, s3, _p(labels_a), _p(labels_b), _OVERLAY_LABEL_CODES[labels_a.dtype],
+                                   Hl, Wl, _p(yt), _p(xt), _p(lut_t), lut_len, lut_stride, _p(pal), int(pal.shape[0]), float(alpha), Fr, H, W,
+                                   int(pad), _stream()), "tt_overlay_grid")
+    return out
+
+
 def kmeans_shape_ok(d: int, k: int) -> bool:
     """Whether ``kmeans_assign`` and ``kmeans_accumulate`` take k centroids of d columns (one rule for both: tt_kmeans_shape_ok)."""
     return bool(_lib.load().tt_kmeans_shape_ok(int(d), int(k)))

@@ -56,10 +56,12 @@ class PredsmIoU(torch.nn.Module):
         return self.compute_miou_from_confusion(conf, gt_unique, pred_unique, pred, many_to_one, precision_based, linear_probe)
 
     def compute_segments(self, gt: torch.Tensor, pred: torch.Tensor, many_to_one: bool = False, precision_based: bool = False,
-                         ignore_gt=None) -> list:
+                         ignore_gt=None, *, with_mapping: bool = False) -> list:
         """``compute`` of S independent segments at once: gt, pred [S, n] -> a list of S ``compute`` tuples (score, tp, fp, fn, None,
-        matched background share), WITHOUT the reordered map.  ``ignore_gt``: elements whose ground truth has this value are left out
-        (Pascal VOC's 255).  One read-back of the two maxima sizes the matrices (any upper bound gives the same scores: the class sets are
+        matched background share), WITHOUT the reordered map; ``with_mapping=True`` puts the host int64 table ``pred value -> matched gt
+        value`` (unmapped values 0, as long as the segment's largest predicted value + 1) in slot 4 instead of None: ``table[pred]`` IS the
+        reordered map, and a renderer takes the table (``visualization.label_panels``).  ``ignore_gt``: elements whose ground truth has
+        this value are left out (Pascal VOC's 255).  One read-back of the two maxima sizes the matrices (any upper bound gives the same scores: the class sets are
         the non-empty rows and columns, as in ``_confusion``), one ``confusion_counts_segments`` call counts and one ``.cpu()`` brings
         every matrix to the host; what was stored with ``update`` is neither used nor changed."""
         gt = gt.long().cuda().contiguous()
@@ -77,7 +79,7 @@ class PredsmIoU(torch.nn.Module):
                 raise ValueError(f"compute_segments: segment {s} has no element to score")
             self.num_pred_classes, self.num_gt_classes = len(pred_unique), len(gt_unique)
             results.append(self.compute_miou_from_confusion(full[np.ix_(gt_unique, pred_unique)], gt_unique, pred_unique, None, many_to_one,
-                                                            precision_based))
+                                                            precision_based, with_mapping=with_mapping))
         return results
 
     def compute_propagation_score(self, is_global_zero: bool):
@@ -132,8 +134,9 @@ class PredsmIoU(torch.nn.Module):
         return tp / np.maximum(tp + fp + fn, 1e-8)
 
     def compute_miou_from_confusion(self, conf, gt_unique, pred_unique, pred=None, many_to_one=False, precision_based=False,
-                                    linear_probe=False):
-        """``compute_miou`` (:357-432) on the confusion matrix ``conf[gt index, pred index]``."""
+                                    linear_probe=False, with_mapping=False):
+        """``compute_miou`` (:357-432) on the confusion matrix ``conf[gt index, pred index]``.  ``with_mapping`` (without ``pred``): slot 4
+        is the table the reordered map is read through, int64 ``lut[pred value] = matched gt value`` (unmapped values 0)."""
         num_gt, num_pred = conf.shape
         mapping: Dict[int, int] = {}          # predicted VALUE -> ground-truth VALUE; unmapped predictions count as 0
         if linear_probe:
@@ -165,11 +168,11 @@ class PredsmIoU(torch.nn.Module):
             if len(jac) == 0:  # the found cluster is solely background (:426-427)
                 jac[0] = 0
         reordered = None
-        if pred is not None:
+        if pred is not None or with_mapping:
             lut = torch.zeros(int(pred_unique.max()) + 1, dtype=torch.int64)
             for p, g in mapping.items():
                 lut[p] = g
-            reordered = lut.to(pred.device)[pred]
+            reordered = lut if pred is None else lut.to(pred.device)[pred]
         return float(np.mean(np.array(list(jac.values())))), tp, fp, fn, reordered, matched_bg_clusters
 
     def _original_match(self, conf, precision_based=False) -> Dict[int, list]:

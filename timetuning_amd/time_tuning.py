@@ -23,6 +23,7 @@ from . import engine
 from . import hip_ops as ops
 from .models import DistributedDataParallelModel, FeatureExtractor
 from .my_utils import cosine_scheduler
+from .visualization import localize_clip, make_overlayed_grid  # noqa: F401  (time_tuning.py:322-341: the reference defines them here)
 
 world_size = 1  # module global, as in the reference (time_tuning.py:75,511-512)
 
@@ -910,6 +911,86 @@ class SwavOptimizer:
 # checkpoints (time_tuning.py:460-505)
 # ------------------------------------------------------------------------------------------------
 
+# ------------------------------------------------------------------------------------------------
+# qualitative logs (time_tuning.py:305-375,433-457)
+# ------------------------------------------------------------------------------------------------
+
+@torch.no_grad()
+def get_similarity_histogram(model, train_loader, mask_features=False, output_size=224):
+    """``time_tuning.get_similarity_histogram`` (time_tuning.py:354-375): how many pixels of ``proto_clustering``'s maps, over every
+    frame of the loader, are assigned to each prototype -> int64 [K] on the device.  The reference builds every [224, 224] map, moves
+    it through ``torch.histc`` and sums the histograms in float32, which stops being exact once a count passes 2^24 (335 frames of
+    224 x 224 can put that many pixels on one prototype); here ``ops.upsample_argmax_hist`` counts in integers and never writes a map.
+    The model is left in the mode it was in (the reference ends with ``model.train()``)."""
+    from .clustering import proto_scores
+    from .models import apply_attention_mask
+
+    was_training = model.training
+    model.eval()
+    fe = model.feature_extractor
+    device = model.prototypes.device
+    hist = torch.zeros(model.prototypes.shape[0], dtype=torch.int64, device=device)
+    for batch in train_loader:
+        data = batch[0]
+        if data.dim() == 6:
+            data = data.squeeze(1)
+        bs, fs, c, h, w = data.shape
+        features, attentions = model(data.to(device).view(bs * fs, c, h, w))
+        num_patches, dim = features.shape[-2:]
+        if mask_features:
+            if attentions is None:
+                raise ValueError("get_similarity_histogram(mask_features=True) needs the attention probabilities: build the FeatureExtractor "
+                                 "with return_attention=True")
+            features, _ = apply_attention_mask(features.view(bs, fs, num_patches, dim), attentions, fe.spatial_resolution)
+        ops.upsample_argmax_hist(proto_scores(features.reshape(bs * fs, num_patches, dim), model.prototypes), output_size, hist)
+    model.train(was_training)
+    return hist
+
+
+def assignment_entropy(assignment_histogram) -> float:
+    """``-(p * log(p + 1e-8)).mean()`` with ``p = hist / hist.sum()`` (time_tuning.py:436-437), in fp64.  A MEAN over the prototypes, not
+    the sum: log K / K for a uniform histogram, 0 when one prototype takes everything."""
+    h = torch.as_tensor(assignment_histogram).detach().double().flatten().cpu()
+    p = h / h.sum()
+    return float(-(p * torch.log(p + 1e-8)).mean())
+
+
+def log_assignment_histogram(model, num_clusters, eval_loader, use_mask, epoch_number, writer=None):
+    """``time_tuning.log_assignment_histogram`` (time_tuning.py:433-442) without the matplotlib bar figure: prints the entropy of the
+    assignment distribution and the number of prototypes no pixel is assigned to - the failure of over-clustering training that the
+    loss does not show - and, given a ``writer``, logs "Scores/entropy" as the reference does.  Returns (histogram, entropy)."""
+    hist = get_similarity_histogram(model, eval_loader, mask_features=use_mask)
+    entropy = assignment_entropy(hist)
+    unassigned = int((hist == 0).sum())
+    print("Epoch: {} Scores/entropy {:.6f} unassigned prototypes {}/{}".format(epoch_number, entropy, unassigned, num_clusters))
+    if writer is not None:
+        writer.add_scalar("Scores/entropy", entropy, global_step=epoch_number)
+        writer.add_scalar("Scores/unassigned_prototypes", unassigned, global_step=epoch_number)
+    return hist, entropy
+
+
+@torch.no_grad()
+def log_clip_localization(model, eval_data, use_mask, evaluation_protocol, logging_directory, epoch_number, input_resolution):
+    """``time_tuning.log_clip_localization`` (time_tuning.py:445-457): the batch's headless features clustered into 200 clusters
+    ("dataset-wise": one k-means over the batch, whatever ``evaluation_protocol`` says - as in the reference), one overlay GIF per
+    clip as ``{logging_directory}/{epoch_number}_{i}.gif``.  ``eval_data`` [bs, fs, 3, H, W] is normalised; the renderer denormalises
+    it with the reference's mean and std (time_tuning.py:457).  The tensorboard figures (:456) are not built.  Returns the paths."""
+    from . import visualization as V
+    from .clustering import cluster_features
+    from .models import apply_attention_mask
+
+    bs, fs, c, h, w = eval_data.shape
+    fe = model.feature_extractor
+    features, attentions = model(eval_data.to(model.prototypes.device).view(bs * fs, c, h, w), use_head=False)
+    num_patches, dim = features.shape[-2:]
+    features = features.view(bs, fs, num_patches, dim)
+    if use_mask:
+        features, _ = apply_attention_mask(features, attentions, fe.spatial_resolution)
+    assignments = cluster_features(features, 200, fe.spatial_resolution, input_resolution, "dataset-wise")
+    os.makedirs(logging_directory, exist_ok=True)
+    return V.localize_clip(eval_data, assignments, logging_directory, str(epoch_number), mean=V.MEAN, std=V.STD)
+
+
 def save_checkpoint(model, optimizer: SwavOptimizer, epch_num: int, filename: str) -> None:
     opt_state, global_step = optimizer.state_dict()
     torch.save({"epoch": epch_num, "global_step": global_step, "model": model.state_dict(), "optimizer": opt_state,
@@ -945,7 +1026,8 @@ def build_parser() -> argparse.ArgumentParser:
     --size_mask_neighborhood --epochs --dataset_path --destination_path`` are parsed but never reach ``get_loss``,
     which uses its signature defaults (eps 0.05, 10 iterations, 7 frames, radius 6, top-5).
     Added (not in the reference): ``--dataset synthetic`` / ``--steps_per_epoch`` / ``--eval_clips`` because the dataset
-    loaders are out of scope here, ``--eval_every`` (the reference hard-codes 4) and ``--precision`` (the arithmetic mode of the
+    loaders are out of scope here, ``--eval_every`` (the reference hard-codes 4), ``--log_localization_every`` (the qualitative logs of
+    :641-642, off by default) and ``--precision`` (the arithmetic mode of the
     matrix products; the library-level default of ``hip_ops.set_gemm_precision`` stays "f32", the training driver's is "f16x3")."""
     p = argparse.ArgumentParser()
     p.add_argument("--architecture", type=str, default="dino-s16")
@@ -987,6 +1069,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--steps_per_epoch", default=8, type=int, help="synthetic data only")
     p.add_argument("--eval_every", default=4, type=int, help="epochs between rank-0 evaluations (the reference hard-codes 4; 0 = never)")
     p.add_argument("--eval_clips", default=8, type=int, help="synthetic evaluation set size")
+    p.add_argument("--log_localization_every", default=0, type=int,
+                   help="at the rank-0 evaluations of the epochs divisible by N: the prototype assignment histogram's entropy (log_assignment_histogram) and the overlay "
+                        "GIFs of the first evaluation batch in --visualization_directory (log_clip_localization); 0 = never")
     p.add_argument("--precision", default="f16x3", choices=["f16x3", "f32", "bf16x6", "bf16x3", "bf16"],
                    help="arithmetic of the matrix products (hip_ops.set_gemm_precision): f16x3 = the fp32-accurate fp16-pair split (per-op error "
                         "under the exact-f32 MFMA kernels', 1.7x their speed), f32 = exact fp32 MFMA, bf16 = BASELINE C4's bf16 path")
@@ -1182,6 +1267,14 @@ def time_tuning(gpu=0, args=None):
                     eval_model.save(os.path.join(args.logging_directory, f"{previous_score}_{epoch}.pth"))
                 scores.append((epoch, eval_score))
                 print("Epoch: {} Scores/localization {:.4f}".format(epoch, eval_score))
+                log_every = getattr(args, "log_localization_every", 0)
+                if log_every > 0 and epoch % log_every == 0:                # :641-642, on the first evaluation batch
+                    first = next(iter(eval_loader))
+                    # (masked features need the attention probabilities, which this driver's extractor does not return)
+                    masked = bool(args.use_mask) and eval_model.feature_extractor.return_attention
+                    log_assignment_histogram(eval_model, args.num_clusters, [first], masked, epoch)
+                    log_clip_localization(eval_model, first[0].squeeze(1), masked, args.evaluation_protocol,
+                                          args.visualization_directory, epoch, args.input_resolution)
             eval_model.train()
         if world_size > 1:
             dist.barrier()                                                  # :647-648: the other ranks wait for rank 0
