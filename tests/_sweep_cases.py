@@ -335,6 +335,188 @@ def _img_blur(rng):
     return BL(int(rng.integers(1, 4)), int(rng.integers(1, 40)), int(rng.integers(1, 40)), _ch(rng, (0.1, 0.37, 0.9, 1.3, 2.0)))
 
 
+# ---- fifth tier: the k-means family beyond the resident pair and the metric counters (checks: tests/_sweep_checks_metric.py)
+KM_ASSIGN_STRIDE = 4096 * 256     # kmeans.hpp, km_assign_blocks: at most 4096 workgroups of 256 points - beyond, a workgroup strides
+KM_MAX_GRID_Y = 65535             # kmeans.hpp: problems / tiles of one launch
+KF_MAXD, KF_MAXN, KF_PREF_LDS, KM_MAX_LDS = 64, 1 << 20, 72 * 1024, 128 * 1024      # kmeans_fit.hip
+CS_TILE, CS_MIN_PER_WG, CS_MAX_GRID_X, CS_LDS_CELLS, CS_MAX_C = 2048, 8192, 1024, 16384, 4096      # confusion.hip
+DV_OC, DV_LDS_BUDGET, BF_LDS_BUDGET, BF_MAX_R = 4, 64 * 1024, 64 * 1024, 63      # davis.hip, bfscore.hip
+DTYPES = ("u8", "i64")
+
+
+def km_accumulate_blocks(P: int) -> tuple:
+    """kmeans.hpp, km_accumulate_blocks -> (blocks, points per block): 128 points per block up to 4096 blocks, ceil(P / 4096) beyond."""
+    b = min(4096, max(1, (P + 127) // 128))
+    return b, (P + b - 1) // b
+
+
+def km_tile_default(d: int) -> int:
+    """kmeans.hpp, km_tile_default: the centroid rows of d columns that fill 64 KB - the default and the largest tile_k."""
+    return KM_MAXKD // d if 1 <= d <= 1024 else 0
+
+
+def km_tile(d: int, tile_k: int) -> int:
+    """kmeans.hip, resolve_tile: 0 = the default."""
+    return tile_k if tile_k else km_tile_default(d)
+
+
+def kf_fit_lds(d: int, k: int, g: int) -> int:
+    """kmeans_fit.hip, kf_fit_lds: fp64 sums and fp32 centroids [k][d], g blocks' fp32 sums, k counts."""
+    return k * d * (8 + 4 * (1 + g)) + 4 * k
+
+
+def kf_fit_ok(n: int, d: int, k: int) -> bool:
+    """kmeans_fit.hip, kf_fit_shape_ok."""
+    return 1 <= d <= KF_MAXD and 1 <= k <= n <= KF_MAXN and kf_fit_lds(d, k, 1) <= KM_MAX_LDS
+
+
+def kf_fit_group(n: int, d: int, k: int) -> int:
+    """kmeans_fit.hip, kf_fit_group: blocks whose fp32 sums one pass holds - what fits 72 KB, at least one, at most all of them."""
+    fixed, per = kf_fit_lds(d, k, 0), 4 * k * d
+    g = (KF_PREF_LDS - fixed) // per if fixed < KF_PREF_LDS else 0
+    return min(max(g, 1), km_accumulate_blocks(n)[0])
+
+
+def kf_fit_kernel(d: int, offset: int) -> tuple:
+    """kmeans_fit.hip, tt_kmeans_fit_batched -> (DREG, VEC): x ``offset`` floats off a 16-byte boundary loads one float at a time."""
+    return (16 if d <= 16 else 64), (1 if offset % 4 else (4 if d % 4 == 0 else (2 if d % 2 == 0 else 1)))
+
+
+def cs_route(Cg: int, Cp: int) -> int:
+    """confusion.hip, cs_route: 0 refused, 1 the LDS histogram (up to 16384 cells), 2 global atomics."""
+    if not (1 <= Cg <= CS_MAX_C and 1 <= Cp <= CS_MAX_C):
+        return 0
+    return 1 if Cg * Cp <= CS_LDS_CELLS else 2
+
+
+def cs_blocks(n: int, Cg: int, Cp: int) -> tuple:
+    """confusion.hip, cs_blocks -> (workgroups of one segment, what set the elements per workgroup: "min", "cells" or "spread")."""
+    cells = Cg * Cp if cs_route(Cg, Cp) == 1 else 0
+    per, why = (CS_MIN_PER_WG, "min") if CS_MIN_PER_WG >= 4 * cells else (4 * cells, "cells")
+    spread = (n + CS_MAX_GRID_X - 1) // CS_MAX_GRID_X
+    if per < spread:
+        per, why = spread, "spread"
+    per = min(per, 1 << 31)
+    return max(1, (n + per - 1) // per), why
+
+
+def _shrink(H: int, W: int, lds_of, budget: int):
+    """The loop davis_tiling and bf_tiling share: TH 32 -> 16 -> 8, then ow down to 1 -> (TH, ow, shrunk) or None."""
+    words = (W + 63) // 64
+    tx = (words + 7) // 8
+    ow, TH, shrunk = (words + tx - 1) // tx, min(H, 32), False
+    while lds_of(TH, ow) > budget:
+        shrunk = True
+        if TH > 8:
+            TH //= 2
+        elif ow > 1:
+            ow -= 1
+        else:
+            return None
+    return TH, ow, shrunk
+
+
+def davis_tiling(H: int, W: int, rows: int, oc: int):
+    """davis.hip, davis_tiling -> (TH, ow) of an element of ``rows`` rows at ``oc`` objects per pass (None: refused)."""
+    t = _shrink(H, W, lambda TH, ow: 4 * oc * (TH + rows) * (ow + 2) * 8, DV_LDS_BUDGET)
+    return None if t is None else t[:2]
+
+
+def bf_tiling(H: int, W: int, R: int):
+    """bfscore.hip, bf_tiling -> (TH, ow, whether the shrink loop ran at all)."""
+    return _shrink(H, W, lambda TH, ow: 8 * (2 * (TH + 2 * R + 2) * (ow + 2) + 2 * (TH + 2 * R) * (ow + 2) + 6 * TH * ow), BF_LDS_BUDGET)
+
+
+def tiles_of(H: int, W: int, TH: int, ow: int) -> tuple:
+    """(tiles_y, tiles_x) of both counters' launchers."""
+    return (H + TH - 1) // TH, ((W + 63) // 64 + ow - 1) // ow
+
+
+def bf_radius(t) -> int:
+    """hip_ops.bf_element_spans: the element radius of the test d < t * t on integer squared distances."""
+    r = 0
+    while (r + 1) * (r + 1) < float(t) * float(t):
+        r += 1
+    return r
+
+
+def KT(P, d, k, tile_k, dup=0) -> dict:
+    """dup: 0 none, 1 a random duplicated pair, 2 the pair (tile - 1, tile) either side of the first tile boundary"""
+    return dict(P=P, d=d, k=k, tile_k=tile_k, dup=dup)
+
+
+def KA(P, d, k, tile_k, mode="rand") -> dict:
+    return dict(P=P, d=d, k=k, tile_k=tile_k, mode=mode)
+
+
+def KB(B, N, d, k) -> dict:
+    return dict(B=B, N=N, d=d, k=k)
+
+
+def KF(B, n, d, k, nredo=2, niter=4, offset=0, sep=2.0, empty=0) -> dict:
+    """sep: blob centres are N(0, sep^2) per column about which the points are N(0, 1); empty: problem 1 holds every point twice and redo 0
+    seeds two clusters on the two copies of one point (tests/test_hip_kmeans_fit.py, test 3)"""
+    return dict(B=B, n=n, d=d, k=k, nredo=nredo, niter=niter, offset=offset, sep=sep, empty=empty)
+
+
+def CSG(S, n, Cg, Cp, dtype="i16", offset=0, ignore="") -> dict:
+    """offset: elements pred's view starts into its storage (gt starts offset % 2 elements in); ignore: "" or the ignored gt value"""
+    return dict(S=S, n=n, Cg=Cg, Cp=Cp, dtype=dtype, offset=offset, ignore=ignore)
+
+
+def DV(T, H, W, O, radius, pt="u8", gtt="u8", void=0) -> dict:
+    return dict(T=T, H=H, W=W, O=O, radius=radius, pt=pt, gtt=gtt, void=void)
+
+
+def BFC(P, H, W, t) -> dict:
+    return dict(P=P, H=H, W=W, t=t)
+
+
+def _kmeans_assign_tiled(rng):
+    d = _ch(rng, (1, 3, 8, 16, 17, 50, 64, 65, 128, 384))
+    k = int(rng.integers(1, 400))
+    tile_k = min(_ch(rng, (0, 1, 2, 5, 7, 13)), km_tile_default(d))
+    return KT(int(rng.integers(1, 20000)), d, k, tile_k, int(rng.integers(0, 3)) if k > km_tile(d, tile_k) else _b(rng, 0.3) * int(k > 1))
+
+
+def _kmeans_accumulate_tiled(rng):
+    d = _ch(rng, (1, 3, 8, 16, 50, 64, 100, 257, 384))
+    return KA(int(rng.integers(1, 30000)), d, int(rng.integers(1, 400)), min(_ch(rng, (0, 1, 3, 7, 64)), km_tile_default(d)), _ch(rng, ("rand", "rand", "skip", "one")))
+
+
+def _kmeans_assign_batched(rng):
+    d = _ch(rng, (1, 3, 16, 17, 50, 64, 65, 128))
+    return KB(int(rng.integers(1, 9)), int(rng.integers(1, 3000)), d, int(rng.integers(1, min(km_max_k(d), 200) + 1)))
+
+
+def _kmeans_fit(rng):
+    # (blob centres N(0, 8^2) per column: most draws are valid input as they come - no empty cluster, no near-tie in any fp64 iteration -
+    # and where two blobs nearly coincide the check draws the blobs again until its fp64 run proves them valid)
+    d = _ch(rng, (1, 2, 3, 6, 12, 16, 17, 50, 64))
+    k = int(rng.integers(1, 9))
+    return KF(int(rng.integers(1, 4)), int(rng.integers(k, 3000)), d, k, int(rng.integers(1, 3)), int(rng.integers(1, 6)), _ch(rng, (0, 0, 1)), 8.0)
+
+
+def _confusion_segments(rng):
+    Cg, Cp = _ch(rng, ((1, 1), (3, 5), (5, 10), (21, 500), (128, 128), (127, 129), (130, 130)))
+    dtype = _ch(rng, ("i16", "i64"))
+    return CSG(int(rng.integers(1, 5)), int(rng.integers(1, 70000)), Cg, Cp, dtype, int(rng.integers(0, 8 if dtype == "i16" else 2)), _ch(rng, ("", 0, 255)))
+
+
+def _davis_counts(rng):
+    if rng.random() < 0.5:      # small: the per-pixel definition runs on these (tests/_sweep_checks_metric.py)
+        return DV(int(rng.integers(1, 3)), int(rng.integers(1, 25)), int(rng.integers(1, 65)), int(rng.integers(1, 6)), _ch(rng, (0, 1, 2, 2.5, 3)),
+                  _ch(rng, DTYPES), _ch(rng, DTYPES), _b(rng))
+    return DV(int(rng.integers(1, 4)), int(rng.integers(1, 100)), int(rng.integers(1, 700)), int(rng.integers(1, 7)), _ch(rng, (1, 4, 8, 20)),
+              _ch(rng, DTYPES), _ch(rng, DTYPES), _b(rng))
+
+
+def _bf_counts(rng):
+    if rng.random() < 0.5:
+        return BFC(int(rng.integers(1, 4)), int(rng.integers(1, 25)), int(rng.integers(1, 65)), _ch(rng, (0, 0.5, 1, 2, 2.5, 5)))
+    return BFC(int(rng.integers(1, 4)), int(rng.integers(1, 100)), int(rng.integers(1, 700)), _ch(rng, (1, 2, 5, 16)))
+
+
 DRAW = {"linear_f32": _linear_f32, "linear_pairs": _linear_pairs, "linear_planes": _linear_planes, "bwd_pairs": _bwd_pairs,
         "layernorm": _layernorm, "l2norm": _l2norm, "attention": _attention, "ce": _ce, "sinkhorn": _sinkhorn,
         "sinkhorn_from_q": _sinkhorn_from_q, "sinkhorn_local": _sinkhorn_local, "queue_push": _queue_push}
@@ -351,8 +533,13 @@ PROP_OPS = tuple(DRAW)[len(STEP_OPS) + len(EVAL_OPS):]
 # (and again: the fourth tier draws after the first three)
 DRAW.update({"probe_logits": _probe_logits, "probe_upsample_ce": _probe_upsample_ce, "bilinear_adjoint": _bilinear_adjoint,
              "probe_wgrad": _probe_wgrad, "sgd": _sgd, "img_resize": _img_resize, "img_color": _img_color, "img_blur": _img_blur})
+HEAD_OPS = tuple(DRAW)[len(STEP_OPS) + len(EVAL_OPS) + len(PROP_OPS):]
+# (and once more: the fifth tier draws after the first four)
+DRAW.update({"kmeans_assign_tiled": _kmeans_assign_tiled, "kmeans_accumulate_tiled": _kmeans_accumulate_tiled,
+             "kmeans_assign_batched": _kmeans_assign_batched, "kmeans_fit": _kmeans_fit, "confusion_segments": _confusion_segments,
+             "davis_counts": _davis_counts, "bf_counts": _bf_counts})
 OPS = tuple(DRAW)
-HEAD_OPS = OPS[len(STEP_OPS) + len(EVAL_OPS) + len(PROP_OPS):]
+METRIC_OPS = OPS[len(STEP_OPS) + len(EVAL_OPS) + len(PROP_OPS) + len(HEAD_OPS):]
 
 COUNTS = {"linear_f32": 6, "linear_pairs": 8, "linear_planes": 4, "bwd_pairs": 6, "layernorm": 5, "l2norm": 3, "attention": 6, "ce": 3,
           "sinkhorn": 6, "sinkhorn_from_q": 3, "sinkhorn_local": 3, "queue_push": 3,
@@ -360,7 +547,9 @@ COUNTS = {"linear_f32": 6, "linear_pairs": 8, "linear_planes": 4, "bwd_pairs": 6
           "confusion_counts": 3, "adamw": 3, "elementwise": 3, "foreground_mask": 4, "pos_embed": 3,
           "label_prop": 6, "label_prop_grid": 4, "upsample_argmax_hw": 4,
           "probe_logits": 4, "probe_upsample_ce": 4, "bilinear_adjoint": 3, "probe_wgrad": 4, "sgd": 3, "img_resize": 4, "img_color": 4,
-          "img_blur": 3}
+          "img_blur": 3,
+          "kmeans_assign_tiled": 4, "kmeans_accumulate_tiled": 4, "kmeans_assign_batched": 3, "kmeans_fit": 4, "confusion_segments": 4,
+          "davis_counts": 4, "bf_counts": 4}
 
 # The route boundaries, pinned (tests/test_sweep_routes.py names the rule each one reaches)
 PINNED = {
@@ -611,6 +800,87 @@ PINNED = {
         # and 37 x 1; the smallest and the largest radius of the training transform
         BL(2, 5, 1, 2.0), BL(2, 1, 5, 2.0), BL(1, 2, 7, 2.0), BL(1, 7, 2, 2.0), BL(1, 3, 3, 2.0), BL(1, 1, 1, 2.0), BL(2, 1, 53, 2.0), BL(2, 37, 1, 2.0),
         BL(1, 1, 53, 0.1), BL(1, 37, 1, 0.1), BL(300, 3, 2, 2.0), BL(2, 37, 53, 0.1),
+    ],
+    # ---- fifth tier (kmeans.hip: the tiled pair and the batched assignment; kmeans_fit.hip; confusion.hip; davis.hip; bfscore.hip)
+    "kmeans_assign_tiled": [
+        # km_assign_blocks: beyond 4096 x 256 points the workgroups stride - on <16>, <0> and <64> with several tiles forced by a small tile
+        # (the point tile is staged again, the centroid tiles are reloaded), and on <0> with ONE tile (`resident`: kept over the strides)
+        KT(1048577, 17, 7, 3, 1), KT(1048700, 65, 5, 2), KT(1100000, 8, 9, 4, 2), KT(1048700, 65, 5, 0), KT(1100000, 8, 9, 0, 1), KT(1048577, 17, 7, 0),
+        # a last tile of 1, 2, 3 and 5 centroids behind whole tiles of 8: the 4-wide block and its tail, on each kernel
+        KT(3000, 16, 9, 8), KT(3000, 50, 10, 8, 2), KT(3000, 65, 11, 8), KT(3000, 16, 13, 8, 2), KT(700, 128, 13, 8, 2),
+        # the first minimum across a tile boundary (dup 2) on each kernel; tile_k 1 (every centroid its own tile)
+        KT(2000, 8, 40, 7, 2), KT(2000, 50, 40, 7, 2), KT(2000, 100, 40, 7, 2), KT(1000, 17, 9, 1, 2), KT(1000, 3, 5, 1, 1),
+        # k one above the default tile (two tiles, the last of one centroid) at d 16, 64 and 128: beyond what the resident pair takes - at
+        # d 64 also with enough points for the excuse rule to allow a label (one per 10 000)
+        KT(3000, 16, 1025, 0, 2), KT(3000, 64, 257, 0, 2), KT(3000, 128, 129, 0, 2), KT(12000, 64, 257, 0, 2),
+        # the last workgroup of 256 points one short, whole, one over; one point; one tile that holds every centroid; d 1024
+        KT(255, 16, 9, 4), KT(256, 50, 9, 4, 1), KT(257, 65, 9, 4), KT(1, 9, 4, 3), KT(5000, 50, 21, 0, 1), KT(300, 1024, 17, 16, 2),
+        KT(5000, 8, 30, 0, 1), KT(700, 100, 30, 0, 1),
+    ],
+    "kmeans_accumulate_tiled": [
+        # more than 65 535 tiles: the launcher's t0 loop (65 541 tiles of one cluster: launches of 65 535 and of 6)
+        KA(3000, 1, 65541, 1),
+        # km_accumulate_blocks beyond P = 524 288: 129 points per block (31 blocks without a point) and 147; exactly at the cap
+        KA(524289, 8, 5, 2), KA(600000, 3, 7, 3, "skip"), KA(524288, 2, 3, 1), KA(700000, 4, 3, 2, "one"),
+        # d 257 (a thread owns two columns) with k above the tile; a last tile of one cluster; every mode; the default tile beyond the
+        # resident limit; one point; tile_k above k
+        KA(900, 257, 70, 63, "skip"), KA(5000, 50, 22, 7), KA(5000, 64, 9, 4, "one"), KA(5000, 50, 30, 7, "skip"), KA(3000, 16, 1025, 0),
+        KA(3000, 128, 129, 0, "skip"), KA(1, 1, 1, 0), KA(129, 16, 4, 64), KA(7001, 50, 500, 0),
+    ],
+    "kmeans_assign_batched": [
+        # launch_assign: the three kernels at B = 3 with a ragged last workgroup; more than 65 535 problems (the y0 loop); the largest
+        # resident k of each kernel; one point per problem
+        KB(3, 700, 16, 9), KB(3, 700, 50, 21), KB(3, 700, 128, 40), KB(65538, 2, 3, 2), KB(2, 300, 16, 1024), KB(2, 300, 64, 252),
+        KB(2, 300, 128, 128), KB(5, 1, 17, 3),
+    ],
+    "kmeans_fit": [
+        # kmeans_fit_kernel<16,2>: d even, no multiple of 4, at most 16; the other five instantiations; x 4 bytes off a 16-byte boundary
+        # at d % 4 == 0 (VEC 1) beside the aligned run of the same case (VEC 4): equal bit for bit
+        KF(3, 257, 2, 3), KF(2, 300, 6, 5), KF(2, 300, 10, 4), KF(2, 515, 14, 7), KF(2, 300, 12, 5), KF(2, 300, 12, 5, offset=1),
+        KF(2, 700, 64, 9), KF(2, 700, 64, 9, offset=1), KF(2, 129, 3, 2), KF(2, 400, 17, 5), KF(2, 400, 50, 10), KF(2, 400, 16, 5),
+        # kf_fit_group: 1 with whole and ragged block counts (6 and 11 blocks: every pass is one block); 3 with 8 blocks (a last pass of
+        # two); all blocks in one pass.  The LDS maxima at d 64 and d 50; d 14 at k 300 (group 1 at a small d)
+        KF(2, 700, 64, 127, niter=3), KF(1, 1300, 50, 80, niter=3), KF(2, 1000, 50, 60, niter=3), KF(1, 1100, 50, 60, nredo=1, niter=3),
+        KF(1, 900, 50, 163, nredo=1, niter=3),
+        KF(1, 1500, 14, 300, nredo=1, niter=3),
+        # fewer points than threads; n = k; one point; more than 128 points per block (147 and 256: the fit's longest fp32 runs; blobs 16
+        # deviations apart, so that none of a million points lies within KM_GAP of a bisector)
+        KF(3, 100, 5, 4), KF(2, 37, 8, 37, nredo=1), KF(3, 1, 1, 1, nredo=1, niter=2), KF(1, 600000, 2, 3, 1, 3, sep=16.0),
+        KF(1, 1048576, 1, 2, 1, 3, sep=16.0),
+        # more problems than one launch carries (the wrapper's chunks of 65 535); an empty cluster on one (problem, redo) only
+        KF(65538, 2, 1, 1, 1, 1), KF(3, 300, 17, 5, 2, 4, empty=1),
+    ],
+    "confusion_segments": [
+        # cs_blocks: one workgroup up to 8192 elements, two from 8193; four elements per LDS cell (21 x 500: 42 000 / 42 001); beyond
+        # 1024 x 8192 elements the workgroups take ceil(n / 1024) each - on the LDS route and on the global one
+        CSG(2, 8192, 5, 10), CSG(2, 8193, 5, 10, "i64", 0, 0), CSG(2, 42000, 21, 500), CSG(2, 42001, 21, 500, "i16", 0, 255),
+        CSG(1, 9000000, 3, 7), CSG(1, 8500000, 130, 130, "i16", 3, 0),
+        # pred 1 ... 7 elements off a 16-byte boundary (int16), 1 (int64), with SEVERAL workgroups per segment: a head and a tail on
+        # workgroup 0 beside the strip loop all of them share - LDS route, then global
+        *[CSG(3, 50176, 5, 10, "i16", o, 0 if o % 2 else "") for o in range(1, 8)], CSG(3, 50176, 5, 10, "i64", 1, 255),
+        *[CSG(3, 50176, 130, 130, "i16", o, 0 if o % 2 else "") for o in range(1, 8)], CSG(3, 50176, 130, 130, "i64", 1),
+        # fewer than 8 elements (no strip); a head longer than the segment; odd n at S > 1 (int16 segments that start 2-byte aligned)
+        CSG(3, 1, 3, 5), CSG(2, 7, 3, 5, "i64", 1), CSG(3, 3, 3, 5, "i16", 1), CSG(2, 5, 130, 130, "i16", 2), CSG(5, 4097, 127, 129, "i16", 0, 0),
+        CSG(4, 777, 1, 1, "i64", 0, 0), CSG(2, 1000, 300, 7, "i16", 3, 255),
+    ],
+    "davis_counts": [
+        # davis_tiling: the 127-row element at four objects per pass leaves TH 8, ow 1 (9 x 5 tiles); W 512 / 513 (one tile column of 8
+        # words / two of 5); 81 rows at TH 8, ow 3 with a second pass of one object; H < 8; 3 x 3 tiles on three frames
+        DV(2, 70, 300, 4, 63, "u8", "i64", 1), DV(2, 40, 513, 4, 8, "i64", "u8", 0), DV(2, 40, 512, 4, 8, "u8", "u8", 1),
+        DV(2, 40, 600, 5, 40, "i64", "i64", 1), DV(2, 6, 200, 4, 63, "i64", "u8", 1), DV(3, 70, 1100, 3, 2, "u8", "i64", 0),
+        # the remaining classes of davis_tiling: TH 32 -> 16 at all eight words; TH 32 -> 16 -> 8 at all eight words; H <= 8 with ow 8 -> 3;
+        # H = 16 (one halving, then ow) with ow 8 -> 3 and with ow 5 -> 1
+        DV(1, 40, 300, 4, 24, "u8", "u8", 0), DV(1, 40, 512, 4, 20, "i64", "u8", 1), DV(1, 6, 512, 4, 40, "u8", "i64", 0),
+        DV(1, 16, 512, 4, 40, "i64", "i64", 0), DV(1, 16, 300, 4, 63, "u8", "u8", 1),
+        # every dtype pair with and without void on small frames (the per-pixel definition runs on these); one pixel; an even element
+        DV(2, 17, 23, 3, 1, "u8", "u8", 0), DV(2, 24, 64, 5, 2, "i64", "i64", 0), DV(1, 9, 33, 2, 3, "u8", "i64", 1), DV(2, 5, 7, 2, 10, "i64", "u8", 0),
+        DV(1, 1, 1, 1, 0, "u8", "u8", 1), DV(1, 20, 40, 2, 2.5, "i64", "i64", 1),
+    ],
+    "bf_counts": [
+        # 3 x 3 tiles on three pairs; R 63 at W 512 / 513; R 30 on two tile columns; H < 32 with W > 512
+        BFC(3, 70, 1100, 2), BFC(2, 40, 513, 64), BFC(2, 40, 512, 64), BFC(2, 40, 600, 31), BFC(2, 20, 700, 5),
+        # small maps (the per-pixel definition runs on these): one pixel, a row, a column, t 0 and 0.5 (no match but the pixel itself)
+        BFC(3, 1, 1, 2), BFC(2, 1, 60, 2), BFC(2, 24, 1, 2.5), BFC(2, 13, 29, 0), BFC(2, 13, 29, 0.5), BFC(2, 24, 64, 5), BFC(1, 20, 33, 16),
     ],
 }
 

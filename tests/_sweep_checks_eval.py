@@ -314,7 +314,7 @@ class HipSide:
 
 
 _TWIN = None
-HOST_WORST: dict = {}      # the host halves' worst errors (tests/test_sweep_eval_host.py, tests/test_sweep_prop_host.py, tests/test_sweep_head_host.py): one TT_SWEEP_REPORT_HOST file
+HOST_WORST: dict = {}      # the host halves' worst errors (tests/test_sweep_eval_host.py, tests/test_sweep_prop_host.py, tests/test_sweep_head_host.py, tests/test_sweep_metric_host.py): one TT_SWEEP_REPORT_HOST file
 
 
 def twin_side():

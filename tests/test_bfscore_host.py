@@ -14,12 +14,12 @@ import numpy as np
 import pytest
 
 import _border_follow as bfl
+from _metric_refs import BF_TABLE as TABLE, bf_np_counts as np_counts, np_mult
 from timetuning_amd import bfscore as BF
 from timetuning_amd import hip_ops
 from timetuning_amd import cluster_based_foreground_extraction as CB
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TABLE = bfl.multiplicity_table()
 
 
 def _generator():
@@ -29,42 +29,7 @@ def _generator():
     return mod
 
 
-# ---- numpy restatement of tt_bf_counts ---------------------------------------------------------------------------------
-
-def np_mult(a):
-    """Per-pixel multiplicity of a binary map from the follower-derived table."""
-    a = np.asarray(a) != 0
-    return np.where(a, TABLE[bfl.neighbourhood_index(a)], 0).astype(np.int64)
-
-
-def np_within(b, t):
-    """bool [H, W]: a set pixel of ``b`` at integer squared distance d < t * t (the bound a Python float, as the reference)."""
-    b = np.asarray(b, bool)
-    H, W = b.shape
-    tt = float(t) * float(t)
-    out = np.zeros_like(b)
-    ys, xs = np.nonzero(b)
-    if not len(ys):
-        return out
-    reach = int(np.ceil(abs(float(t)))) + 1
-    for dy in range(-reach, reach + 1):
-        for dx in range(-reach, reach + 1):
-            if dy * dy + dx * dx < tt:
-                y, x = ys - dy, xs - dx
-                ok = (y >= 0) & (y < H) & (x >= 0) & (x < W)
-                out[y[ok], x[ok]] = True
-    return out
-
-
-def np_counts(gt, pr, t):
-    """int64 [P, 4] = {n_pr, hit_pr, n_gt, hit_gt} of binary maps [P, H, W]."""
-    gt, pr = np.asarray(gt), np.asarray(pr)
-    out = np.zeros((gt.shape[0], 4), np.int64)
-    for k in range(gt.shape[0]):
-        mp, mg = np_mult(pr[k]), np_mult(gt[k])
-        out[k] = [mp.sum(), mp[np_within(mg > 0, t)].sum(), mg.sum(), mg[np_within(mp > 0, t)].sum()]
-    return out
-
+# ---- numpy restatement of tt_bf_counts: tests/_metric_refs.py (shared with the sweep's fifth tier) -----------------------
 
 def np_bfscore(gt, pr, t):
     """bfscore through the restated counts and the product's host code."""

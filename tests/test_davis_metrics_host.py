@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from _metric_refs import davis_np_counts as np_counts, np_dilate, np_seg2bmap
 from timetuning_amd import hip_ops
 from timetuning_amd import mask_propagation as MP
 
@@ -23,52 +24,7 @@ def _generator():
     return mod
 
 
-# ---- numpy restatement of tt_davis_jf_counts ---------------------------------------------------------------------------
-
-def np_seg2bmap(seg):
-    s = np.asarray(seg) != 0
-    H, W = s.shape
-    e = np.zeros_like(s)
-    e[:, :-1] = s[:, 1:]
-    d = np.zeros_like(s)
-    d[:-1, :] = s[1:, :]
-    de = np.zeros_like(s)
-    de[:-1, :-1] = s[1:, 1:]
-    b = (s ^ e) | (s ^ d) | (s ^ de)
-    b[H - 1, :] = s[H - 1, :] ^ e[H - 1, :]
-    b[:, W - 1] = s[:, W - 1] ^ d[:, W - 1]
-    b[H - 1, W - 1] = False
-    return b
-
-
-def np_dilate(b, element):
-    b = np.asarray(b, bool)
-    H, W = b.shape
-    el = np.asarray(element) != 0
-    ay, ax = el.shape[0] // 2, el.shape[1] // 2
-    pad = np.zeros((H + 2 * el.shape[0], W + 2 * el.shape[1]), bool)
-    pad[el.shape[0]:el.shape[0] + H, el.shape[1]:el.shape[1] + W] = b
-    out = np.zeros_like(b)
-    for i, j in zip(*np.nonzero(el)):
-        y0, x0 = el.shape[0] + i - ay, el.shape[1] + j - ax
-        out |= pad[y0:y0 + H, x0:x0 + W]
-    return out
-
-
-def np_counts(pred, gt, num_objects, element, void=None):
-    """int64 [O, T, 6] = {J intersection, J union, n_fg, n_gt, fg_match, gt_match} of objects 1..O."""
-    pred, gt = np.asarray(pred), np.asarray(gt)
-    T = pred.shape[0]
-    keep = np.ones(pred.shape, bool) if void is None else np.asarray(void) == 0
-    out = np.zeros((num_objects, T, 6), np.int64)
-    for o in range(1, num_objects + 1):
-        for t in range(T):
-            p, g = (pred[t] == o) & keep[t], (gt[t] == o) & keep[t]
-            fb, gb = np_seg2bmap(p), np_seg2bmap(g)
-            out[o - 1, t] = [(p & g).sum(), (p | g).sum(), fb.sum(), gb.sum(), (fb & np_dilate(gb, element)).sum(),
-                             (gb & np_dilate(fb, element)).sum()]
-    return out
-
+# ---- numpy restatement of tt_davis_jf_counts: tests/_metric_refs.py (shared with the sweep's fifth tier) -------------------
 
 def golden_labels(g, name):
     T, H, W, O, seed = [int(v) for v in g[f"{name}_cfg"]]

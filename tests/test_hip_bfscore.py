@@ -9,7 +9,8 @@ import pytest
 import torch
 
 import _border_follow as bfl
-from test_bfscore_host import _generator, bits_equal, np_bfscore, np_counts, np_image_scores
+from _metric_refs import bf_np_counts as np_counts
+from test_bfscore_host import _generator, bits_equal, np_bfscore, np_image_scores
 from timetuning_amd import _lib, hip_ops as ops
 from timetuning_amd import bfscore as BF
 from timetuning_amd import cluster_based_foreground_extraction as CB

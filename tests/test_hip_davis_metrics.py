@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_davis_metrics_host import bits_equal, golden_labels, np_counts, np_seg2bmap
+from _metric_refs import davis_np_counts as np_counts, np_seg2bmap
+from test_davis_metrics_host import bits_equal, golden_labels
 from timetuning_amd import _lib, hip_ops as ops
 from timetuning_amd import mask_propagation as MP
 

@@ -17,6 +17,11 @@ The fourth tier - the linear probe's kernels and the clip input pipeline (HEAD_O
 references at the existing linear-probe bounds, bit equality with the Pillow-pinned image oracle; tests/test_sweep_head_host.py is its host
 half, and the probe's domain edges follow the second tier's.
 
+The fifth tier - the tiled k-means pair, the batched assignment, the fused batched fit and the three metric counters (METRIC_OPS) - runs the
+checks of tests/_sweep_checks_metric.py: fp64 references at the second tier's k-means rules, oracle.timet_oracle.kmeans_lloyd for the fit, the
+k-means contract's bit equalities, exact equality with the NumPy restatements of the counters; tests/test_sweep_metric_host.py is its host
+half.  Its refusals at the edge stand beside the second tier's below.
+
 ``run_case`` is also what tools/fuzz_ops.py runs on more seeds of the same generator."""
 import json
 import os
@@ -27,9 +32,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _sweep_cases import EVAL_OPS, HEAD_OPS, PAIR_EPILOGUES, PROP_OPS, case_id, table
+from _sweep_cases import EVAL_OPS, HEAD_OPS, METRIC_OPS, PAIR_EPILOGUES, PROP_OPS, case_id, table
 from _sweep_checks_eval import HipSide, run_eval_case
 from _sweep_checks_head import HeadHip, run_head_case
+from _sweep_checks_metric import MetricHip, run_metric_case
 from _sweep_checks_prop import PropHip, run_prop_case
 
 pytestmark = pytest.mark.gpu
@@ -342,6 +348,8 @@ def run_case(op: str, params: dict, worst: dict = None) -> None:
             run_prop_case(PropHip(), op, params, WORST)
         elif op in HEAD_OPS:
             run_head_case(HeadHip(), op, params, WORST)
+        elif op in METRIC_OPS:
+            run_metric_case(MetricHip(), op, params, WORST)
         else:
             CHECK[op](ops, params, _gen(op, params), _note(op))
     finally:
@@ -468,6 +476,93 @@ def test_mask_position_and_row_op_limits():
     with _refused("l2norm_fwd: bad arguments"):
         ops.normalize_rows_(_z(2, 1025))
     assert rel_err(ops.normalize_rows_(torch.full((2, 1024), 2.0, device="cuda")), torch.full((2, 1024), 2.0 / 64.0)) < TOL_F32
+
+
+# ---- the accepted domains of the fifth tier's entries, at the edge (kmeans_fit.hip: kf_fit_shape_ok; kmeans.hip: km_tiled_shape_ok,
+# resolve_tile; confusion.hip: cs_route and the entry's own checks).  The largest accepted shapes compute correctly as cases of the table
+# above (the fit at (64, 127) and (50, 163), d = 1024 tiled, n = 2^20); every refusal below is a host-side TT_REQUIRE: nothing is launched.
+@pytest.mark.parametrize("n,d,k,msg", [(700, 64, 128, r"n = 700, d = 64, k = 128: need 1 <= d <= 64, 1 <= k <= n <= 1048576 and 16 k d \+ 4 k = 131584 bytes of LDS within 131072"),
+                                       (900, 50, 164, r"n = 900, d = 50, k = 164: need .* 16 k d \+ 4 k = 131856 bytes of LDS within 131072"),
+                                       (300, 65, 3, r"n = 300, d = 65, k = 3: need 1 <= d <= 64"),
+                                       (3, 2, 5, r"n = 3 points are fewer than k = 5 clusters"),
+                                       ((1 << 20) + 1, 1, 1, r"n = 1048577, d = 1, k = 1: need 1 <= d <= 64, 1 <= k <= n <= 1048576")])
+def test_fused_fit_refuses_beyond_its_domain(n, d, k, msg):
+    from timetuning_amd import _lib, hip_ops as ops
+
+    assert not ops.kmeans_fit_shape_ok(n, d, k) and _lib.load().tt_kmeans_fit_lds_bytes(n, d, k) == 0
+    assert _lib.load().tt_kmeans_fit_workspace_bytes(1, 1, n, d, k) == 0
+    x, init = _z(1, n, d), torch.zeros((1, k), dtype=torch.int32)
+    with _refused("kmeans_fit_batched: " + msg):
+        ops.kmeans_fit_batched(x, init, 2)
+    # ... and through the C entry on outputs filled beforehand: none of them is written
+    lib = _lib.load()
+    cent, obj, status = torch.full((1, 1, k, d), 7.0, device="cuda"), torch.full((1, 1), 7.0, dtype=torch.float64, device="cuda"), torch.full((1, 1), 7, dtype=torch.int32, device="cuda")
+    ws = _z(4 * n + 16, dtype=torch.uint8)
+    rc = lib.tt_kmeans_fit_batched(x.data_ptr(), init.cuda().data_ptr(), init.data_ptr(), cent.data_ptr(), obj.data_ptr(), status.data_ptr(), 1, n, d, k, 1, 2,
+                                   ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc != 0 and bool((cent == 7).all()) and float(obj) == 7.0 and int(status) == 7
+
+
+def test_fused_fit_refuses_a_seed_outside_the_points():
+    from timetuning_amd import hip_ops as ops
+
+    x = torch.randn(2, 300, 5, generator=torch.Generator().manual_seed(3)).cuda()
+    ok = torch.tensor([[0, 1, 299]], dtype=torch.int32)
+    assert (ops.kmeans_fit_batched(x, ok, 1)[2] >= 0).all()                       # the last row is a seed like any other
+    with _refused(r"kmeans_fit_batched: init\[1\]\[2\] = 300 is outside \[0, 300\)"):
+        ops.kmeans_fit_batched(x, torch.tensor([[0, 1, 2], [3, 4, 300]], dtype=torch.int32), 1)
+    with _refused(r"kmeans_fit_batched: init\[0\]\[0\] = -1 is outside \[0, 300\)"):
+        ops.kmeans_fit_batched(x, torch.tensor([[-1, 1, 2]], dtype=torch.int32), 1)
+    with _refused(r"kmeans_fit_batched: niter = 0, nredo = 1"):
+        ops.kmeans_fit_batched(x, ok, 0)
+
+
+def test_tiled_pair_refuses_beyond_its_domain():
+    from timetuning_amd import hip_ops as ops
+
+    lab = _z(40, dtype=torch.int32)
+    for d in (1, 17, 64, 1024):      # the default tile is the largest: one row more is refused by both entries
+        most = ops.kmeans_tile_centroids(d)
+        assert most == 16384 // d
+        for fn, args in ((ops.kmeans_assign_tiled, (_z(40, d), _z(3, d))), (ops.kmeans_accumulate_tiled, (_z(40, d), lab, 3))):
+            with _refused(rf"{fn.__name__}: tile_k = {most + 1} is outside 1 \.\.\. {most}, the centroids of d = {d} columns"):
+                fn(*args, tile_k=most + 1)
+            with _refused(rf"{fn.__name__}: tile_k = -1 is outside"):
+                fn(*args, tile_k=-1)
+    assert ops.kmeans_tiled_shape_ok(1024, 3) and not ops.kmeans_tiled_shape_ok(1025, 3) and ops.kmeans_tile_centroids(1025) == 0
+    with _refused(r"kmeans_assign_tiled: k = 3, d = 1025: need 1 <= d <= 1024"):
+        ops.kmeans_assign_tiled(_z(40, 1025), _z(3, 1025))
+    with _refused(r"kmeans_accumulate_tiled: k = 3, d = 1025: need 1 <= d <= 1024"):
+        ops.kmeans_accumulate_tiled(_z(40, 1025), lab, 3)
+
+
+def test_confusion_segments_refuses_beyond_its_domain():
+    from timetuning_amd import _lib, hip_ops as ops
+
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    z16, z64 = _z(2, 8, dtype=torch.int16), _z(2, 8, dtype=torch.int64)
+    for Cg, Cp in ((4097, 3), (3, 4097)):
+        with _refused(rf"confusion_counts_segments: Cg = {Cg}, Cp = {Cp}: need 1 <= Cg, Cp <= 4096"):
+            ops.confusion_counts_segments(z16, z64, Cg, Cp)
+    # S * Cg * Cp cells beyond 2^32 (257 matrices of 4096 x 4096), through the C entry: the counts are never touched, so a small buffer serves
+    S = 257
+    p1, g1, counts = _z(S, 1, dtype=torch.int64), _z(S, 1, dtype=torch.int64), torch.full((16,), 7, dtype=torch.int64, device="cuda")
+    with _refused(r"confusion_counts_segments: S = 257 matrices of 4096 x 4096 are 4311744512 cells, more than the 4294967296"):
+        _lib.check(lib.tt_confusion_counts_segments(p1.data_ptr(), 1, g1.data_ptr(), S, 1, 4096, 4096, 0, 0, counts.data_ptr(), st), "tt_confusion_counts_segments")
+    # a pred pointer off its element size (one byte into int16 labels; four bytes into int64 labels) and a gt pointer off 8 bytes
+    for pred, code, off, size in ((z16, 0, 1, 2), (z64, 1, 4, 8)):
+        with _refused(rf"confusion_counts_segments: pred \(.*\) must be aligned to its {size}-byte elements"):
+            _lib.check(lib.tt_confusion_counts_segments(pred.data_ptr() + off, code, z64.data_ptr(), 1, 4, 3, 3, 0, 0, counts.data_ptr(), st), "tt_confusion_counts_segments")
+    with _refused(r"confusion_counts_segments: pred \(.*\) must be aligned to its 2-byte elements and gt \(.*\) to 8 bytes"):
+        _lib.check(lib.tt_confusion_counts_segments(z16.data_ptr(), 0, z64.data_ptr() + 4, 1, 4, 3, 3, 0, 0, counts.data_ptr(), st), "tt_confusion_counts_segments")
+    with _refused(r"confusion_counts_segments: Cg = 0, Cp = 3: need 1 <= Cg, Cp <= 4096"):
+        _lib.check(lib.tt_confusion_counts_segments(z16.data_ptr(), 0, z64.data_ptr(), 1, 4, 0, 3, 0, 0, counts.data_ptr(), st), "tt_confusion_counts_segments")
+    with _refused(r"confusion_counts_segments: S = 0 segments of n = 4 elements"):
+        _lib.check(lib.tt_confusion_counts_segments(z16.data_ptr(), 0, z64.data_ptr(), 0, 4, 3, 3, 0, 0, counts.data_ptr(), st), "tt_confusion_counts_segments")
+    torch.cuda.synchronize()
+    assert bool((counts == 7).all())                                              # nothing was launched, nothing cleared
 
 
 # ---- the accepted domain of the linear probe's entries, at the edge (include/timetuning_hip.h, N5; linear_probe.hip: probe_shape_error,

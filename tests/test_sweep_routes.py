@@ -8,9 +8,10 @@ import itertools
 
 import pytest
 
-from _sweep_cases import (ADJOINT_LONG_RUN, EVAL_OPS, GRAY_SUM_CAP, HEAD_OPS, IMG_MODES, KM_MAXKD, LP_CAND_CAP, OPS, PAIR_EPILOGUES, PROP_OPS, STEP_OPS,
-                          WGRAD_LONG_RUN, adjoint_run, case_id, gather_tp_log2, km_max_k, lp_caps, lp_chunk, lp_cmax, probe_logits_kernel, sgd_lengths,
-                          table, wgrad_split)
+from _sweep_cases import (ADJOINT_LONG_RUN, BF_MAX_R, DTYPES, DV_OC, EVAL_OPS, GRAY_SUM_CAP, HEAD_OPS, IMG_MODES, KM_ASSIGN_STRIDE, KM_MAX_GRID_Y, KM_MAXKD,
+                          LP_CAND_CAP, METRIC_OPS, OPS, PAIR_EPILOGUES, PROP_OPS, STEP_OPS, WGRAD_LONG_RUN, adjoint_run, bf_radius, bf_tiling, case_id,
+                          cs_blocks, cs_route, davis_tiling, gather_tp_log2, kf_fit_group, kf_fit_kernel, kf_fit_lds, kf_fit_ok, km_accumulate_blocks,
+                          km_max_k, km_tile, km_tile_default, lp_caps, lp_chunk, lp_cmax, probe_logits_kernel, sgd_lengths, table, tiles_of, wgrad_split)
 from timetuning_amd import _lib, hip_ops
 
 NCU = 256
@@ -220,7 +221,7 @@ def test_second_tier_is_appended_and_complete():
     assert STEP_OPS == ("linear_f32", "linear_pairs", "linear_planes", "bwd_pairs", "layernorm", "l2norm", "attention", "ce", "sinkhorn",
                         "sinkhorn_from_q", "sinkhorn_local", "queue_push")
     ops_in_order = list(dict.fromkeys(o for o, _ in CASES))
-    assert tuple(ops_in_order) == STEP_OPS + EVAL_OPS + PROP_OPS + HEAD_OPS == OPS   # appended: the first tier's draws - and case ids - are untouched
+    assert tuple(ops_in_order) == STEP_OPS + EVAL_OPS + PROP_OPS + HEAD_OPS + METRIC_OPS == OPS   # appended: the first tier's draws - and case ids - are untouched
     ids = [case_id(o, p) for o, p in CASES]
     assert len(set(ids)) == len(ids)
     # (the first and the last case of the first tier, as they were before the second tier existed)
@@ -508,7 +509,7 @@ def test_fourth_tier_is_appended_and_the_first_three_are_what_they_were():
     import zlib
 
     assert HEAD_OPS == ("probe_logits", "probe_upsample_ce", "bilinear_adjoint", "probe_wgrad", "sgd", "img_resize", "img_color", "img_blur")
-    earlier = [case_id(o, p) for o, p in CASES if o not in HEAD_OPS]
+    earlier = [case_id(o, p) for o, p in CASES if o not in HEAD_OPS + METRIC_OPS]
     assert len(earlier) == 383 and zlib.crc32("\n".join(earlier).encode()) == 1936048768      # the ids of the first three tiers, unchanged
     assert earlier[-1].startswith("upsample_argmax_hw[") and [o for o, _ in CASES][383] == "probe_logits"
     # every op of the table has a check on the side it runs on (tools/fuzz_ops.py draws from OPS and runs tests/test_hip_sweep.py::run_case)
@@ -632,3 +633,189 @@ def test_clip_pipeline_edges():
     for side in ("H", "W"):
         assert {p[side] for p in bl if p["radius"] == 2.0} >= {1, 2, 3}, side
     assert {(p["H"], p["W"]) for p in bl} >= {(1, 53), (37, 1)} and {p["radius"] for p in bl} >= {0.1, 2.0} and any(p["F"] > 256 for p in bl)
+
+
+# ---- the fifth tier: the k-means family beyond the resident pair (kmeans.hip, kmeans_fit.hip) and the metric counters (confusion.hip,
+# davis.hip, bfscore.hip).  tt_kmeans_fit_shape_ok / tt_kmeans_fit_lds_bytes / tt_kmeans_tile_centroids / tt_confusion_segments_route are host
+# queries and are compared with the restated rules; the tilings of the two counters have none, so their rules stand in
+# tests/_sweep_cases.py with the function they come from.
+def test_fifth_tier_is_appended_and_the_first_four_are_what_they_were():
+    import zlib
+
+    assert METRIC_OPS == ("kmeans_assign_tiled", "kmeans_accumulate_tiled", "kmeans_assign_batched", "kmeans_fit", "confusion_segments", "davis_counts",
+                          "bf_counts")
+    earlier = [case_id(o, p) for o, p in CASES if o not in METRIC_OPS]
+    assert len(earlier) == 558 and zlib.crc32("\n".join(earlier).encode()) == 3298991197      # the ids of the first four tiers, unchanged
+    assert earlier[-1].startswith("img_blur[") and [o for o, _ in CASES][558] == "kmeans_assign_tiled"
+    from _sweep_checks_metric import CHECK as METRIC_CHECK      # (tools/fuzz_ops.py draws from OPS and runs tests/test_hip_sweep.py::run_case)
+
+    assert set(METRIC_CHECK) == set(METRIC_OPS)
+
+
+def test_fit_rules_are_the_librarys(lib):
+    for n, d, k in itertools.product((1, 2, 100, 700, 1300, 5000, 600000, 1 << 20, (1 << 20) + 1), (0, 1, 2, 14, 16, 17, 50, 64, 65),
+                                     (0, 1, 2, 60, 80, 127, 128, 163, 164, 300, 2000)):
+        assert bool(lib.tt_kmeans_fit_shape_ok(n, d, k)) == kf_fit_ok(n, d, k), (n, d, k)
+        assert lib.tt_kmeans_fit_lds_bytes(n, d, k) == (kf_fit_lds(d, k, kf_fit_group(n, d, k)) if kf_fit_ok(n, d, k) else 0), (n, d, k)
+    # the LDS maxima (16 k d + 4 k <= 128 KB): k = 127 at d = 64, 163 at d = 50
+    assert kf_fit_ok(700, 64, 127) and not kf_fit_ok(700, 64, 128) and kf_fit_ok(900, 50, 163) and not kf_fit_ok(900, 50, 164)
+    assert kf_fit_lds(64, 127, 1) == 130556 and kf_fit_lds(50, 163, 1) == 131052
+    # kf_fit_group = 1 from 12 k d + 4 k >= 72 KB on (and just below, where not even one block's fp32 sums fit beside the fixed part)
+    assert kf_fit_group(700, 64, 127) == 1 and kf_fit_group(1500, 14, 300) == 1 and kf_fit_group(1000, 50, 60) == 3 and kf_fit_group(257, 50, 10) == 3
+
+
+def test_fit_every_instantiation_group_regime_and_block_length():
+    cases = _of("kmeans_fit")
+    assert all(kf_fit_ok(p["n"], p["d"], p["k"]) and 1 <= p["niter"] <= 5 and 1 <= p["nredo"] <= 2 for p in cases)
+    # kmeans_fit.hip, tt_kmeans_fit_batched: DREG by km_assign_route, VEC by d % 4 / d % 2 - and 1 whenever x is off a 16-byte boundary
+    assert {kf_fit_kernel(p["d"], p["offset"]) for p in cases} == set(itertools.product((16, 64), (1, 2, 4)))
+    assert {p["d"] for p in cases if kf_fit_kernel(p["d"], p["offset"]) == (16, 2)} >= {2, 6, 10, 14}
+    for dreg, d in ((16, 12), (64, 64)):      # the unaligned fallback at d % 4 == 0 on both register sizes, beside the aligned run of the same case
+        off = [p for p in cases if p["offset"] % 4 and p["d"] == d]
+        assert off and all(kf_fit_kernel(d, p["offset"]) == (dreg, 1) for p in off) and any(dict(p, offset=0) in cases for p in off), d
+    assert any(p["offset"] == 0 and kf_fit_kernel(p["d"], 0)[1] == 1 for p in cases)      # VEC 1 because d is odd
+    # kf_fit_group against the blocks of km_accumulate_blocks
+    gb = [(kf_fit_group(p["n"], p["d"], p["k"]), *km_accumulate_blocks(p["n"]), p) for p in cases]
+    assert any(g == 1 and b == 6 and (p["d"], p["k"]) == (64, 127) for g, b, _, p in gb) and any(g == 1 and b == 11 and (p["d"], p["k"]) == (50, 80) for g, b, _, p in gb)
+    assert any(1 < g < b and b % g for g, b, _, p in gb) and any(1 < g < b and b % g == 0 for g, b, _, p in gb)      # a ragged last pass; whole passes
+    assert any(g == b > 1 for g, b, _, p in gb) and any(g == b == 1 for g, b, _, p in gb)
+    assert any(g == 1 and b > 1 and p["d"] <= 16 for g, b, _, p in gb)                      # group 1 on the 16-register kernel (d 14, k 300)
+    # both LDS maxima are FITTED, not only queried
+    assert any((p["d"], p["k"]) == (64, 127) for p in cases) and any((p["d"], p["k"]) == (50, 163) for p in cases)
+    # points per block: up to 128 with several blocks, and beyond (n > 524 288: 147 and 256, the longest fp32 runs of the fit)
+    assert any(ppb <= 128 and b > 1 for _, b, ppb, _ in gb) and {ppb for _, _, ppb, _ in gb if ppb > 128} == {147, 256}
+    assert any(p["n"] == 1 << 20 for p in cases)                                             # KF_MAXN itself
+    # threads without a point; every point a cluster; one point; more problems than one launch; the flagged problem
+    assert any(p["n"] < 512 for p in cases) and any(p["n"] == p["k"] > 1 for p in cases) and any(p["n"] == 1 for p in cases)
+    assert any(p["B"] > KM_MAX_GRID_Y for p in cases) and sum(p["empty"] for p in cases) == 1 and all(p["B"] >= 3 for p in cases if p["empty"])
+    assert all(p["B"] * p["n"] * p["d"] * 4 <= 300 << 20 for p in cases)
+
+
+def test_tiled_assignment_every_kernel_tile_count_and_stride(lib):
+    cases = _of("kmeans_assign_tiled")
+    assert all(lib.tt_kmeans_tile_centroids(d) == km_tile_default(d) for d in list(range(1, 200)) + [1023, 1024, 1025, 0])
+    assert all(0 <= p["tile_k"] <= km_tile_default(p["d"]) and p["P"] * p["d"] * 4 <= 300 << 20 for p in cases)
+    several = lambda p: km_tile(p["d"], p["tile_k"]) < p["k"]
+    # kmeans_assign_tiled_kernel<16>, <64>, <0> x {one tile, several} x {at most 4096 x 256 points, the grid-stride loop}: <64> stages the
+    # point tile again on every stride, <0> keeps ONE tile resident over the strides and reloads several
+    seen = {(km_assign_kernel(p["d"]), several(p), p["P"] > KM_ASSIGN_STRIDE) for p in cases}
+    assert seen == set(itertools.product((16, 64, 0), (False, True), (False, True)))         # ((0, False, True): `resident` kept past the first stride)
+    # the last tile's size: 1, 2, 3 and 5 behind whole tiles (the 4-wide block and its tail); tile_k 1; the last workgroup's points
+    last = {p["k"] - (p["k"] - 1) // km_tile(p["d"], p["tile_k"]) * km_tile(p["d"], p["tile_k"]) for p in cases if several(p)}
+    assert last >= {1, 2, 3, 5} and any(p["tile_k"] == 1 and p["k"] > 1 for p in cases)
+    assert {p["P"] for p in cases} >= {1, 255, 256, 257}
+    # a duplicate either side of the first tile boundary on each kernel; k one above the default tile at d 16, 64, 128
+    for kern in (16, 64, 0):
+        assert any(p["dup"] == 2 and several(p) and km_assign_kernel(p["d"]) == kern for p in cases), kern
+    assert all(several(p) for p in cases if p["dup"] == 2)
+    for d in (16, 64, 128):
+        assert any(p["d"] == d and p["tile_k"] == 0 and p["k"] == km_tile_default(d) + 1 and not lib.tt_kmeans_shape_ok(d, p["k"]) for p in cases), d
+    assert any(p["d"] == 1024 for p in cases)
+
+
+def test_tiled_accumulation_every_regime():
+    cases = _of("kmeans_accumulate_tiled")
+    tiles = lambda p: (p["k"] + km_tile(p["d"], p["tile_k"]) - 1) // km_tile(p["d"], p["tile_k"])
+    assert all(0 <= p["tile_k"] <= km_tile_default(p["d"]) for p in cases)
+    assert any(tiles(p) > KM_MAX_GRID_Y for p in cases) and any(tiles(p) == 1 for p in cases) and any(1 < tiles(p) <= KM_MAX_GRID_Y for p in cases)
+    assert {p["mode"] for p in cases} == {"rand", "skip", "one"}
+    grids = [km_accumulate_grid(p["P"]) for p in cases]
+    assert {p["P"] for p in cases} >= {524288, 524289, 600000} and any(ppb > 128 for _, ppb, _ in grids) and any(e > 0 for _, _, e in grids)
+    assert all(km_accumulate_blocks(p["P"]) == km_accumulate_grid(p["P"])[:2] for p in cases)
+    assert any(p["mode"] == "one" and km_accumulate_grid(p["P"])[1] > 128 for p in cases)
+    assert any(p["d"] == 257 and tiles(p) > 1 for p in cases)                                # a thread owns two columns, k above the tile
+    assert any(tiles(p) > 1 and p["k"] % km_tile(p["d"], p["tile_k"]) == 1 for p in cases)   # a last tile of one cluster
+    assert any(p["tile_k"] == 0 and p["k"] > km_max_k(p["d"]) for p in cases) and any(p["tile_k"] > p["k"] for p in cases)
+
+
+def test_batched_assignment_every_kernel_and_the_problem_loop():
+    cases = _of("kmeans_assign_batched")
+    assert all(p["k"] <= km_max_k(p["d"]) for p in cases)
+    for kern in (16, 64, 0):
+        assert any(km_assign_kernel(p["d"]) == kern and p["B"] == 3 and p["N"] % 256 for p in cases), kern
+        assert any(km_assign_kernel(p["d"]) == kern and p["k"] == km_max_k(p["d"]) and p["B"] > 1 for p in cases), kern
+    assert any(p["B"] > KM_MAX_GRID_Y for p in cases) and any(p["N"] == 1 for p in cases)      # launch_assign's y0 loop
+
+
+def test_confusion_segments_every_route_regime_and_misalignment(lib):
+    cases = _of("confusion_segments")
+    for Cg, Cp in itertools.product((0, 1, 3, 127, 128, 129, 4096, 4097), repeat=2):
+        assert lib.tt_confusion_segments_route(Cg, Cp) == cs_route(Cg, Cp)
+    assert all(cs_route(p["Cg"], p["Cp"]) for p in cases)
+    # cs_blocks: elements per workgroup set by CS_MIN_PER_WG, by four per LDS cell, by the cap of 1024 workgroups.  The global route has no
+    # cells to zero or flush, so only two of the three regimes exist there
+    regimes = lambda route: {cs_blocks(p["n"], p["Cg"], p["Cp"])[1] for p in cases if cs_route(p["Cg"], p["Cp"]) == route}
+    assert regimes(1) == {"min", "cells", "spread"} and regimes(2) == {"min", "spread"}
+    assert cs_blocks(8192, 5, 10) == (1, "min") and cs_blocks(8193, 5, 10) == (2, "min")
+    assert cs_blocks(42000, 21, 500) == (1, "cells") and cs_blocks(42001, 21, 500) == (2, "cells")
+    assert cs_blocks(9000000, 3, 7) == (1024, "spread") and cs_blocks(1024 * 8192, 3, 7) == (1024, "min")
+    have = {(p["n"], p["Cg"], p["Cp"]) for p in cases}
+    assert have >= {(8192, 5, 10), (8193, 5, 10), (42000, 21, 500), (42001, 21, 500), (9000000, 3, 7)}
+    # pred off a 16-byte boundary with MORE THAN ONE workgroup per segment: heads of 1 ... 7 elements (int16) and 1 (int64), on both routes
+    for route in (1, 2):
+        multi = [p for p in cases if cs_route(p["Cg"], p["Cp"]) == route and cs_blocks(p["n"], p["Cg"], p["Cp"])[0] > 1 and p["S"] > 1]
+        assert {p["offset"] for p in multi if p["dtype"] == "i16"} >= set(range(1, 8)), route
+        assert any(p["offset"] == 1 and p["dtype"] == "i64" for p in multi), route
+        assert any(p["n"] % 8 for p in multi)                                                 # a tail behind the last strip
+    head = lambda p: (8 - p["offset"]) % 8 if p["dtype"] == "i16" else p["offset"] % 2
+    assert any(p["n"] < 8 for p in cases) and any(head(p) > p["n"] for p in cases) and any(p["n"] % 2 and p["S"] > 1 and p["dtype"] == "i16" for p in cases)
+    assert {p["ignore"] for p in cases} >= {"", 0, 255} and {p["dtype"] for p in cases} == {"i16", "i64"}
+    assert all(p["S"] * p["n"] * 10 <= 300 << 20 for p in cases)
+
+
+def _davis_rows(radius):
+    from timetuning_amd import mask_propagation as MP
+
+    return MP.disk(radius).shape[0]
+
+
+def davis_class(H, W, rows, oc):
+    """How far davis_tiling shrank: (halvings of TH, whether ow stayed / shrank / shrank to one word)."""
+    words = (W + 63) // 64
+    ow0 = (words + (words + 7) // 8 - 1) // ((words + 7) // 8)
+    TH, ow = davis_tiling(H, W, rows, oc)
+    th0, halvings = min(H, 32), 0
+    while th0 > TH:
+        th0, halvings = th0 // 2, halvings + 1
+    assert th0 == TH
+    return halvings, ("full" if ow == ow0 else ("one" if ow == 1 else "shrunk"))
+
+
+def test_davis_every_tiling_class_and_block_decomposition():
+    cases = _of("davis_counts")
+    # every class davis_tiling returns over a wide grid of (H, W, element rows, objects per pass) - and nothing is ever refused
+    grid = {davis_class(H, W, rows, oc) for H, W, rows, oc in itertools.product((1, 6, 8, 9, 16, 20, 31, 32, 40, 70, 480), (1, 64, 65, 200, 300, 512, 513, 600, 854, 1100, 4000),
+                                                                                (1, 3, 6, 17, 41, 81, 127), (1, 2, 3, 4))}
+    mine = {davis_class(p["H"], p["W"], _davis_rows(p["radius"]), min(p["O"], DV_OC)) for p in cases}
+    assert mine == grid, (sorted(grid - mine), sorted(mine - grid))
+    tiling = lambda p: davis_tiling(p["H"], p["W"], _davis_rows(p["radius"]), min(p["O"], DV_OC))
+    assert davis_tiling(70, 300, 127, 4) == (8, 1) and tiles_of(70, 300, 8, 1) == (9, 5)
+    assert davis_tiling(40, 600, 81, 4) == (8, 3) and davis_tiling(40, 512, 17, 4)[1] == 8 and davis_tiling(40, 513, 17, 4)[1] == 5
+    have = {(p["T"], p["H"], p["W"], p["O"], p["radius"]) for p in cases}
+    assert have >= {(2, 70, 300, 4, 63), (2, 40, 513, 4, 8), (2, 40, 512, 4, 8), (2, 40, 600, 5, 40), (2, 6, 200, 4, 63), (3, 70, 1100, 3, 2)}
+    # block index -> (frame, tile row, tile column) with all three above 1
+    assert any(p["T"] > 1 and min(tiles_of(p["H"], p["W"], *tiling(p))) > 1 for p in cases)
+    assert any(p["T"] > 2 and min(tiles_of(p["H"], p["W"], *tiling(p))) > 2 for p in cases)
+    assert any(p["O"] > DV_OC and p["O"] % DV_OC == 1 for p in cases) and any(p["H"] < 8 and p["W"] > 64 for p in cases)
+    assert {(p["pt"], p["gtt"], p["void"]) for p in cases} == set(itertools.product(DTYPES, DTYPES, (0, 1)))
+    assert any(_davis_rows(p["radius"]) % 2 == 0 for p in cases) and any(_davis_rows(p["radius"]) == 127 for p in cases)
+
+
+def test_bf_tiling_never_shrinks_and_block_decomposition():
+    # bfscore.hip, bf_tiling: over the entry's whole domain (R <= 63, up to 8 words per tile, TH <= 32) the planes need at most 63 168 bytes
+    # of the 64 KB budget: its shrink loop never runs.  A change of the budget or of the LDS layout that makes it live shows here
+    worst = 0
+    for H, W, R in itertools.product((1, 2, 8, 31, 32, 33, 100, 480), list(range(1, 1100, 61)) + [512, 513, 1024, 1025, 4096, 100000], range(0, BF_MAX_R + 1)):
+        TH, ow, shrunk = bf_tiling(H, W, R)
+        assert not shrunk and TH == min(H, 32) and ow <= 8, (H, W, R)
+        worst = max(worst, 8 * (2 * (TH + 2 * R + 2) * (ow + 2) + 2 * (TH + 2 * R) * (ow + 2) + 6 * TH * ow))
+    assert worst == 63168
+    assert bf_radius(64) == 63 and bf_radius(63.9) == 63 and bf_radius(2) == 1 and bf_radius(0) == 0 and bf_radius(31) == 30
+    cases = _of("bf_counts")
+    tiling = lambda p: bf_tiling(p["H"], p["W"], bf_radius(p["t"]))[:2]
+    assert any(p["P"] > 2 and min(tiles_of(p["H"], p["W"], *tiling(p))) > 2 for p in cases)      # pair, tile row, tile column all above 1
+    for W, ow in ((512, 8), (513, 5)):      # one tile column of 8 words / two of 5, at the largest element
+        assert any(p["W"] == W and bf_radius(p["t"]) == BF_MAX_R and tiling(p)[1] == ow and p["P"] > 1 for p in cases), W
+    have = {(p["P"], p["H"], p["W"], p["t"]) for p in cases}
+    assert have >= {(3, 70, 1100, 2), (2, 40, 513, 64), (2, 40, 512, 64), (2, 40, 600, 31)}
+    assert any(p["H"] < 32 and p["W"] > 512 for p in cases) and any(p["t"] == 0 for p in cases) and any(p["H"] * p["W"] == 1 for p in cases)
