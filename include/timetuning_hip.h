@@ -162,7 +162,11 @@ int tt_layernorm_fwd(const float* x, const float* gamma, const float* beta, floa
  * bytes of device memory (16 floats 256 bytes apart: the waves of a kernel spread their atomics over them, thousands on one address
  * serialise) that the caller ZEROED - or NULL.  The kernel raises the slot to max |.| of the gradient it writes (relaxed atomic max on
  * the non-negative floats' bits: deterministic).  That gradient is the dy of the next Linear's backward: tt_split_pairs_dual_parts takes
- * the slot as amax_in and needs no max pass of its own for the power-of-two scale of the split (measured: C2 -0.8 %, C1 -1 %). */
+ * the slot as amax_in and needs no max pass of its own for the power-of-two scale of the split (measured: C2 -0.8 %, C1 -1 %).
+ * The published value is max |dx| over the rows the call WROTE.  tt_layernorm_bwd with skip_group never visits token 0's rows of dx:
+ * without add_to_dx the caller zeroed them and the value is max |dx| of the whole tensor; with add_to_dx they keep what was accumulated
+ * before, which the maximum would miss - amax_out together with add_to_dx and skip_group is therefore REFUSED (no call site needs it:
+ * the residual-branch norms accumulate without skip_group, the final norm drops token 0 into a zeroed dx). */
 size_t tt_amax_slot_bytes(void);
 int tt_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                      float* dx, float* dgamma, float* dbeta, int rows, int D, int add_to_dx, int skip_group,

@@ -612,6 +612,7 @@ int tt_cpu_layernorm_bwd(const float* dy, const float* x, const float* gamma, co
                          float* dgamma, float* dbeta, int rows, int D, int add_to_dx, int skip_group, void* workspace,
                          size_t workspace_bytes, float* amax_out, tt_stream_t stream) {
   (void)workspace; (void)workspace_bytes; (void)stream;
+  if (amax_out && add_to_dx && skip_group) return -1;   /* refused as by tt_layernorm_bwd: token 0's rows of dx are not visited */
   double* dg = (double*)calloc((size_t)2 * D, sizeof(double));
   if (!dg) return -3;
   double* db = dg + D;

@@ -517,6 +517,198 @@ def _bf_counts(rng):
     return BFC(int(rng.integers(1, 4)), int(rng.integers(1, 100)), int(rng.integers(1, 700)), _ch(rng, (1, 2, 5, 16)))
 
 
+# ---- sixth tier: the operand-preparation kernels (gemm_planes.hip) and the gradient producers' published maxima (common.hpp amax_publish)
+# (checks: tests/_sweep_checks_prep.py, on the C twin and on the HIP library)
+CONVERT_CAP = 4096 * 256 * 8      # gemm_planes.hip, tt_split_pairs / tt_join_pairs / tt_split_planes: 4096 workgroups x 256 threads x 8 elements - beyond, the stride loop
+AMAX_PART, AMAX_PARTS_CAP = 4096, 256      # gemm_planes.hip, split_pairs_dual_impl: n_part = min(ceil(R C / 4096), kAmaxParts)
+MULTI_MAXN = 32                   # gemm_planes.hip, PairTable::MAXN: entries per launch of tt_split_pairs_dual_multi
+LN_BWD_WG_CAP, LN_MAX_D = 1024, 1024      # rowops.hip, ln_bwd_wgs; 64 * kMaxPerLane
+VALUE_KINDS = ("normal", "loguniform", "big", "inf", "nan", "zero", "subnormal")
+MULTI_SHAPES = ((1, 1, "t"), (65, 96, "both"), (33, 32, "row"), (64, 64, "t"), (197, 160, "both"), (31, 65, "t"), (130, 128, "row"), (641, 449, "t"),
+                (32, 96, "both"), (63, 33, "t"), (1, 32, "row"))      # (R, C, outputs) of entry (i + rot) % 11 of a split_multi table
+
+
+def ceil_to(v: int, m: int) -> int:
+    return (v + m - 1) // m * m
+
+
+def sd_rpad(p: dict) -> int:
+    """Rpad of a split_dual / transpose_pairs case: the default ceil32(R) plus ``rpad`` (0, 32 or 64)."""
+    return ceil_to(p["R"], 32) + p["rpad"]
+
+
+def sd_kernel(p: dict) -> tuple:
+    """gemm_planes.hip, split_pairs_dual_impl -> ("rows", SUM) for split_rows_kernel<SUM> (dr && !dt && C % 128 == 0 && 16-byte aligned source and
+    row output && TT_SPLIT_ROWS != 0), else ("tile", ROW, SUM) for transpose_pairs_kernel<false, ROW, SUM>."""
+    if p["row"] and not p["t"] and p["C"] % 128 == 0 and p["off"] == 0 and p["sr"]:
+        return ("rows", bool(p["colsum"]))
+    return ("tile", bool(p["row"]), bool(p["colsum"]))
+
+
+def amax_n_part(n: int) -> tuple:
+    """split_pairs_dual_impl -> (n_part, its class: "1", "2..255", "256" or "capped", whether amax_partial_kernel's scalar tail runs)."""
+    want = (n + AMAX_PART - 1) // AMAX_PART
+    cls = "1" if want == 1 else ("2..255" if want < AMAX_PARTS_CAP else ("256" if want == AMAX_PARTS_CAP else "capped"))
+    return min(want, AMAX_PARTS_CAP), cls, n % 4 != 0
+
+
+def tp_rpad(p: dict) -> int:
+    """Rpad of a transpose_planes case: "R" = R itself, "c64" = ceil64(R) (the wrapper's default), "c64+64"."""
+    return {"R": p["R"], "c64": ceil_to(p["R"], 64), "c64+64": ceil_to(p["R"], 64) + 64}[p["rpad"]]
+
+
+def tp_store_branch(rpad: int) -> str:
+    """gemm_planes.hip, transpose_planes_kernel: 8-byte stores of four bf16 when Rpad % 4 == 0 (aligned for every row), else one bf16 per lane."""
+    return "scalar" if rpad % 4 else ("quad" if rpad % 64 else "quad64")
+
+
+def multi_entries(p: dict) -> list:
+    return [MULTI_SHAPES[(i + p["rot"]) % len(MULTI_SHAPES)] for i in range(p["n"])]
+
+
+def ln_bwd_plan(rows: int, D: int, off: int = 0) -> tuple:
+    """rowops.hip, tt_layernorm_bwd -> (kernel: "vec1" / "vec3" / "vec6" at D 128 / 384 / 768 with 8-byte aligned buffers, else "general";
+    workgroups = min(ceil(rows / 8), 1024); rows per workgroup; workgroups that own no row)."""
+    wgs = max(1, min((rows + 7) // 8, LN_BWD_WG_CAP))
+    rpw = (rows + wgs - 1) // wgs
+    kern = {128: "vec1", 384: "vec3", 768: "vec6"}.get(D, "general") if off % 2 == 0 else "general"
+    return kern, wgs, rpw, wgs - (rows + rpw - 1) // rpw
+
+
+def CV(what, n, vals="normal", P=0) -> dict:
+    """what: "pairs" (tt_split_pairs and tt_join_pairs of its result) or "planes" (tt_split_planes at P planes)"""
+    return dict(what=what, P=P, n=n, vals=vals)
+
+
+def SD(R, C, t=1, row=0, colsum="", scale="", mag=1.0, vals="normal", rpad=0, off=0, sr=1) -> dict:
+    """colsum: "", "fold" (tt_split_pairs_dual) or "parts" (tt_split_pairs_dual_parts); scale: "", "own" (the split's max pass) or "slot" (a
+    producer's amax slot); off: floats the source starts off a 16-byte boundary; sr: 0 = TT_SPLIT_ROWS 0 for the call"""
+    assert (t or row) and (not row or C % 32 == 0) and not (off and scale)
+    return dict(R=R, C=C, rpad=rpad, t=t, row=row, colsum=colsum, scale=scale, mag=mag, vals=vals, off=off, sr=sr)
+
+
+def SM(n, rot=0) -> dict:
+    return dict(n=n, rot=rot)
+
+
+def TPP(R, C, rpad=0) -> dict:
+    return dict(R=R, C=C, rpad=rpad)
+
+
+def TPL(R, C, rpad="c64", colsum=0) -> dict:
+    return dict(R=R, C=C, rpad=rpad, colsum=colsum)
+
+
+def GA(producer, rows, D, N=0, gscale=1.0, accum=0, off=0) -> dict:
+    """producer: "ln_bwd" (N: tokens per frame of a call that drops token 0 - rows are then F (N - 1); 0 = none) or "l2_bwd"; off: floats
+    every buffer starts off a 16-byte boundary (1: the 8-byte LayerNorm kernels fall back to the general one)"""
+    assert not (N and accum), "refused by tt_layernorm_bwd with an amax slot (include/timetuning_hip.h)"
+    return dict(producer=producer, rows=rows, D=D, N=N, gscale=gscale, accum=accum, off=off)
+
+
+def GAT(producer, F, N, H, gscale=1.0, dslot=0) -> dict:
+    """producer: "attn_bwd" or "attn_bwd_pairs" (dslot: max |dout| comes from a producer's slot, not from the call's own max pass)"""
+    return dict(producer=producer, F=F, N=N, H=H, gscale=gscale, dslot=dslot)
+
+
+def GD(M, N, K, gelu=0, gscale=1e-3) -> dict:
+    """tt_linear_bwd_data_pairs with an amax slot, dx [M, K] = dy [M, N] @ w [N, K]: "dgrad_general" (no gelu_pre: pairs8_try declines, the
+    general kernel runs) or "dgrad_gelu" (x gelu'(pre): the persistent kernels' epilogue where the shape is theirs)"""
+    return dict(producer="dgrad_gelu" if gelu else "dgrad_general", M=M, N=N, K=K, gscale=gscale)
+
+
+def pairs_general_tile(M: int, N: int, K: int, splits: int = 1, ncu: int = 256) -> str:
+    """gemm_planes.hip, linear_pairs_impl: the general pair kernel's tile for an output [M, N] - "big" (128 x 128), "wide" (64 x 128), or
+    64 x 64 with a ring of four slabs while the grid is under two workgroups per CU ("small4"), of three beyond ("small3")."""
+    t128 = ((M + 127) // 128) * (N // 128)
+    if N % 128 == 0 and t128 * splits >= 3 * 256:
+        return "big"
+    if N % 128 == 0 and ((M + 63) // 64) * (N // 128) * splits >= 2 * 256:
+        return "wide"
+    return "small4" if ((M + 63) // 64) * (N // 64) * splits <= 2 * ncu else "small3"
+
+
+TWIN_MAX_MACS = 2e7      # the twin's products are naive loops over pair_dot: beyond this many multiply-adds a case runs on the GPU only
+
+
+def prep_case_on_twin(op: str, p: dict) -> bool:
+    if op == "grad_amax" and p["producer"].startswith("dgrad"):
+        return p["M"] * p["N"] * p["K"] <= TWIN_MAX_MACS
+    if op == "patch_embed":
+        return p["F"] * (p["gh"] * p["gw"] + 1) * p["D"] * p["C"] * p["P"] * p["P"] <= TWIN_MAX_MACS
+    return True
+
+
+def PE(mode, F, C, P, gh, gw, D, fmap="", lean=1) -> dict:
+    """mode: "f32", "pairs", "planes"; fmap: "" (frame f of F), "rev" (reversed), "repeat" (F draws from a source of three more frames than it
+    uses); lean: 0 = TT_PATCH_LEAN 0 for the call (the f32 entry's general kernel on a lean shape)"""
+    return dict(mode=mode, F=F, C=C, P=P, gh=gh, gw=gw, D=D, fmap=fmap, lean=lean)
+
+
+def patch_f32_route(p: dict, tile: int) -> str:
+    """gemm_nt_fast.hip, try_launch_patch_embed_fast: the lean kernel at P 16, D % 64 == 0, W % 4 == 0 (and TT_PATCH_LEAN != 0), 128 rows per
+    tile where ``tile`` = tt_gemm_tile_choice(F n, D, 1) is 0 or 2, else 64; the general kernel otherwise."""
+    if p["P"] != 16 or p["D"] % 64 or (p["gw"] * p["P"]) % 4 or not p["lean"]:
+        return "general"
+    return "lean128" if tile in (0, 2) else "lean64"
+
+
+def LNL(Fr, Nt, D, drop=0) -> dict:
+    return dict(Fr=Fr, Nt=Nt, D=D, drop=drop)
+
+
+def _convert(rng):
+    if rng.random() < 0.5:
+        return CV("pairs", 32 * int(rng.integers(1, 40000)), _ch(rng, VALUE_KINDS))
+    return CV("planes", 8 * int(rng.integers(1, 160000)), _ch(rng, VALUE_KINDS), int(rng.integers(1, 4)))
+
+
+def _split_dual(rng):
+    row = _b(rng)
+    t = 1 if not row else _b(rng)
+    C = 32 * int(rng.integers(1, 10)) if row else int(rng.integers(1, 300))
+    scale = _ch(rng, ("", "own", "slot"))
+    vals = _ch(rng, ("normal", "normal", "normal", "zero", "big", "inf"))
+    return SD(int(rng.integers(1, 700)), C, t, row, _ch(rng, ("", "fold", "parts")), scale, _ch(rng, (1.0, 1e-3, 3e-8, 1e-30)) if vals == "normal" else 1.0,
+              vals, _ch(rng, (0, 0, 32, 64)), 0 if scale else _b(rng, 0.2), _b(rng, 0.8))
+
+
+def _split_multi(rng):
+    return SM(int(rng.integers(1, 70)), int(rng.integers(0, len(MULTI_SHAPES))))
+
+
+def _transpose_pairs(rng):
+    return TPP(int(rng.integers(1, 700)), 32 * int(rng.integers(1, 10)), _ch(rng, (0, 32, 64)))
+
+
+def _transpose_planes(rng):
+    return TPL(int(rng.integers(1, 700)), int(rng.integers(1, 300)), _ch(rng, ("R", "c64", "c64+64")), _b(rng))
+
+
+def _grad_amax(rng):
+    if rng.random() < 0.3:
+        return GA("l2_bwd", int(rng.integers(1, 300)), _ch(rng, (1, 3, 64, 65, 500, 1024)), gscale=_ch(rng, (1.0, 1e-7)))
+    if rng.random() < 0.2:
+        return GAT(_ch(rng, ("attn_bwd", "attn_bwd_pairs")), int(rng.integers(1, 3)), int(rng.integers(1, 300)), int(rng.integers(1, 4)), _ch(rng, (1.0, 1e-7)), _b(rng))
+    if rng.random() < 0.2:
+        return GD(int(rng.integers(1, 700)), 64 * int(rng.integers(1, 4)), 64 * int(rng.integers(1, 7)), _b(rng), _ch(rng, (1e-3, 3e-8)))
+    N = _ch(rng, (0, 0, 2, 5, 17))
+    F = int(rng.integers(1, 40))
+    return GA("ln_bwd", F * (N - 1) if N else int(rng.integers(1, 600)), _ch(rng, (1, 63, 64, 65, 96, 128, 384, 768, 1000)), N, _ch(rng, (1.0, 1e-7)),
+              0 if N else _b(rng), _b(rng, 0.3))
+
+
+def _patch_embed(rng):
+    mode = _ch(rng, ("f32", "pairs", "planes"))
+    P = _ch(rng, (4, 8, 16))
+    C = _ch(rng, [c for c in (1, 2, 3, 4) if (c * P * P) % (64 if mode == "planes" else (32 if mode == "pairs" else 1)) == 0])
+    return PE(mode, int(rng.integers(1, 5)), C, P, int(rng.integers(1, 6)), int(rng.integers(1, 6)), _ch(rng, (64, 128, 192)), _ch(rng, ("", "rev", "repeat")))
+
+
+def _layernorm_long(rng):
+    return LNL(int(rng.integers(1, 9)), int(rng.integers(2, 40)), _ch(rng, (64, 96, 128, 384, 768, 1000)), _b(rng))
+
+
 DRAW = {"linear_f32": _linear_f32, "linear_pairs": _linear_pairs, "linear_planes": _linear_planes, "bwd_pairs": _bwd_pairs,
         "layernorm": _layernorm, "l2norm": _l2norm, "attention": _attention, "ce": _ce, "sinkhorn": _sinkhorn,
         "sinkhorn_from_q": _sinkhorn_from_q, "sinkhorn_local": _sinkhorn_local, "queue_push": _queue_push}
@@ -538,8 +730,12 @@ HEAD_OPS = tuple(DRAW)[len(STEP_OPS) + len(EVAL_OPS) + len(PROP_OPS):]
 DRAW.update({"kmeans_assign_tiled": _kmeans_assign_tiled, "kmeans_accumulate_tiled": _kmeans_accumulate_tiled,
              "kmeans_assign_batched": _kmeans_assign_batched, "kmeans_fit": _kmeans_fit, "confusion_segments": _confusion_segments,
              "davis_counts": _davis_counts, "bf_counts": _bf_counts})
+METRIC_OPS = tuple(DRAW)[len(STEP_OPS) + len(EVAL_OPS) + len(PROP_OPS) + len(HEAD_OPS):]
+# (and the sixth tier after the first five)
+DRAW.update({"convert": _convert, "split_dual": _split_dual, "split_multi": _split_multi, "transpose_pairs": _transpose_pairs,
+             "transpose_planes": _transpose_planes, "patch_embed": _patch_embed, "grad_amax": _grad_amax, "layernorm_long": _layernorm_long})
 OPS = tuple(DRAW)
-METRIC_OPS = OPS[len(STEP_OPS) + len(EVAL_OPS) + len(PROP_OPS) + len(HEAD_OPS):]
+PREP_OPS = OPS[len(STEP_OPS) + len(EVAL_OPS) + len(PROP_OPS) + len(HEAD_OPS) + len(METRIC_OPS):]
 
 COUNTS = {"linear_f32": 6, "linear_pairs": 8, "linear_planes": 4, "bwd_pairs": 6, "layernorm": 5, "l2norm": 3, "attention": 6, "ce": 3,
           "sinkhorn": 6, "sinkhorn_from_q": 3, "sinkhorn_local": 3, "queue_push": 3,
@@ -549,7 +745,8 @@ COUNTS = {"linear_f32": 6, "linear_pairs": 8, "linear_planes": 4, "bwd_pairs": 6
           "probe_logits": 4, "probe_upsample_ce": 4, "bilinear_adjoint": 3, "probe_wgrad": 4, "sgd": 3, "img_resize": 4, "img_color": 4,
           "img_blur": 3,
           "kmeans_assign_tiled": 4, "kmeans_accumulate_tiled": 4, "kmeans_assign_batched": 3, "kmeans_fit": 4, "confusion_segments": 4,
-          "davis_counts": 4, "bf_counts": 4}
+          "davis_counts": 4, "bf_counts": 4,
+          "convert": 4, "split_dual": 4, "split_multi": 3, "transpose_pairs": 3, "transpose_planes": 4, "patch_embed": 4, "grad_amax": 4, "layernorm_long": 3}
 
 # The route boundaries, pinned (tests/test_sweep_routes.py names the rule each one reaches)
 PINNED = {
@@ -881,6 +1078,101 @@ PINNED = {
         BFC(3, 70, 1100, 2), BFC(2, 40, 513, 64), BFC(2, 40, 512, 64), BFC(2, 40, 600, 31), BFC(2, 20, 700, 5),
         # small maps (the per-pixel definition runs on these): one pixel, a row, a column, t 0 and 0.5 (no match but the pixel itself)
         BFC(3, 1, 1, 2), BFC(2, 1, 60, 2), BFC(2, 24, 1, 2.5), BFC(2, 13, 29, 0), BFC(2, 13, 29, 0.5), BFC(2, 24, 64, 5), BFC(1, 20, 33, 16),
+    ],
+    # ---- sixth tier (gemm_planes.hip: the conversions, the dual split and its table form, the two transposes; rowops.hip: the backward
+    # producers' maxima)
+    "convert": [
+        # one pair group / one 8-element chunk with every kind of value; the grid cap of 8 388 608 elements exactly and one group / chunk
+        # beyond it (the stride loop: workgroup 0's first thread comes round again), at 1, 2 and 3 planes
+        *[CV("pairs", 32, v) for v in VALUE_KINDS], *[CV("planes", 8, v, P) for v, P in zip(VALUE_KINDS, (1, 2, 3, 1, 2, 3, 3))],
+        CV("pairs", CONVERT_CAP), CV("pairs", CONVERT_CAP + 32, "loguniform"), CV("planes", CONVERT_CAP, "normal", 1),
+        CV("planes", CONVERT_CAP + 8, "loguniform", 3), CV("planes", CONVERT_CAP + 8, "subnormal", 2), CV("pairs", 4128, "subnormal"),
+        CV("pairs", 96000, "big"), CV("pairs", 96000, "inf"), CV("pairs", 96000, "nan"), CV("planes", 96008, "nan", 3), CV("planes", 96008, "inf", 2),
+    ],
+    "split_dual": [
+        # transpose_pairs_kernel<false, ROW, SUM>, the four of them, at R 1 ... 197 (Rpad % 64 == 32 at R 1, 31, 32, 65, 197: the last tile's
+        # second pair group lies beyond Rpad) - transposed pairs alone at C 1, 31, 33, 65; with row pairs at C 32, 96, 160
+        SD(1, 1), SD(31, 31), SD(32, 33), SD(33, 65), SD(63, 1, colsum="fold"), SD(64, 31, colsum="parts"), SD(65, 33, colsum="fold"), SD(197, 65, colsum="parts"),
+        SD(1, 32, row=1), SD(31, 96, row=1), SD(32, 160, row=1), SD(33, 32, row=1, colsum="fold"), SD(63, 96, row=1, colsum="parts"),
+        SD(64, 160, row=1, colsum="fold"), SD(65, 32, row=1, colsum="parts"), SD(197, 96, row=1, colsum="fold"), SD(197, 160, row=1),
+        # Rpad beyond the default: 32 and 64 more (whole tiles of zero rows)
+        SD(33, 65, rpad=32), SD(65, 96, row=1, rpad=64, colsum="fold"), SD(197, 33, rpad=64, colsum="parts"), SD(32, 32, row=1, rpad=32),
+        # no transposed output.  The streaming kernel either side of its gate: C 128 and 256 against 96 and 160; the same source one float
+        # off a 16-byte boundary; TT_SPLIT_ROWS 0; R 1 ... 130 (a wave owns 16 rows of a 64-row block)
+        *[SD(R, C, t=0, row=1, colsum=cs) for R, C, cs in ((1, 128, ""), (15, 256, "fold"), (16, 128, "parts"), (17, 256, ""), (63, 128, "fold"),
+                                                          (65, 256, "parts"), (130, 128, "fold"), (130, 256, ""))],
+        SD(65, 96, t=0, row=1, colsum="fold"), SD(130, 160, t=0, row=1, colsum="parts"), SD(17, 96, t=0, row=1),
+        SD(65, 128, t=0, row=1, colsum="fold", off=1), SD(130, 256, t=0, row=1, off=1), SD(65, 128, t=0, row=1, colsum="fold", sr=0),
+        SD(130, 256, t=0, row=1, colsum="parts", sr=0),
+        # long columns: from 4096 rows on the sums take the long-run rule; 20 000 x 128 on the streaming kernel
+        SD(4096, 128, t=0, row=1, colsum="fold"), SD(20000, 128, t=0, row=1, colsum="fold"), SD(4100, 33, colsum="fold"),
+        # the split's own max pass: R C = 5, 4095, 4096, 4097 (one and two partials), 255 x 4096 + 1 and 256 x 4096 (256 partials), 4099 x 257
+        # (odd, capped at 256 partials); a scalar tail wherever R C % 4 != 0
+        SD(5, 1, scale="own"), SD(65, 63, scale="own"), SD(64, 64, row=1, scale="own"), SD(241, 17, scale="own", colsum="fold"),
+        SD(1044481, 1, scale="own"), SD(8192, 128, t=0, row=1, scale="own", colsum="parts"), SD(4099, 257, scale="own", colsum="parts"),
+        # gradient magnitudes, all zero, one 7e4 (S = 2^-3: no flag, where the unscaled split raises it), one inf (S = 1, flag) - on the tile
+        # kernel and on the streaming one, from the own max pass and from a producer's slot
+        *[SD(197, 96, row=1, scale="own", mag=m, colsum="parts") for m in (1e-3, 3e-8, 1e-30)],
+        *[SD(130, 128, t=0, row=1, scale="slot", mag=m, colsum="parts") for m in (1.0, 1e-3, 3e-8, 1e-30)],
+        *[SD(65, 96, row=1, scale=sc, vals=v) for sc in ("own", "slot") for v in ("zero", "big", "inf")], SD(65, 96, row=1, vals="big"),
+        SD(130, 128, t=0, row=1, scale="own", vals="big"), SD(130, 128, t=0, row=1, scale="slot", vals="inf"), SD(33, 65, scale="slot", mag=3e-8),
+        SD(130, 128, t=0, row=1, scale="slot", vals="zero"),
+    ],
+    "split_multi": [
+        # 1, 2 and 32 entries (one launch), 33 (two), 65 (three); the 641 x 449 entry (88 tiles) takes tile0 across 64 wherever it stands
+        SM(1), SM(1, 1), SM(2), SM(2, 6), SM(32), SM(33, 3), SM(65, 5),
+    ],
+    "transpose_pairs": [
+        *[TPP(R, C) for R, C in zip((1, 31, 32, 33, 63, 64, 65, 197), (32, 96, 160, 32, 96, 160, 32, 96))],
+        TPP(1, 160, 64), TPP(33, 96, 64), TPP(64, 32, 64), TPP(197, 160, 64), TPP(65, 96, 32),
+    ],
+    "transpose_planes": [
+        # Rpad = R: odd (one bf16 per lane), % 4 == 0 but not % 64, % 64 == 0; the padded forms; with and without the column sums
+        *[TPL(R, C, "R", cs) for R, C, cs in ((1, 1, 0), (3, 63, 1), (63, 64, 0), (65, 65, 1), (197, 200, 0), (197, 1, 1), (65, 200, 0))],
+        *[TPL(R, C, "R", cs) for R, C, cs in ((4, 63, 1), (68, 65, 0), (196, 200, 1), (64, 64, 0), (64, 200, 1), (192, 65, 0))],
+        *[TPL(R, C, "c64", cs) for R, C, cs in ((1, 63, 1), (3, 200, 0), (63, 65, 1), (64, 1, 0), (65, 64, 1), (197, 200, 1))],
+        *[TPL(R, C, "c64+64", cs) for R, C, cs in ((1, 64, 0), (63, 200, 1), (64, 65, 0), (197, 63, 1))],
+        TPL(4100, 65, "R", 1), TPL(4101, 33, "R", 1),
+    ],
+    "patch_embed": [
+        # gh != gw both ways and a grid of one row / one column, at P 4, 8 and 16, C 1 ... 3, D 64 ... 192, token counts F (n + 1) that are no
+        # multiple of 64, every frame map - in all three modes (pairs need C P P % 32 == 0, planes % 64)
+        *[PE(m, 3, 3, 16, 2, 5, 64, "rev") for m in ("f32", "pairs", "planes")], *[PE(m, 2, 1, 8, 5, 2, 128, "repeat") for m in ("f32", "pairs", "planes")],
+        *[PE(m, 5, 2, 8, 1, 7, 192) for m in ("f32", "pairs", "planes")], *[PE(m, 2, 3, 16, 6, 1, 128, "repeat") for m in ("f32", "pairs", "planes")],
+        PE("f32", 3, 3, 4, 3, 5, 64, "rev"), PE("pairs", 3, 2, 4, 5, 3, 64, "repeat"), PE("planes", 2, 4, 4, 3, 4, 64), PE("f32", 2, 1, 4, 2, 3, 192),
+        PE("pairs", 4, 1, 16, 3, 2, 192, "rev"), PE("planes", 3, 1, 16, 4, 3, 192, "rev"),
+        # the f32 entry's general kernel: P 8 (above), D 72, TT_PATCH_LEAN 0 on a lean shape; its lean kernel at 64 rows per tile (above)
+        # and at 128 (16 280 patch rows at D 128: 256 tiles of 128 x 64)
+        PE("f32", 2, 3, 16, 2, 3, 72), PE("f32", 3, 3, 16, 2, 5, 64, "rev", lean=0), PE("f32", 407, 1, 16, 5, 8, 128, "repeat"),
+        # rows enough for the persistent GEMMs (10 783 rows: K 64 into D 384 on pairs, K 128 into D 768 on planes)
+        PE("pairs", 263, 1, 8, 5, 8, 384, "repeat"), PE("planes", 263, 2, 8, 5, 8, 768, "repeat"),
+    ],
+    "grad_amax": [
+        # layernorm_bwd_kernel: D 1 ... 1000; 1, 3, 7, 9 rows (one workgroup, then two of five rows), 8192 (1024 workgroups of 8), 8193 and
+        # 8200 (the cap: 9 rows each, trailing workgroups without a row); dropping token 0; accumulating
+        GA("ln_bwd", 1, 1), GA("ln_bwd", 3, 63, accum=1), GA("ln_bwd", 7, 64, gscale=1e-7), GA("ln_bwd", 9, 65), GA("ln_bwd", 8192, 96, accum=1),
+        GA("ln_bwd", 8193, 64, gscale=1e-7), GA("ln_bwd", 8200, 1000), GA("ln_bwd", 8, 96), GA("ln_bwd", 5, 1024, accum=1), GA("ln_bwd", 8200, 96, N=201),
+        GA("ln_bwd", 12, 63, N=5), GA("ln_bwd", 1, 1000, N=2, gscale=1e-7), GA("ln_bwd", 196, 65, N=197),
+        # layernorm_bwd_vec_kernel<1|3|6> at 1, 2, 3, 8 and 17 rows - and the same shapes one float off 8-byte alignment (the general kernel)
+        *[GA("ln_bwd", r, D, accum=a) for r, D, a in ((1, 128, 0), (2, 384, 1), (3, 768, 0), (8, 128, 1), (17, 384, 0), (17, 768, 1), (8193, 384, 0))],
+        GA("ln_bwd", 16, 384, N=17), GA("ln_bwd", 8471, 768, gscale=1e-7), GA("ln_bwd", 1, 384), GA("ln_bwd", 8, 384, gscale=1e-7),
+        *[GA("ln_bwd", r, D, accum=a, off=1) for r, D, a in ((2, 384, 1), (3, 768, 0), (17, 128, 0))],
+        # l2norm_bwd_kernel: a wave per row, four per workgroup - 1, 3, 4 and 5 rows
+        GA("l2_bwd", 1, 1), GA("l2_bwd", 3, 64, gscale=1e-7), GA("l2_bwd", 4, 65), GA("l2_bwd", 5, 1024), GA("l2_bwd", 70, 1024, gscale=1e-7),
+        # attention_bwd_dq / dkv_kernel, fp32 and on pairs (max |dout| from the call's own pass and from a slot): N 1 ... 257, H 1 and 3
+        *[GAT("attn_bwd", F, N, H, g) for F, N, H, g in ((1, 1, 1, 1.0), (2, 63, 3, 1e-7), (1, 64, 1, 1.0), (2, 65, 1, 1.0), (1, 197, 3, 1.0), (1, 257, 1, 1e-7))],
+        *[GAT("attn_bwd_pairs", F, N, H, g, d) for F, N, H, g, d in ((1, 1, 1, 1.0, 1), (2, 63, 3, 1e-7, 0), (1, 64, 1, 1.0, 1), (2, 65, 1, 1e-7, 1),
+                                                                    (1, 197, 3, 1.0, 0), (1, 257, 1, 1e-7, 1), (2, 197, 3, 1e-7, 1))],
+        # the general pair kernel's epilogue (no gelu'): its four tiles - 128 x 128, 64 x 128, 64 x 64 on four slabs and on three - on a
+        # reduction of 64; M 1, 63, 65, 130 on the small grids
+        GD(8200, 64, 1536), GD(8200, 64, 1024), GD(8200, 64, 320), GD(1, 64, 64), GD(63, 128, 192, gscale=3e-8), GD(65, 64, 128), GD(130, 192, 320, gscale=3e-8),
+        # x gelu': the persistent kernels' regimes (half tiles, round robin, K-split) with a ragged last row tile, and the general kernel
+        GD(4000, 64, 1024, 1), GD(6300, 64, 1024, 1, 3e-8), GD(8300, 768, 1024, 1), GD(65, 64, 128, 1), GD(591, 192, 320, 1, 3e-8),
+    ],
+    "layernorm_long": [
+        # the first tier's layernorm check beyond 8192 rows: ln_bwd_wgs' cap of 1024 workgroups (9 rows each, trailing workgroups without a
+        # row) on the general kernel (D 64) and on layernorm_bwd_vec_kernel<3>
+        LNL(1, 8193, 64), LNL(1, 8193, 384), LNL(43, 197, 64), LNL(43, 197, 384), LNL(43, 197, 384, 1),
     ],
 }
 

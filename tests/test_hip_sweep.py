@@ -22,6 +22,12 @@ checks of tests/_sweep_checks_metric.py: fp64 references at the second tier's k-
 k-means contract's bit equalities, exact equality with the NumPy restatements of the counters; tests/test_sweep_metric_host.py is its host
 half.  Its refusals at the edge stand beside the second tier's below.
 
+The sixth tier - the operand-preparation kernels of gemm_planes.hip (the pair / plane conversions, the dual split, its table form, the two
+transposes, the patch embeddings' im2col front ends) and the maxima the backward producers publish for the split's scale (PREP_OPS) - runs
+the checks of tests/_sweep_checks_prep.py through the C ABI into guarded buffers: bit equality with the NumPy restatements of the two
+formats, exact maxima, fp64 references for the sums, the tokens and the producers' dx; tests/test_sweep_prep_host.py is its host half.  Its
+refusals at the edge are at the end of this file.
+
 ``run_case`` is also what tools/fuzz_ops.py runs on more seeds of the same generator."""
 import json
 import os
@@ -32,10 +38,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _sweep_cases import EVAL_OPS, HEAD_OPS, METRIC_OPS, PAIR_EPILOGUES, PROP_OPS, case_id, table
+from _sweep_cases import EVAL_OPS, HEAD_OPS, METRIC_OPS, PAIR_EPILOGUES, PREP_OPS, PROP_OPS, case_id, table
 from _sweep_checks_eval import HipSide, run_eval_case
 from _sweep_checks_head import HeadHip, run_head_case
 from _sweep_checks_metric import MetricHip, run_metric_case
+from _sweep_checks_prep import PrepHip, assert_refused, domain_edges, ln_refuses_amax_with_drop_and_accum, run_prep_case
 from _sweep_checks_prop import PropHip, run_prop_case
 
 pytestmark = pytest.mark.gpu
@@ -350,6 +357,8 @@ def run_case(op: str, params: dict, worst: dict = None) -> None:
             run_head_case(HeadHip(), op, params, WORST)
         elif op in METRIC_OPS:
             run_metric_case(MetricHip(), op, params, WORST)
+        elif op in PREP_OPS:
+            run_prep_case(PrepHip(), op, params, WORST)
         else:
             CHECK[op](ops, params, _gen(op, params), _note(op))
     finally:
@@ -751,3 +760,34 @@ def test_grid_entry_and_its_upsampler_at_the_edge():
     assert torch.equal(ops.upsample_argmax_hw(x, (1, 1), (2, 2)), x.argmax(-1).view(-1, 1, 1).expand(65535, 2, 2))
     with _refused("upsample_argmax_hw: 65536 maps of 2x2 exceed one launch"):
         ops.upsample_argmax_hw(_z(65536, 1, 3, dtype=torch.float64), (1, 1), (2, 2))
+
+
+# ---- the sixth tier's entries at the edge of their domains (include/timetuning_hip.h).  The last accepted values are cases of the sweep
+# (Rpad = ceil32(R) with Rpad % 64 == 32, C = 32, n = 32 and 8, D = 1024, workspaces of exactly the size the queries return); the first
+# value beyond is refused with the launcher's own message before anything is launched: every output still holds its prefill.
+_EDGES = []
+
+
+def _edges():
+    if not _EDGES:
+        _EDGES.extend(domain_edges(PrepHip()))
+    return _EDGES
+
+
+@pytest.mark.parametrize("i", range(27))
+def test_preparation_entries_refuse_the_first_value_beyond_their_domain(i):
+    edges = _edges()
+    assert len(edges) == 27
+    assert_refused(PrepHip(), *edges[i])
+
+
+def test_the_last_accepted_values_are_cases_of_the_sweep():
+    have = {case_id(o, p) for o, p in CASES}
+    for cid in ("split_dual[R=33,C=32,rpad=0,t=1,row=1,colsum=fold,scale=,mag=1.0,vals=normal,off=0,sr=1]", "transpose_pairs[R=33,C=32,rpad=0]",
+                "convert[what=pairs,P=0,n=32,vals=normal]", "convert[what=planes,P=1,n=8,vals=normal]",
+                "grad_amax[producer=ln_bwd,rows=5,D=1024,N=0,gscale=1.0,accum=1,off=0]", "transpose_planes[R=63,C=64,rpad=R,colsum=0]"):
+        assert cid in have, cid
+
+
+def test_layernorm_bwd_refuses_a_maximum_with_drop_and_accumulate():
+    ln_refuses_amax_with_drop_and_accum(PrepHip())

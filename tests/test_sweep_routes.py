@@ -8,6 +8,8 @@ import itertools
 
 import pytest
 
+from _sweep_cases import (AMAX_PARTS_CAP, CONVERT_CAP, LN_BWD_WG_CAP, MULTI_MAXN, PREP_OPS, VALUE_KINDS, amax_n_part, ceil_to, ln_bwd_plan, multi_entries,
+                          pairs_general_tile, patch_f32_route, prep_case_on_twin, sd_kernel, sd_rpad, tp_rpad, tp_store_branch)
 from _sweep_cases import (ADJOINT_LONG_RUN, BF_MAX_R, DTYPES, DV_OC, EVAL_OPS, GRAY_SUM_CAP, HEAD_OPS, IMG_MODES, KM_ASSIGN_STRIDE, KM_MAX_GRID_Y, KM_MAXKD,
                           LP_CAND_CAP, METRIC_OPS, OPS, PAIR_EPILOGUES, PROP_OPS, STEP_OPS, WGRAD_LONG_RUN, adjoint_run, bf_radius, bf_tiling, case_id,
                           cs_blocks, cs_route, davis_tiling, gather_tp_log2, kf_fit_group, kf_fit_kernel, kf_fit_lds, kf_fit_ok, km_accumulate_blocks,
@@ -221,7 +223,7 @@ def test_second_tier_is_appended_and_complete():
     assert STEP_OPS == ("linear_f32", "linear_pairs", "linear_planes", "bwd_pairs", "layernorm", "l2norm", "attention", "ce", "sinkhorn",
                         "sinkhorn_from_q", "sinkhorn_local", "queue_push")
     ops_in_order = list(dict.fromkeys(o for o, _ in CASES))
-    assert tuple(ops_in_order) == STEP_OPS + EVAL_OPS + PROP_OPS + HEAD_OPS + METRIC_OPS == OPS   # appended: the first tier's draws - and case ids - are untouched
+    assert tuple(ops_in_order) == STEP_OPS + EVAL_OPS + PROP_OPS + HEAD_OPS + METRIC_OPS + PREP_OPS == OPS   # appended: the first tier's draws - and case ids - are untouched
     ids = [case_id(o, p) for o, p in CASES]
     assert len(set(ids)) == len(ids)
     # (the first and the last case of the first tier, as they were before the second tier existed)
@@ -509,7 +511,7 @@ def test_fourth_tier_is_appended_and_the_first_three_are_what_they_were():
     import zlib
 
     assert HEAD_OPS == ("probe_logits", "probe_upsample_ce", "bilinear_adjoint", "probe_wgrad", "sgd", "img_resize", "img_color", "img_blur")
-    earlier = [case_id(o, p) for o, p in CASES if o not in HEAD_OPS + METRIC_OPS]
+    earlier = [case_id(o, p) for o, p in CASES if o not in HEAD_OPS + METRIC_OPS + PREP_OPS]
     assert len(earlier) == 383 and zlib.crc32("\n".join(earlier).encode()) == 1936048768      # the ids of the first three tiers, unchanged
     assert earlier[-1].startswith("upsample_argmax_hw[") and [o for o, _ in CASES][383] == "probe_logits"
     # every op of the table has a check on the side it runs on (tools/fuzz_ops.py draws from OPS and runs tests/test_hip_sweep.py::run_case)
@@ -644,7 +646,7 @@ def test_fifth_tier_is_appended_and_the_first_four_are_what_they_were():
 
     assert METRIC_OPS == ("kmeans_assign_tiled", "kmeans_accumulate_tiled", "kmeans_assign_batched", "kmeans_fit", "confusion_segments", "davis_counts",
                           "bf_counts")
-    earlier = [case_id(o, p) for o, p in CASES if o not in METRIC_OPS]
+    earlier = [case_id(o, p) for o, p in CASES if o not in METRIC_OPS + PREP_OPS]
     assert len(earlier) == 558 and zlib.crc32("\n".join(earlier).encode()) == 3298991197      # the ids of the first four tiers, unchanged
     assert earlier[-1].startswith("img_blur[") and [o for o, _ in CASES][558] == "kmeans_assign_tiled"
     from _sweep_checks_metric import CHECK as METRIC_CHECK      # (tools/fuzz_ops.py draws from OPS and runs tests/test_hip_sweep.py::run_case)
@@ -819,3 +821,149 @@ def test_bf_tiling_never_shrinks_and_block_decomposition():
     have = {(p["P"], p["H"], p["W"], p["t"]) for p in cases}
     assert have >= {(3, 70, 1100, 2), (2, 40, 513, 64), (2, 40, 512, 64), (2, 40, 600, 31)}
     assert any(p["H"] < 32 and p["W"] > 512 for p in cases) and any(p["t"] == 0 for p in cases) and any(p["H"] * p["W"] == 1 for p in cases)
+
+
+# ---- the sixth tier: the operand-preparation kernels (gemm_planes.hip) and the producers' maxima (rowops.hip, attention_bwd.hip, the pair
+# GEMMs' epilogues).  Only the patch embeddings' GEMMs have host queries; every other rule is restated in tests/_sweep_cases.py beside the
+# function it comes from.
+def test_sixth_tier_is_appended_and_the_first_five_are_what_they_were():
+    import zlib
+
+    assert PREP_OPS == ("convert", "split_dual", "split_multi", "transpose_pairs", "transpose_planes", "patch_embed", "grad_amax", "layernorm_long")
+    earlier = [case_id(o, p) for o, p in CASES if o not in PREP_OPS]
+    assert len(earlier) == 718 and zlib.crc32("\n".join(earlier).encode()) == 2905359468      # the ids of the first five tiers, unchanged
+    assert earlier[-1].startswith("bf_counts[") and [o for o, _ in CASES][718] == "convert"
+    from _sweep_checks_prep import CHECK as PREP_CHECK      # (tools/fuzz_ops.py draws from OPS and runs tests/test_hip_sweep.py::run_case)
+
+    assert set(PREP_CHECK) == set(PREP_OPS)
+    # the layernorm cases the issue adds live under their own op, so that the first tier's draws keep their ids
+    assert {(p["Fr"], p["Nt"], p["D"]) for p in _of("layernorm_long")} >= {(1, 8193, 64), (1, 8193, 384), (43, 197, 64), (43, 197, 384)}
+
+
+def test_conversions_reach_the_grid_cap_and_every_kind_of_value():
+    cases = _of("convert")
+    # tt_split_pairs / tt_join_pairs / tt_split_planes: min(ceil(n / 8 / 256), 4096) workgroups of 256 threads x 8 elements - the stride loop
+    # runs from n = 8 388 608 + 8 on
+    assert CONVERT_CAP == 4096 * 256 * 8
+    for what, step in (("pairs", 32), ("planes", 8)):
+        ns = {p["n"] for p in cases if p["what"] == what}
+        assert {step, CONVERT_CAP, CONVERT_CAP + step} <= ns, what
+        assert {p["vals"] for p in cases if p["what"] == what} == set(VALUE_KINDS), what
+    assert {p["P"] for p in cases if p["what"] == "planes"} == {1, 2, 3}
+    assert {p["P"] for p in cases if p["what"] == "planes" and p["n"] > CONVERT_CAP} >= {2, 3}
+    assert max(p["n"] for p in cases) == CONVERT_CAP + 32                                      # the largest tensors of the tier
+
+
+def test_dual_split_every_instantiation_route_partial_count_and_scale():
+    cases = _of("split_dual")
+    kernels = {sd_kernel(p) for p in cases}
+    # transpose_pairs_kernel<false, ROW, SUM> x 4, split_rows_kernel<SUM> x 2 (gemm_planes.hip, split_pairs_dual_impl)
+    assert kernels == {("tile", r, s) for r in (False, True) for s in (False, True)} | {("rows", False), ("rows", True)}
+    tile = [p for p in cases if sd_kernel(p)[0] == "tile"]
+    assert {p["R"] for p in tile if p["t"]} >= {1, 31, 32, 33, 63, 64, 65, 197}
+    assert {p["C"] for p in tile if p["t"] and not p["row"]} >= {1, 31, 33, 65} and {p["C"] for p in tile if p["t"] and p["row"]} >= {32, 96, 160}
+    assert any(sd_rpad(p) % 64 == 32 and p["t"] for p in tile) and {p["rpad"] for p in cases} == {0, 32, 64}
+    # the streaming kernel either side of each term of its gate: C % 128, the transposed output, alignment, the knob
+    rows = [p for p in cases if sd_kernel(p)[0] == "rows"]
+    assert {p["C"] for p in rows} >= {128, 256} and {p["R"] for p in rows} >= {1, 15, 16, 17, 63, 65, 130, 20000}
+    off_gate = [p for p in cases if p["row"] and not p["t"] and sd_kernel(p)[0] == "tile"]
+    assert {p["C"] for p in off_gate} >= {96, 160} and any(p["off"] and p["C"] % 128 == 0 for p in off_gate) and any(not p["sr"] and p["C"] % 128 == 0 for p in off_gate)
+    # the max pass: n_part 1, 2 ... 255, 256 and capped; the scalar tail (R C % 4 != 0)
+    own = [amax_n_part(p["R"] * p["C"]) for p in cases if p["scale"] == "own"]
+    assert {c for _, c, _ in own} == {"1", "2..255", "256", "capped"} and {t for _, _, t in own} == {False, True}
+    assert {p["R"] * p["C"] for p in cases if p["scale"] == "own"} >= {5, 4095, 4096, 4097, 255 * 4096 + 1, 256 * 4096, 4099 * 257}
+    assert amax_n_part(4096) == (1, "1", False) and amax_n_part(4097) == (2, "2..255", True) and amax_n_part(256 * 4096)[:2] == (AMAX_PARTS_CAP, "256")
+    assert amax_n_part(4099 * 257) == (AMAX_PARTS_CAP, "capped", True)
+    for scale in ("own", "slot"):      # every magnitude and special value, from the own pass and from a slot, on both kernels
+        mine = [p for p in cases if p["scale"] == scale]
+        assert {p["mag"] for p in mine} >= {1.0, 1e-3, 3e-8, 1e-30} and {p["vals"] for p in mine} >= {"normal", "zero", "big", "inf"}, scale
+        assert {sd_kernel(p)[0] for p in mine} == {"tile", "rows"}, scale
+    from _sweep_checks_prep import slot_way      # the slot's way that carries the maximum: both halves of the 16 (a fold of 8 ways misses one)
+
+    assert {slot_way(p) // 8 for p in cases if p["scale"] == "slot" and p["vals"] == "normal"} == {0, 1}
+    assert {p["colsum"] for p in cases} == {"", "fold", "parts"} and any(p["R"] >= 4096 and p["colsum"] for p in rows) and any(p["R"] >= 4096 and p["colsum"] for p in tile)
+    assert max(p["R"] * p["C"] for p in cases) == 20000 * 128
+
+
+def test_table_split_every_launch_count():
+    cases = _of("split_multi")
+    assert {p["n"] for p in cases} >= {1, 2, MULTI_MAXN, MULTI_MAXN + 1, 2 * MULTI_MAXN + 1}      # PairTable::MAXN entries per launch
+    assert {(p["n"] + MULTI_MAXN - 1) // MULTI_MAXN for p in cases} >= {1, 2, 3}
+    for p in cases:
+        ents = multi_entries(p)
+        tile0 = list(itertools.accumulate([0] + [((ceil_to(R, 32) + 63) // 64) * ((C + 63) // 64) for R, C, _ in ents[:MULTI_MAXN]]))
+        if p["n"] >= MULTI_MAXN:
+            assert {o for _, _, o in ents} == {"t", "row", "both"} and (1, 1, "t") in ents and (65, 96, "both") in ents
+            assert any(a // 64 != b // 64 for a, b in zip(tile0, tile0[1:]))                         # tile0 crosses a multiple of 64
+
+
+def test_transposes_every_store_branch():
+    cases = _of("transpose_planes")
+    assert {tp_store_branch(tp_rpad(p)) for p in cases if p["rpad"] == "R"} == {"scalar", "quad", "quad64"}      # transpose_planes_kernel: Rpad % 4, % 64
+    for cs in (0, 1):
+        assert {tp_store_branch(tp_rpad(p)) for p in cases if p["colsum"] == cs} == {"scalar", "quad", "quad64"}, cs
+    assert {p["rpad"] for p in cases} == {"R", "c64", "c64+64"}
+    assert {p["R"] for p in cases} >= {1, 3, 63, 64, 65, 197} and {p["C"] for p in cases} >= {1, 63, 64, 65, 200}
+    assert any(p["R"] >= 4096 and p["colsum"] for p in cases)
+    tp = _of("transpose_pairs")
+    assert {p["R"] for p in tp} >= {1, 31, 32, 33, 63, 64, 65, 197} and {p["C"] for p in tp} >= {32, 96, 160} and {p["rpad"] for p in tp} >= {0, 64}
+
+
+def test_patch_embedding_every_route(lib):
+    cases = _of("patch_embed")
+    n_of = lambda p: p["gh"] * p["gw"]
+    f32 = [p for p in cases if p["mode"] == "f32"]
+    routes = {patch_f32_route(p, lib.tt_gemm_tile_choice(p["F"] * n_of(p), p["D"], 1)) for p in f32}
+    assert routes == {"lean64", "lean128", "general"}
+    general = [p for p in f32 if patch_f32_route(p, 3) == "general"]
+    assert any(p["P"] == 8 for p in general) and any(p["D"] % 64 for p in general) and any(not p["lean"] and p["P"] == 16 and p["D"] % 64 == 0 for p in general)
+    for mode, K_mod in (("f32", 1), ("pairs", 32), ("planes", 64)):
+        mine = [p for p in cases if p["mode"] == mode]
+        assert all((p["C"] * p["P"] * p["P"]) % K_mod == 0 for p in mine), mode
+        assert any(p["gh"] > p["gw"] > 1 for p in mine) and any(1 < p["gh"] < p["gw"] for p in mine), mode      # a gh / gw mix-up changes the result
+        assert any(p["gh"] == 1 for p in mine) and any(p["gw"] == 1 for p in mine) and {p["P"] for p in mine} == {4, 8, 16}, mode
+        assert {p["D"] for p in mine} >= {64, 128, 192} and {p["fmap"] for p in mine} == {"", "rev", "repeat"}, mode
+        assert all((p["F"] * (n_of(p) + 1)) % 64 for p in mine if p["F"] < 100), mode
+    assert {p["C"] for p in cases} >= {1, 2, 3}
+    M_K = lambda p: (p["F"] * (n_of(p) + 1), p["C"] * p["P"] * p["P"])
+    # (the GEMM of the pair / plane entries: residual = y = tokens, bias, no activation)
+    assert {lib.tt_linear_fwd_pairs_route(M_K(p)[0], p["D"], M_K(p)[1], 0, 1, 1, 1, 0, 0) for p in cases if p["mode"] == "pairs"} == {0, 8}
+    assert {lib.tt_linear_fwd_planes_route(1, M_K(p)[0], p["D"], M_K(p)[1], 0, 1, 1, 1, 0, 0) != 0 for p in cases if p["mode"] == "planes"} == {False, True}
+    persistent = [p for p in cases if p["mode"] != "f32" and p["F"] > 100]
+    assert len(persistent) == 2 and not any(prep_case_on_twin("patch_embed", p) for p in persistent)
+
+
+def test_gradient_maxima_every_producer_kernel_and_regime(lib):
+    cases = _of("grad_amax")
+    ln = [p for p in cases if p["producer"] == "ln_bwd"]
+    plans = [ln_bwd_plan(p["rows"], p["D"], p["off"]) for p in ln]
+    # rowops.hip, tt_layernorm_bwd: the general kernel and layernorm_bwd_vec_kernel<1|3|6>; ln_bwd_wgs: 1, 8 and more than 8 rows per
+    # workgroup, and workgroups without a row behind the cap of 1024
+    assert {k for k, *_ in plans} == {"general", "vec1", "vec3", "vec6"}
+    for kern in ("general", "vec3"):
+        assert {min(rpw, 9) for k, _, rpw, _ in plans if k == kern} >= {1, 8, 9}, kern
+    assert any(w == LN_BWD_WG_CAP and idle > 0 for _, w, _, idle in plans) and ln_bwd_plan(8193, 64) == ("general", 1024, 9, 113)
+    assert {p["D"] for p in ln if ln_bwd_plan(p["rows"], p["D"], p["off"])[0] == "general" and not p["off"]} >= {1, 63, 64, 65, 96, 1000}
+    assert {p["rows"] for p in ln} >= {1, 2, 3, 7, 8, 9, 17, 8192, 8193, 8200}
+    assert {p["D"] for p in ln if p["off"]} >= {128, 384, 768}                                    # the same D, one float off 8-byte alignment
+    assert any(p["N"] for p in ln) and any(p["accum"] for p in ln) and not any(p["N"] and p["accum"] for p in ln)      # (together: refused)
+    for kern in ("general", "vec1", "vec3", "vec6"):
+        assert any(p["accum"] for p in ln if ln_bwd_plan(p["rows"], p["D"], p["off"])[0] == kern), kern
+    l2 = [p for p in cases if p["producer"] == "l2_bwd"]
+    assert {p["rows"] for p in l2} >= {1, 3, 4, 5} and {p["D"] for p in l2} >= {1, 64, 65, 1024}
+    for prod in ("attn_bwd", "attn_bwd_pairs"):
+        at = [p for p in cases if p["producer"] == prod]
+        assert {p["N"] for p in at} >= {1, 63, 64, 65, 197, 257} and {p["H"] for p in at} >= {1, 3} and {p["F"] for p in at} >= {1, 2}, prod
+    assert {p["dslot"] for p in cases if p["producer"] == "attn_bwd_pairs"} == {0, 1}
+    assert {p["gscale"] for p in cases if "gscale" in p} >= {1.0, 1e-7}
+    # the general pair kernel (dx [M, K]: the GEMM's N is K, its reduction N): linear_pairs_impl's four tiles; small M on the small grids
+    gen = [p for p in cases if p["producer"] == "dgrad_general"]
+    assert {pairs_general_tile(p["M"], p["K"], p["N"], 1, NCU) for p in gen} == {"big", "wide", "small4", "small3"}
+    assert {p["M"] for p in gen if pairs_general_tile(p["M"], p["K"], p["N"]) == "small4"} >= {1, 63, 65, 130}
+    # x gelu': each regime of the persistent kernel (pairs8_regime above) with a ragged last row tile, and the general kernel
+    gg = [p for p in cases if p["producer"] == "dgrad_gelu"]
+    assert {pairs8_regime(p["M"], p["K"], p["N"]) for p in gg} == {"half", "round_robin", "ksplit", None}
+    for p in gg:
+        persistent = pairs8_regime(p["M"], p["K"], p["N"]) is not None
+        assert persistent == hip_ops.linear_bwd_data_pairs_is_persistent(p["M"], p["N"], p["K"]), p
+        assert not persistent or (p["M"] % 256 and not prep_case_on_twin("grad_amax", p)), p

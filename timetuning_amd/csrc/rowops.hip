@@ -796,6 +796,9 @@ extern "C" int tt_layernorm_bwd(const float* dy, const float* x, const float* ga
   TT_REQUIRE(skip_group == 0 || (skip_group >= 2 && rows % (skip_group - 1) == 0), "layernorm_bwd: rows must be a multiple of skip_group - 1");
   TT_REQUIRE(dy && x && gamma && mean && rstd && dx, "layernorm_bwd: null pointer");
   TT_REQUIRE(rows > 0 && D > 0 && D <= 64 * kMaxPerLane, "layernorm_bwd: need 0 < D <= %d", 64 * kMaxPerLane);
+  // (the kernels never visit token 0's rows: what add_to_dx left there would be part of dx and not of the published maximum)
+  TT_REQUIRE(!(amax_out && add_to_dx && skip_group), "layernorm_bwd: amax_out with add_to_dx and skip_group together is not supported "
+             "(token 0's rows of dx are not visited)");
   const bool want = dgamma || dbeta;
   TT_REQUIRE(!want || (dgamma && dbeta), "layernorm_bwd: dgamma and dbeta must be given together");
   const int wgs = ln_bwd_wgs(rows);

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Randomised shape fuzz of the HIP ops against torch fp64 / the oracle (development aid; run on the GPU box).
 Each round draws one case per op from the generator of the suite's sweep (tests/_sweep_cases.py) and checks it with the sweep's own
-checks and bounds (tests/test_hip_sweep.py::run_case): more seeds of that sweep, all five tiers - the kernels of the training step, the
+checks and bounds (tests/test_hip_sweep.py::run_case): more seeds of that sweep, all six tiers - the kernels of the training step, the
 evaluator / optimizer / mask kernels (tests/_sweep_checks_eval.py), label propagation on square and rectangular grids with its
 up-sampler (tests/_sweep_checks_prop.py: one-frame fp64 reference), the linear probe with the clip input pipeline
 (tests/_sweep_checks_head.py) and the tiled / batched / fused k-means kernels with the metric counters (tests/_sweep_checks_metric.py: the
 checks make their inputs valid by construction - fit blobs are drawn again until the fp64 run proves them valid, points within the
-excuse gap of a tie beyond the allowed share are replaced - and tests/test_sweep_metric_host.py runs hundreds of draws per op to hold that).  Then the ops the sweep does not cover.
+excuse gap of a tie beyond the allowed share are replaced - and tests/test_sweep_metric_host.py runs hundreds of draws per op to hold that)
+and the operand-preparation kernels with the producers' gradient maxima (tests/_sweep_checks_prep.py: bit equality with NumPy restatements
+of the pair and plane formats inside guarded buffers).  Then the ops the sweep does not cover.
 usage: fuzz_ops.py [rounds=40] [seed=0]"""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
