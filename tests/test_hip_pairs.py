@@ -59,6 +59,45 @@ def test_layernorm_pairs():
         assert yd.shape == (3 * 196, 2 * D) and rel_err(join(yd.cpu()).view(3, 196, D), ref[:, 1:]) < TOL_F32
 
 
+# D = 128 NV: every instantiation of the two-columns-per-lane kernel; 64 / 96 / 640 (a D % 128 == 0 that is none of them) / 1000 (no pair
+# layout: fp32 and planes only): the one-column kernel; (384, True): x one float into a larger buffer - 4-byte aligned only, so all three
+# entries leave the vectorised route
+@pytest.mark.parametrize("drop", [False, True])
+@pytest.mark.parametrize("D,offset", [(D, False) for D in (128, 256, 384, 512, 768, 1024, 64, 96, 640, 1000)] + [(384, True)])
+def test_layernorm_formats_carry_one_fp32_value(D, offset, drop):
+    """The three LayerNorm entries are one arithmetic and three stores: the pair and plane outputs are, bit for bit, the split of the fp32
+    output, and the statistics are the same words.  18 rows (15 with the class token dropped): a tail on the 8-row workgroup and a wave
+    whose second row is missing."""
+    from timetuning_amd import hip_ops as ops
+
+    Fr, Nt = 3, 6
+    x = 2.0 * rnd(f"lnfmt.x{D}", Fr, Nt, D) + 0.3
+    g, b = (1.0 + 0.1 * rnd(f"lnfmt.g{D}", D)).cuda(), (0.1 * rnd(f"lnfmt.b{D}", D)).cuda()
+    if offset:
+        buf = torch.zeros(x.numel() + 4, device="cuda")
+        buf[1:1 + x.numel()] = x.reshape(-1).cuda()
+        xd = buf[1:1 + x.numel()].view(Fr, Nt, D)
+        assert xd.data_ptr() % 8 == 4
+    else:
+        xd = x.cuda()
+    f = _flag_clear(ops)
+    y, mean, rstd = ops.layernorm_fwd(xd, g, b, save_stats=True, drop_first_token=drop)
+    y = y.reshape(-1, D)
+    assert y.shape[0] == (15 if drop else 18)
+    stats = [(mean, rstd)]
+    if D % 32 == 0:
+        yq, mq, rq = ops.layernorm_fwd_pairs(xd, g, b, save_stats=True, drop_first_token=drop)
+        assert torch.equal(yq.view(torch.int16), ops.split_pairs(y).view(torch.int16))
+        stats.append((mq, rq))
+    for planes in (1, 2, 3):
+        yp, mp, rp = ops.layernorm_fwd_planes(xd, g, b, planes, save_stats=True, drop_first_token=drop)
+        assert torch.equal(yp.view(torch.int16), ops.split_planes(y, planes).view(torch.int16)), planes
+        stats.append((mp, rp))
+    for m_, r_ in stats[1:]:
+        assert torch.equal(m_.view(torch.int32), mean.view(torch.int32)) and torch.equal(r_.view(torch.int32), rstd.view(torch.int32))
+    assert int(f[0].item()) == 0
+
+
 # persistent kernel (whole 256 x 128 tiles, K % 96 == 0, a grid that fills the chip) and the general one (ragged M, 64-wide N, K % 32)
 SHAPES = [(25216, 1152, 384), (25216, 384, 1536), (8192, 1536, 384), (6304, 384, 384), (788, 384, 384), (1000, 1152, 384), (6272, 256, 512),
           (394, 64, 1536), (2048, 768, 3072), (300, 128, 96), (33000, 128, 96)]

@@ -213,6 +213,75 @@ __device__ __forceinline__ float join_pair(_Float16 hi, _Float16 lo) { return fm
 // index of element i of a row-major array whose length is a multiple of 32, in the pair layout: hi at pair_index(i), lo 32 further
 __host__ __device__ __forceinline__ long long pair_index(long long i) { return ((i >> 5) << 6) + (i & 31); }
 
+// ---- operand writers: how a row-wise producer (rowops.hip layernorm_fwd*, gemm_planes.hip split_kernel / patch_rows_kernel) stores its fp32
+// result in one of the three operand formats.  put<V>(base, c, v, bad) stores the V adjacent values v as elements base + c .. base + c + V - 1
+// of the row-major array (base % 32 == 0: a row start or a group of 32 inside a row; c % V == 0, V | 32) and returns `bad` or "a pair
+// hi left fp16's range" (constant false for fp32 and planes); finish(bad) raises the range flag.  The only place these kernels learn the
+// plane stride and the pair group layout from.
+template <class T, int V> __device__ __forceinline__ void store_vec(T* p, const T (&a)[V]) {
+  if constexpr (V == 1) {
+    *p = a[0];
+  } else {
+    typedef T vec __attribute__((ext_vector_type(V)));
+    vec q;
+#pragma unroll
+    for (int e = 0; e < V; ++e) q[e] = a[e];
+    *reinterpret_cast<vec*>(p) = q;
+  }
+}
+struct OutF32 {
+  float* y;
+  template <int V> __device__ __forceinline__ bool put(long long base, long long c, const float (&v)[V], bool) const {
+    store_vec(y + base + c, v);
+    return false;
+  }
+  __device__ __forceinline__ void finish(bool) const {}
+};
+struct OutPlanes {   // y = p0 + p1 + p2: `planes` (1..3) bf16 arrays `stride` elements apart
+  __bf16* y;
+  long long stride;
+  int planes;
+  template <int V> __device__ __forceinline__ bool put(long long base, long long c, const float (&v)[V], bool) const {
+    __bf16* d = y + base + c;
+    __bf16 p0[V], p1[V], p2[V];
+    float r1[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) p0[e] = (__bf16)v[e];
+    store_vec(d, p0);
+    if (planes > 1) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        r1[e] = v[e] - (float)p0[e];
+        p1[e] = (__bf16)r1[e];
+      }
+      store_vec(d + stride, p1);
+      if (planes > 2) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) p2[e] = (__bf16)(r1[e] - (float)p1[e]);
+        store_vec(d + 2 * stride, p2);
+      }
+    }
+    return false;
+  }
+  __device__ __forceinline__ void finish(bool) const {}
+};
+struct OutPairs {   // [hi x 32][lo x 32] groups: 2 fp16 per element
+  _Float16* y;
+  int* range_flag;
+  template <int V> __device__ __forceinline__ bool put(long long base, long long c, const float (&v)[V], bool bad) const {
+    _Float16 hi[V], lo[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) split_pair(v[e], hi[e], lo[e]);
+#pragma unroll
+    for (int e = 0; e < V; ++e) bad = bad || pair_hi_bad(hi[e]);
+    _Float16* d = y + 2 * base + pair_index(c);
+    store_vec(d, hi);
+    store_vec(d + 32, lo);
+    return bad;
+  }
+  __device__ __forceinline__ void finish(bool bad) const { range_flag_raise(range_flag, bad); }
+};
+
 // epilogue kinds of the persistent pair kernels (gemm_pairs8.hip: gemm_pairs8s_kernel, gemm_pairs4_kernel)
 // F32 / F32_RES: fp32 y (+ residual); PAIR / PAIR_GELU: y in pairs (after GELU); F32_GELUGRAD: fp32 y * gelu'(pre[m][n]) (a data-gradient
 // product); BOTH: fp32 y AND the same value in pairs; BOTH_GELU: the fp32 PRE-activation and GELU of it in pairs (a forward that keeps

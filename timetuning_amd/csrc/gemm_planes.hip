@@ -407,24 +407,18 @@ static int launch_planes(const PlaneArgs& g, hipStream_t s) {
   return TT_OK;
 }
 
-// ---- f32 -> bf16 planes (weights once per change, activations whose producer is an fp32 kernel)
-__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, long long stride, int planes,
-                                                           long long n8) {
+// ---- f32 -> bf16 planes (weights once per change, activations whose producer is an fp32 kernel) or fp16 pairs (common.hpp OutPlanes /
+// OutPairs); a thread converts 8 elements
+template <class Out>
+__global__ __launch_bounds__(256) void split_kernel(const float* __restrict__ src, Out out, long long n8) {
+  bool bad = false;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
     float v[8];
     *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(src + 8 * i);
     *reinterpret_cast<float4*>(v + 4) = *reinterpret_cast<const float4*>(src + 8 * i + 4);
-    bf16x8 q0, q1, q2;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      __bf16 p0, p1, p2;
-      split3(v[e], p0, p1, p2);
-      q0[e] = p0; q1[e] = p1; q2[e] = p2;
-    }
-    *reinterpret_cast<bf16x8*>(dst + 8 * i) = q0;
-    if (planes > 1) *reinterpret_cast<bf16x8*>(dst + stride + 8 * i) = q1;
-    if (planes > 2) *reinterpret_cast<bf16x8*>(dst + 2 * stride + 8 * i) = q2;
+    bad = out.put(0, 8 * i, v, bad);
   }
+  out.finish(bad);
 }
 
 // ---- fp32 [R][C] -> bf16 [C][Rpad] (transpose; columns R..Rpad-1 zero): the operands of the backward products in the layout
@@ -469,29 +463,7 @@ __global__ __launch_bounds__(256) void transpose_planes_kernel(const float* __re
   }
 }
 
-// ---- f32 <-> fp16 pairs (common.hpp split_pair): groups of 32 elements as [hi x 32][lo x 32]; a thread converts 8 elements
-__global__ __launch_bounds__(256) void split_pairs_kernel(const float* __restrict__ src, _Float16* __restrict__ dst, long long n8, int* range_flag) {
-  typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-  bool bad = false;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
-    float v[8];
-    *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(src + 8 * i);
-    *reinterpret_cast<float4*>(v + 4) = *reinterpret_cast<const float4*>(src + 8 * i + 4);
-    f16x8 qh, ql;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      _Float16 hi_, lo_;
-      split_pair(v[e], hi_, lo_);
-      qh[e] = hi_;
-      ql[e] = lo_;
-      bad |= pair_hi_bad(hi_);
-    }
-    _Float16* d = dst + pair_index(8 * i);
-    *reinterpret_cast<f16x8*>(d) = qh;
-    *reinterpret_cast<f16x8*>(d + 32) = ql;
-  }
-  range_flag_raise(range_flag, bad);
-}
+// ---- fp16 pairs -> f32 (common.hpp join_pair): groups of 32 elements as [hi x 32][lo x 32]; a thread converts 8 elements
 __global__ __launch_bounds__(256) void join_pairs_kernel(const _Float16* __restrict__ src, float* __restrict__ dst, long long n8) {
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
@@ -725,57 +697,26 @@ int planes8_try(const void* x_planes, long long x_plane_stride, const void* w_pl
 int planes8_would_run(int planes, int M, int N, int K, int act, int has_bias, int has_residual, int has_y, int y_nplanes);
 
 
-// PatchEmbed rows for the bf16-plane path (dino_vision_transformer.py:166-171,236-247): one workgroup per token row m = (frame f, token t).
-//   a [F (n + 1)][C P P] bf16: the im2col row of patch t - 1 (k = (c P + y) P + x, the conv weight's own order), ZERO for the class token
+// PatchEmbed rows for the bf16-plane and fp16-pair paths (dino_vision_transformer.py:166-171,236-247): one workgroup per token row
+// m = (frame f, token t).
+//   a [F (n + 1)][C P P] as ONE bf16 plane or as pairs (OutPlanes / OutPairs; 4 adjacent k lie in one group of 32): the im2col row of patch
+//   t - 1 (k = (c P + y) P + x, the conv weight's own order), ZERO for the class token
 //   tokens [F][n + 1][D] fp32: what the GEMM's residual epilogue adds to - pos[t], and cls + pos[0] - bias for the class token (its zero
 //   row meets the bias in the epilogue)
-// so that ONE plane GEMM over all F (n + 1) rows (tt_linear_fwd_planes, residual = y = tokens) leaves prepare_tokens' result: no row
-// gather, no separate class-token pass.
-__global__ __launch_bounds__(256) void patch_rows_planes_kernel(const float* __restrict__ img, const int* __restrict__ frame_map,
-                                                                  const float* __restrict__ bias, const float* __restrict__ cls,
-                                                                  const float* __restrict__ pos, __bf16* __restrict__ a,
-                                                                  float* __restrict__ tokens, int C, int H, int W, int P, int D, int gw, int n) {
+// so that ONE GEMM over all F (n + 1) rows (tt_linear_fwd_planes / linear_pairs_impl, residual = y = tokens) leaves prepare_tokens' result:
+// no row gather, no separate class-token pass.
+template <class Out>
+__global__ __launch_bounds__(256) void patch_rows_kernel(const float* __restrict__ img, const int* __restrict__ frame_map,
+                                                         const float* __restrict__ bias, const float* __restrict__ cls,
+                                                         const float* __restrict__ pos, Out a, float* __restrict__ tokens, int C, int H, int W,
+                                                         int P, int D, int gw, int n) {
   const int m = blockIdx.x, f = m / (n + 1), t = m - f * (n + 1);
   const int K = C * P * P;
-  typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-  bf16x4* arow = reinterpret_cast<bf16x4*>(a + (long long)m * K);
   float4* trow = reinterpret_cast<float4*>(tokens + (long long)m * D);
   const float4* prow = reinterpret_cast<const float4*>(pos + (long long)t * D);
   if (t == 0) {
-    for (int i = threadIdx.x; i < K / 4; i += 256) arow[i] = (bf16x4){(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-    for (int i = threadIdx.x; i < D / 4; i += 256) {
-      const float4 c = reinterpret_cast<const float4*>(cls)[i], b = reinterpret_cast<const float4*>(bias)[i], q = prow[i];
-      trow[i] = make_float4(c.x + q.x - b.x, c.y + q.y - b.y, c.z + q.z - b.z, c.w + q.w - b.w);
-    }
-    return;
-  }
-  const int src = frame_map ? frame_map[f] : f;
-  const int gy = (t - 1) / gw, gx = (t - 1) - gy * gw;
-  const float* base = img + ((long long)src * C * H + gy * P) * W + gx * P;
-  const int P4 = P / 4;
-  for (int i = threadIdx.x; i < K / 4; i += 256) {
-    const int x4 = i % P4, cy = i / P4, y = cy % P, c = cy / P;
-    const float4 v = *reinterpret_cast<const float4*>(base + ((long long)c * H + y) * W + 4 * x4);
-    arow[i] = (bf16x4){(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-  }
-  for (int i = threadIdx.x; i < D / 4; i += 256) trow[i] = prow[i];
-}
-
-// The same rows for the fp16-PAIR path ("f16x3"): a [F (n + 1)][2 C P P] fp16 in pairs (groups of 32 k as [hi x 32][lo x 32]), the class
-// token's row zero; tokens prefilled as above.  ONE pair GEMM over all rows (residual = y = tokens) then leaves prepare_tokens' result.
-__global__ __launch_bounds__(256) void patch_rows_pairs_kernel(const float* __restrict__ img, const int* __restrict__ frame_map,
-                                                                 const float* __restrict__ bias, const float* __restrict__ cls,
-                                                                 const float* __restrict__ pos, _Float16* __restrict__ a,
-                                                                 float* __restrict__ tokens, int C, int H, int W, int P, int D, int gw, int n,
-                                                                 int* range_flag) {
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  const int m = blockIdx.x, f = m / (n + 1), t = m - f * (n + 1);
-  const int K = C * P * P;
-  _Float16* arow = a + (long long)m * 2 * K;
-  float4* trow = reinterpret_cast<float4*>(tokens + (long long)m * D);
-  const float4* prow = reinterpret_cast<const float4*>(pos + (long long)t * D);
-  if (t == 0) {
-    for (int i = threadIdx.x; i < K / 2; i += 256) reinterpret_cast<f16x4*>(arow)[i] = (f16x4){(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+    const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < K / 4; i += 256) a.put((long long)m * K, 4 * i, zero, false);
     for (int i = threadIdx.x; i < D / 4; i += 256) {
       const float4 c = reinterpret_cast<const float4*>(cls)[i], b = reinterpret_cast<const float4*>(bias)[i], q = prow[i];
       trow[i] = make_float4(c.x + q.x - b.x, c.y + q.y - b.y, c.z + q.z - b.z, c.w + q.w - b.w);
@@ -790,14 +731,10 @@ __global__ __launch_bounds__(256) void patch_rows_pairs_kernel(const float* __re
   for (int i = threadIdx.x; i < K / 4; i += 256) {
     const int x4 = i % P4, cy = i / P4, y = cy % P, c = cy / P;
     const float4 v = *reinterpret_cast<const float4*>(base + ((long long)c * H + y) * W + 4 * x4);
-    _Float16 h0, l0, h1, l1, h2, l2, h3, l3;
-    split_pair(v.x, h0, l0); split_pair(v.y, h1, l1); split_pair(v.z, h2, l2); split_pair(v.w, h3, l3);
-    bad = bad || pair_hi_bad(h0) || pair_hi_bad(h1) || pair_hi_bad(h2) || pair_hi_bad(h3);
-    _Float16* p = arow + pair_index(4 * i);   // k = 4 i .. 4 i + 3 lie in one group of 32
-    *reinterpret_cast<f16x4*>(p) = (f16x4){h0, h1, h2, h3};
-    *reinterpret_cast<f16x4*>(p + 32) = (f16x4){l0, l1, l2, l3};
+    const float o[4] = {v.x, v.y, v.z, v.w};
+    bad = a.put((long long)m * K, 4 * i, o, bad);
   }
-  range_flag_raise(range_flag, bad);
+  a.finish(bad);
   for (int i = threadIdx.x; i < D / 4; i += 256) trow[i] = prow[i];
 }
 
@@ -839,8 +776,8 @@ extern "C" int tt_split_planes(const float* src, void* dst_planes, long long pla
              "multiples of 8 elements and the buffers 16-byte aligned");
   long long blocks = (n / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), src, static_cast<__bf16*>(dst_planes),
-                     plane_stride, planes, n / 8);
+  hipLaunchKernelGGL(split_kernel<OutPlanes>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), src,
+                     OutPlanes{static_cast<__bf16*>(dst_planes), plane_stride, planes}, n / 8);
   TT_CHECK_LAUNCH("split_planes");
   return TT_OK;
 }
@@ -969,7 +906,8 @@ extern "C" int tt_split_pairs(const float* src, void* dst_pairs, long long n, in
   TT_REQUIRE(n % 32 == 0 && aligned16(src) && aligned16(dst_pairs), "split_pairs: n must be a multiple of 32 and the buffers 16-byte aligned");
   long long blocks = (n / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(split_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), src, static_cast<_Float16*>(dst_pairs), n / 8, range_flag);
+  hipLaunchKernelGGL(split_kernel<OutPairs>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), src,
+                     OutPairs{static_cast<_Float16*>(dst_pairs), range_flag}, n / 8);
   TT_CHECK_LAUNCH("split_pairs");
   return TT_OK;
 }
@@ -1208,8 +1146,8 @@ extern "C" int tt_patch_embed_fwd_planes(const float* img, const int32_t* frame_
              "patch_embed_planes: buffers must be 16-byte aligned");
   TT_REQUIRE(M * (long long)(K > D ? K : D) < (1ll << 31), "patch_embed_planes: F (n + 1) max(C P P, D) exceeds the int range");
   TT_REQUIRE(workspace_bytes >= tt_patch_embed_planes_workspace_bytes(F, C, H, W, P), "patch_embed_planes: workspace too small");
-  hipLaunchKernelGGL(patch_rows_planes_kernel, dim3((unsigned)M), dim3(256), 0, as_stream(stream), img, frame_map, bias, cls, pos,
-                     static_cast<__bf16*>(workspace), tokens, C, H, W, P, D, W / P, n);
+  hipLaunchKernelGGL(patch_rows_kernel<OutPlanes>, dim3((unsigned)M), dim3(256), 0, as_stream(stream), img, frame_map, bias, cls, pos,
+                     OutPlanes{static_cast<__bf16*>(workspace), 0, 1}, tokens, C, H, W, P, D, W / P, n);
   TT_CHECK_LAUNCH("patch_embed_planes.rows");
   void* kws = static_cast<unsigned char*>(workspace) + patch_rows_bytes(F, C, H, W, P, 2);
   const int rc = patch_ksplit_init(kws, stream);
@@ -1237,8 +1175,8 @@ extern "C" int tt_patch_embed_fwd_pairs(const float* img, const int32_t* frame_m
              "patch_embed_pairs: buffers must be 16-byte aligned");
   TT_REQUIRE(M * (long long)(K > D ? K : D) < (1ll << 31), "patch_embed_pairs: F (n + 1) max(C P P, D) exceeds the int range");
   TT_REQUIRE(workspace_bytes >= tt_patch_embed_pairs_workspace_bytes(F, C, H, W, P), "patch_embed_pairs: workspace too small");
-  hipLaunchKernelGGL(patch_rows_pairs_kernel, dim3((unsigned)M), dim3(256), 0, as_stream(stream), img, frame_map, bias, cls, pos,
-                     static_cast<_Float16*>(workspace), tokens, C, H, W, P, D, W / P, n, range_flag);
+  hipLaunchKernelGGL(patch_rows_kernel<OutPairs>, dim3((unsigned)M), dim3(256), 0, as_stream(stream), img, frame_map, bias, cls, pos,
+                     OutPairs{static_cast<_Float16*>(workspace), range_flag}, tokens, C, H, W, P, D, W / P, n);
   TT_CHECK_LAUNCH("patch_embed_pairs.rows");
   void* kws = static_cast<unsigned char*>(workspace) + patch_rows_bytes(F, C, H, W, P, 4);
   const int rc = patch_ksplit_init(kws, stream);

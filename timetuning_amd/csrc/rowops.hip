@@ -2,6 +2,13 @@
 // deterministic column sums, cls-token rows, AdamW over a tensor table, EMA lerp, queue FIFO update.
 // One 64-lane wave owns one row; a row (D <= 1024) is held in registers between the statistics pass
 // and the output pass so that each element is read once and written once.
+// The LayerNorm forward is two kernels - one column per lane and pass (any D), two adjacent columns per lane for D = 128 NV - templated on
+// the operand writer (common.hpp OutF32 / OutPlanes / OutPairs): plain fp32, 1..3 bf16 planes (y = p0 + p1 + p2, the operand layout of
+// gemm_planes.hip) or fp16 pairs ([rows][2 D], groups of 32 columns as [hi x 32][lo x 32], the operand format of gemm_pairs8.hip), so that
+// the consuming nn.Linear finds its A operand pre-split.  Every format carries the same fp32 value: the writer only stores
+// (tests/test_hip_pairs.py pins it).  The two-column kernel that writes pairs is the one exception: it stays a kernel of its own.
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace tt {
@@ -11,16 +18,17 @@ constexpr int kMaxPerLane = 16;  // D <= 1024
 // ------------------------------------------------------------------------------------------------
 // LayerNorm (dino_vision_transformer.py:139,143,196)
 // ------------------------------------------------------------------------------------------------
+template <class Out>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, float* __restrict__ y,
-                                                            float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                            int rows, int D, float eps, int skip_group) {
+                                                            const float* __restrict__ beta, Out out, float* __restrict__ mean_out,
+                                                            float* __restrict__ rstd_out, int rows, int D, float eps, int skip_group) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   // skip_group = N: the input is [F][N][D] tokens and the output drops token 0 (cls) of every frame
   const long long in_row = skip_group ? (long long)(row / (skip_group - 1)) * skip_group + 1 + row % (skip_group - 1) : row;
   const float* xr = x + in_row * D;
+  bool bad = false;
   float v[kMaxPerLane];
   float s = 0.f;
 #pragma unroll
@@ -38,128 +46,28 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     q += d * d;
   }
   const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-  float* yr = y + (long long)row * D;
-#pragma unroll
-  for (int i = 0; i < kMaxPerLane; ++i) {
-    const int c = lane + 64 * i;
-    if (c < D) yr[c] = (v[i] - mean) * rstd * gamma[c] + beta[c];
-  }
-  if (lane == 0) {
-    if (mean_out) mean_out[row] = mean;
-    if (rstd_out) rstd_out[row] = rstd;
-  }
-}
-
-// D = 128 NV (ViT-S 384, ViT-B 768, the 1024 / 512 / 256-wide head layers): 8-byte loads and stores, a compile-time trip count
-// and R rows per wave in flight.  Same arithmetic; the per-lane partial sums group the elements differently.
-template <int NV, int R>
-__global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, float* __restrict__ y,
-                                                                float* __restrict__ mean_out, float* __restrict__ rstd_out, int rows,
-                                                                float eps, int skip_group) {
-  constexpr int D = 128 * NV;
-  const int lane = threadIdx.x & 63;
-  const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
-  if (row0 >= rows) return;
-  float2 v[R][NV];
-  float s[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    s[r] = 0.f;
-    const int row = row0 + r < rows ? row0 + r : row0;
-    const long long in_row = skip_group ? (long long)(row / (skip_group - 1)) * skip_group + 1 + row % (skip_group - 1) : row;
-    const float2* xr = reinterpret_cast<const float2*>(x + in_row * D);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      v[r][i] = xr[lane + 64 * i];
-      s[r] += v[r][i].x + v[r][i].y;
-    }
-  }
-  float2 gm[NV], bt[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    gm[i] = reinterpret_cast<const float2*>(gamma)[lane + 64 * i];
-    bt[i] = reinterpret_cast<const float2*>(beta)[lane + 64 * i];
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (row0 + r >= rows) break;
-    const float mean = wave_sum(s[r]) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const float dx = v[r][i].x - mean, dy = v[r][i].y - mean;
-      q += dx * dx + dy * dy;
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-    float2* yr = reinterpret_cast<float2*>(y + (long long)(row0 + r) * D);
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-      yr[lane + 64 * i] = make_float2((v[r][i].x - mean) * rstd * gm[i].x + bt[i].x, (v[r][i].y - mean) * rstd * gm[i].y + bt[i].y);
-    if (lane == 0) {
-      if (mean_out) mean_out[row0 + r] = mean;
-      if (rstd_out) rstd_out[row0 + r] = rstd;
-    }
-  }
-}
-
-// The same with the result written as 1..3 bf16 planes (y = p0 + p1 + p2): the operand layout of gemm_planes.hip, so the
-// consuming nn.Linear finds its A operand pre-split and nothing is converted on its path.
-__global__ __launch_bounds__(256) void layernorm_fwd_planes_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                                   const float* __restrict__ beta, __bf16* __restrict__ y, long long stride,
-                                                                   int planes, float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                                   int rows, int D, float eps, int skip_group) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long in_row = skip_group ? (long long)(row / (skip_group - 1)) * skip_group + 1 + row % (skip_group - 1) : row;
-  const float* xr = x + in_row * D;
-  float v[kMaxPerLane];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < kMaxPerLane; ++i) {
-    const int c = lane + 64 * i;
-    v[i] = (c < D) ? xr[c] : 0.f;
-    s += v[i];
-  }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < kMaxPerLane; ++i) {
-    const int c = lane + 64 * i;
-    const float d = (c < D) ? v[i] - mean : 0.f;
-    q += d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-  __bf16* yr = y + (long long)row * D;
 #pragma unroll
   for (int i = 0; i < kMaxPerLane; ++i) {
     const int c = lane + 64 * i;
     if (c < D) {
-      const float o = (v[i] - mean) * rstd * gamma[c] + beta[c];
-      const __bf16 p0 = (__bf16)o;
-      yr[c] = p0;
-      if (planes > 1) {
-        const float r1 = o - (float)p0;
-        const __bf16 p1 = (__bf16)r1;
-        yr[stride + c] = p1;
-        if (planes > 2) yr[2 * stride + c] = (__bf16)(r1 - (float)p1);
-      }
+      const float o[1] = {(v[i] - mean) * rstd * gamma[c] + beta[c]};
+      bad = out.put((long long)row * D + 64 * i, lane, o, bad);
     }
   }
+  out.finish(bad);
   if (lane == 0) {
     if (mean_out) mean_out[row] = mean;
     if (rstd_out) rstd_out[row] = rstd;
   }
 }
 
-// The plane-writing LayerNorm for D = 128 NV: 8-byte loads, 4-byte (two bf16) stores per plane, two rows per wave in flight.
-template <int NV, int R>
-__global__ __launch_bounds__(256) void layernorm_fwd_planes_vec_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                                       const float* __restrict__ beta, __bf16* __restrict__ y, long long stride,
-                                                                       int planes, float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                                       int rows, float eps, int skip_group) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+// D = 128 NV (ViT-S 384, ViT-B 768, the 1024 / 512 / 256-wide head layers): 8-byte loads, two adjacent columns per lane and store, a
+// compile-time trip count and R rows per wave in flight.  Same arithmetic; the per-lane partial sums group the elements differently.
+template <class Out, int NV, int R>
+__global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, Out out, float* __restrict__ mean_out,
+                                                                float* __restrict__ rstd_out, int rows, float eps, int skip_group) {
+  bool bad = false;
   constexpr int D = 128 * NV;
   const int lane = threadIdx.x & 63;
   const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
@@ -195,32 +103,23 @@ __global__ __launch_bounds__(256) void layernorm_fwd_planes_vec_kernel(const flo
       q += dx * dx + dy * dy;
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-    bf16x2* yr = reinterpret_cast<bf16x2*>(y + (long long)(row0 + r) * D);
-    const long long st2 = stride / 2;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const float o0 = (v[r][i].x - mean) * rstd * gm[i].x + bt[i].x, o1 = (v[r][i].y - mean) * rstd * gm[i].y + bt[i].y;
-      bf16x2 p0 = {(__bf16)o0, (__bf16)o1};
-      yr[lane + 64 * i] = p0;
-      if (planes > 1) {
-        const float r0 = o0 - (float)p0[0], r1 = o1 - (float)p0[1];
-        bf16x2 p1 = {(__bf16)r0, (__bf16)r1};
-        yr[st2 + lane + 64 * i] = p1;
-        if (planes > 2) {
-          bf16x2 p2 = {(__bf16)(r0 - (float)p1[0]), (__bf16)(r1 - (float)p1[1])};
-          yr[2 * st2 + lane + 64 * i] = p2;
-        }
-      }
+      const float o[2] = {(v[r][i].x - mean) * rstd * gm[i].x + bt[i].x, (v[r][i].y - mean) * rstd * gm[i].y + bt[i].y};
+      bad = out.put((long long)(row0 + r) * D + 128 * i, 2 * lane, o, bad);
     }
     if (lane == 0) {
       if (mean_out) mean_out[row0 + r] = mean;
       if (rstd_out) rstd_out[row0 + r] = rstd;
     }
   }
+  out.finish(bad);
 }
 
-// LayerNorm whose result is written as fp16 PAIRS (common.hpp split_pair; the operand format of gemm_pairs8.hip): [rows][2 D] fp16,
-// groups of 32 columns as [hi x 32][lo x 32].  D = 128 NV: 8-byte loads, two columns per lane -> 4-byte hi and lo stores.
+// The pair-writing form of layernorm_fwd_vec_kernel, kept as its own kernel: as an instance of the template the compiler contracts the
+// variance sums of NV = 6 and 8 differently (it pairs the squares with the writer's packed conversions), and mean / rstd / y then differ in
+// the last bit from the fp32 and plane kernels' ("one LayerNorm forward").  [rows][2 D] fp16, groups of 32 columns as
+// [hi x 32][lo x 32]; two columns per lane -> 4-byte hi and lo stores.
 template <int NV, int R>
 __global__ __launch_bounds__(256) void layernorm_fwd_pairs_vec_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                       const float* __restrict__ beta, _Float16* __restrict__ y,
@@ -284,50 +183,30 @@ __global__ __launch_bounds__(256) void layernorm_fwd_pairs_vec_kernel(const floa
   range_flag_raise(range_flag, bad);
 }
 
-// any D % 32 == 0 (<= 1024): one column per lane and pass
-__global__ __launch_bounds__(256) void layernorm_fwd_pairs_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                                  const float* __restrict__ beta, _Float16* __restrict__ y,
-                                                                  float* __restrict__ mean_out, float* __restrict__ rstd_out, int rows, int D,
-                                                                  float eps, int skip_group, int* range_flag) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long in_row = skip_group ? (long long)(row / (skip_group - 1)) * skip_group + 1 + row % (skip_group - 1) : row;
-  const float* xr = x + in_row * D;
-  bool bad = false;
-  float v[kMaxPerLane];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < kMaxPerLane; ++i) {
-    const int c = lane + 64 * i;
-    v[i] = (c < D) ? xr[c] : 0.f;
-    s += v[i];
-  }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < kMaxPerLane; ++i) {
-    const int c = lane + 64 * i;
-    const float d = (c < D) ? v[i] - mean : 0.f;
-    q += d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-  _Float16* yr = y + (long long)row * (2 * D);
-#pragma unroll
-  for (int i = 0; i < kMaxPerLane; ++i) {
-    const int c = lane + 64 * i;
-    if (c < D) {
-      _Float16 hi, lo;
-      split_pair((v[i] - mean) * rstd * gamma[c] + beta[c], hi, lo);
-      bad |= pair_hi_bad(hi);
-      yr[pair_index(c)] = hi;
-      yr[pair_index(c) + 32] = lo;
-    }
-  }
-  range_flag_raise(range_flag, bad);
-  if (lane == 0) {
-    if (mean_out) mean_out[row] = mean;
-    if (rstd_out) rstd_out[row] = rstd;
+template <class Out, int NV, int R>
+static void launch_layernorm_fwd_vec(const float* x, const float* gamma, const float* beta, Out out, float* mean, float* rstd, int rows, float eps,
+                                     int skip_group, hipStream_t s) {
+  const dim3 grid((rows + 4 * R - 1) / (4 * R)), block(256);
+  if constexpr (std::is_same<Out, OutPairs>::value)
+    hipLaunchKernelGGL((layernorm_fwd_pairs_vec_kernel<NV, R>), grid, block, 0, s, x, gamma, beta, out.y, mean, rstd, rows, eps, skip_group, out.range_flag);
+  else
+    hipLaunchKernelGGL((layernorm_fwd_vec_kernel<Out, NV, R>), grid, block, 0, s, x, gamma, beta, out, mean, rstd, rows, eps, skip_group);
+}
+
+// The vectorised route (the entries add their own alignment conditions) for D = 128 NV, NV in {1, 2, 3, 4, 6, 8}; else the general kernel.
+template <class Out>
+static void launch_layernorm_fwd(bool vec_ok, const float* x, const float* gamma, const float* beta, Out out, float* mean, float* rstd, int rows,
+                                 int D, float eps, int skip_group, hipStream_t s) {
+  constexpr int R = 2;   // rows in flight per wave: 14.8 / 13.4 / 13.6 us at 1 / 2 / 4 on 25216 x 384 (15.8 for the scalar kernel)
+  switch (vec_ok && D % 128 == 0 ? D / 128 : 0) {
+    case 1: launch_layernorm_fwd_vec<Out, 1, R>(x, gamma, beta, out, mean, rstd, rows, eps, skip_group, s); break;
+    case 2: launch_layernorm_fwd_vec<Out, 2, R>(x, gamma, beta, out, mean, rstd, rows, eps, skip_group, s); break;
+    case 3: launch_layernorm_fwd_vec<Out, 3, R>(x, gamma, beta, out, mean, rstd, rows, eps, skip_group, s); break;
+    case 4: launch_layernorm_fwd_vec<Out, 4, R>(x, gamma, beta, out, mean, rstd, rows, eps, skip_group, s); break;
+    case 6: launch_layernorm_fwd_vec<Out, 6, R>(x, gamma, beta, out, mean, rstd, rows, eps, skip_group, s); break;
+    case 8: launch_layernorm_fwd_vec<Out, 8, R>(x, gamma, beta, out, mean, rstd, rows, eps, skip_group, s); break;
+    default:
+      hipLaunchKernelGGL(layernorm_fwd_kernel<Out>, dim3((rows + 3) / 4), dim3(256), 0, s, x, gamma, beta, out, mean, rstd, rows, D, eps, skip_group);
   }
 }
 
@@ -700,25 +579,7 @@ extern "C" int tt_layernorm_fwd(const float* x, const float* gamma, const float*
   TT_REQUIRE(rows > 0 && D > 0 && D <= 64 * kMaxPerLane, "layernorm_fwd: need 0 < D <= %d (got %d)", 64 * kMaxPerLane, D);
   const bool al8 = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gamma) |
                      reinterpret_cast<uintptr_t>(beta)) & 7u) == 0;
-  if (al8 && D % 128 == 0 && D <= 1024) {
-    constexpr int R = 2;   // rows in flight per wave: 14.8 / 13.4 / 13.6 us at 1 / 2 / 4 on 25216 x 384 (15.8 for the scalar kernel)
-    const dim3 grid((rows + 4 * R - 1) / (4 * R)), block(256);
-    hipStream_t s = as_stream(stream);
-    switch (D / 128) {
-      case 1: hipLaunchKernelGGL((layernorm_fwd_vec_kernel<1, R>), grid, block, 0, s, x, gamma, beta, y, mean, rstd, rows, eps, skip_group); break;
-      case 2: hipLaunchKernelGGL((layernorm_fwd_vec_kernel<2, R>), grid, block, 0, s, x, gamma, beta, y, mean, rstd, rows, eps, skip_group); break;
-      case 3: hipLaunchKernelGGL((layernorm_fwd_vec_kernel<3, R>), grid, block, 0, s, x, gamma, beta, y, mean, rstd, rows, eps, skip_group); break;
-      case 4: hipLaunchKernelGGL((layernorm_fwd_vec_kernel<4, R>), grid, block, 0, s, x, gamma, beta, y, mean, rstd, rows, eps, skip_group); break;
-      case 6: hipLaunchKernelGGL((layernorm_fwd_vec_kernel<6, R>), grid, block, 0, s, x, gamma, beta, y, mean, rstd, rows, eps, skip_group); break;
-      case 8: hipLaunchKernelGGL((layernorm_fwd_vec_kernel<8, R>), grid, block, 0, s, x, gamma, beta, y, mean, rstd, rows, eps, skip_group); break;
-      default: goto general;
-    }
-    TT_CHECK_LAUNCH("layernorm_fwd");
-    return TT_OK;
-  }
-general:
-  hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, as_stream(stream), x, gamma, beta, y, mean, rstd,
-                     rows, D, eps, skip_group);
+  launch_layernorm_fwd(al8, x, gamma, beta, OutF32{y}, mean, rstd, rows, D, eps, skip_group, as_stream(stream));
   TT_CHECK_LAUNCH("layernorm_fwd");
   return TT_OK;
 }
@@ -731,24 +592,8 @@ extern "C" int tt_layernorm_fwd_planes(const float* x, const float* gamma, const
   TT_REQUIRE(rows > 0 && D > 0 && D <= 64 * kMaxPerLane, "layernorm_fwd_planes: need 0 < D <= %d (got %d)", 64 * kMaxPerLane, D);
   const bool al = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 7u) == 0 &&
                   (reinterpret_cast<uintptr_t>(y_planes) & 3u) == 0 && plane_stride % 2 == 0;
-  if (al && (D == 384 || D == 768 || D == 128 || D == 256 || D == 512 || D == 1024)) {
-    constexpr int R = 2;
-    const dim3 grid((rows + 4 * R - 1) / (4 * R)), block(256);
-    hipStream_t s = as_stream(stream);
-    __bf16* yp = static_cast<__bf16*>(y_planes);
-    switch (D / 128) {
-      case 1: hipLaunchKernelGGL((layernorm_fwd_planes_vec_kernel<1, R>), grid, block, 0, s, x, gamma, beta, yp, plane_stride, planes, mean, rstd, rows, eps, skip_group); break;
-      case 2: hipLaunchKernelGGL((layernorm_fwd_planes_vec_kernel<2, R>), grid, block, 0, s, x, gamma, beta, yp, plane_stride, planes, mean, rstd, rows, eps, skip_group); break;
-      case 3: hipLaunchKernelGGL((layernorm_fwd_planes_vec_kernel<3, R>), grid, block, 0, s, x, gamma, beta, yp, plane_stride, planes, mean, rstd, rows, eps, skip_group); break;
-      case 4: hipLaunchKernelGGL((layernorm_fwd_planes_vec_kernel<4, R>), grid, block, 0, s, x, gamma, beta, yp, plane_stride, planes, mean, rstd, rows, eps, skip_group); break;
-      case 6: hipLaunchKernelGGL((layernorm_fwd_planes_vec_kernel<6, R>), grid, block, 0, s, x, gamma, beta, yp, plane_stride, planes, mean, rstd, rows, eps, skip_group); break;
-      default: hipLaunchKernelGGL((layernorm_fwd_planes_vec_kernel<8, R>), grid, block, 0, s, x, gamma, beta, yp, plane_stride, planes, mean, rstd, rows, eps, skip_group); break;
-    }
-    TT_CHECK_LAUNCH("layernorm_fwd_planes");
-    return TT_OK;
-  }
-  hipLaunchKernelGGL(layernorm_fwd_planes_kernel, dim3((rows + 3) / 4), dim3(256), 0, as_stream(stream), x, gamma, beta,
-                     static_cast<__bf16*>(y_planes), plane_stride, planes, mean, rstd, rows, D, eps, skip_group);
+  launch_layernorm_fwd(al, x, gamma, beta, OutPlanes{static_cast<__bf16*>(y_planes), plane_stride, planes}, mean, rstd, rows, D, eps, skip_group,
+                       as_stream(stream));
   TT_CHECK_LAUNCH("layernorm_fwd_planes");
   return TT_OK;
 }
@@ -761,23 +606,7 @@ extern "C" int tt_layernorm_fwd_pairs(const float* x, const float* gamma, const 
              64 * kMaxPerLane, D);
   const bool al = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta)) & 7u) == 0 &&
                   (reinterpret_cast<uintptr_t>(y_pairs) & 3u) == 0;
-  _Float16* yp = static_cast<_Float16*>(y_pairs);
-  hipStream_t s = as_stream(stream);
-  if (al && (D == 384 || D == 768 || D == 128 || D == 256 || D == 512 || D == 1024)) {
-    constexpr int R = 2;
-    const dim3 grid((rows + 4 * R - 1) / (4 * R)), block(256);
-    switch (D / 128) {
-      case 1: hipLaunchKernelGGL((layernorm_fwd_pairs_vec_kernel<1, R>), grid, block, 0, s, x, gamma, beta, yp, mean, rstd, rows, eps, skip_group, range_flag); break;
-      case 2: hipLaunchKernelGGL((layernorm_fwd_pairs_vec_kernel<2, R>), grid, block, 0, s, x, gamma, beta, yp, mean, rstd, rows, eps, skip_group, range_flag); break;
-      case 3: hipLaunchKernelGGL((layernorm_fwd_pairs_vec_kernel<3, R>), grid, block, 0, s, x, gamma, beta, yp, mean, rstd, rows, eps, skip_group, range_flag); break;
-      case 4: hipLaunchKernelGGL((layernorm_fwd_pairs_vec_kernel<4, R>), grid, block, 0, s, x, gamma, beta, yp, mean, rstd, rows, eps, skip_group, range_flag); break;
-      case 6: hipLaunchKernelGGL((layernorm_fwd_pairs_vec_kernel<6, R>), grid, block, 0, s, x, gamma, beta, yp, mean, rstd, rows, eps, skip_group, range_flag); break;
-      default: hipLaunchKernelGGL((layernorm_fwd_pairs_vec_kernel<8, R>), grid, block, 0, s, x, gamma, beta, yp, mean, rstd, rows, eps, skip_group, range_flag); break;
-    }
-    TT_CHECK_LAUNCH("layernorm_fwd_pairs");
-    return TT_OK;
-  }
-  hipLaunchKernelGGL(layernorm_fwd_pairs_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, gamma, beta, yp, mean, rstd, rows, D, eps, skip_group, range_flag);
+  launch_layernorm_fwd(al, x, gamma, beta, OutPairs{static_cast<_Float16*>(y_pairs), range_flag}, mean, rstd, rows, D, eps, skip_group, as_stream(stream));
   TT_CHECK_LAUNCH("layernorm_fwd_pairs");
   return TT_OK;
 }

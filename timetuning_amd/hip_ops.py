@@ -443,8 +443,10 @@ def pos_embed_interpolate(pos, grid_h: int, grid_w: int):
     return out
 
 
-def layernorm_fwd(x, gamma, beta, eps=1e-6, save_stats=False, out=None, drop_first_token=False):
-    """LayerNorm over the last dim.  drop_first_token: x is [F,N,D] and the result is [F*(N-1), D] (cls row removed)."""
+def _layernorm_fwd_into(entry, alloc, x, gamma, beta, eps, save_stats, drop_first_token, *tail):
+    """The bookkeeping the three ``layernorm_fwd*`` wrappers share: rows and the ``skip_group`` of ``drop_first_token``, the statistics, the call.
+    ``alloc(rows, D)`` returns the output and the arguments that stand between ``beta`` and ``mean`` in the entry's signature (y first);
+    ``tail``: what stands between ``skip_group`` and the stream."""
     lib = _lib.load()
     _chk(x, "x"); _chk(gamma, "gamma"); _chk(beta, "beta")
     D = x.shape[-1]
@@ -453,13 +455,20 @@ def layernorm_fwd(x, gamma, beta, eps=1e-6, save_stats=False, out=None, drop_fir
     if drop_first_token:
         skip = x.shape[-2]
         rows = rows // skip * (skip - 1)
-        y = out if out is not None else torch.empty((rows, D), dtype=f32, device=x.device)
-    else:
-        y = out if out is not None else torch.empty_like(x)
+    y, *y_args = alloc(rows, D)
     mean = torch.empty((rows,), dtype=f32, device=x.device) if save_stats else None
     rstd = torch.empty((rows,), dtype=f32, device=x.device) if save_stats else None
-    _lib.check(lib.tt_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, float(eps), skip, _stream()), "tt_layernorm_fwd")
+    _lib.check(getattr(lib, entry)(_p(x), _p(gamma), _p(beta), _p(y), *y_args, _p(mean), _p(rstd), rows, D, float(eps), skip, *tail, _stream()), entry)
     return (y, mean, rstd) if save_stats else y
+
+
+def layernorm_fwd(x, gamma, beta, eps=1e-6, save_stats=False, out=None, drop_first_token=False):
+    """LayerNorm over the last dim.  drop_first_token: x is [F,N,D] and the result is [F*(N-1), D] (cls row removed)."""
+    def alloc(rows, D):
+        if out is not None:
+            return (out,)
+        return (torch.empty((rows, D), dtype=f32, device=x.device) if drop_first_token else torch.empty_like(x),)
+    return _layernorm_fwd_into("tt_layernorm_fwd", alloc, x, gamma, beta, eps, save_stats, drop_first_token)
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, need_wgrad=True, dx_accum=None, drop_first_token=False, dg_out=None, db_out=None, amax_out=None):
@@ -1336,20 +1345,9 @@ def split_planes(x, planes: int, out=None):
 
 def layernorm_fwd_planes(x, gamma, beta, planes: int, eps=1e-6, save_stats=False, drop_first_token=False):
     """LayerNorm whose result is written as bf16 planes [planes, rows, D] (see ``layernorm_fwd`` for the arguments)."""
-    lib = _lib.load()
-    _chk(x, "x"); _chk(gamma, "gamma"); _chk(beta, "beta")
-    D = x.shape[-1]
-    rows = x.numel() // D
-    skip = 0
-    if drop_first_token:
-        skip = x.shape[-2]
-        rows = rows // skip * (skip - 1)
-    y = torch.empty((planes, rows, D), dtype=bf16, device=x.device)
-    mean = torch.empty((rows,), dtype=f32, device=x.device) if save_stats else None
-    rstd = torch.empty((rows,), dtype=f32, device=x.device) if save_stats else None
-    _lib.check(lib.tt_layernorm_fwd_planes(_p(x), _p(gamma), _p(beta), _p(y), rows * D, int(planes), _p(mean), _p(rstd), rows, D, float(eps),
-                                           skip, _stream()), "tt_layernorm_fwd_planes")
-    return (y, mean, rstd) if save_stats else y
+    def alloc(rows, D):
+        return torch.empty((planes, rows, D), dtype=bf16, device=x.device), rows * D, int(planes)
+    return _layernorm_fwd_into("tt_layernorm_fwd_planes", alloc, x, gamma, beta, eps, save_stats, drop_first_token)
 
 
 def linear_fwd_planes(xp, wp, bias=None, residual=None, act: int = 0, out_f32: bool = True, out_planes: int = 0, save_pre: bool = False,
@@ -1426,20 +1424,9 @@ def join_pairs(xp):
 
 def layernorm_fwd_pairs(x, gamma, beta, eps=1e-6, save_stats=False, drop_first_token=False):
     """LayerNorm whose result is written as fp16 pairs [rows, 2 D] (see ``layernorm_fwd`` for the arguments)."""
-    lib = _lib.load()
-    _chk(x, "x"); _chk(gamma, "gamma"); _chk(beta, "beta")
-    D = x.shape[-1]
-    rows = x.numel() // D
-    skip = 0
-    if drop_first_token:
-        skip = x.shape[-2]
-        rows = rows // skip * (skip - 1)
-    y = torch.empty((rows, 2 * D), dtype=f16, device=x.device)
-    mean = torch.empty((rows,), dtype=f32, device=x.device) if save_stats else None
-    rstd = torch.empty((rows,), dtype=f32, device=x.device) if save_stats else None
-    _lib.check(lib.tt_layernorm_fwd_pairs(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, float(eps), skip,
-                                          _p(range_flag(x.device)), _stream()), "tt_layernorm_fwd_pairs")
-    return (y, mean, rstd) if save_stats else y
+    def alloc(rows, D):
+        return (torch.empty((rows, 2 * D), dtype=f16, device=x.device),)
+    return _layernorm_fwd_into("tt_layernorm_fwd_pairs", alloc, x, gamma, beta, eps, save_stats, drop_first_token, _p(range_flag(x.device)))
 
 
 def linear_fwd_pairs(xp, wp, bias=None, residual=None, act: int = 0, out_f32: bool = True, out_pairs: bool = False, save_pre: bool = False,
