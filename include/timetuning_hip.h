@@ -719,6 +719,30 @@ int tt_kmeans_fit_batched(const float* x, const int32_t* init, const int32_t* in
 int tt_kmeans_assign_batched(const float* x, const float* centroids, int32_t* labels, float* dist2, int B, long long N, int d, int k,
                              tt_stream_t stream);
 
+/* ---- N18: tt_kmeans_fit_batched with faiss' split of empty clusters done on the device - what Clustering::train does between the
+ *      iterations of the same faiss.Kmeans(50, k, niter=50, nredo=5).train(x) calls (clustering.py:39-41,55-57; split_clusters as
+ *      clustering.Kmeans._split_empty restates it), the normal case under use_mask=True (evaluation.py:411-427,461-462), where the
+ *      background tokens are one and the same point.
+ *   tt_kmeans_fit_batched_split   the arguments, outputs, arithmetic and refusals of tt_kmeans_fit_batched, plus draws fp64 [n_draws]
+ *                              in device memory: the first n_draws values of numpy.random.RandomState(1234).random_sample(), the
+ *                              generator the host re-creates at every split call.  After the update of an iteration whose counts
+ *                              hold a zero the workgroup splits on its own centroids and counts and goes on (the draw index starts
+ *                              at 0 at every such call):
+ *                                the empty clusters ci in increasing order; the whole call stops where n <= k or the largest count
+ *                                is <= 1; the donor walk starts at cj = 0 and accepts where draw < (double)(count[cj] - 1) /
+ *                                (double)(n - k), else cj = (cj + 1) % k, and after more than 64 k refusals takes the first arg-max
+ *                                of the counts; c[ci][j] = c[cj][j] * s_j from the old donor row, then c[cj][j] = c[cj][j] * (2 - s_j),
+ *                                s_j = 1 + 2^-10 (j even), 1 - 2^-10 (j odd), single fp32 products; count[ci] = count[cj] / 2, then
+ *                                count[cj] -= count[ci].  Later splits of a call see what earlier ones changed.
+ *                              obj is taken before the split, which also runs after the last update.  status = 0, or the 1-based
+ *                              iteration whose split would have read past the table: that (problem, redo) ends there, centroids and
+ *                              obj unspecified, and the caller reruns the problem on the loop.  Trip counts are bounded by n_draws
+ *                              and 64 k + 1 tries per empty cluster; no workgroup waits on another; the LDS rule is unchanged.
+ *   Refused like tt_kmeans_fit_batched, and for a null draws or n_draws < 1. */
+int tt_kmeans_fit_batched_split(const float* x, const int32_t* init, const int32_t* init_host, float* centroids, double* obj,
+                                int32_t* status, int B, long long n, int d, int k, int nredo, int niter, void* workspace,
+                                size_t workspace_bytes, const double* draws, int n_draws, tt_stream_t stream);
+
 /* ---- N3(SURVEY.md 8(f)): the clip input pipeline - the pixel work of video_transformations.py as wired at
  *      time_tuning.py:588-593, bit-exact with Pillow (which the reference calls per frame on the host).
  *   Frames are interleaved uint8 RGB [F, H, W, 3] in device memory.

@@ -167,6 +167,7 @@ SIGNATURES = {
     "tt_kmeans_fit_lds_bytes": (c_sz, [c_ll, c_i, c_i]),
     "tt_kmeans_fit_workspace_bytes": (c_sz, [c_i, c_i, c_ll, c_i, c_i]),
     "tt_kmeans_fit_batched": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_ll, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
+    "tt_kmeans_fit_batched_split": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_ll, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp, c_i, c_vp]),
     "tt_kmeans_assign_batched": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_ll, c_i, c_i, c_vp]),
     "tt_label_propagate_sims": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
     "tt_label_propagate_from_sims": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_vp, c_sz, c_vp]),

@@ -17,6 +17,11 @@ layouts.  The reference leans on two third-party CPU libraries here: scikit-lear
                         reproduced (``torch.Generator`` / ``numpy.RandomState`` with the same seed formulas), so cluster ids
                         and, on hard data, the local optimum can differ from a faiss run: parity here is "unpinned" and the
                         tests check the algorithm against a NumPy restatement fed with the same random draws.
+
+The frame-wise and sample-wise protocols fit all their problems of one k in one launch (``KmeansBatch``, N13).  The split of empty
+clusters draws from ``numpy.RandomState(1234)``, re-created at every call; ``split_draws`` holds that one sequence as a table, with which
+the fused kernel splits on the device (N18: ``KmeansBatch(split="device")``, ``split_empty_from_table`` is its host statement), so a
+masked evaluation batch, whose every fit meets empty clusters, stays off the host-driven loop.
 """
 from __future__ import annotations
 
@@ -243,24 +248,91 @@ class Kmeans:
         return ops.nearest_upsample_labels(labels.view(M, n_tok), iy, ix)
 
 
+# -- the split of empty clusters as a table walk (N18) -------------------------------------------------------------------------------
+# ``Kmeans._split_empty`` re-creates ``numpy.random.RandomState(1234)`` at every call, so every call consumes a prefix of ONE fixed
+# sequence.  With that sequence in a table the split needs no generator: ``split_empty_from_table`` is ``_split_empty`` stated that way
+# on the host (the tests hold the two to each other), and kf_split_empty of csrc/kmeans_fit.hip is the same statement in the kernel.
+
+DEVICE_SPLIT = True          # _kmeans_maps_grouped builds KmeansBatch(split="device"); False forces the fall-back to the loop
+SPLIT_DRAWS = 4096           # ten times the most one _split_empty call was seen to draw at the evaluator's shapes (393, at k = 21)
+_split_tables: dict = {}
+
+
+def split_draws(n_draws: int = SPLIT_DRAWS, device=None) -> torch.Tensor:
+    """float64 [n_draws]: the first values of ``numpy.random.RandomState(1234).random_sample()`` - what ``_split_empty`` draws, in its
+    order.  On ``device`` (default: the host); one tensor per (device, n_draws), built once."""
+    key = (str(torch.device("cpu" if device is None else device)), int(n_draws))
+    if key not in _split_tables:
+        _split_tables[key] = torch.from_numpy(np.random.RandomState(1234).random_sample(int(n_draws))).to(key[0])
+    return _split_tables[key]
+
+
+def split_empty_from_table(cent: torch.Tensor, counts: np.ndarray, n: int, draws) -> int:
+    """``Kmeans._split_empty(cent, counts, n)`` with the generator's draws read from ``draws`` (float64, ``split_draws``), from index 0:
+    ``cent`` [k, d] and ``counts`` [k] are changed the same way.  Returns the number of splits, or -1 where a draw beyond the table was
+    needed (``cent`` and ``counts`` are then part-way through the call).  The kernel's split is written against this function."""
+    k, d = cent.shape
+    draws = np.asarray(draws.cpu() if isinstance(draws, torch.Tensor) else draws, dtype=np.float64)
+    eps = 1.0 / 1024.0
+    sign = torch.tensor([1.0 + eps if j % 2 == 0 else 1.0 - eps for j in range(d)], device=cent.device)
+    nsplit, nxt = 0, 0
+    for ci in range(k):
+        if counts[ci] != 0:
+            continue
+        if n <= k or counts.max() <= 1:
+            break
+        cj, tries = 0, 0
+        while True:
+            if nxt >= len(draws):
+                return -1
+            p = (counts[cj] - 1.0) / float(n - k)
+            nxt += 1
+            if draws[nxt - 1] < p:
+                break
+            cj = (cj + 1) % k
+            tries += 1
+            if tries > 64 * k:
+                cj = int(np.argmax(counts))
+                break
+        cent[ci] = cent[cj] * sign
+        cent[cj] = cent[cj] * (2.0 - sign)
+        counts[ci] = counts[cj] // 2
+        counts[cj] -= counts[ci]
+        nsplit += 1
+    return nsplit
+
+
 class KmeansBatch:
     """``Kmeans(d, k, ...)`` for B problems of equal shape at once: ``train(points [B, n, d])`` runs every problem's redos and Lloyd
     iterations in ONE launch (``ops.kmeans_fit_batched``) and reads the objectives and the empty-cluster flags back once.  Per problem
     the subsample, the seeds and the arithmetic are those of ``Kmeans.train``, so the centroids are the same bits - with one
     reservation: the per-redo objective is the kernel's own fixed-order fp64 sum, not torch's reduction (they agree to about
-    n * 2^-53 relative), so the redo kept can differ where two DISTINCT objectives lie that close.  A problem in which any redo met an
-    empty cluster is rerun whole on the loop (``Kmeans._fit``), which knows faiss' split; ``fallback`` says which."""
+    n * 2^-53 relative), so the redo kept can differ where two DISTINCT objectives lie that close.
 
-    def __init__(self, d: int, k: int, niter: int = 50, nredo: int = 5, seed: int = 1, max_points_per_centroid: int = 256):
+    ``split`` says who splits an empty cluster.  ``"host"``: a problem in which any redo met one is rerun whole on the loop
+    (``Kmeans._fit``), which knows faiss' split.  ``"device"`` (N18): the flagged problems - those alone, so a batch without empty
+    clusters is the one launch it was - are fitted again by the kernel that splits from the table of ``split_draws``, and only a
+    problem whose status is still non-zero, because one split call needed more draws than the table holds, goes to the loop.
+    ``fallback`` says which problems the loop fitted; ``status`` is that of the last launch that fitted the problem."""
+
+    def __init__(self, d: int, k: int, niter: int = 50, nredo: int = 5, seed: int = 1, max_points_per_centroid: int = 256, split: str = "host"):
+        if split not in ("host", "device"):
+            raise ValueError(f"KmeansBatch: split = {split!r}: expected 'host' or 'device'")
         self.d, self.k, self.niter, self.nredo, self.seed = d, k, niter, nredo, seed
         self.max_points_per_centroid = max_points_per_centroid
+        self.split = split
         self.centroids: Optional[torch.Tensor] = None   # [B, k, d] on the device
         self.obj: list = []                             # per problem, the per-redo objectives (as Kmeans.obj)
         self.fallback: list = []                        # per problem, whether the loop replaced the kernel's result
-        self.status: Optional[np.ndarray] = None        # [B, nredo]: 0, or the iteration at which the kernel met an empty cluster
+        self.status: Optional[np.ndarray] = None        # [B, nredo]: 0, or the iteration at which the kernel ended that redo
 
-    def train(self, points, init_indices=None) -> list:
+    def _read_back(self, obj: torch.Tensor, status: torch.Tensor):
+        host = torch.cat([obj, status.to(torch.float64)], dim=1).cpu().numpy()   # one read-back per launch
+        return host[:, : self.nredo], host[:, self.nredo:]
+
+    def train(self, points, init_indices=None, *, _draws: Optional[torch.Tensor] = None) -> list:
         """points [B, n, d].  ``init_indices`` [nredo, k] optionally fixes the initial centroids of every problem (testing aid).
+        ``_draws``: another table than ``split_draws()`` for ``split="device"`` (testing aid: a table that is too short).
         Returns the best objective of each problem."""
         x = torch.as_tensor(points, dtype=torch.float32)
         if not x.is_cuda:
@@ -274,8 +346,14 @@ class KmeansBatch:
         x = x.contiguous()
         init = _redo_seeds(x.shape[1], k, self.seed, self.nredo, init_indices)
         cent, obj, status = ops.kmeans_fit_batched(x, init.to(torch.int32), self.niter)
-        host = torch.cat([obj, status.to(torch.float64)], dim=1).cpu().numpy()   # the one read-back
-        obj_h, status_h = host[:, : self.nredo], host[:, self.nredo:]
+        obj_h, status_h = self._read_back(obj, status)
+        flagged = [b for b in range(B) if (status_h[b] != 0).any()]
+        if flagged and self.split == "device":   # those problems again, whole, on the kernel that splits
+            table = split_draws(device=x.device) if _draws is None else _draws
+            sel = torch.as_tensor(flagged, device=x.device)
+            c2, o2, s2 = ops.kmeans_fit_batched(x if len(flagged) == B else x[sel].contiguous(), init.to(torch.int32), self.niter, table)
+            cent[sel] = c2
+            obj_h[flagged], status_h[flagged] = self._read_back(o2, s2)
         self.status = status_h.astype(np.int32)
         self.obj, self.fallback, best_obj, pick = [], [], [], []
         for b in range(B):
@@ -331,14 +409,15 @@ def _kmeans_maps(points: torch.Tensor, num_clusters: int) -> torch.Tensor:
 def _kmeans_maps_grouped(points: torch.Tensor, ks) -> torch.Tensor:
     """``_kmeans_maps`` of every problem of points [B, N, d], problem b with ks[b] clusters -> labels int64 [B, N].  The problems of one
     k run as one ``KmeansBatch`` where the fused fit takes their (subsampled) shape, and one after the other on the loop otherwise;
-    both return the same bits (the reservation on nearly equal objectives: ``KmeansBatch``)."""
+    both return the same bits (the reservation on nearly equal objectives: ``KmeansBatch``).  Empty clusters - the normal case under
+    ``use_mask``, where the background tokens are one point - are split on the device unless ``DEVICE_SPLIT`` is off."""
     B, N, d = points.shape
     out = torch.empty((B, N), dtype=torch.int64, device=points.device)
     for k in sorted(set(ks)):
         idx = [b for b in range(B) if ks[b] == k]
         if ops.kmeans_fit_shape_ok(min(N, 256 * k), d, k):
             group = points if len(idx) == B else points[torch.as_tensor(idx, device=points.device)]
-            kb = KmeansBatch(d, k, niter=50, nredo=5, seed=1)
+            kb = KmeansBatch(d, k, niter=50, nredo=5, seed=1, split="device" if DEVICE_SPLIT else "host")
             kb.train(group)
             labels = kb.assign(group)[1]
             if len(idx) == B:

@@ -7,8 +7,12 @@
 //                                another: there is no flag, counter or barrier between workgroups.
 // The final index.search(x, 1) of every problem is tt_kmeans_assign_batched (kmeans.hip).
 // The arithmetic per output number is that of kmeans.hip's resident pair - km_nearest and km_accumulate_blocks are kmeans.hpp's, the
-// contract is spelled out in the header - so a fit that meets no empty cluster returns the bits of the loop; one that does is flagged
-// and left to the loop.
+// contract is spelled out in the header - so a fit that meets no empty cluster returns the bits of the loop.  One that does is
+//   tt_kmeans_fit_batched         flagged (status = the iteration) and left to the loop;
+//   tt_kmeans_fit_batched_split   (N18) carried on: the SPLIT instantiations run faiss' split - Kmeans._split_empty, statement for
+//                                 statement - on the workgroup's LDS centroids and counts after the update (kf_split_empty, one wave), from
+//                                 the caller's table of the draws numpy.random.RandomState(1234) hands the host, and return the loop's bits
+//                                 there too.  A split call that would read past the table ends its (problem, redo) with the same flag.
 #include "kmeans.hpp"
 
 namespace tt {
@@ -35,6 +39,63 @@ static int kf_fit_group(long long n, int d, int k) {
   return (int)(g > blocks ? blocks : g);
 }
 
+// ---- faiss' split of the empty clusters, clustering.Kmeans._split_empty statement for statement, run by ONE wave on a workgroup's LDS
+// centroids cs [k][d] and counts cnt [k] after the update (the host restatement is clustering.split_empty_from_table).  draws holds the
+// first n_draws values of numpy.random.RandomState(1234).random_sample(): the host re-creates that generator at every call, so every
+// call reads a prefix of one sequence and the index starts at 0 here.  Lane 0 decides - it alone reads and writes the counts and the
+// table - and hands each decision to the wave by a shuffle; lane j < d <= 64 owns column j of every row, so no lane reads what another
+// wrote.  Trip counts: k clusters, at most 64 k + 1 tries each and at most n_draws draws in all.  False: a draw beyond the table was
+// needed (cs and cnt are then part-way through the call and must not be used).
+__device__ __forceinline__ bool kf_split_empty(float* cs, int* cnt, int n, int d, int k, const double* __restrict__ draws, int n_draws,
+                                               int lane) {
+  constexpr int SKIP = -1, STOP = -2, SHORT = -3;
+  const float s = (lane & 1) ? 1.0f - 1.0f / 1024.0f : 1.0f + 1.0f / 1024.0f;   // both, and 2 - s, are exact in fp32
+  int next = 0;   // lane 0's index of the next draw
+  for (int ci = 0; ci < k; ++ci) {
+    int dec = SKIP;   // the donor cj >= 0, or one of the three above
+    if (lane == 0 && cnt[ci] == 0) {
+      int most = cnt[0], arg = 0;   // the first arg-max (numpy.argmax)
+      for (int j = 1; j < k; ++j)
+        if (cnt[j] > most) most = cnt[j], arg = j;
+      if (n <= k || most <= 1) {
+        dec = STOP;
+      } else {
+        const double span = (double)(n - k);
+        int cj = 0, tries = 0;
+        for (;;) {
+          if (next >= n_draws) {
+            dec = SHORT;
+            break;
+          }
+          if (draws[next++] < (double)(cnt[cj] - 1) / span) {
+            dec = cj;
+            break;
+          }
+          cj = cj + 1 == k ? 0 : cj + 1;
+          if (++tries > 64 * k) {   // vanishing acceptance: the largest cluster
+            dec = arg;
+            break;
+          }
+        }
+      }
+    }
+    dec = __shfl(dec, 0, 64);
+    if (dec == STOP) break;
+    if (dec == SHORT) return false;
+    if (dec == SKIP) continue;
+    if (lane < d) {   // single fp32 products, the new row from the OLD donor row
+      const float old = cs[dec * d + lane];
+      cs[ci * d + lane] = old * s;
+      cs[dec * d + lane] = old * (2.0f - s);
+    }
+    if (lane == 0) {
+      cnt[ci] = cnt[dec] / 2;
+      cnt[dec] -= cnt[ci];
+    }
+  }
+  return true;
+}
+
 // ---- the fused fit.  grid (nredo, B), KF_THREADS threads.  Per iteration:
 //   assignment    one thread per point (stride KF_THREADS); the row goes from global memory (L2 at these sizes) into registers, the
 //                 centroids are read from LDS at one address per wave (broadcast).  The label goes to the workspace, the count to an
@@ -45,11 +106,12 @@ static int kf_fit_group(long long n, int d, int k) {
 //   update        c = (float)(sum / (double)count) where count > 0.
 // The objective is taken in the last iteration only: per thread over its points in order, across a wave by a fixed shuffle tree,
 // across the waves in order - fp64, a function of (n, KF_THREADS) alone.
-template <int DREG, int VEC>
+template <int DREG, int VEC, bool SPLIT = false>
 __global__ __launch_bounds__(KF_THREADS) void kmeans_fit_kernel(const float* __restrict__ x, const int32_t* __restrict__ init,
                                                                 float* __restrict__ cent_out, double* __restrict__ obj_out,
                                                                 int32_t* __restrict__ status_out, int32_t* __restrict__ labels_ws,
-                                                                int n, int d, int k, int niter, int blocks, int ppb, int group) {
+                                                                int n, int d, int k, int niter, int blocks, int ppb, int group,
+                                                                const double* __restrict__ draws, int n_draws) {
   extern __shared__ __attribute__((aligned(16))) unsigned char kf_smem[];
   const int kd = k * d;
   double* sums = reinterpret_cast<double*>(kf_smem);   // [k][d]
@@ -58,6 +120,7 @@ __global__ __launch_bounds__(KF_THREADS) void kmeans_fit_kernel(const float* __r
   int* cnt = reinterpret_cast<int*>(part + (size_t)group * kd);   // [k]
   __shared__ double wave_obj[KF_WAVES];
   __shared__ int empty;
+  __shared__ int split_short;   // SPLIT: the draw table ended inside a split call
 
   const int redo = blockIdx.x, nredo = gridDim.x, b = blockIdx.y, tid = threadIdx.x;
   const float* xb = x + (size_t)b * n * d;
@@ -65,7 +128,7 @@ __global__ __launch_bounds__(KF_THREADS) void kmeans_fit_kernel(const float* __r
   const int32_t* seeds = init + (size_t)redo * k;
 
   for (int i = tid; i < kd; i += KF_THREADS) cs[i] = xb[(size_t)seeds[i / d] * d + (i % d)];
-  if (tid == 0) empty = 0;
+  if (tid == 0) empty = 0, split_short = 0;
 
   for (int it = 0; it < niter; ++it) {
     for (int i = tid; i < kd; i += KF_THREADS) sums[i] = 0.0;
@@ -108,7 +171,7 @@ __global__ __launch_bounds__(KF_THREADS) void kmeans_fit_kernel(const float* __r
     for (int i = tid; i < k; i += KF_THREADS)
       if (cnt[i] == 0) empty = 1;
     __syncthreads();
-    if (empty) {   // the split is the loop's business (clustering.KmeansBatch reruns this problem there)
+    if (!SPLIT && empty) {   // the split is the loop's business (clustering.KmeansBatch reruns this problem there)
       if (tid == 0) status_out[(size_t)b * nredo + redo] = it + 1;
       return;
     }
@@ -158,6 +221,20 @@ __global__ __launch_bounds__(KF_THREADS) void kmeans_fit_kernel(const float* __r
       if (c > 0) cs[i] = (float)(sums[i] / (double)c);
     }
     __syncthreads();
+
+    // -- split (SPLIT only): Kmeans._split_empty on the updated centroids and this iteration's counts, by the first wave
+    if (SPLIT && empty) {
+      if (tid < 64) {
+        const bool ok = kf_split_empty(cs, cnt, n, d, k, draws, n_draws, tid);
+        if (tid == 0 && !ok) split_short = 1;
+      }
+      __syncthreads();   // the split centroids; every thread has read `empty`
+      if (split_short) {   // nothing diverges silently: this (problem, redo) ends as an empty cluster does without SPLIT
+        if (tid == 0) status_out[(size_t)b * nredo + redo] = it + 1;
+        return;
+      }
+      if (tid == 0) empty = 0;   // (next written two barriers into the next iteration)
+    }
   }
 
   float* co = cent_out + ((size_t)b * nredo + redo) * kd;
@@ -187,24 +264,29 @@ extern "C" size_t tt_kmeans_fit_workspace_bytes(int B, int nredo, long long n, i
   return (size_t)B * nredo * (size_t)n * sizeof(int32_t);
 }
 
-extern "C" int tt_kmeans_fit_batched(const float* x, const int32_t* init, const int32_t* init_host, float* centroids, double* obj,
-                                     int32_t* status, int B, long long n, int d, int k, int nredo, int niter, void* workspace,
-                                     size_t workspace_bytes, tt_stream_t stream) {
-  TT_REQUIRE(x && init && init_host && centroids && obj && status && workspace, "kmeans_fit_batched: null pointer");
-  TT_REQUIRE(B >= 1 && B <= KM_MAX_GRID_Y, "kmeans_fit_batched: B = %d problems: need 1 ... %d per call", B, KM_MAX_GRID_Y);
-  TT_REQUIRE(niter >= 1 && nredo >= 1 && nredo <= KM_MAX_GRID_Y, "kmeans_fit_batched: niter = %d, nredo = %d: need niter >= 1, 1 <= nredo <= %d",
-             niter, nredo, KM_MAX_GRID_Y);
-  TT_REQUIRE(n >= k, "kmeans_fit_batched: n = %lld points are fewer than k = %d clusters", n, k);
+// Both entries: `who` names the entry in every message; split = the SPLIT instantiations with the draw table.
+static int kf_fit_launch(const char* who, bool split, const float* x, const int32_t* init, const int32_t* init_host, float* centroids,
+                         double* obj, int32_t* status, int B, long long n, int d, int k, int nredo, int niter, void* workspace,
+                         size_t workspace_bytes, const double* draws, int n_draws, tt_stream_t stream) {
+  TT_REQUIRE(x && init && init_host && centroids && obj && status && workspace && (!split || draws), "%s: null pointer", who);
+  TT_REQUIRE(!split || n_draws >= 1, "%s: n_draws = %d: the table of draws needs at least one", who, n_draws);
+  TT_REQUIRE(B >= 1 && B <= KM_MAX_GRID_Y, "%s: B = %d problems: need 1 ... %d per call", who, B, KM_MAX_GRID_Y);
+  TT_REQUIRE(niter >= 1 && nredo >= 1 && nredo <= KM_MAX_GRID_Y, "%s: niter = %d, nredo = %d: need niter >= 1, 1 <= nredo <= %d", who, niter, nredo,
+             KM_MAX_GRID_Y);
+  TT_REQUIRE(n >= k, "%s: n = %lld points are fewer than k = %d clusters", who, n, k);
   TT_REQUIRE(kf_fit_shape_ok(n, d, k),
-             "kmeans_fit_batched: n = %lld, d = %d, k = %d: need 1 <= d <= %d, 1 <= k <= n <= %lld and 16 k d + 4 k = %zu bytes of LDS within %zu",
-             n, d, k, KF_MAXD, KF_MAXN, kf_fit_lds(d > 0 ? d : 0, k > 0 ? k : 0, 1), KM_MAX_LDS);
+             "%s: n = %lld, d = %d, k = %d: need 1 <= d <= %d, 1 <= k <= n <= %lld and 16 k d + 4 k = %zu bytes of LDS within %zu", who, n, d, k,
+             KF_MAXD, KF_MAXN, kf_fit_lds(d > 0 ? d : 0, k > 0 ? k : 0, 1), KM_MAX_LDS);
   for (long long i = 0; i < (long long)nredo * k; ++i)
-    TT_REQUIRE(init_host[i] >= 0 && init_host[i] < n, "kmeans_fit_batched: init[%lld][%lld] = %d is outside [0, %lld)", i / k, i % k, init_host[i], n);
+    TT_REQUIRE(init_host[i] >= 0 && init_host[i] < n, "%s: init[%lld][%lld] = %d is outside [0, %lld)", who, i / k, i % k, init_host[i], n);
   const size_t need = tt_kmeans_fit_workspace_bytes(B, nredo, n, d, k);
-  TT_REQUIRE(workspace_bytes >= need, "kmeans_fit_batched: workspace of %zu bytes is too small (%zu needed)", workspace_bytes, need);
-  static const bool lds_attr_set = km_raise_lds({KM_KERNEL(kmeans_fit_kernel<16, 1>), KM_KERNEL(kmeans_fit_kernel<16, 2>), KM_KERNEL(kmeans_fit_kernel<16, 4>),
-                                                 KM_KERNEL(kmeans_fit_kernel<64, 1>), KM_KERNEL(kmeans_fit_kernel<64, 2>), KM_KERNEL(kmeans_fit_kernel<64, 4>)});
-  TT_REQUIRE(lds_attr_set, "kmeans_fit_batched: could not raise the dynamic LDS limit");
+  TT_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes is too small (%zu needed)", who, workspace_bytes, need);
+  static const bool lds_attr_set = km_raise_lds(
+      {KM_KERNEL(kmeans_fit_kernel<16, 1>), KM_KERNEL(kmeans_fit_kernel<16, 2>), KM_KERNEL(kmeans_fit_kernel<16, 4>),
+       KM_KERNEL(kmeans_fit_kernel<64, 1>), KM_KERNEL(kmeans_fit_kernel<64, 2>), KM_KERNEL(kmeans_fit_kernel<64, 4>),
+       KM_KERNEL(kmeans_fit_kernel<16, 1, true>), KM_KERNEL(kmeans_fit_kernel<16, 2, true>), KM_KERNEL(kmeans_fit_kernel<16, 4, true>),
+       KM_KERNEL(kmeans_fit_kernel<64, 1, true>), KM_KERNEL(kmeans_fit_kernel<64, 2, true>), KM_KERNEL(kmeans_fit_kernel<64, 4, true>)});
+  TT_REQUIRE(lds_attr_set, "%s: could not raise the dynamic LDS limit", who);
   const int blocks = km_accumulate_blocks(n);
   const int ppb = (int)((n + blocks - 1) / blocks);
   const int group = kf_fit_group(n, d, k);
@@ -213,14 +295,37 @@ extern "C" int tt_kmeans_fit_batched(const float* x, const int32_t* init, const 
   int32_t* labels = static_cast<int32_t*>(workspace);
   hipStream_t s = as_stream(stream);
   const dim3 grid(nredo, B), block(KF_THREADS);
-#define KF_LAUNCH(DREG, VEC) \
-  hipLaunchKernelGGL((kmeans_fit_kernel<DREG, VEC>), grid, block, lds, s, x, init, centroids, obj, status, labels, (int)n, d, k, niter, blocks, ppb, group)
+#define KF_LAUNCH(DREG, VEC)                                                                                                                     \
+  do {                                                                                                                                           \
+    if (split)                                                                                                                                   \
+      hipLaunchKernelGGL((kmeans_fit_kernel<DREG, VEC, true>), grid, block, lds, s, x, init, centroids, obj, status, labels, (int)n, d, k, niter, \
+                         blocks, ppb, group, draws, n_draws);                                                                                    \
+    else                                                                                                                                         \
+      hipLaunchKernelGGL((kmeans_fit_kernel<DREG, VEC>), grid, block, lds, s, x, init, centroids, obj, status, labels, (int)n, d, k, niter,      \
+                         blocks, ppb, group, static_cast<const double*>(nullptr), 0);                                                            \
+  } while (0)
   if (km_assign_route(d) == 16) {
     if (vec == 4) KF_LAUNCH(16, 4); else if (vec == 2) KF_LAUNCH(16, 2); else KF_LAUNCH(16, 1);
   } else {
     if (vec == 4) KF_LAUNCH(64, 4); else if (vec == 2) KF_LAUNCH(64, 2); else KF_LAUNCH(64, 1);
   }
 #undef KF_LAUNCH
-  TT_CHECK_LAUNCH("kmeans_fit_batched");
+  TT_CHECK_LAUNCH(who);
   return TT_OK;
 }
+
+extern "C" int tt_kmeans_fit_batched(const float* x, const int32_t* init, const int32_t* init_host, float* centroids, double* obj,
+                                     int32_t* status, int B, long long n, int d, int k, int nredo, int niter, void* workspace,
+                                     size_t workspace_bytes, tt_stream_t stream) {
+  return kf_fit_launch("kmeans_fit_batched", false, x, init, init_host, centroids, obj, status, B, n, d, k, nredo, niter, workspace, workspace_bytes,
+                       nullptr, 0, stream);
+}
+
+// The same fit with faiss' split of empty clusters done in the kernel (kf_split_empty) from the caller's table of draws.
+extern "C" int tt_kmeans_fit_batched_split(const float* x, const int32_t* init, const int32_t* init_host, float* centroids, double* obj,
+                                           int32_t* status, int B, long long n, int d, int k, int nredo, int niter, void* workspace,
+                                           size_t workspace_bytes, const double* draws, int n_draws, tt_stream_t stream) {
+  return kf_fit_launch("kmeans_fit_batched_split", true, x, init, init_host, centroids, obj, status, B, n, d, k, nredo, niter, workspace,
+                       workspace_bytes, draws, n_draws, stream);
+}
+

@@ -1160,12 +1160,20 @@ def kmeans_fit_shape_ok(n: int, d: int, k: int) -> bool:
     return bool(_lib.load().tt_kmeans_fit_shape_ok(int(n), int(d), int(k)))
 
 
-def kmeans_fit_batched(x, init, niter: int):
+def kmeans_fit_batched(x, init, niter: int, split_draws=None):
     """The Lloyd loops of B problems in one launch: x [B, n, d], init int32 [nredo, k] on the HOST (rows of each problem's points that
     seed redo r) -> centroids [B, nredo, k, d], obj fp64 [B, nredo], status int32 [B, nredo] (0, or the 1-based iteration at which an
-    empty cluster ended that redo: its centroids and objective are then unspecified).  Everything stays on the device."""
+    empty cluster ended that redo: its centroids and objective are then unspecified).  Everything stays on the device.
+    ``split_draws``: None = tt_kmeans_fit_batched (an empty cluster ends the redo); a float64 tensor on x's device - the first values of
+    ``numpy.random.RandomState(1234).random_sample()``, ``clustering.split_draws`` - = tt_kmeans_fit_batched_split: empty clusters are
+    split in the kernel as ``Kmeans._split_empty`` does, and a redo ends with a non-zero status only where one split call would read
+    past the table."""
     lib = _lib.load()
     _chk(x, "x")
+    if split_draws is not None:
+        _chk(split_draws, "split_draws", torch.float64)
+        if split_draws.dim() != 1 or split_draws.device != x.device:
+            raise ValueError(f"split_draws: expected a 1-d table on {x.device}, got {tuple(split_draws.shape)} on {split_draws.device}")
     B, n, d = x.shape
     init_h = torch.as_tensor(init, dtype=torch.int32).cpu().contiguous()
     if init_h.dim() != 2:
@@ -1180,8 +1188,12 @@ def kmeans_fit_batched(x, init, niter: int):
     ws = _ws(nb, x.device)
     for b0 in range(0, B, step):
         b1 = min(b0 + step, B)
-        _lib.check(lib.tt_kmeans_fit_batched(_p(x[b0:b1]), _p(init_d), _p(init_h), _p(cent[b0:b1]), _p(obj[b0:b1]), _p(status[b0:b1]), b1 - b0, n, d, k,
-                                             nredo, int(niter), _p(ws), nb, _stream()), "tt_kmeans_fit_batched")
+        args = (_p(x[b0:b1]), _p(init_d), _p(init_h), _p(cent[b0:b1]), _p(obj[b0:b1]), _p(status[b0:b1]), b1 - b0, n, d, k, nredo, int(niter),
+                _p(ws), nb)
+        if split_draws is None:
+            _lib.check(lib.tt_kmeans_fit_batched(*args, _stream()), "tt_kmeans_fit_batched")
+        else:
+            _lib.check(lib.tt_kmeans_fit_batched_split(*args, _p(split_draws), split_draws.numel(), _stream()), "tt_kmeans_fit_batched_split")
     return cent, obj, status
 
 
