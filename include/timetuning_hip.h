@@ -116,6 +116,13 @@ int tt_linear_fwd_planes_route(int planes, int M, int N, int K, int act, int has
  *   Accepted domain: D a multiple of 4, pos and out 16-byte aligned, positive scales; any g, gh, gw > 0 (gh != gw, 1 included). */
 int tt_pos_embed_interpolate(const float* pos, float* out, int g, int gh, int gw, int D, float scale_h, float scale_w,
                              tt_stream_t stream);
+/* Its adjoint (autograd of the nn.functional.interpolate call at dino_vision_transformer.py:226-230, and of the torch.cat at :233):
+ * the gradient of the stored position table from the gradient of the resampled one, dtable [1 + gh*gw, D] -> dpos [1 + g*g, D].
+ * Gather form - every source cell sums, output rows then columns ascending, the outputs that tap it, with the forward's own weights
+ * (same scales, A = -0.75, border-clamped taps adding up on the border cells); the class row is copied.  No atomics: the same bits on
+ * every call.  Accepted domain: as tt_pos_embed_interpolate. */
+int tt_pos_embed_interpolate_bwd(const float* dtable, float* dpos, int g, int gh, int gw, int D, float scale_h, float scale_w,
+                                 tt_stream_t stream);
 
 /* `precision`: the arithmetic of the fp32-OPERAND forward products - an ARGUMENT of every entry point that has one (ABI 8; until ABI 7 a
  * process-wide switch, tt_set_gemm_precision: hidden state this interface promises not to have).  Taken by tt_linear_fwd,
@@ -139,6 +146,26 @@ int tt_pos_embed_interpolate(const float* pos, float* out, int g, int gh, int gw
 int tt_patch_embed_fwd(const float* img, const int32_t* frame_map, const float* w, const float* bias,
                        const float* cls, const float* pos, float* tokens, int F, int C, int H, int W, int P, int D,
                        tt_stream_t stream);
+/* ---- k1,k2 backward: the adjoint of prepare_tokens (autograd of dino_vision_transformer.py:166-171, 236-247) for everything below
+ *      block 0.  dtok [F, n+1, D] = the gradient of the tokens; img, frame_map as in the forward.  Any of the four outputs may be NULL:
+ *   dw     [D, C*P*P] = sum over (f, p) of dtok[f, 1+p, :] (x) patch(img[frame_map[f]], p)   (PatchEmbed.proj.weight, :166-171)
+ *   dbias  [D]        = sum over (f, p) of dtok[f, 1+p, :]                                   (PatchEmbed.proj.bias)
+ *   dcls   [D]        = sum over f of dtok[f, 0, :]                                          (cls_token, :239-240)
+ *   dtable [n+1, D]   = sum over f of dtok[f]                                                (the position table added at :243; on
+ *                       the stored square grid this IS the gradient of pos_embed, otherwise tt_pos_embed_interpolate_bwd takes it there)
+ *   dw is an exact-f32 MFMA product (v_mfma_f32_32x32x2_f32) whose patch operand is gathered from img inside the kernel (no im2col
+ *   buffer); its F*n rows are split across workgroups, partial tiles go to `workspace` and are folded in slice order.  Every sum has a
+ *   fixed order and there are no float atomics: two calls give the same bits.  Nothing allocates or synchronises (legal under stream
+ *   capture); img may be NULL when dw is.
+ *   Accepted domain (tt_patch_embed_bwd_shape_ok; a refusal names the rule in tt_last_error and launches nothing): P % 4 == 0,
+ *   W % 4 == 0, D % 4 == 0, H and W multiples of P, every pointer 16-byte aligned, n < 2^20, F (n+1) D < 2^31 - any F, C, D / 64 and
+ *   C*P*P / 64 remainders included.  workspace: tt_patch_embed_bwd_workspace_bytes(...) bytes, 16-byte aligned (needed when dw's rows are split
+ *   or dbias is asked for without dtable; contents on entry are irrelevant). */
+int tt_patch_embed_bwd(const float* dtok, const float* img, const int32_t* frame_map, float* dw, float* dbias, float* dcls,
+                       float* dtable, int F, int C, int H, int W, int P, int D, void* workspace, size_t workspace_bytes,
+                       tt_stream_t stream);
+size_t tt_patch_embed_bwd_workspace_bytes(int F, int C, int H, int W, int P, int D);
+int tt_patch_embed_bwd_shape_ok(int F, int C, int H, int W, int P, int D);   /* 1 = taken, 0 = refused */
 /* The same on bf16 operands - BASELINE C4's bf16 path, what torch.autocast makes of the conv (dino_vision_transformer.py:166-171):
  * w_planes = tt_split_planes(w, 1 plane) [D, C*P*P] bf16, the patches rounded to bf16 on the way into an im2col buffer, fp32
  * accumulation, fp32 tokens.  One row pass + ONE tt_linear_fwd_planes over all F (n + 1) token rows (the class-token rows are zero

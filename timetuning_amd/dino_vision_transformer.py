@@ -94,12 +94,13 @@ class VisionTransformer(nn.Module):
     def pos_table(self, H: int, W: int) -> torch.Tensor:
         """``interpolate_pos_encoding`` (dino_vision_transformer.py:214-234) as a [1 + rows*cols, D] table: the stored
         ``pos_embed`` when the token grid is the stored square one, else its bicubic resampling (computed once per input size
-        and parameter version)."""
+        and parameter version - ``engine._param_tag``: a trainable or EMA'd table is rewritten through raw pointers, which torch's
+        version counter does not see)."""
         P, D = self.patch_embed.patch_size, self.embed_dim
         rows, cols = H // P, W // P
         if rows * cols == self.pos_embed.shape[1] - 1 and rows == cols:
             return self.pos_embed.view(-1, D)
-        key = (rows, cols, self.pos_embed.data_ptr(), self.pos_embed._version)
+        key = engine._param_tag(self.pos_embed, (rows, cols))
         cache = self.__dict__.setdefault("_pos_cache", {})
         if key not in cache:
             cache.clear()

@@ -310,6 +310,52 @@ def block_backward(dx_out: torch.Tensor, blk, num_heads: int, sv: dict, f0: int,
     return dx_in if need_dx else None
 
 
+def stem_parameters(vit) -> List[torch.nn.Parameter]:
+    """The tensors below block 0 (``prepare_tokens``' own): patch projection weight and bias, cls token, position table."""
+    pe = vit.patch_embed.proj
+    return [pe.weight, pe.bias, vit.cls_token, vit.pos_embed]
+
+
+def stem_backward(vit, dx: torch.Tensor, img: torch.Tensor, frame_map: Optional[torch.Tensor], grads: Dict[torch.nn.Parameter, torch.Tensor],
+                  out=None) -> None:
+    """Backward of ``prepare_tokens`` (dino_vision_transformer.py:236-247): dx [F * N, D] = the gradient entering block 0 for the F frames
+    ``img[frame_map]`` (``frame_map`` None: the frames of ``img`` in order).  Writes into ``grads`` the gradients of the stem tensors that
+    train: ``patch_embed.proj.weight`` / ``.bias``, ``cls_token`` and ``pos_embed`` - on the stored square grid the summed token gradient IS
+    the position table's, on any other grid it goes through the adjoint of the bicubic resampling.  ``out(param)``: as ``block_backward``.
+    The weight product is a leaf like the blocks' weight gradients: under ``ops.wgrad_fork`` it runs on the side stream."""
+    pe = vit.patch_embed.proj
+    D, P = pe.weight.shape[0], vit.patch_embed.patch_size
+    rows, cols = img.shape[-2] // P, img.shape[-1] // P
+    N = 1 + rows * cols
+    dtok = dx.view(-1, N, D)
+    out = out or (lambda p: None)
+    if pe.weight.requires_grad:
+        dst = out(pe.weight)
+        r = ops.wgrad_call(lambda: ops.patch_embed_bwd(dtok, img, P, frame_map, need=("dw",), dw_out=dst), keep=(dtok, img))
+        grads[pe.weight] = r["dw"].view(pe.weight.shape)
+    need, kw = [], {}
+    if pe.bias is not None and pe.bias.requires_grad:
+        need.append("dbias"); kw["dbias_out"] = out(pe.bias)
+    if vit.cls_token.requires_grad:
+        need.append("dcls"); kw["dcls_out"] = out(vit.cls_token)
+    g = int(round((vit.pos_embed.shape[1] - 1) ** 0.5))
+    native = rows * cols == vit.pos_embed.shape[1] - 1 and rows == cols   # VisionTransformer.pos_table's own rule
+    if vit.pos_embed.requires_grad:
+        need.append("dtable")
+        if native:
+            kw["dtable_out"] = out(vit.pos_embed)
+    if not need:
+        return
+    r = ops.patch_embed_bwd(dtok, img, P, frame_map, need=tuple(need), **kw)
+    if "dbias" in need:
+        grads[pe.bias] = r["dbias"]
+    if "dcls" in need:
+        grads[vit.cls_token] = r["dcls"].view(vit.cls_token.shape)
+    if "dtable" in need:
+        dpos = r["dtable"] if native else ops.pos_embed_interpolate_bwd(r["dtable"], g, rows, cols, out=out(vit.pos_embed))
+        grads[vit.pos_embed] = dpos.view(vit.pos_embed.shape)
+
+
 def patch_weight_planes(pe) -> torch.Tensor:
     """[1, D, C*P*P] bf16 plane of the patch-embedding weight (cached like the block weights: weight_planes)."""
     return weight_planes(pe.weight, 1).view(1, pe.weight.shape[0], -1)

@@ -443,6 +443,68 @@ def pos_embed_interpolate(pos, grid_h: int, grid_w: int):
     return out
 
 
+def pos_embed_interpolate_bwd(dtable, g: int, grid_h: int, grid_w: int, out=None):
+    """The adjoint of ``pos_embed_interpolate``: dtable [1+grid_h*grid_w, D] (the gradient of the resampled table) -> the gradient of the
+    stored table [1+g*g, D] (``out``: a caller-owned destination)."""
+    lib = _lib.load()
+    _chk(dtable, "dtable")
+    D = dtable.shape[-1]
+    if dtable.numel() != (1 + grid_h * grid_w) * D:
+        raise ValueError(f"dtable {tuple(dtable.shape)} is not a [1 + {grid_h} * {grid_w}, D] table")
+    dpos = _chk(out, "out") if out is not None else torch.empty((1 + g * g, D), dtype=f32, device=dtable.device)
+    if dpos.numel() != (1 + g * g) * D:
+        raise ValueError(f"out {tuple(dpos.shape)} is not a [1 + {g} * {g}, {D}] table")
+    _lib.check(lib.tt_pos_embed_interpolate_bwd(_p(dtable), _p(dpos), g, grid_h, grid_w, D, (grid_h + 0.1) / g, (grid_w + 0.1) / g, _stream()),
+               "tt_pos_embed_interpolate_bwd")
+    return dpos
+
+
+def patch_embed_bwd_ok(F: int, C_: int, H: int, W: int, patch: int, D: int) -> bool:
+    """Shapes ``patch_embed_bwd`` takes (tt_patch_embed_bwd_shape_ok)."""
+    return bool(_lib.load().tt_patch_embed_bwd_shape_ok(F, C_, H, W, patch, D))
+
+
+def patch_embed_bwd(dtok, img, patch: int, frame_map=None, need=("dw", "dbias", "dcls", "dtable"), dw_out=None, dbias_out=None,
+                    dcls_out=None, dtable_out=None, workspace=None):
+    """The adjoint of ``patch_embed_fwd`` (tt_patch_embed_bwd): dtok [F, n+1, D] = the gradient of the tokens, img [F_src, C, H, W] and
+    ``frame_map`` as in the forward.  Returns a dict with the entries named in ``need``: ``dw`` [D, C*P*P], ``dbias`` [D], ``dcls`` [D],
+    ``dtable`` [n+1, D] (the gradient of the position table the forward added).  ``*_out``: caller-owned destinations (the gradient
+    exchange's flat buckets), implied needed.  ``workspace``: a uint8 buffer of at least ``tt_patch_embed_bwd_workspace_bytes`` (default: one
+    is allocated)."""
+    lib = _lib.load()
+    _chk(dtok, "dtok"); _chk(img, "img")
+    Fs, Cc, H, W = img.shape
+    if dtok.dim() != 3:
+        raise ValueError(f"dtok must be [F, n + 1, D], got {tuple(dtok.shape)}")
+    F, N, D = dtok.shape
+    if frame_map is not None:
+        _chk(frame_map, "frame_map", torch.int32)
+        if frame_map.numel() != F:
+            raise ValueError(f"frame_map has {frame_map.numel()} entries for {F} frames of dtok")
+    elif Fs != F:
+        raise ValueError(f"dtok has {F} frames, img {Fs} (and no frame_map)")
+    if patch > 0 and H % patch == 0 and W % patch == 0 and N != (H // patch) * (W // patch) + 1:
+        raise ValueError(f"dtok has {N} token rows per frame; a {H} x {W} input at patch size {patch} has {(H // patch) * (W // patch) + 1}")
+    K = Cc * patch * patch
+    outs = dict(dw=dw_out, dbias=dbias_out, dcls=dcls_out, dtable=dtable_out)
+    shapes = dict(dw=(D, K), dbias=(D,), dcls=(D,), dtable=(N, D))
+    unknown = set(need) - set(shapes)
+    if unknown:
+        raise ValueError(f"need: unknown outputs {sorted(unknown)}")
+    for name, shape in shapes.items():
+        if outs[name] is not None:
+            _chk(outs[name], name + "_out")
+            if outs[name].numel() != int(np.prod(shape)):
+                raise ValueError(f"{name}_out has {outs[name].numel()} elements, expected {shape}")
+        elif name in need:
+            outs[name] = torch.empty(shape, dtype=f32, device=dtok.device)
+    nb = lib.tt_patch_embed_bwd_workspace_bytes(F, Cc, H, W, patch, D)
+    ws = workspace if workspace is not None else _ws(nb, dtok.device)
+    _lib.check(lib.tt_patch_embed_bwd(_p(dtok), _p(img), _p(frame_map), _p(outs["dw"]), _p(outs["dbias"]), _p(outs["dcls"]), _p(outs["dtable"]),
+                                      F, Cc, H, W, patch, D, _p(ws), ws.numel() * ws.element_size(), _stream()), "tt_patch_embed_bwd")
+    return {k: v for k, v in outs.items() if v is not None}
+
+
 def _layernorm_fwd_into(entry, alloc, x, gamma, beta, eps, save_stats, drop_first_token, *tail):
     """The bookkeeping the three ``layernorm_fwd*`` wrappers share: rows and the ``skip_group`` of ``drop_first_token``, the statistics, the call.
     ``alloc(rows, D)`` returns the output and the arguments that stand between ``beta`` and ``mean`` in the entry's signature (y first);

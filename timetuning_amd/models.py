@@ -66,10 +66,11 @@ class FeatureExtractor(nn.Module):
     second full backbone pass for (:968) although nothing on the default training path reads it."""
 
     def __init__(self, arcitecture, model_path="", head_layer_list: Sequence[int] = (), unfreeze_layers: Sequence[str] = (),
-                 kqv="all", *, vit_cfg: Optional[dict] = None, init: str = "dino", seed: int = 1, return_attention: bool = True):
+                 kqv="all", *, vit_cfg: Optional[dict] = None, init: str = "dino", seed: int = 1, return_attention: bool = True,
+                 train_stem: bool = False):
         super().__init__()
         self.backbone = get_backbone(arcitecture, model_path, vit_cfg, init, seed)
-        self.freeze_backbone(unfreeze_layers=unfreeze_layers)
+        self.freeze_backbone(unfreeze_layers=unfreeze_layers, train_stem=train_stem)
         self.architecture = arcitecture
         self.kqv = kqv
         self.return_attention = return_attention
@@ -89,17 +90,19 @@ class FeatureExtractor(nn.Module):
                 self.head.load_state_dict({k: torch.from_numpy(v) for k, v in hw.items()}, strict=True)
             self.feature_dim = head_layer_list[-1]
 
-    def freeze_backbone(self, unfreeze_layers=()):
+    def freeze_backbone(self, unfreeze_layers=(), train_stem: bool = False):
         """models.py:929-935: a backbone parameter trains iff one of ``unfreeze_layers`` is a SUBSTRING of its name - whole blocks
         (``"blocks.11"``), parts of one (``"blocks.11.attn"``, ``"blocks.10.mlp.fc2.weight"``) or the final ``"norm"``.
-        The backward of this build runs from the loss down to the FIRST block that holds a trainable tensor and stops there, so
-        the tensors below every block - ``patch_embed.*``, ``pos_embed``, ``cls_token`` - cannot be trained: asking for them raises
-        here, at construction, instead of silently leaving them without gradients."""
+        The backward runs from the loss down to the FIRST block that holds a trainable tensor and stops there.  The tensors below
+        every block - ``patch_embed.*``, ``pos_embed``, ``cls_token``, the stem - train only with ``train_stem=True`` (the match is
+        then the reference's, with no exceptions: the backward runs through EVERY block and ends in ``engine.stem_backward``); without
+        it, asking for them raises here, at construction, instead of silently leaving them without gradients."""
         for name, param in self.backbone.named_parameters():
             param.requires_grad = any(u in name for u in unfreeze_layers)
-            if param.requires_grad and not (name.startswith("blocks.") or name.startswith("norm.")):
-                raise NotImplementedError(f"unfreeze_layers={list(unfreeze_layers)} selects '{name}': gradients of the patch embedding, the "
-                                          "position embedding and the cls token are not built (the backward stops at the first trainable block)")
+            if param.requires_grad and not train_stem and not (name.startswith("blocks.") or name.startswith("norm.")):
+                raise NotImplementedError(f"unfreeze_layers={list(unfreeze_layers)} selects '{name}': the patch embedding, the position "
+                                          "embedding and the cls token train only with train_stem=True (the backward then runs through "
+                                          "every block instead of stopping at the first trainable one)")
             # frozen tensors never change (no optimizer step, no EMA - they are the EMA's source): derived copies of them, such as the
             # bf16 planes of the plane-GEMM modes, may be cached (engine.weight_planes re-checks requires_grad, storage and version)
             param._tt_static = not param.requires_grad
@@ -109,6 +112,21 @@ class FeatureExtractor(nn.Module):
         substring match allows) is on the backward path as a whole: all of its gradients are computed, those of its frozen tensors
         are dropped before they reach autograd / the optimizer / the gradient exchange."""
         return [i for i, blk in enumerate(self.backbone.blocks) if any(p.requires_grad for p in blk.parameters())]
+
+    def stem_trainable(self) -> bool:
+        """True when a tensor below block 0 trains (``patch_embed.proj.weight`` / ``.bias``, ``pos_embed``, ``cls_token``; only with
+        ``train_stem=True``)."""
+        return any(p.requires_grad for p in engine.stem_parameters(self.backbone))
+
+    def backward_block_ids(self) -> List[int]:
+        """Blocks the backward runs through: from the first block that holds a trainable tensor to the last one - EVERY block when a
+        stem tensor trains (the gradient has to reach the tokens).  The weight gradients of the frozen blocks on that path are computed
+        and dropped, as those of a partly unfrozen block's frozen tensors are."""
+        depth = len(self.backbone.blocks)
+        if self.stem_trainable():
+            return list(range(depth))
+        ids = self.trainable_block_ids()
+        return list(range(min(ids), depth)) if ids else []
 
     # -- forward surface ---------------------------------------------------------------------------
     @torch.no_grad()
@@ -144,9 +162,9 @@ class FeatureExtractor(nn.Module):
         norm's statistics and the head's activations."""
         vit = self.backbone
         xi = vit._check(x)
-        ids = self.trainable_block_ids()
+        ids = self.backward_block_ids()
         first = min(ids) if ids else None
-        save = {i: {} for i in range(first, len(vit.blocks))} if first is not None else None
+        save = {i: {} for i in ids} if ids else None
         tok, probs = engine.vit_tokens(vit, xi, None, save, last_block_probs=self.return_attention)
         Fr, N, D = tok.shape
         feats, mean_f, rstd_f = ops.layernorm_fwd(tok, vit.norm.weight, vit.norm.bias, save_stats=True, drop_first_token=True)
@@ -155,7 +173,8 @@ class FeatureExtractor(nn.Module):
         if self.head is not None and use_head:
             sv_head = {}
             out = engine.head_forward(feats, self.head, sv_head)
-        saved = dict(first=first, blocks=save, tok=tok, mean=mean_f, rstd=rstd_f, head=sv_head, shape=(Fr, N, D))
+        saved = dict(first=first, blocks=save, tok=tok, mean=mean_f, rstd=rstd_f, head=sv_head, shape=(Fr, N, D),
+                     img=xi if self.stem_trainable() else None)   # the stem's backward gathers the patches from the frames again
         return out.view(Fr, N - 1, -1), probs, saved
 
     def _backward_saved(self, saved: dict, dfeats: torch.Tensor) -> Dict[nn.Parameter, torch.Tensor]:
@@ -172,9 +191,12 @@ class FeatureExtractor(nn.Module):
             if wg:
                 grads[vit.norm.weight], grads[vit.norm.bias] = dg, db
             if first is not None:
+                stem = saved["img"] is not None
                 dx = dx.view(Fr * N, D)
                 for i in range(len(vit.blocks) - 1, first - 1, -1):
-                    dx = engine.block_backward(dx, vit.blocks[i], vit.num_heads, saved["blocks"][i], 0, Fr, grads, need_dx=i > first)
+                    dx = engine.block_backward(dx, vit.blocks[i], vit.num_heads, saved["blocks"][i], 0, Fr, grads, need_dx=i > first or stem)
+                if stem:   # (first == 0: dx is the gradient of prepare_tokens' output)
+                    engine.stem_backward(vit, dx, saved["img"], None, grads)
         return {p: g for p, g in grads.items() if p.requires_grad}
 
 

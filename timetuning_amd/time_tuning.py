@@ -577,12 +577,16 @@ class TimeT(nn.Module):
         xf = vit._check(x.reshape(Fr, c, h, w))
         dev = xf.device
         depth = len(vit.blocks)
-        all_train_ids = fe.trainable_block_ids()
+        # the blocks on the backward path: from the first one that holds a trainable tensor on - all of them when a stem tensor trains
+        # (models.FeatureExtractor.backward_block_ids; the backward then ends in engine.stem_backward)
+        stem = fe.stem_trainable()
+        all_train_ids = fe.backward_block_ids()
         train_ids = all_train_ids if need_grad else []
         first = min(train_ids) if train_ids else None
         save = {i: {} for i in range(first, depth)} if first is not None else None
         # EMA teacher that still shares the student's frozen tensors: its blocks [0, t_first) would reproduce the student's
-        # activations of frame 0, so they are tapped from the student's pass instead of recomputed
+        # activations of frame 0, so they are tapped from the student's pass instead of recomputed.  A trainable stem is the student's
+        # alone after its first update (the teacher's is its EMA): t_first = 0, the teacher embeds frame 0 itself
         t_first = (min(all_train_ids) if all_train_ids else depth) if self.teacher_shares_frozen_blocks() else 0
         tap: Optional[dict] = {"block": t_first, "rows": bs} if t_first > 0 else None
 
@@ -796,7 +800,7 @@ class TimeT(nn.Module):
             for i in range(len(vit.blocks) - 1, first - 1, -1):
                 # the LAST block of the backward has nothing after it to hide its bucket behind: its MLP gradients (two thirds of
                 # the block) leave as soon as they exist, so only the attention third is exposed
-                dx = engine.block_backward(dx, vit.blocks[i], vit.num_heads, save[i], b0, b1, grads, need_dx=i > first,
+                dx = engine.block_backward(dx, vit.blocks[i], vit.num_heads, save[i], b0, b1, grads, need_dx=i > first or stem,
                                            after_mlp=(lambda: exchange.push(grads)) if i == first else None, out=out,
                                            dx_out_amax=a_tok, amax_pool=pool)
                 if pool is not None:
@@ -805,6 +809,11 @@ class TimeT(nn.Module):
                     dbg(f"dx_in{i}", dx)
                 if i > first:
                     exchange.push(grads)  # this block's gradients travel while the next block's backward runs
+            if stem:
+                # the stem's gradients follow block 0's into the exchange.  dx holds the kept frames' rows - the target frames, the last
+                # bs of the time-major pass - so the patches are gathered through that slice of the frame map
+                exchange.push(grads)
+                engine.stem_backward(vit, dx, xf, self._frame_map(bs, fs, dev)[f0:], grads, out=out)
         grads = {p: g for p, g in grads.items() if p.requires_grad}
         ops.wgrad_join()
         return loss, exchange.finish(grads, scale=not prescaled)
@@ -1027,7 +1036,7 @@ def build_parser() -> argparse.ArgumentParser:
     which uses its signature defaults (eps 0.05, 10 iterations, 7 frames, radius 6, top-5).
     Added (not in the reference): ``--dataset synthetic`` / ``--steps_per_epoch`` / ``--eval_clips`` because the dataset
     loaders are out of scope here, ``--eval_every`` (the reference hard-codes 4), ``--log_localization_every`` (the qualitative logs of
-    :641-642, off by default) and ``--precision`` (the arithmetic mode of the
+    :641-642, off by default), ``--unfreeze_layers`` (the reference hard-codes the two blocks, :574) and ``--precision`` (the arithmetic mode of the
     matrix products; the library-level default of ``hip_ops.set_gemm_precision`` stays "f32", the training driver's is "f16x3")."""
     p = argparse.ArgumentParser()
     p.add_argument("--architecture", type=str, default="dino-s16")
@@ -1066,6 +1075,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-g", "--gpus", default=1, type=int)
     p.add_argument("-nr", "--nr", default=0, type=int)
     p.add_argument("--epochs", default=3000, type=int, metavar="N")
+    p.add_argument("--unfreeze_layers", nargs="+", default=["blocks.11", "blocks.10"],
+                   help="substrings of backbone parameter names that train (the reference hard-codes this list, time_tuning.py:574); "
+                        "blocks patch_embed pos_embed cls_token = full fine-tuning")
     p.add_argument("--steps_per_epoch", default=8, type=int, help="synthetic data only")
     p.add_argument("--eval_every", default=4, type=int, help="epochs between rank-0 evaluations (the reference hard-codes 4; 0 = never)")
     p.add_argument("--eval_clips", default=8, type=int, help="synthetic evaluation set size")
@@ -1213,8 +1225,8 @@ def time_tuning(gpu=0, args=None):
     if world_size > 1 and not dist.is_initialized():
         dist.init_process_group(backend=os.environ.get("TT_DIST_BACKEND", "nccl"), init_method="env://", world_size=world_size, rank=rank)
     if args.use_projection_head:
-        fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], unfreeze_layers=["blocks.11", "blocks.10"],
-                              return_attention=False)
+        fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256],
+                              unfreeze_layers=list(getattr(args, "unfreeze_layers", ("blocks.11", "blocks.10"))), return_attention=False, train_stem=True)
     else:
         fe = FeatureExtractor(args.architecture, args.model_path, return_attention=False)
     model = TimeT(fe, args.num_clusters).to(device)
