@@ -489,6 +489,38 @@ int tt_confusion_segments_route(int Cg, int Cp);
 int tt_confusion_counts_segments(const void* pred, int pred_dtype, const int64_t* gt, int S, long long n, int Cg, int Cp, long long ignore_gt,
                                  int has_ignore, unsigned long long* counts, tt_stream_t stream);
 
+/* ---- N20: matching and scoring of every segment on the device - what PredsmIoU.compute_miou (metrics.py:357-432, with compute_score_matrix
+ *      :435-474, scipy's linear_sum_assignment in _hungarian_match :481-488 and _original_match :489-505) derives from one confusion matrix, for ALL segments of an
+ *      evaluate_localizations call in one launch straight behind tt_confusion_counts_segments.
+ *   tt_match_segments           counts uint64 [S, Cg, Cp] (what tt_confusion_counts_segments wrote) -> per segment s
+ *                                 score[s]       fp64: the mean Jaccard index over the present gt values (without gt value 0 unless
+ *                                                involve_bg; 0.0 where nothing is left), summed in numpy's order;
+ *                                 matched_bg[s]  fp64: 1 / n_gt (Hungarian), or the share of the present preds matched to the FIRST present
+ *                                                gt class (many-to-one);
+ *                                 tp, fp, fn     int64 [S, Cg], indexed by gt VALUE, 0 where the value is absent: the counts after every
+ *                                                present pred value is renamed to its matched gt value (unmatched ones to 0);
+ *                                 lut            int64 [S, Cp]: pred value -> matched gt value, 0 where unmapped or absent;
+ *                                 info           int32 [S, 4]: status, n_gt, n_pred (present values), largest present pred value.
+ *                               mode TT_MATCH_HUNGARIAN: linear_sum_assignment(1 - IoU) as scipy computes it, ties included (the transpose
+ *                               where n_pred < n_gt, a descending column list, the last minimal unassigned or else the first minimal
+ *                               position, swap-remove); TT_MATCH_MANY_TO_ONE: every present pred goes to the present gt class of largest
+ *                               IoU, or precision where precision_based != 0 (read in this mode only), the first maximum in ascending
+ *                               gt order.  fp64 throughout, correctly rounded divisions, no contraction: the bits of the host path.
+ *                               status 0 = scored; 1 = no present gt value (an empty segment); 2 = a search overran its bound or met a
+ *                               non-finite minimum; 3 = the segment total is 2^53 or more (counts no longer exact in fp64).  With a
+ *                               non-zero status the segment's other outputs are 0 (n_gt, n_pred and the largest pred value stay).
+ *                               One wave64 per segment, segments on the grid, any S >= 1; no allocation, no synchronisation, no
+ *                               workspace.
+ *   tt_match_segments_shape_ok  host only: 1 where 1 <= Cg <= 128 (numpy's mean stays inside one summation block) and 1 <= Cp <= 1024
+ *                               (the per-segment vectors fit in LDS: 54 KB at 128 x 1024), else 0.
+ *   Refused with TT_EINVAL and a message naming the numbers, nothing launched: null pointers, S < 1, a shape outside the rule, an unknown
+ *   mode code, a misaligned pointer (8 bytes; info 4). */
+#define TT_MATCH_HUNGARIAN 0
+#define TT_MATCH_MANY_TO_ONE 1
+int tt_match_segments_shape_ok(int Cg, int Cp);
+int tt_match_segments(const unsigned long long* counts, int S, int Cg, int Cp, int mode, int precision_based, int involve_bg, double* score,
+                      double* matched_bg, long long* tp, long long* fp, long long* fn, long long* lut, int* info, tt_stream_t stream);
+
 /* ---- N17: overlay rendering and the prototype histogram - the qualitative side (time_tuning.py:305-457, evaluation.py:255-300).
  *   tt_overlay_grid   renders ALL F frames of a batch in one launch as out uint8 [F, 3, H + 2 pad, n W + (n + 1) pad]:
  *                     torchvision.utils.make_grid's layout for n tiles in one row (pad value 0, tile t at column t (W + pad) + pad, row

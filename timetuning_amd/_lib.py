@@ -180,6 +180,8 @@ SIGNATURES = {
     "tt_confusion_counts": (c_i, [c_vp, c_vp, c_ll, c_i, c_vp, c_vp]),
     "tt_confusion_segments_route": (c_i, [c_i, c_i]),
     "tt_confusion_counts_segments": (c_i, [c_vp, c_i, c_vp, c_i, c_ll, c_i, c_i, c_ll, c_i, c_vp, c_vp]),
+    "tt_match_segments_shape_ok": (c_i, [c_i, c_i]),
+    "tt_match_segments": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tt_overlay_grid": (c_i, [c_vp, c_i, c_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_i, c_i, c_vp,
                               c_i, c_d, c_i, c_i, c_i, c_i, c_vp]),
     "tt_upsample_argmax_hist_f32": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),

@@ -881,6 +881,61 @@ def confusion_counts_segments(pred, gt, num_gt: int, num_pred: int, ignore_gt: O
     return counts
 
 
+MATCH_MODES = {"hungarian": 0, "many_to_one": 1}   # TT_MATCH_HUNGARIAN / TT_MATCH_MANY_TO_ONE
+
+
+def match_segments_shape_ok(num_gt: int, num_pred: int) -> bool:
+    """The shape rule of ``match_segments``: 1 <= num_gt <= 128 and 1 <= num_pred <= 1024 (``tt_match_segments_shape_ok``)."""
+    return bool(_lib.load().tt_match_segments_shape_ok(int(num_gt), int(num_pred)))
+
+
+class MatchedSegments:
+    """The outputs of ``match_segments``, views of ONE int64 allocation ``packed``: score, matched_bg float64 [S]; tp, fp, fn int64
+    [S, Cg] by gt value; lut int64 [S, Cp]; info int32 [S, 4] = (status, n_gt, n_pred, largest present pred value).  ``cpu()`` brings
+    all of them to the host in one copy."""
+
+    def __init__(self, packed: torch.Tensor, S: int, Cg: int, Cp: int):
+        self.packed, self.shape = packed, (S, Cg, Cp)
+        at = 0
+
+        def take(words, *view):
+            nonlocal at
+            part = packed[at:at + words]
+            at += words
+            return part.view(*view) if view else part
+
+        self.score = take(S).view(torch.float64)
+        self.matched_bg = take(S).view(torch.float64)
+        self.tp, self.fp, self.fn = take(S * Cg, S, Cg), take(S * Cg, S, Cg), take(S * Cg, S, Cg)
+        self.lut = take(S * Cp, S, Cp)
+        self.info = take(2 * S).view(torch.int32).view(S, 4)
+
+    @staticmethod
+    def words(S: int, Cg: int, Cp: int) -> int:
+        return 2 * S + 3 * S * Cg + S * Cp + 2 * S
+
+    def cpu(self) -> "MatchedSegments":
+        return MatchedSegments(self.packed.cpu(), *self.shape)
+
+
+def match_segments(counts, mode: str = "hungarian", precision_based: bool = False, involve_bg: bool = False) -> MatchedSegments:
+    """counts int64 [S, Cg, Cp] (``confusion_counts_segments``) -> the matched scores of all S segments from one launch: what
+    ``PredsmIoU.compute_miou_from_confusion`` returns for each matrix, with its bits.  ``mode``: "hungarian" or "many_to_one"
+    (``precision_based`` is read in the latter only)."""
+    lib = _lib.load()
+    _chk(counts, "counts", torch.int64)
+    if counts.dim() != 3:
+        raise ValueError(f"counts: expected [S, Cg, Cp], got {tuple(counts.shape)}")
+    if mode not in MATCH_MODES:
+        raise ValueError(f"mode: expected one of {sorted(MATCH_MODES)}, got {mode!r}")
+    S, Cg, Cp = counts.shape
+    out = MatchedSegments(torch.empty(MatchedSegments.words(S, Cg, Cp), dtype=torch.int64, device=counts.device), S, Cg, Cp)
+    _lib.check(lib.tt_match_segments(_p(counts), S, Cg, Cp, MATCH_MODES[mode], int(bool(precision_based)), int(bool(involve_bg)), _p(out.score),
+                                     _p(out.matched_bg), _p(out.tp), _p(out.fp), _p(out.fn), _p(out.lut), _p(out.info), _stream()),
+               "tt_match_segments")
+    return out
+
+
 # ---- clip input pipeline (uint8 frames [F, H, W, 3]) ------------------------------------------------------------------
 
 def img_resample_h(frames, coeffs, bounds, y0: int, x0: int, h: int):

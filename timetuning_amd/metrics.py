@@ -7,8 +7,9 @@ score matrix, the matching, tp / fp / fn after remapping - is a function of the 
 pass (``tt_confusion_counts``) builds that matrix and the rest is exact integer bookkeeping on a few hundred numbers.
 
 ``compute_segments`` scores MANY independent (gt, pred) pairs - the frames or clips of one ``evaluate_localizations`` call - from one
-launch (``tt_confusion_counts_segments``) and one read-back; ``compute_propagation_score`` (``metrics.py:271-346``) reads the per-frame
-true / false positives and false negatives of every object off the same per-frame matrices.
+launch (``tt_confusion_counts_segments``), matches and scores them in a second one (``tt_match_segments``) and reads the results back
+once; ``compute_propagation_score`` (``metrics.py:271-346``) reads the per-frame true / false positives and false negatives of every
+object off the same per-frame matrices.
 """
 from __future__ import annotations
 
@@ -20,6 +21,12 @@ import torch
 from scipy.optimize import linear_sum_assignment
 
 from . import hip_ops as ops
+
+# ``compute_segments`` matches and scores on the device (``hip_ops.match_segments``, N20) where the counts are in GPU memory and the shape
+# is inside ``match_segments_shape_ok``; everywhere else, and with the switch off, the host loop over ``compute_miou_from_confusion`` runs.
+# The two routes return equal objects, so the switch does not show in any score.  On: every protocol of
+# tools/bench_eval_scoring.py was faster than the host loop in both rounds, one-segment calls included (profiles/n20_match_segments.txt).
+DEVICE_MATCH = True
 
 
 class PredsmIoU(torch.nn.Module):
@@ -62,24 +69,54 @@ class PredsmIoU(torch.nn.Module):
         value`` (unmapped values 0, as long as the segment's largest predicted value + 1) in slot 4 instead of None: ``table[pred]`` IS the
         reordered map, and a renderer takes the table (``visualization.label_panels``).  ``ignore_gt``: elements whose ground truth has
         this value are left out (Pascal VOC's 255).  One read-back of the two maxima sizes the matrices (any upper bound gives the same scores: the class sets are
-        the non-empty rows and columns, as in ``_confusion``), one ``confusion_counts_segments`` call counts and one ``.cpu()`` brings
-        every matrix to the host; what was stored with ``update`` is neither used nor changed."""
+        the non-empty rows and columns, as in ``_confusion``), one ``confusion_counts_segments`` call counts, one ``match_segments`` call
+        matches and scores every matrix on the device and one ``.cpu()`` brings its outputs to the host (``DEVICE_MATCH``; with counts in
+        host memory, a shape beyond ``match_segments_shape_ok`` or the switch off, one ``.cpu()`` brings every matrix to the host and
+        ``compute_miou_from_confusion`` runs per segment - the same objects either way); what was stored with ``update`` is neither used
+        nor changed."""
         gt = gt.long().cuda().contiguous()
         pred = (pred if pred.dtype in (torch.int16, torch.int64) else pred.long()).cuda().contiguous()
         if gt.dim() != 2 or gt.shape != pred.shape:
             raise ValueError(f"compute_segments: expected gt and pred of one shape [S, n], got {tuple(gt.shape)} and {tuple(pred.shape)}")
         counted_gt = gt if ignore_gt is None else torch.where(gt == ignore_gt, -1, gt)
         gt_max, pred_max = torch.stack([counted_gt.max(), pred.max().long()]).tolist()
-        counts = ops.confusion_counts_segments(pred, gt, max(gt_max, 0) + 1, max(pred_max, 0) + 1, ignore_gt).cpu().numpy()
+        counts = ops.confusion_counts_segments(pred, gt, max(gt_max, 0) + 1, max(pred_max, 0) + 1, ignore_gt)
+        _, Cg, Cp = counts.shape
+        if DEVICE_MATCH and counts.is_cuda and ops.match_segments_shape_ok(Cg, Cp):
+            return self._segments_on_device(counts, many_to_one, precision_based, with_mapping)
+        return [self._segment_on_host(s, full, many_to_one, precision_based, with_mapping) for s, full in enumerate(counts.cpu().numpy())]
+
+    def _segment_on_host(self, s, full, many_to_one, precision_based, with_mapping):
+        """One segment of ``compute_segments`` from its matrix ``full[gt value, pred value]`` on the host."""
+        gt_unique = np.nonzero(full.sum(1))[0]
+        pred_unique = np.nonzero(full.sum(0))[0]
+        if len(gt_unique) == 0:
+            raise ValueError(f"compute_segments: segment {s} has no element to score")
+        self.num_pred_classes, self.num_gt_classes = len(pred_unique), len(gt_unique)
+        return self.compute_miou_from_confusion(full[np.ix_(gt_unique, pred_unique)], gt_unique, pred_unique, None, many_to_one, precision_based,
+                                                with_mapping=with_mapping)
+
+    def _segments_on_device(self, counts, many_to_one, precision_based, with_mapping):
+        """``compute_segments`` behind the counts: one ``match_segments`` launch and one read-back of its packed outputs; the host only
+        builds the dicts.  A segment the kernel flags (status 2 or 3) is scored by the host path - the counts are read back for that alone."""
+        m = ops.match_segments(counts, "many_to_one" if many_to_one else "hungarian", precision_based, self.involve_bg).cpu()
+        score, bg, info = m.score.tolist(), m.matched_bg.tolist(), m.info.tolist()
+        tp_all, fp_all, fn_all = m.tp.tolist(), m.fp.tolist(), m.fn.tolist()
+        host_counts = None
         results = []
-        for s, full in enumerate(counts):                            # [gt value, pred value] of segment s
-            gt_unique = np.nonzero(full.sum(1))[0]
-            pred_unique = np.nonzero(full.sum(0))[0]
-            if len(gt_unique) == 0:
+        for s, (status, n_gt, n_pred, pred_max) in enumerate(info):
+            if status == 1:
                 raise ValueError(f"compute_segments: segment {s} has no element to score")
-            self.num_pred_classes, self.num_gt_classes = len(pred_unique), len(gt_unique)
-            results.append(self.compute_miou_from_confusion(full[np.ix_(gt_unique, pred_unique)], gt_unique, pred_unique, None, many_to_one,
-                                                            precision_based, with_mapping=with_mapping))
+            if status != 0:
+                if host_counts is None:
+                    host_counts = counts.cpu().numpy()
+                results.append(self._segment_on_host(s, host_counts[s], many_to_one, precision_based, with_mapping))
+                continue
+            self.num_pred_classes, self.num_gt_classes = n_pred, n_gt
+            tp_s, fp_s, fn_s = tp_all[s], fp_all[s], fn_all[s]
+            present = [g for g in range(len(tp_s)) if tp_s[g] + fn_s[g] > 0]                # a present gt value has a non-empty row
+            table = m.lut[s, :pred_max + 1].clone() if with_mapping else None
+            results.append((score[s], {g: tp_s[g] for g in present}, {g: fp_s[g] for g in present}, {g: fn_s[g] for g in present}, table, bg[s]))
         return results
 
     def compute_propagation_score(self, is_global_zero: bool):

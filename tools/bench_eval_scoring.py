@@ -27,6 +27,10 @@ measured - and the fraction of it the segmented kernel reached.  The one-atomic-
     tools/build_variant.sh confseg_nomerge confusion.hip -DTT_CONFSEG_NO_MERGE
     TT_LIB_PATH=tools/bin/libconfseg_nomerge.so python tools/bench_eval_scoring.py --kernel
 
+``--match`` (this tree only, N20): HIP events around ``hip_ops.match_segments`` alone, ``--kernel-reps`` calls after one warm-up, on the
+counts of such maps: 64 segments of 5 x 10 and of 21 x 21, Hungarian, and one segment of 21 x 500, many-to-one.  Each line carries the
+statuses the kernel reported and the largest class sets it met.
+
 Prints one JSON line per case.
 """
 from __future__ import annotations
@@ -144,11 +148,36 @@ def kernel(args, tree, torch):
             report(what="confusion_counts", case=name, n=S * n, C=C, pred="torch.int64", ms=old, lib=_lib.LIB_PATH)
 
 
+def match(args, tree, torch):
+    """HIP events around ``hip_ops.match_segments`` alone, on the counts of block maps like the scoring cases'."""
+    from timetuning_amd import _lib
+    from timetuning_amd import hip_ops as ops
+
+    for name, S, R, classes, k, mode in (("frame-wise", 64, 224, 5, 10, "hungarian"), ("frame-wise 21", 64, 224, 21, 21, "hungarian"),
+                                         ("dataset-wise 500", 1, 112, 21, 500, "many_to_one")):
+        frames = S if S > 1 else 1449
+        gts, preds = block_maps(torch, frames, R, classes, k, 3, border=S == 1)
+        counts = ops.confusion_counts_segments(preds.view(S, -1), gts.view(S, -1), classes, k, 255)
+        ops.match_segments(counts, mode)   # warm-up
+        ms = []
+        for _ in range(args.kernel_reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            out = ops.match_segments(counts, mode)
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        info = out.info.cpu()
+        report(what="match_segments", case=name, S=S, Cg=classes, Cp=k, mode=mode, statuses=sorted(set(info[:, 0].tolist())),
+               n_gt=int(info[:, 1].max()), n_pred=int(info[:, 2].max()), ms=ms, lib=_lib.LIB_PATH)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", default=HERE, help="the checkout whose timetuning_amd is timed (default: the one this file is in)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--kernel", action="store_true", help="time the segmented kernel alone instead of the scoring step")
+    ap.add_argument("--match", action="store_true", help="time match_segments alone instead of the scoring step")
     ap.add_argument("--kernel-reps", type=int, default=10)
     args = ap.parse_args(argv)
     tree = os.path.abspath(args.tree)
@@ -158,7 +187,7 @@ def main(argv=None):
 
     if not torch.cuda.is_available():
         raise SystemExit("bench_eval_scoring.py needs a GPU: there is nothing to time without one")
-    (kernel if args.kernel else scoring)(args, tree, torch)
+    (kernel if args.kernel else match if args.match else scoring)(args, tree, torch)
 
 
 if __name__ == "__main__":
