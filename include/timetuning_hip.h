@@ -37,6 +37,9 @@ typedef void* tt_stream_t;
 
 const char* tt_last_error(void);
 int tt_abi_version(void);   /* 8 = this header (7: before `precision` became an argument - tt_set_gemm_precision, a process-wide switch, is gone; 6: before the caller-owned K-split workspace and the range flag; 5: before the transpose-free weight gradient, the batched operand refresh and the distributed Sinkhorn steps; 4: before the fp16-pair entry points; 3: before tt_vit_params.patch_wp; 2: before the coarse entry points) */
+/* Still 8 without the two host queries of the one-launch Sinkhorn solve (a default-off experiment, retired): only this
+ * repository's own front end and tests called them, no signature a caller relies on changed, and a binding that still asks for them
+ * fails loudly at symbol lookup, not silently. */
 /* Tuning knobs of the dispatchers (names and defaults: the one list TT_KNOB_LIST in csrc/common.hpp) are read ONCE from the
  * environment; this setter changes one afterwards - for the A/B tools and tests only.  An unknown name is TT_EINVAL. */
 int tt_set_tuning_knob(const char* name, int value);
@@ -247,15 +250,6 @@ int tt_normalize_rows_inplace(float* w, int rows, int D, tt_stream_t stream);
 int tt_sinkhorn(const float* scores, float* q_out, int B_total, int K, int row0, int rows_out, float eps,
                 int iters, void* workspace, size_t workspace_bytes, tt_stream_t stream);
 size_t tt_sinkhorn_workspace_bytes(int B_total, int K);
-/*   Host queries of the one-launch solve (knob TT_SK_PERSIST; off by default):
- *     tt_sinkhorn_partials_offset   byte offset of the partial region in the workspace: a multiple of 256 for every B_total * K (the
- *                                   one-launch solve exchanges 8-byte granules there).  Its status word - nonzero when a wait for
- *                                   another workgroup's partial sums gave up and q is wrong - is the 32-bit word at byte
- *                                   tt_sinkhorn_workspace_bytes(B_total, K) - 256; the call zeroes it, the caller reads it afterwards.
- *     tt_sinkhorn_persistent_grid   the workgroups of the one-launch solve a tt_sinkhorn call of this shape takes under the current
- *                                   knobs, 0 when it takes the launch-per-iteration kernels. */
-size_t tt_sinkhorn_partials_offset(int B_total, int K);
-int tt_sinkhorn_persistent_grid(int B_total, int K);
 /*   The reference's own DISTRIBUTED form (my_utils.py:250-272: the columns stay on their rank, the K row sums are all-reduced once per
  *   iteration), one rank's share in steps - the caller all-reduces u[K] (sum) between them and passes the SAME workspace to all three:
  *     tt_sinkhorn_local_begin   scores [B_loc, K] -> E = exp(scores / eps) in the workspace, u_out[k] = the local row sums

@@ -77,7 +77,9 @@ def _sinkhorn(rng):
     B, K = int(rng.integers(1, 9000)), int(rng.integers(1, 513))
     row0 = int(rng.integers(0, B)) if rng.random() < 0.4 else 0
     rows_out = int(rng.integers(1, B - row0 + 1)) if row0 or rng.random() < 0.3 else B - row0
-    return dict(B=B, K=K, iters=_ch(rng, (0, 1, 3, 10)), row0=row0, rows_out=rows_out, persist=_b(rng))
+    iters = _ch(rng, (0, 1, 3, 10))
+    _b(rng)   # a draw nobody reads (it chose the retired one-launch solve): every later op draws from this generator, their cases stay
+    return dict(B=B, K=K, iters=iters, row0=row0, rows_out=rows_out)
 
 
 def _sinkhorn_from_q(rng):
@@ -788,15 +790,15 @@ PINNED = {
     ],
     "ce": [dict(rows=37, K=K, weighted=int(i % 2)) for i, K in enumerate(CE_K)],
     "sinkhorn": [
-        # the launch-per-iteration kernels: KPL 4 / 8 either side of K = 256; workgroup counts below the cap, AT it (2048 rows: 64 of 64),
-        # beyond it (2049: 64 workgroups of 33 rows - the last one gets none), 50176 rows (the cap of 256)
-        dict(B=2048, K=256, iters=3, row0=0, rows_out=2048, persist=0), dict(B=2049, K=257, iters=1, row0=100, rows_out=1500, persist=0),
-        dict(B=1, K=1, iters=0, row0=0, rows_out=1, persist=0), dict(B=50176, K=200, iters=2, row0=6272, rows_out=6272, persist=0),
-        # the one-launch solve: odd B * K (777 x 333: 9 workgroups; 1001 x 255), KPL 4 and 8, iters 0 and 1, row windows, one workgroup,
-        # and a problem too big for it (it falls back)
-        dict(B=777, K=333, iters=5, row0=0, rows_out=777, persist=1), dict(B=1001, K=255, iters=1, row0=3, rows_out=997, persist=1),
-        dict(B=6272, K=200, iters=0, row0=2000, rows_out=99, persist=1), dict(B=33, K=511, iters=10, row0=0, rows_out=33, persist=1),
-        dict(B=1705, K=1, iters=3, row0=0, rows_out=1705, persist=1), dict(B=50176, K=200, iters=2, row0=0, rows_out=50176, persist=1),
+        # KPL 4 / 8 either side of K = 256; workgroup counts below the cap, AT it (2048 rows: 64 of 64), beyond it (2049: 64 workgroups of
+        # 33 rows - the last one gets none), 50176 rows (the cap of 256)
+        dict(B=2048, K=256, iters=3, row0=0, rows_out=2048), dict(B=2049, K=257, iters=1, row0=100, rows_out=1500),
+        dict(B=1, K=1, iters=0, row0=0, rows_out=1), dict(B=50176, K=200, iters=2, row0=6272, rows_out=6272),
+        # odd B * K (777 x 333; 1001 x 255), KPL 4 and 8, iters 0 and 1, row windows that start past row 0 and end before B, one workgroup,
+        # one column, and an output launch of more than 8192 rows
+        dict(B=777, K=333, iters=5, row0=0, rows_out=777), dict(B=1001, K=255, iters=1, row0=3, rows_out=997),
+        dict(B=6272, K=200, iters=0, row0=2000, rows_out=99), dict(B=33, K=511, iters=10, row0=0, rows_out=33),
+        dict(B=1705, K=1, iters=3, row0=0, rows_out=1705), dict(B=50176, K=200, iters=2, row0=0, rows_out=50176),
     ],
     "sinkhorn_from_q": [dict(B=777, K=333, iters=5, transposed=0), dict(B=2049, K=256, iters=0, transposed=1), dict(B=65, K=511, iters=1, transposed=1)],
     "sinkhorn_local": [dict(B=777, K=333, iters=5), dict(B=2049, K=257, iters=0), dict(B=31, K=64, iters=1)],

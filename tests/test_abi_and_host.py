@@ -153,11 +153,11 @@ def _knob_table():
 def test_tuning_knob_setter_knows_every_documented_knob_and_no_retired_one():
     """tt_set_tuning_knob takes every knob of the library's list (tt_tuning_knob_info) and setting a knob back to its default restores the
     default dispatch - seen through the route queries for the knobs that have one, among them the entries that follow the two retired names
-    in the table.  A retired knob is an error, not a silent no-op: a tool that still passes TT_Q8_STREAM (the round-4 pair kernel) or
-    TT_PAIRS_NBUF (a forced ring depth) must hear about it."""
+    in the table.  A retired knob is an error, not a silent no-op: a tool that still passes TT_Q8_STREAM (the round-4 pair kernel),
+    TT_PAIRS_NBUF (a forced ring depth) or TT_SK_PERSIST / TT_SKP_ROWS (the one-launch Sinkhorn solve) must hear about it."""
     lib = _lib.load()
     table = _knob_table()
-    assert len(table) == 32 and len(set(n for n, _ in table)) == 32
+    assert len(table) == 30 and len(set(n for n, _ in table)) == 30
     pairs = lambda M, N, K: lib.tt_linear_fwd_pairs_route(M, N, K, 0, 1, 0, 1, 0, 0)
     planes = lambda: lib.tt_linear_fwd_planes_route(1, 25216, 768, 3072, 0, 1, 1, 1, 0, 0)
     # knob -> (a non-default value, the route query it moves, its answer at the default, its answer at that value); no device: 256 CUs
@@ -172,7 +172,7 @@ def test_tuning_knob_setter_knows_every_documented_knob_and_no_retired_one():
             assert query() == at_default, name
             assert lib.tt_set_tuning_knob(name.encode(), value) == 0 and query() == at_value, name
             assert lib.tt_set_tuning_knob(name.encode(), dict(table)[name]) == 0 and query() == at_default, name
-        for retired in ("TT_Q8_STREAM", "TT_PAIRS_NBUF"):
+        for retired in ("TT_Q8_STREAM", "TT_PAIRS_NBUF", "TT_SK_PERSIST", "TT_SKP_ROWS"):
             assert lib.tt_set_tuning_knob(retired.encode(), 1) == -1                 # TT_EINVAL
             assert "unknown knob" in lib.tt_last_error().decode() and retired in lib.tt_last_error().decode()
     finally:

@@ -140,14 +140,6 @@ def sk_kpl(K):                              # SK_LAUNCH_KPL: 4 columns per lane 
     return 4 if K <= 256 else 8
 
 
-def skp_grid(B, K):
-    """tt_sinkhorn_persistent_grid under TT_SK_PERSIST = 1 (sk_persistent_kernel: skp_lds_rows, G <= CUs and G <= SK_MAXWG / 2)."""
-    kpad = (K + 63) // 64 * 64
-    rows = (38400 - 64 * 8 - 16 * kpad) // K
-    G = (B + rows - 1) // rows if rows > 0 else NCU + 1
-    return G if (G <= NCU and G <= 128) else 0
-
-
 def _empty_wgs(B, G):
     rows = (B + G - 1) // G
     return G - (B + rows - 1) // rows
@@ -155,30 +147,22 @@ def _empty_wgs(B, G):
 
 def test_sinkhorn_every_launch_regime():
     cases = _of("sinkhorn")
-    per_it = cases + [dict(p, persist=0) for p in cases if p["persist"] and skp_grid(p["B"], p["K"]) == 0]
-    # the launch-per-iteration kernels: both KPLs; workgroup counts below, at and beyond the cap; a workgroup that gets no rows
-    assert {sk_kpl(p["K"]) for p in per_it} == {4, 8}
+    # both KPLs; workgroup counts below, at and beyond the cap; a workgroup that gets no rows
+    assert {sk_kpl(p["K"]) for p in cases} == {4, 8}
     w = lambda B: (B + 31) // 32
-    assert any(w(p["B"]) < sk_default_cap(p["B"]) for p in per_it)
-    assert any(w(p["B"]) == sk_default_cap(p["B"]) for p in per_it)
-    assert any(w(p["B"]) > sk_default_cap(p["B"]) for p in per_it)
-    assert any(sk_wgs(p["B"]) == 256 for p in per_it)
-    assert any(_empty_wgs(p["B"], sk_wgs(p["B"])) > 0 for p in per_it)
+    assert any(w(p["B"]) < sk_default_cap(p["B"]) for p in cases)
+    assert any(w(p["B"]) == sk_default_cap(p["B"]) for p in cases)
+    assert any(w(p["B"]) > sk_default_cap(p["B"]) for p in cases)
+    assert any(sk_wgs(p["B"]) == 256 for p in cases)
+    assert any(_empty_wgs(p["B"], sk_wgs(p["B"])) > 0 for p in cases)
     # windows and iteration counts
     assert {p["iters"] for p in cases} >= {0, 1}
     assert any(p["row0"] > 0 for p in cases) and any(p["row0"] + p["rows_out"] < p["B"] for p in cases)
-    assert any(p["rows_out"] > 8192 for p in cases)        # the output launch's own workgroup count (SK_LAST_WIDE up to 8192 rows)
-    # the one-launch solve: taken and refused; odd B * K; both KPLs; more than one workgroup; iters 0 and 1; windows
-    pers = [p for p in cases if p["persist"]]
-    taken = [p for p in pers if skp_grid(p["B"], p["K"])]
-    assert taken and len(taken) < len(pers)
-    assert any(p["B"] * p["K"] % 2 for p in taken)
-    assert {sk_kpl(p["K"]) for p in taken} == {4, 8}
-    assert any(skp_grid(p["B"], p["K"]) > 1 for p in taken)
-    # (no workgroup of the one-launch solve is ever empty: G = ceil(B / cap) gives B > (G - 1) * cap >= (G - 1) * ceil(B / G))
-    assert all(_empty_wgs(p["B"], skp_grid(p["B"], p["K"])) == 0 for p in taken)
-    assert {0, 1} <= {p["iters"] for p in taken}
-    assert any(p["row0"] > 0 and p["row0"] + p["rows_out"] < p["B"] for p in taken)
+    assert any(p["rows_out"] > 8192 for p in cases)        # the output launch's own workgroup count (one per 32 rows up to 8192 rows)
+    # what else the pinned shapes are in the table for (both KPLs and the iteration counts 0 and 1: above): an odd B * K - the partial
+    # region then does not start where E ends - and ONE window that starts past row 0 and ends before B
+    assert any(p["B"] * p["K"] % 2 for p in cases)
+    assert any(p["row0"] > 0 and p["row0"] + p["rows_out"] < p["B"] for p in cases)
 
 
 def test_sinkhorn_entries_and_queue():
@@ -199,22 +183,12 @@ def test_rows_ops_edges():
     assert any(p["zero_row"] for p in l2) and any(not p["zero_row"] for p in l2) and max(p["D"] for p in l2) == 1024
 
 
-# ---- the Sinkhorn workspace layout (the one-launch solve's 8-byte granules)
+# ---- the Sinkhorn workspace layout: E, padding to a 256-byte boundary, two partial buffers of SK_MAXWG = 256 rows
 @pytest.mark.parametrize("B,K", [(777, 333), (6272, 200), (1, 1), (50176, 200), (3, 511), (1001, 255)])
-def test_sinkhorn_workspace_places_the_granules_on_an_8_byte_boundary(lib, B, K):
-    off, nb = lib.tt_sinkhorn_partials_offset(B, K), lib.tt_sinkhorn_workspace_bytes(B, K)
-    assert off % 256 == 0 and off >= B * K * 4                       # (the old rule put them at B * K * 4 bytes: 4-byte aligned when B * K is odd)
-    assert off + 2 * 256 * K * 4 + 16 <= nb                          # both partial buffers, then the status block
-    assert nb - 256 == off + 2 * 256 * K * 4                         # the status word hip_ops.sinkhorn reads
+def test_sinkhorn_workspace_is_e_padded_to_256_bytes_and_two_partial_buffers(lib, B, K):
+    nb = lib.tt_sinkhorn_workspace_bytes(B, K)
+    assert nb == (B * K * 4 + 255) // 256 * 256 + 2 * 256 * K * 4
     assert lib.tt_sinkhorn_local_workspace_bytes(B, K) == nb
-
-
-def test_sinkhorn_persistent_grid_follows_the_knob(lib):
-    assert lib.tt_sinkhorn_persistent_grid(777, 333) == 0            # the knob is off by default
-    with hip_ops.tuning_knob("TT_SK_PERSIST", 1):
-        for B, K in [(777, 333), (50176, 200), (6272, 200), (33, 511), (1705, 1)]:
-            assert lib.tt_sinkhorn_persistent_grid(B, K) == skp_grid(B, K), (B, K)
-    assert lib.tt_sinkhorn_persistent_grid(777, 333) == 0
 
 
 # ---- the second tier: the evaluator, optimizer and mask kernels.  Their launchers branch without a host query, so each rule is restated
@@ -381,7 +355,7 @@ def test_third_tier_is_appended_and_the_first_two_are_what_they_were():
 
     assert PROP_OPS == ("label_prop", "label_prop_grid", "upsample_argmax_hw")
     earlier = [case_id(o, p) for o, p in CASES if o in STEP_OPS + EVAL_OPS]
-    assert len(earlier) == 290 and zlib.crc32("\n".join(earlier).encode()) == 681109916      # the ids of the first two tiers, unchanged
+    assert len(earlier) == 290 and zlib.crc32("\n".join(earlier).encode()) == 3949057654      # the ids of the first two tiers, unchanged (but Sinkhorn's: no persist key since the one-launch solve left)
     assert earlier[-1].startswith("pos_embed[") and [o for o, _ in CASES][290] == "label_prop"
 
 
@@ -512,7 +486,7 @@ def test_fourth_tier_is_appended_and_the_first_three_are_what_they_were():
 
     assert HEAD_OPS == ("probe_logits", "probe_upsample_ce", "bilinear_adjoint", "probe_wgrad", "sgd", "img_resize", "img_color", "img_blur")
     earlier = [case_id(o, p) for o, p in CASES if o not in HEAD_OPS + METRIC_OPS + PREP_OPS]
-    assert len(earlier) == 383 and zlib.crc32("\n".join(earlier).encode()) == 1936048768      # the ids of the first three tiers, unchanged
+    assert len(earlier) == 383 and zlib.crc32("\n".join(earlier).encode()) == 2502457127      # the ids of the first three tiers, unchanged (but Sinkhorn's: no persist key since the one-launch solve left)
     assert earlier[-1].startswith("upsample_argmax_hw[") and [o for o, _ in CASES][383] == "probe_logits"
     # every op of the table has a check on the side it runs on (tools/fuzz_ops.py draws from OPS and runs tests/test_hip_sweep.py::run_case)
     from _sweep_checks_eval import CHECK as EVAL_CHECK
@@ -647,7 +621,7 @@ def test_fifth_tier_is_appended_and_the_first_four_are_what_they_were():
     assert METRIC_OPS == ("kmeans_assign_tiled", "kmeans_accumulate_tiled", "kmeans_assign_batched", "kmeans_fit", "confusion_segments", "davis_counts",
                           "bf_counts")
     earlier = [case_id(o, p) for o, p in CASES if o not in METRIC_OPS + PREP_OPS]
-    assert len(earlier) == 558 and zlib.crc32("\n".join(earlier).encode()) == 3298991197      # the ids of the first four tiers, unchanged
+    assert len(earlier) == 558 and zlib.crc32("\n".join(earlier).encode()) == 4217683      # the ids of the first four tiers, unchanged (but Sinkhorn's: no persist key since the one-launch solve left)
     assert earlier[-1].startswith("img_blur[") and [o for o, _ in CASES][558] == "kmeans_assign_tiled"
     from _sweep_checks_metric import CHECK as METRIC_CHECK      # (tools/fuzz_ops.py draws from OPS and runs tests/test_hip_sweep.py::run_case)
 
@@ -831,7 +805,7 @@ def test_sixth_tier_is_appended_and_the_first_five_are_what_they_were():
 
     assert PREP_OPS == ("convert", "split_dual", "split_multi", "transpose_pairs", "transpose_planes", "patch_embed", "grad_amax", "layernorm_long")
     earlier = [case_id(o, p) for o, p in CASES if o not in PREP_OPS]
-    assert len(earlier) == 718 and zlib.crc32("\n".join(earlier).encode()) == 2905359468      # the ids of the first five tiers, unchanged
+    assert len(earlier) == 718 and zlib.crc32("\n".join(earlier).encode()) == 2505003073      # the ids of the first five tiers, unchanged (but Sinkhorn's: no persist key since the one-launch solve left)
     assert earlier[-1].startswith("bf_counts[") and [o for o, _ in CASES][718] == "convert"
     from _sweep_checks_prep import CHECK as PREP_CHECK      # (tools/fuzz_ops.py draws from OPS and runs tests/test_hip_sweep.py::run_case)
 

@@ -51,13 +51,11 @@ int device_cu_count();   // core.cpp: multiprocessors of the CURRENT device (loo
   X(TN_WGS, "TT_TN_WGS", 0)                       /* gemm_pairs_tn.hip: workgroups (0 = 1.5 per CU) */                                 \
   X(TN_XCD, "TT_TN_XCD", 1)                       /* gemm_pairs_tn.hip: whole splits per XCD */                                        \
   X(Q8_MIN_TILES, "TT_Q8_MIN_TILES", 128)         /* gemm_pairs8.hip */                                                                \
-  X(SK_PERSIST, "TT_SK_PERSIST", 0)               /* sinkhorn.hip: the one-launch solve */                                             \
   X(ATTN_PAIRS_PERSIST, "TT_ATTN_PAIRS_PERSIST", 1) /* attention_pairs.hip: one workgroup per CU */                                    \
   X(Q4, "TT_Q4", 0)                               /* gemm_pairs8.hip: gemm_pairs4_kernel (an experiment) */                            \
   X(Q4_SMALL, "TT_Q4_SMALL", 0)                   /* gemm_pairs8.hip */                                                                \
   X(SPLIT_ROWS, "TT_SPLIT_ROWS", 1)               /* gemm_planes.hip: the streaming row-pair split */                                  \
   X(SK_WGS, "TT_SK_WGS", 0)                       /* sinkhorn.hip sk_wgs: workgroup cap (0 = sk_default_cap) */                        \
-  X(SKP_ROWS, "TT_SKP_ROWS", 0)                   /* sinkhorn.hip: rows per workgroup of the one-launch solve (0 = the LDS capacity) */ \
   X(FORCE_TILE, "TT_FORCE_TILE", -1)              /* gemm_f32.hip gemm_tile_choice: 0..3 forces that tile */                           \
   X(TILE_RULE, "TT_TILE_RULE", 1)                 /* gemm_f32.hip gemm_tile_choice: 0 = the plain rule */                              \
   X(SPLIT_TARGET, "TT_SPLIT_TARGET", 0)           /* gemm_f32.hip gemm_splitk_choice: workgroups aimed at (0 = 1024) */                \

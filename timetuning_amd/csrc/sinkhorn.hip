@@ -37,9 +37,7 @@ static int sk_default_cap(int B) {
   if (B >= 4096 && c < 128) c = 128;
   return c < 64 ? 64 : (c > SK_MAXWG ? SK_MAXWG : c);
 }
-#ifndef SK_FOLD_BATCH
-#define SK_FOLD_BATCH 64
-#endif
+constexpr int SK_FOLD_BATCH = 64;
 constexpr int SK_THREADS = 1024;
 constexpr int SK_WAVES = SK_THREADS / 64;
 
@@ -75,9 +73,10 @@ __device__ __forceinline__ void fold_waves(const float (&acc)[KPL], float (*red)
   }
 }
 
-// E = exp(scores/eps); partial[wg][k] = sum over this workgroup's rows of E[b][k]
-template <int KPL>
-__global__ __launch_bounds__(SK_THREADS) void sk_init_kernel(const float* __restrict__ scores, float* __restrict__ E,
+// E = exp(src/eps) with src = scores; partial[wg][k] = sum over this workgroup's rows of E[b][k].  FROM_E: src is E itself (tt_sinkhorn_from_q:
+// no exp / log round trip) - only the sums, nothing is written to E and eps is not read.
+template <bool FROM_E, int KPL>
+__global__ __launch_bounds__(SK_THREADS) void sk_init_kernel(const float* __restrict__ src, float* __restrict__ E,
                                                              float* __restrict__ partial, int B, int K, float eps, int rows_per_wg) {
   __shared__ float red[SK_WAVES][64 * KPL];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -90,16 +89,20 @@ __global__ __launch_bounds__(SK_THREADS) void sk_init_kernel(const float* __rest
     for (int i = 0; i < KPL; ++i) {
       const int k = lane + 64 * i;
       if (k < K) {
-        const float e = expf(scores[(long long)b * K + k] / eps);
-        E[(long long)b * K + k] = e;
-        acc[i] += e;
+        if (FROM_E) {
+          acc[i] += src[(long long)b * K + k];
+        } else {
+          const float e = expf(src[(long long)b * K + k] / eps);
+          E[(long long)b * K + k] = e;
+          acc[i] += e;
+        }
       }
     }
   }
   fold_waves<KPL>(acc, red, partial + (long long)blockIdx.x * K, K);
 }
 
-// The same from the positive matrix itself, Q[k][b] = exp(scores[b][k] / eps) as my_utils.sinkhorn receives it ([K][B], :246):
+// From the positive matrix itself, Q[k][b] = exp(scores[b][k] / eps) as my_utils.sinkhorn receives it ([K][B], :246):
 // E[b][k] = Q[k][b] (a transposing copy through LDS, 64 x 64 tiles), no exp / log round trip.
 __global__ __launch_bounds__(256) void sk_transpose_kernel(const float* __restrict__ Q, float* __restrict__ E, int B, int K) {
   __shared__ float t[64][65];
@@ -110,25 +113,6 @@ __global__ __launch_bounds__(256) void sk_transpose_kernel(const float* __restri
   __syncthreads();
   for (int r = r4; r < 64; r += 4)
     if (b0 + r < B && k0 + c < K) E[(long long)(b0 + r) * K + k0 + c] = t[c][r];
-}
-
-template <int KPL>
-__global__ __launch_bounds__(SK_THREADS) void sk_init_from_e_kernel(const float* __restrict__ E, float* __restrict__ partial, int B, int K,
-                                                                    int rows_per_wg) {
-  __shared__ float red[SK_WAVES][64 * KPL];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r0 = blockIdx.x * rows_per_wg, r1 = min(B, r0 + rows_per_wg);
-  float acc[KPL];
-#pragma unroll
-  for (int i = 0; i < KPL; ++i) acc[i] = 0.f;
-  for (int b = r0 + wave; b < r1; b += SK_WAVES) {
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-      const int k = lane + 64 * i;
-      if (k < K) acc[i] += E[(long long)b * K + k];
-    }
-  }
-  fold_waves<KPL>(acc, red, partial + (long long)blockIdx.x * K, K);
 }
 
 // (Round 6 tried to cut this kernel's two latency chains - the fold of the nwg_in x K partials spread over all 1024 threads in four slices
@@ -226,199 +210,6 @@ __global__ __launch_bounds__(SK_THREADS) void sk_iter_kernel(const float* __rest
   fold_waves<KPL>(acc, red, partial_out + (long long)blockIdx.x * K, K);
 }
 
-// ---- the whole solve in ONE launch ----------------------------------------------------------------------------------------------
-// SURVEY 2.4 k12's persistent form.  G workgroups (one per CU: 1024 threads and most of the LDS), each owning a run of rows whose
-// E = exp(scores / eps) it keeps in LDS for the whole solve (6272 x 200 at C2: 37 workgroups); per iteration the only thing that crosses
-// workgroups is the K-vector of row sums.
-// Round 5 built the exchange from the expensive primitives (4-byte write-through stores, `s_waitcnt vmcnt(0)` + barrier, ONE arrival
-// counter everybody polls, then the partials): ~ 8 us per iteration, 105 us per solve against 78 for a launch per iteration.  Round 6: the
-// exchange is a TAGGED GRANULE all-gather (MI355X_MICROARCH.md "Valid forms": an aligned 8-byte {data, tag} written by ONE store is seen
-// whole or not at all) - a workgroup's partial sum of column k travels as {float bits, iteration tag} in one 8-byte agent-scope store, a
-// reader polls the granules it needs (all of its loads in flight, re-issuing only those whose tag is not this iteration's yet) and sums
-// them in workgroup order once they are all there.  No counter, no fence, no wait for the stores, no barrier between publishing and
-// gathering: one fabric write + one fabric read per iteration.  Tags are iteration + 1 and the granule buffers are zeroed by the launch
-// function (a tag never matches memory that was not written by this solve); two granule buffers alternate - a workgroup publishes iteration
-// i + 1 only after it has gathered iteration i, i.e. after EVERY workgroup has published i, i.e. after every workgroup has finished
-// gathering i - 1 from the buffer that i + 1 overwrites.  The fold order is fixed (run-to-run bit equality); every spin is bounded (status
-// word).  Needs every workgroup resident at once (G <= CUs: they wait for each other) and 2 G K granules in the workspace's partial region
-// (G <= SK_MAXWG / 2); larger problems (the 8-rank global problem: 50176 rows) take the launch-per-iteration path.
-struct SkpArgs {
-  const float* scores;          // [B][K]
-  unsigned long long* gran;     // [2][G][K] granules: float bits | (tag << 32)
-  unsigned* status;             // [0]: 1 = a spin gave up (zeroed by the launch function)
-  float* q_out;                 // [rows_out][K]
-  int B, K, G, rows_per_wg, row0, rows_out, iters;
-  float eps;
-  int b_norm;
-};
-constexpr int SKP_LDS_FLOATS = 38400;   // 150 KB
-__host__ __device__ inline int skp_kpad(int K) { return (K + 63) / 64 * 64; }
-__host__ __device__ inline int skp_lds_rows(int K) { return (SKP_LDS_FLOATS - 64 * SK_KPL - SK_WAVES * skp_kpad(K)) / K; }
-
-__global__ __launch_bounds__(SK_THREADS) void sk_persistent_kernel(SkpArgs g) {
-  __shared__ float sm[SKP_LDS_FLOATS];
-  const int K = g.K, KP = skp_kpad(K);
-  float* a_s = sm;                              // [64 SK_KPL]
-  float* red = sm + 64 * SK_KPL;                // [SK_WAVES][KP]
-  float* El = red + SK_WAVES * KP;              // [rows_per_wg][K]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wg = blockIdx.x;
-  const int r0 = wg * g.rows_per_wg, r1 = min(g.B, r0 + g.rows_per_wg);
-  auto e_ptr = [&](int b) -> float* { return El + (size_t)(b - r0) * K; };
-  float acc[SK_KPL], a[SK_KPL];
-
-  // fold the 16 waves' register partials (LDS) and publish the K sums of phase `ph` as granules
-  auto publish = [&](int ph) {
-#pragma unroll
-    for (int i = 0; i < SK_KPL; ++i)
-      if (lane + 64 * i < K) red[wave * KP + lane + 64 * i] = acc[i];
-    __syncthreads();
-    unsigned long long* out = g.gran + ((size_t)(ph & 1) * g.G + wg) * K;
-    for (int k = threadIdx.x; k < K; k += SK_THREADS) {
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < SK_WAVES; ++w) s += red[w * KP + k];
-      const unsigned long long v = (unsigned long long)__float_as_uint(s) | ((unsigned long long)(unsigned)(ph + 1) << 32);
-      __hip_atomic_store(out + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  };
-  // a_k = (1 / K) / sum over the workgroups' phase-`ph` partials (fixed order), each taken when its granule carries this phase's tag
-  auto gather = [&](int ph) {
-    const unsigned tag = (unsigned)(ph + 1);
-    const unsigned long long* in = g.gran + (size_t)(ph & 1) * g.G * K;
-    const int NJ = SK_THREADS / KP;
-    const int k = threadIdx.x % KP, j = threadIdx.x / KP;
-    float u = 0.f;
-    if (k < K && j < NJ) {
-      // thread (k, j) takes the workgroups w = j, j + NJ, ... - sixteen granules in flight, re-polled until they are all this phase's
-      for (int w0 = j; w0 < g.G; w0 += 16 * NJ) {
-        float v[16];
-        unsigned need = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          v[q] = 0.f;
-          if (w0 + q * NJ < g.G) need |= 1u << q;
-        }
-        unsigned spins = 0;
-        while (need) {
-          unsigned long long raw[16];
-#pragma unroll
-          for (int q = 0; q < 16; ++q)
-            if (need >> q & 1u) raw[q] = __hip_atomic_load(in + (size_t)(w0 + q * NJ) * K + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-          for (int q = 0; q < 16; ++q)
-            if ((need >> q & 1u) && (unsigned)(raw[q] >> 32) == tag) {
-              v[q] = __uint_as_float((unsigned)raw[q]);
-              need &= ~(1u << q);
-            }
-          if (need) {
-            if (++spins > (1u << 22)) { __hip_atomic_store(g.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-            __builtin_amdgcn_s_sleep(1);
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) u += v[q];
-      }
-    }
-    __syncthreads();   // (red: publish's readers are done)
-    if (j < NJ) red[j * KP + k] = u;
-    __syncthreads();
-    for (int k2 = threadIdx.x; k2 < K; k2 += SK_THREADS) {
-      float t = 0.f;
-      for (int j2 = 0; j2 < NJ; ++j2) t += red[j2 * KP + k2];
-      a_s[k2] = (1.0f / (float)K) / t;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < SK_KPL; ++i) a[i] = (lane + 64 * i < K) ? a_s[lane + 64 * i] : 0.f;
-  };
-
-  // ---- phase 0: E = exp(scores / eps) for this workgroup's rows (kept in LDS), their column sums; four rows of a wave in flight
-#pragma unroll
-  for (int i = 0; i < SK_KPL; ++i) acc[i] = 0.f;
-  for (int b = r0 + wave; b < r1; b += 4 * SK_WAVES) {
-    float v[4][SK_KPL];
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int bj = b + jj * SK_WAVES;
-      const int bc = min(bj, r1 - 1);                   // (clamped, not predicated: the loads of a pass then issue back to back)
-#pragma unroll
-      for (int i = 0; i < SK_KPL; ++i) {
-        const int k = lane + 64 * i;
-        if (64 * i < K) v[jj][i] = g.scores[(long long)bc * K + min(k, K - 1)];
-      }
-    }
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int bj = b + jj * SK_WAVES;
-      if (bj < r1) {
-        float* er = e_ptr(bj);
-#pragma unroll
-        for (int i = 0; i < SK_KPL; ++i) {
-          const int k = lane + 64 * i;
-          if (64 * i < K && k < K) {
-            const float e = expf(v[jj][i] / g.eps);
-            er[k] = e;
-            acc[i] += e;
-          }
-        }
-      }
-    }
-  }
-  if (g.iters > 0) publish(0);
-  else __syncthreads();
-  const float c = 1.0f / (float)g.b_norm;
-  for (int it = 0; it < g.iters || it == 0; ++it) {
-    if (g.iters > 0) gather(it);
-    else {
-#pragma unroll
-      for (int i = 0; i < SK_KPL; ++i) a[i] = (lane + 64 * i < K) ? 1.0f : 0.f;
-    }
-    const bool last = it + 1 >= g.iters;
-    if (last) {
-      // the last row step's a, the final column normalisation, written for the requested rows this workgroup owns
-      const int o0 = max(r0, g.row0), o1 = min(r1, g.row0 + g.rows_out);
-      for (int b = o0 + wave; b < o1; b += SK_WAVES) {
-        const float* er = e_ptr(b);
-        float e[SK_KPL], t = 0.f;
-#pragma unroll
-        for (int i = 0; i < SK_KPL; ++i) {
-          e[i] = (lane + 64 * i < K) ? er[lane + 64 * i] : 0.f;
-          t += a[i] * e[i];
-        }
-        t = wave_sum(t);
-#pragma unroll
-        for (int i = 0; i < SK_KPL; ++i)
-          if (lane + 64 * i < K) g.q_out[(long long)(b - g.row0) * K + lane + 64 * i] = a[i] * e[i] / t;
-      }
-      break;
-    }
-    // column step over this workgroup's rows (LDS), two rows per wave in flight; the row sums that follow
-#pragma unroll
-    for (int i = 0; i < SK_KPL; ++i) acc[i] = 0.f;
-    for (int b = r0 + wave; b < r1; b += 2 * SK_WAVES) {
-      const int b2 = b + SK_WAVES;
-      const bool has2 = b2 < r1;
-      const float* er = e_ptr(b);
-      const float* fr = e_ptr(has2 ? b2 : b);
-      float e[SK_KPL], f[SK_KPL], t = 0.f, t2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < SK_KPL; ++i) {
-        const int k = lane + 64 * i;
-        e[i] = (k < K) ? er[k] : 0.f;
-        f[i] = (k < K && has2) ? fr[k] : 0.f;
-        t += a[i] * e[i];
-        t2 += a[i] * f[i];
-      }
-      t = wave_sum(t);
-      t2 = wave_sum(t2);
-      const float bb = c / t, bb2 = has2 ? c / t2 : 0.f;
-#pragma unroll
-      for (int i = 0; i < SK_KPL; ++i) acc[i] += e[i] * bb + f[i] * bb2;
-    }
-    publish(it + 1);   // (red: the gather above ended with a barrier behind its last reader)
-  }
-}
-
 // ---- cross entropy -----------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ scores, const int64_t* __restrict__ labels,
                                                  const float* __restrict__ row_weight, float* __restrict__ row_loss,
@@ -471,28 +262,20 @@ __global__ __launch_bounds__(256) void mean_kernel(const float* __restrict__ v, 
 
 using namespace tt;
 
-// Workspace layout: E [B_total][K] floats | padding to a 256-byte boundary | two partial buffers [SK_MAXWG][K] floats (the persistent kernel's
-// granules [2][G][K] of 8 bytes each live there) | a 256-byte block whose first word is the persistent kernel's status.  The partial region
-// starts on the boundary whatever B_total * K is: the granules are 8-byte atomics, and with E's B_total * K floats in front of them an odd
-// count left them 4-byte aligned (a misaligned 8-byte store is not seen whole or not at all).
-extern "C" size_t tt_sinkhorn_partials_offset(int B_total, int K) { return ((size_t)B_total * K * sizeof(float) + 255) / 256 * 256; }
+// Workspace layout, the one rule of tt_sinkhorn, tt_sinkhorn_from_q and the tt_sinkhorn_local_* steps: E [B][K] floats | padding to a 256-byte
+// boundary | two partial buffers [SK_MAXWG][K] floats.  The partial region starts on the boundary whatever B * K is.
+static size_t sk_part_offset(int B, int K) { return ((size_t)B * K * sizeof(float) + 255) / 256 * 256; }
 
-extern "C" size_t tt_sinkhorn_workspace_bytes(int B_total, int K) {
-  return tt_sinkhorn_partials_offset(B_total, K) + 2ull * SK_MAXWG * K * sizeof(float) + 256;   // ... | the status block
+struct SkWorkspace {
+  float* E;
+  float* part[2];
+};
+static SkWorkspace sk_carve(void* workspace, int B, int K) {
+  float* part0 = reinterpret_cast<float*>(static_cast<char*>(workspace) + sk_part_offset(B, K));
+  return {static_cast<float*>(workspace), {part0, part0 + (size_t)SK_MAXWG * K}};
 }
 
-// The grid of the one-launch solve (sk_persistent_kernel) for a tt_sinkhorn call of this shape, or 0 when the call takes the launch-per-iteration
-// kernels (knob TT_SK_PERSIST off, or the rows of E do not fit the chip's LDS).  tt_sinkhorn_from_q never takes it.
-extern "C" int tt_sinkhorn_persistent_grid(int B_total, int K) {
-  if (B_total <= 0 || K <= 0 || K > 64 * SK_KPL || tuning_knob(KNOB_SK_PERSIST) == 0) return 0;
-  const int ncu = device_cu_count();
-  const int cap = skp_lds_rows(K);
-  const int rows_env = tuning_knob(KNOB_SKP_ROWS);   // tuning aid
-  int rows = rows_env > 0 ? rows_env : cap;
-  if (rows > cap) rows = cap;
-  const int G = rows > 0 ? (B_total + rows - 1) / rows : ncu + 1;
-  return (G <= ncu && G <= SK_MAXWG / 2) ? G : 0;
-}
+extern "C" size_t tt_sinkhorn_workspace_bytes(int B_total, int K) { return sk_part_offset(B_total, K) + 2ull * SK_MAXWG * K * sizeof(float); }
 
 static int sinkhorn_impl(const float* scores, const float* Q, int q_rows_are_columns, float* q_out, int B_total, int K, int row0,
                          int rows_out, float eps, int iters, void* workspace, size_t workspace_bytes, tt_stream_t stream);
@@ -518,54 +301,32 @@ static int sinkhorn_impl(const float* scores, const float* Q, int q_rows_are_col
   TT_REQUIRE(iters >= 0 && eps > 0.f, "sinkhorn: bad iters/eps");
   TT_REQUIRE(workspace_bytes >= tt_sinkhorn_workspace_bytes(B_total, K), "sinkhorn: workspace too small");
   hipStream_t s = as_stream(stream);
-  float* Ews = static_cast<float*>(workspace);
-  float* part0 = reinterpret_cast<float*>(static_cast<char*>(workspace) + tt_sinkhorn_partials_offset(B_total, K));
-  float* part[2] = {part0, part0 + (size_t)SK_MAXWG * K};
+  const SkWorkspace ws = sk_carve(workspace, B_total, K);
   // E [B][K]: built in the workspace, or - when the caller already holds the positive matrix in that layout - read in place
-  const float* E = (Q && q_rows_are_columns) ? Q : Ews;
-  // ---- one persistent launch (sk_persistent_kernel): from scores, every workgroup resident at once with its rows of E in LDS, the
-  // granule buffers inside the workspace's partial region.  Knob TT_SK_PERSIST: 0 never, 1 whenever it applies.
-  if (!Q) {
-    if (const int G = tt_sinkhorn_persistent_grid(B_total, K)) {
-      TT_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "sinkhorn: the workspace must be 8-byte aligned");
-      const int rows = (B_total + G - 1) / G;   // even shares
-      unsigned long long* gran = reinterpret_cast<unsigned long long*>(part0);
-      unsigned* status = reinterpret_cast<unsigned*>(part0 + 2ull * SK_MAXWG * K);
-      // tags start at 1: zeroed granules never match.  The status word sits right behind the partial region: one memset for both.
-      // The host reads it back (hip_ops.sinkhorn) and raises when a gather gave up.
-      if (hipMemsetAsync(gran, 0, 2ull * SK_MAXWG * K * sizeof(float) + 16, s) != hipSuccess) { set_error("sinkhorn: hipMemsetAsync failed"); return TT_ELAUNCH; }
-      SkpArgs a{scores, gran, status, q_out, B_total, K, G, rows, row0, rows_out, iters, eps, B_total};
-      hipLaunchKernelGGL(sk_persistent_kernel, dim3(G), dim3(SK_THREADS), 0, s, a);
-      TT_CHECK_LAUNCH("sinkhorn (persistent)");
-      return TT_OK;
-    }
-  }
+  const float* E = (Q && q_rows_are_columns) ? Q : ws.E;
   const int wgs = sk_wgs(B_total);
   const int rpw = (B_total + wgs - 1) / wgs;
   if (Q) {
-    if (!q_rows_are_columns) hipLaunchKernelGGL(sk_transpose_kernel, dim3((B_total + 63) / 64, (K + 63) / 64), dim3(256), 0, s, Q, Ews, B_total, K);
-    SK_LAUNCH_KPL(sk_init_from_e_kernel<4>, sk_init_from_e_kernel<8>, dim3(wgs), E, part[0], B_total, K, rpw);
+    if (!q_rows_are_columns) hipLaunchKernelGGL(sk_transpose_kernel, dim3((B_total + 63) / 64, (K + 63) / 64), dim3(256), 0, s, Q, ws.E, B_total, K);
+    SK_LAUNCH_KPL((sk_init_kernel<true, 4>), (sk_init_kernel<true, 8>), dim3(wgs), E, (float*)nullptr, ws.part[0], B_total, K, eps, rpw);
   } else {
-    SK_LAUNCH_KPL(sk_init_kernel<4>, sk_init_kernel<8>, dim3(wgs), scores, Ews, part[0], B_total, K, eps, rpw);
+    SK_LAUNCH_KPL((sk_init_kernel<false, 4>), (sk_init_kernel<false, 8>), dim3(wgs), scores, ws.E, ws.part[0], B_total, K, eps, rpw);
   }
   int cur = 0;
   for (int it = 0; it + 1 < iters; ++it) {  // iterations 1 .. iters-1 (each prepares the next row step)
-    SK_LAUNCH_KPL((sk_iter_kernel<false, 4>), (sk_iter_kernel<false, 8>), dim3(wgs), E, part[cur], part[cur ^ 1], (float*)nullptr, B_total, K, wgs,
+    SK_LAUNCH_KPL((sk_iter_kernel<false, 4>), (sk_iter_kernel<false, 8>), dim3(wgs), E, ws.part[cur], ws.part[cur ^ 1], (float*)nullptr, B_total, K, wgs,
                   rpw, 0, 0, 0, B_total);
     cur ^= 1;
   }
   // last iteration's row step + column normalisation, written straight to q for the requested rows
-  // (the output launch leaves no partials for anybody to fold: as many workgroups as give a wave its two rows - SK_LAST_WIDE, round 6)
-#ifndef SK_LAST_WIDE
-#define SK_LAST_WIDE 1
-#endif
+  // (the output launch leaves no partials for anybody to fold: as many workgroups as give a wave its two rows - round 6)
   int owgs = sk_wgs(rows_out);
-  if (SK_LAST_WIDE && rows_out <= 8192) {   // (6 272 rows: 71.1 -> 69.9 us per solve; 12 544: 83.2 -> 84.9; 50 176: no change)
+  if (rows_out <= 8192) {   // (6 272 rows: 71.1 -> 69.9 us per solve; 12 544: 83.2 -> 84.9; 50 176: no change)
     owgs = (rows_out + 2 * SK_WAVES - 1) / (2 * SK_WAVES);
     owgs = owgs > SK_MAXWG ? SK_MAXWG : (owgs < 1 ? 1 : owgs);   // (one workgroup per CU at most: 1 024 of them measured slower at 50 176 rows)
   }
   const int orpw = (rows_out + owgs - 1) / owgs;
-  SK_LAUNCH_KPL((sk_iter_kernel<true, 4>), (sk_iter_kernel<true, 8>), dim3(owgs), E, part[cur], (float*)nullptr, q_out, B_total, K, wgs, orpw,
+  SK_LAUNCH_KPL((sk_iter_kernel<true, 4>), (sk_iter_kernel<true, 8>), dim3(owgs), E, ws.part[cur], (float*)nullptr, q_out, B_total, K, wgs, orpw,
                 row0, rows_out, iters == 0 ? 1 : 0, B_total);
   TT_CHECK_LAUNCH("sinkhorn");
   return TT_OK;
@@ -615,11 +376,10 @@ extern "C" int tt_sinkhorn_local_begin(const float* scores, float* u_out, int B_
   TT_REQUIRE(scores && u_out && eps > 0.f, "sinkhorn_local_begin: null pointer / bad eps");
   if (const int rc = sk_local_check(workspace, workspace_bytes, B_loc, K)) return rc;
   hipStream_t s = as_stream(stream);
-  float* E = static_cast<float*>(workspace);
-  float* part = E + (size_t)B_loc * K;
+  const SkWorkspace ws = sk_carve(workspace, B_loc, K);
   const int wgs = sk_wgs(B_loc), rpw = (B_loc + wgs - 1) / wgs;
-  SK_LAUNCH_KPL(sk_init_kernel<4>, sk_init_kernel<8>, dim3(wgs), scores, E, part, B_loc, K, eps, rpw);
-  hipLaunchKernelGGL(sk_fold_kernel, dim3((K + 255) / 256), dim3(256), 0, s, part, u_out, wgs, K);
+  SK_LAUNCH_KPL((sk_init_kernel<false, 4>), (sk_init_kernel<false, 8>), dim3(wgs), scores, ws.E, ws.part[0], B_loc, K, eps, rpw);
+  hipLaunchKernelGGL(sk_fold_kernel, dim3((K + 255) / 256), dim3(256), 0, s, ws.part[0], u_out, wgs, K);
   TT_CHECK_LAUNCH("sinkhorn_local_begin");
   return TT_OK;
 }
@@ -629,11 +389,10 @@ extern "C" int tt_sinkhorn_local_step(const float* u_in, float* u_out, int B_loc
   TT_REQUIRE(u_in && u_out && B_total >= B_loc, "sinkhorn_local_step: null pointer / B_total < B_loc");
   if (const int rc = sk_local_check(workspace, workspace_bytes, B_loc, K)) return rc;
   hipStream_t s = as_stream(stream);
-  float* E = static_cast<float*>(workspace);
-  float* part = E + (size_t)B_loc * K;
+  const SkWorkspace ws = sk_carve(workspace, B_loc, K);
   const int wgs = sk_wgs(B_loc), rpw = (B_loc + wgs - 1) / wgs;
-  SK_LAUNCH_KPL((sk_iter_kernel<false, 4>), (sk_iter_kernel<false, 8>), dim3(wgs), E, u_in, part, (float*)nullptr, B_loc, K, 1, rpw, 0, 0, 0, B_total);
-  hipLaunchKernelGGL(sk_fold_kernel, dim3((K + 255) / 256), dim3(256), 0, s, part, u_out, wgs, K);
+  SK_LAUNCH_KPL((sk_iter_kernel<false, 4>), (sk_iter_kernel<false, 8>), dim3(wgs), ws.E, u_in, ws.part[0], (float*)nullptr, B_loc, K, 1, rpw, 0, 0, 0, B_total);
+  hipLaunchKernelGGL(sk_fold_kernel, dim3((K + 255) / 256), dim3(256), 0, s, ws.part[0], u_out, wgs, K);
   TT_CHECK_LAUNCH("sinkhorn_local_step");
   return TT_OK;
 }
@@ -643,7 +402,7 @@ extern "C" int tt_sinkhorn_local_end(const float* u_in, float* q_out, int B_loc,
   TT_REQUIRE(q_out && rows_out > 0 && rows_out <= B_loc, "sinkhorn_local_end: null pointer / rows_out outside (0, B_loc]");
   if (const int rc = sk_local_check(workspace, workspace_bytes, B_loc, K)) return rc;
   hipStream_t s = as_stream(stream);
-  const float* E = static_cast<const float*>(workspace);
+  const float* E = sk_carve(workspace, B_loc, K).E;
   const int owgs = sk_wgs(rows_out), orpw = (rows_out + owgs - 1) / owgs;
   SK_LAUNCH_KPL((sk_iter_kernel<true, 4>), (sk_iter_kernel<true, 8>), dim3(owgs), E, u_in, (float*)nullptr, q_out, B_loc, K, 1, orpw, 0, rows_out,
                 u_in ? 0 : 1, B_loc);

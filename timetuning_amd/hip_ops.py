@@ -666,23 +666,22 @@ def normalize_rows_(w):
     return w
 
 
+def _sinkhorn_solve(what: str, src, B: int, K: int, row0: int, rows_out: Optional[int], launch):
+    """Allocates q [rows_out, K] and the workspace of a [B, K] solve, runs ``launch(lib, q, rows_out, ws, nb)`` and checks its return code."""
+    lib = _lib.load()
+    rows_out = B - row0 if rows_out is None else rows_out
+    q = torch.empty((rows_out, K), dtype=f32, device=src.device)
+    nb = lib.tt_sinkhorn_workspace_bytes(B, K)
+    _lib.check(launch(lib, q, rows_out, _ws(nb, src.device), nb), what)
+    return q
+
+
 def sinkhorn(scores, iters: int, eps: float = 0.05, row0: int = 0, rows_out: Optional[int] = None):
     """scores [B_total, K] -> q [rows_out, K] for rows [row0, row0+rows_out)."""
-    lib = _lib.load()
     _chk(scores, "scores")
     B, K = scores.shape
-    rows_out = B - row0 if rows_out is None else rows_out
-    q = torch.empty((rows_out, K), dtype=f32, device=scores.device)
-    nb = lib.tt_sinkhorn_workspace_bytes(B, K)
-    ws = _ws(nb, scores.device)
-    _lib.check(lib.tt_sinkhorn(_p(scores), _p(q), B, K, row0, rows_out, float(eps), int(iters), _p(ws), nb, _stream()), "tt_sinkhorn")
-    # the one-launch solve (knob TT_SK_PERSIST) waits for the other workgroups' partial sums; a wait that gave up leaves q wrong and says so in
-    # the status word at the workspace's last 256 bytes.  Read it (a synchronisation: the knob is off by default) - not under a graph capture
-    if lib.tt_sinkhorn_persistent_grid(B, K) and not torch.cuda.is_current_stream_capturing():
-        if int(ws[nb - 256:nb - 252].view(torch.int32).item()) != 0:
-            raise _lib.HipLibraryError(f"tt_sinkhorn: the one-launch solve (TT_SK_PERSIST) missed a partial-sum exchange (B_total {B}, K {K}); "
-                                       "its q is not valid")
-    return q
+    return _sinkhorn_solve("tt_sinkhorn", scores, B, K, row0, rows_out, lambda lib, q, rows, ws, nb: lib.tt_sinkhorn(
+        _p(scores), _p(q), B, K, row0, rows, float(eps), int(iters), _p(ws), nb, _stream()))
 
 
 class SinkhornLocal:
@@ -731,16 +730,10 @@ class SinkhornLocal:
 def sinkhorn_from_q(Q, iters: int, row0: int = 0, rows_out: Optional[int] = None, transposed: bool = False):
     """Q positive = exp(scores / eps): [K, B_total] as my_utils.sinkhorn receives it, or [B_total, K] with ``transposed``
     -> q [rows_out, K]."""
-    lib = _lib.load()
     _chk(Q, "Q")
     B, K = Q.shape if transposed else Q.shape[::-1]
-    rows_out = B - row0 if rows_out is None else rows_out
-    q = torch.empty((rows_out, K), dtype=f32, device=Q.device)
-    nb = lib.tt_sinkhorn_workspace_bytes(B, K)
-    ws = _ws(nb, Q.device)
-    _lib.check(lib.tt_sinkhorn_from_q(_p(Q), int(transposed), _p(q), B, K, row0, rows_out, int(iters), _p(ws), nb, _stream()),
-               "tt_sinkhorn_from_q")
-    return q
+    return _sinkhorn_solve("tt_sinkhorn_from_q", Q, B, K, row0, rows_out, lambda lib, q, rows, ws, nb: lib.tt_sinkhorn_from_q(
+        _p(Q), int(transposed), _p(q), B, K, row0, rows, int(iters), _p(ws), nb, _stream()))
 
 
 def label_propagate_sims(xn, K: int, n_last_frames=7):
