@@ -1016,6 +1016,57 @@ int tt_adamw_ema_step(const tt_adamw_tensor* tensors, int count, int step, float
 /* features * mask[..., None] (models.py:142) and its backward: x[r][:] *= row_scale[r], cols % 4 == 0, x 16-byte aligned. */
 int tt_scale_rows_inplace(float* x, const float* row_scale, int rows, int cols, tt_stream_t stream);
 
+/* ---- N21: JPEG frames decoded on the device - what Image.open does inside the reference's DataLoader workers (data_loader.py:595-614),
+   bit-equal to Pillow's decode (libjpeg-turbo defaults: accurate integer IDCT, triangle-filter chroma up-sampling, 16-bit colour tables).
+   The HOST half (jpeg_scan.cpp: no HIP, no state, no allocation, re-entrant; every read checked against `len`) parses the markers and
+   undoes the Huffman coding; the DEVICE half (jpeg.hip) dequantises, runs the IDCT, up-samples and colour-converts a whole batch in two
+   launches.
+   Supported: SOF0 / 8-bit SOF1, three components, luma 1x1 / 2x1 / 2x2 over chroma 1x1, DRI / RSTn, one interleaved scan, YCbCr.
+   Status of both host entries: TT_JPEG_OK; > 0 a well-formed file this decoder does not take (the caller falls back); < 0 a broken file
+   or a bad argument. */
+#define TT_JPEG_OK 0
+#define TT_JPEG_UNSUPPORTED_FRAME 1        /* progressive, lossless, hierarchical, a DNL height */
+#define TT_JPEG_UNSUPPORTED_ARITHMETIC 2
+#define TT_JPEG_UNSUPPORTED_COMPONENTS 3   /* grayscale, CMYK */
+#define TT_JPEG_UNSUPPORTED_PRECISION 4    /* 12-bit samples */
+#define TT_JPEG_UNSUPPORTED_SAMPLING 5
+#define TT_JPEG_UNSUPPORTED_SCANS 6        /* more than one scan */
+#define TT_JPEG_UNSUPPORTED_QTABLE 7       /* 16-bit quantisation tables */
+#define TT_JPEG_UNSUPPORTED_COLOUR 8       /* RGB stored without a transform */
+#define TT_JPEG_EMALFORMED (-1)            /* markers / segment lengths / tables */
+#define TT_JPEG_ETRUNCATED (-2)            /* the scan data ends early */
+#define TT_JPEG_EHUFFMAN (-3)              /* a code no table holds */
+#define TT_JPEG_ERUN (-4)                  /* a run past coefficient 63 */
+#define TT_JPEG_ERESTART (-5)              /* a missing or misnumbered RSTn */
+#define TT_JPEG_EARGUMENT (-6)             /* null pointer, coefficient buffer too small */
+#define TT_JPEG_444 0                      /* sampling codes: luma 1x1, */
+#define TT_JPEG_422 1                      /* 2x1, */
+#define TT_JPEG_420 2                      /* 2x2 */
+/* Per component the block grid is (ceil(H / (8 vmax)) v) x (ceil(W / (8 hmax)) h) blocks; n_coeffs = 64 x the three grids' blocks. */
+int tt_jpeg_probe(const uint8_t* data, size_t len, int* H, int* W, int* sampling, long long* n_coeffs);
+/* coeffs: int16, 64 per block in natural (row-major) order, component after component, each in block-grid raster order; all n_coeffs are
+   written (zeros included).  qtables: uint16 [3][64], natural order, the table OF component 0, 1, 2.  On a non-zero status the buffers'
+   contents are unspecified, but nothing outside them is touched. */
+int tt_jpeg_scan(const uint8_t* data, size_t len, int16_t* coeffs, long long coeffs_capacity, uint16_t* qtables);
+/* One row per frame.  Offsets: coeff_off in int16 elements into `coeffs` (multiples of 8), qslot in 64-entry tables into `qtables`,
+   plane_off in bytes into the workspace (multiples of 8; component c's plane is its block grid x 64 bytes), out_off in bytes into `out`
+   (the frame's uint8 [H, W, 3]). */
+typedef struct {
+  int64_t H, W, sampling;
+  int64_t coeff_off[3], qslot[3], plane_off[3];
+  int64_t out_off;
+  int64_t reserved[3];
+} tt_jpeg_frame;
+/* The workspace the table's plane offsets need (0: a row is not a frame).  Pure host function. */
+size_t tt_jpeg_decode_batch_workspace_bytes(const tt_jpeg_frame* frame_table, int n_frames);
+/* Decodes n_frames frames, which may differ in size and sampling, in two launches.  frame_table is the HOST copy of the table and is
+   checked in full - every offset and extent against n_coeffs, n_qtables, out_bytes and workspace_bytes - before anything is launched
+   (TT_EINVAL, no launch); frame_table_dev is the same table in device memory, which the kernels read and trust.  coeffs and qtables are
+   device pointers, 16-byte aligned.  Allocates nothing. */
+int tt_jpeg_decode_batch(const int16_t* coeffs, long long n_coeffs, const uint16_t* qtables, int n_qtables, const tt_jpeg_frame* frame_table,
+                         const tt_jpeg_frame* frame_table_dev, int n_frames, uint8_t* out, long long out_bytes, void* workspace,
+                         size_t workspace_bytes, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -207,6 +207,10 @@ SIGNATURES = {
     "tt_flow_gray_u8": (c_i, [c_vp, c_vp, c_i, c_i, c_i, c_vp]),
     "tt_farneback_flow": (c_i, [c_vp, c_i, c_i, c_i, c_vp, c_i, c_d, c_i, c_i, c_i, c_i, c_d, c_i, c_vp, c_vp, c_sz, c_vp]),
     "tt_remap_nearest_labels": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_f, c_i, c_vp]),
+    "tt_jpeg_probe": (c_i, [c_vp, c_sz, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_ll)]),
+    "tt_jpeg_scan": (c_i, [c_vp, c_sz, c_vp, c_ll, c_vp]),
+    "tt_jpeg_decode_batch_workspace_bytes": (c_sz, [c_vp, c_i]),
+    "tt_jpeg_decode_batch": (c_i, [c_vp, c_ll, c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_ll, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

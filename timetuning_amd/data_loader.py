@@ -1,0 +1,312 @@
+"""The reference's ``VideoDataset`` over directories of frames (``data_loader.py:543-767``) with the decode on the device (N21).
+
+A dataset is a frames root ``<root>/<video>/*.jpg`` and an optional annotations root ``<root>/<video>/*.png``.  The two video lists are
+sorted and paired by position (``:575-577, 746-752``); inside a video the files are the sorted ``*.jpg``, else the sorted ``*.png``
+(``read_clips``, ``:595-599``); ``generate_indices`` makes the reference's ``random`` calls in the reference's order (``:617-642``), so a
+run seeded like the reference picks the reference's frames.  ``__getitem__`` returns ``(data, annotations, label)``, and ``read_batch``
+ends with the ``(255 * a).uint8`` conversion (``video_transformations.annotations_to_uint8``).
+
+What differs, on purpose:
+* JPEG frames are entropy-decoded on the host (``hip_ops.jpeg_scan_batch``: a thread pool over ``tt_jpeg_scan``) and reconstructed on the
+  device (``tt_jpeg_decode_batch``), bit-equal to ``Image.open``; the clip a transform receives is ``uint8 [fs, H, W, 3]`` in GPU memory.
+  A file ``hip_ops.jpeg_probe`` reports as unsupported (progressive, grayscale, CMYK, ...) - or a frame that is not a JPEG at all - is
+  decoded with Pillow on the host and uploaded, and COUNTED (``fallback_frames``).  A supported file that fails to decode raises: the
+  fallback never hides a decoder failure.
+* Annotation PNGs (mode ``P`` / ``L`` -> indices) are decoded with Pillow on the host and uploaded as ``uint8 [fs, H, W]``: they are small
+  and carry no arithmetic.
+* A video's length is the number of its frame files (the reference counts every directory entry, ``:590-592``); its label is its position
+  in the sorted list (the reference: its position in ``os.listdir``'s arbitrary order).
+* ``frame_transformation`` errors raise (the reference prints "Error in frame transformation" and goes on with the untransformed clip).
+Not reproduced (out of scope): the extraction of video files with cv2 and the ``mkdir`` / ``remove`` it performs (``:509-540``), the
+hard-coded per-host dataset roots, the ``meta.json`` category mapping of ``YVOSDataset``, ``Kinetics`` and the Pascal VOC readers.
+
+``ClipLoader`` stands in for ``make_loader``'s ``DataLoader`` + ``DistributedSampler`` (``:1047-1110``).
+"""
+from __future__ import annotations
+
+import glob
+import io
+import os
+import random
+from concurrent.futures import ThreadPoolExecutor
+from enum import Enum
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import hip_ops as ops
+from . import video_transformations as VT
+
+
+class SamplingMode(Enum):
+    UNIFORM = 0
+    DENSE = 1
+    Full = 2
+    Regular = 3
+
+
+def generate_indices(size: int, sampling_num: int, sampling_mode: SamplingMode, num_clips: int = 1, regular_step: int = 1, rng=random) -> list:
+    """``VideoDataset.generate_indices`` (``data_loader.py:617-642``): the same calls on ``rng`` (the ``random`` module or a
+    ``random.Random``) in the same order, the same lists / ranges back."""
+    indices = []
+    for _ in range(num_clips):
+        if sampling_mode == SamplingMode.UNIFORM:
+            if size < sampling_num:
+                idx = rng.choices(range(0, size), k=sampling_num)   # sample repeatedly
+            else:
+                idx = rng.sample(range(0, size), sampling_num)
+            idx.sort()
+            indices.append(idx)
+        elif sampling_mode == SamplingMode.DENSE:
+            base = rng.randint(0, size - sampling_num)
+            indices.append(range(base, base + sampling_num))
+        elif sampling_mode == SamplingMode.Full:
+            indices.append(range(0, size))
+        elif sampling_mode == SamplingMode.Regular:
+            step = size // sampling_num if size < sampling_num * regular_step else regular_step
+            base = rng.randint(0, size - (sampling_num * step))
+            indices.append(range(base, base + (sampling_num * step), step))
+    return indices
+
+
+def list_videos(root: str) -> List[str]:
+    """The video directories of a root, sorted."""
+    return sorted(os.path.join(root, d) for d in os.listdir(root) if os.path.isdir(os.path.join(root, d)))
+
+
+def list_frames(path: str) -> List[str]:
+    """``read_clips``' file order: the sorted ``*.jpg``, else the sorted ``*.png``."""
+    files = sorted(glob.glob(os.path.join(path, "*.jpg")))
+    if len(files) == 0:
+        files = sorted(glob.glob(os.path.join(path, "*.png")))
+    return files
+
+
+def decode_annotation(data: bytes) -> np.ndarray:
+    """A mode ``P`` / ``L`` image -> its indices, uint8 [H, W]."""
+    from PIL import Image
+
+    im = Image.open(io.BytesIO(data))
+    if im.mode not in ("P", "L"):
+        raise ValueError(f"annotation image of mode {im.mode}: expected a palette (P) or gray (L) label map")
+    return np.asarray(im, np.uint8)
+
+
+def decode_frame_on_host(data: bytes) -> np.ndarray:
+    """The counted fallback: Pillow's decode, uint8 [H, W, 3]."""
+    from PIL import Image
+
+    return np.array(Image.open(io.BytesIO(data)).convert("RGB"), np.uint8)   # (a writable copy)
+
+
+def _read(path: str) -> bytes:
+    with open(path, "rb") as f:
+        return f.read()
+
+
+class _HostSample:
+    """One video's clips as the host leaves them: the frame files' bytes and the decoded annotation maps, per clip."""
+
+    def __init__(self, frames, annotations, label):
+        self.frames, self.annotations, self.label = frames, annotations, label
+
+
+class _HostBatch:
+    def __init__(self, samples, scanned, device_slots, host_frames):
+        self.samples, self.scanned, self.device_slots, self.host_frames = samples, scanned, device_slots, host_frames
+
+
+class VideoDataset:
+    """``VideoDataset(classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, ...)`` (``:552``).  ``rng`` draws the
+    frame indices (default: the ``random`` module, as in the reference); ``device`` and ``threads`` belong to the decode."""
+
+    def __init__(self, classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, num_labels=1, frame_transform=None,
+                 target_transform=None, video_transform=None, meta_file_directory=None, regular_step=1, device=None, threads=8, rng=None):
+        if num_labels != 1:
+            raise NotImplementedError("nested class directories (num_labels > 1) are not reproduced")
+        if meta_file_directory is not None:
+            raise NotImplementedError("the meta.json category mapping is out of scope")
+        self.keys = list_videos(classes_directory)
+        if len(self.keys) == 0:
+            raise FileNotFoundError(f"no video directories under {classes_directory}")
+        self.train_dict = {k: np.array([i]) for i, k in enumerate(self.keys)}
+        self.files = {k: list_frames(k) for k in self.keys}
+        self.train_dict_lenghts = {k: len(v) for k, v in self.files.items()}
+        if annotations_directory and os.path.exists(annotations_directory):
+            self.annotation_keys = list_videos(annotations_directory)
+            if len(self.annotation_keys) != len(self.keys):
+                raise ValueError(f"{len(self.keys)} videos but {len(self.annotation_keys)} annotation directories: they are paired by position")
+            self.annotation_files = {k: list_frames(k) for k in self.annotation_keys}
+            self.use_annotations = True
+        else:
+            self.use_annotations = False
+        self.sampling_mode, self.num_clips, self.num_frames, self.regular_step = sampling_mode, num_clips, num_frames, regular_step
+        self.frame_transform, self.target_transform, self.video_transform = frame_transform, target_transform, video_transform
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None and torch.cuda.is_available() else device
+        self.threads = int(threads)
+        self.rng = random if rng is None else rng
+        self.fallback_frames = 0
+
+    def __len__(self):
+        return len(self.keys)
+
+    def generate_indices(self, size, sampling_num, rng=None):
+        return generate_indices(size, sampling_num, self.sampling_mode, self.num_clips, self.regular_step, self.rng if rng is None else rng)
+
+    # ---- host half: index draws, file reads, annotation decode (no GPU call: a background thread may run it)
+    def read_host(self, idx: int, rng=None) -> _HostSample:
+        path = self.keys[idx]
+        clip_indices = self.generate_indices(self.train_dict_lenghts[path], self.num_frames, rng)
+        files = self.files[path]
+        frames = [[_read(files[j]) for j in clip] for clip in clip_indices]
+        annotations = None
+        if self.use_annotations:
+            afiles = self.annotation_files[self.annotation_keys[idx]]
+            annotations = [np.stack([decode_annotation(_read(afiles[j])) for j in clip]) for clip in clip_indices]
+        return _HostSample(frames, annotations, np.tile(self.train_dict[path], (self.num_clips,)))
+
+    def scan_host(self, samples: List[_HostSample]) -> _HostBatch:
+        """Classifies every frame of the samples, entropy-decodes the supported ones into one pinned buffer and decodes the others with
+        Pillow."""
+        flat = [f for s in samples for clip in s.frames for f in clip]
+        device_slots, host_frames, supported = [], {}, []
+        for k, data in enumerate(flat):
+            if data[:2] == b"\xff\xd8" and ops.jpeg_probe(data).supported:   # a broken JPEG raises here
+                device_slots.append(k)
+                supported.append(data)
+            else:
+                host_frames[k] = decode_frame_on_host(data)
+        scanned = ops.jpeg_scan_batch(supported, self.threads) if supported else None
+        return _HostBatch(samples, scanned, device_slots, host_frames)
+
+    # ---- device half: reconstruction, transforms
+    def finish(self, batch: _HostBatch):
+        """-> per sample (data, annotations, label) as ``__getitem__`` returns them."""
+        flat = [None] * (len(batch.device_slots) + len(batch.host_frames))
+        if batch.scanned is not None:
+            for k, f in zip(batch.device_slots, ops.jpeg_decode_scanned(batch.scanned, self.device)):
+                flat[k] = f
+        for k, arr in batch.host_frames.items():
+            flat[k] = torch.from_numpy(arr).to(self.device)
+        self.fallback_frames += len(batch.host_frames)
+        out, at = [], 0
+        for s in batch.samples:
+            clips = []
+            for clip in s.frames:
+                clips.append(ops.frames_as_clip(flat[at:at + len(clip)]))
+                at += len(clip)
+            ann = None if s.annotations is None else [torch.from_numpy(a).to(self.device) for a in s.annotations]
+            out.append(self._transform(clips, ann) + (torch.Tensor(s.label),))
+        return out
+
+    def _transform(self, clips, annotations):
+        """``read_batch`` behind the file reads (``:653-680``)."""
+        anns = [] if annotations is None else list(annotations)
+        if anns and self.target_transform is not None:
+            anns = [self.target_transform(a) for a in anns]
+        if self.frame_transform is not None:
+            clips = [self.frame_transform(c) for c in clips]
+        if self.video_transform is not None:
+            for i in range(len(clips)):
+                if anns:
+                    clips[i], anns[i] = self.video_transform(clips[i], anns[i])
+                else:
+                    clips[i] = self.video_transform(clips[i])
+        data = torch.stack(clips)
+        if anns:
+            stacked = torch.stack(anns)
+            sampled = VT.annotations_to_uint8(stacked) if stacked.is_floating_point() else stacked
+        else:
+            sampled = torch.empty(0)
+        return data, sampled
+
+    def __getitem__(self, idx):
+        """(data [num_clips, fs, 3, R, R], annotations uint8 [num_clips, fs, R, R] or an empty tensor, label [num_clips])."""
+        return self.finish(self.scan_host([self.read_host(idx)]))[0]
+
+
+class ClipLoader:
+    """``make_loader``'s ``DataLoader`` (+ ``DistributedSampler`` when ``world_size`` > 1): yields ``(data [bs, num_clips, fs, 3, R, R] float32,
+    annotations, label)`` on the device.  Per batch: the files' bytes are read and all ``bs * num_clips * fs`` frames entropy-decoded in the
+    thread pool, ONE ``tt_jpeg_decode_batch`` call reconstructs them, and the GPU transforms run per clip.  A background thread prepares
+    the host half of batch i + 1 while the caller works on batch i; it draws the frame indices from the loader's own ``random.Random``
+    (``seed``), so the transforms' draws from the ``random`` module on the caller's thread are not disturbed.  The last batch may be short
+    (``drop_last=False``, the DataLoader default)."""
+
+    def __init__(self, dataset: VideoDataset, batch_size: int, shuffle: bool = False, world_size: int = 1, rank: int = 0, seed: int = 0,
+                 prefetch: bool = True):
+        self.dataset, self.batch_size, self.shuffle, self.world_size, self.rank, self.seed = dataset, int(batch_size), shuffle, world_size, rank, seed
+        self.prefetch, self.epoch = prefetch, 0
+        self.rng = random.Random(seed * 1000003 + rank)
+
+    @property
+    def fallback_frames(self) -> int:
+        return self.dataset.fallback_frames
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+
+    def _order(self) -> List[int]:
+        n = len(self.dataset)
+        if self.shuffle:
+            g = torch.Generator()
+            g.manual_seed(self.seed + self.epoch)
+            order = torch.randperm(n, generator=g).tolist()
+        else:
+            order = list(range(n))
+        if self.world_size > 1:   # DistributedSampler: pad to a multiple of world_size with the head of the list, then every world_size-th
+            total = -(-n // self.world_size) * self.world_size
+            order = (order * (total // n + 1))[:total]
+            order = order[self.rank:total:self.world_size]
+        return order
+
+    def __len__(self):
+        n = len(self.dataset)
+        local = -(-n // self.world_size) if self.world_size > 1 else n
+        return -(-local // self.batch_size)
+
+    def _host(self, indices) -> _HostBatch:
+        dev = self.dataset.device
+        if dev is not None and torch.device(dev).type == "cuda":
+            with torch.cuda.device(dev):   # a new thread starts on device 0: the pinned buffers belong to this rank's device
+                return self.dataset.scan_host([self.dataset.read_host(i, self.rng) for i in indices])
+        return self.dataset.scan_host([self.dataset.read_host(i, self.rng) for i in indices])
+
+    def __iter__(self):
+        order = self._order()
+        batches = [order[i:i + self.batch_size] for i in range(0, len(order), self.batch_size)]
+        if not batches:
+            return
+        pool = ThreadPoolExecutor(1) if self.prefetch else None
+        try:
+            pending = pool.submit(self._host, batches[0]) if pool else None
+            for k in range(len(batches)):
+                host = pending.result() if pool else self._host(batches[k])
+                if pool and k + 1 < len(batches):
+                    pending = pool.submit(self._host, batches[k + 1])
+                items = self.dataset.finish(host)
+                data = torch.stack([d for d, _, _ in items])
+                annotations = torch.stack([a for _, a, _ in items])
+                label = torch.stack([l for _, _, l in items])
+                yield data, annotations, label
+        finally:
+            if pool:
+                pool.shutdown(wait=True)
+
+
+def make_loader(dataset_path: str, num_clip_frames: int, batch_size: int, regular_step: int = 1, sampling_mode: SamplingMode = SamplingMode.UNIFORM,
+                frame_transform=None, target_transform=None, video_transform=None, shuffle: bool = False, num_workers: int = 6, world_size: int = 1,
+                rank: int = 0, device=None, seed: int = 0) -> ClipLoader:
+    """``make_loader`` (``:1047``) for the layout every ``VideoDataset`` branch of it reads: frames under ``<dataset_path>/JPEGImages/``,
+    annotations under ``<dataset_path>/Annotations/`` when present.  ``num_workers`` is the thread count of the host decode (at most 16
+    are used)."""
+    frames = os.path.join(dataset_path, "JPEGImages")
+    if not os.path.isdir(frames):
+        # (the reference maps a dataset NAME to a hard-coded root and a layout of its own per name, :1055-1104: not reproduced)
+        raise NotImplementedError(f"dataset readers: only the layout <dataset_path>/JPEGImages/<video>/*.jpg (+ <dataset_path>/Annotations/"
+                                  f"<video>/*.png) is read, and {frames} is not a directory; point --dataset_path at such a tree, or run "
+                                  "with --dataset synthetic / synthetic_frames")
+    dataset = VideoDataset(frames, os.path.join(dataset_path, "Annotations"), sampling_mode, 1, num_clip_frames, 1, frame_transform,
+                           target_transform, video_transform, regular_step=regular_step, device=device, threads=num_workers)
+    return ClipLoader(dataset, batch_size, shuffle=shuffle, world_size=world_size, rank=rank, seed=seed)

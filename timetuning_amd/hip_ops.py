@@ -2381,3 +2381,210 @@ def remap_nearest_labels(first, flows, scale: float = 1.0):
     _lib.check(lib.tt_remap_nearest_labels(_p(first), _p(flows), _p(out), N, steps, H, W, float(scale), first.element_size(), _stream()),
                "tt_remap_nearest_labels")
     return out
+
+
+# ---- N21: JPEG frames.  The host half (tt_jpeg_probe / tt_jpeg_scan: markers and Huffman codes, pure host functions that ctypes runs
+# without the GIL) in a thread pool, the arithmetic half (tt_jpeg_decode_batch) in two launches for the whole batch.
+JPEG_MAX_THREADS = 16
+JPEG_UNSUPPORTED = {1: "progressive, lossless or hierarchical frame", 2: "arithmetic coding", 3: "not three components", 4: "12-bit samples",
+                    5: "sampling factors other than 4:4:4 / 4:2:2 / 4:2:0", 6: "more than one scan", 7: "16-bit quantisation tables",
+                    8: "RGB stored without a colour transform"}
+JPEG_MALFORMED = {-1: "broken markers, segment lengths or tables", -2: "the scan data ends early", -3: "a Huffman code no table holds",
+                  -4: "a run past coefficient 63", -5: "a missing or misnumbered restart marker", -6: "bad argument"}
+_JPEG_ROW = 16     # int64 words of one tt_jpeg_frame
+
+
+class JpegUnsupported(Exception):
+    """A well-formed JPEG file the device decoder does not take (``status`` > 0: TT_JPEG_UNSUPPORTED_*).  hip_ops has no CPU fallback;
+    data_loader decodes such a file with Pillow and counts it."""
+
+    def __init__(self, status: int, index: Optional[int] = None):
+        self.status, self.index = int(status), index
+        where = "" if index is None else f"file {index}: "
+        super().__init__(f"{where}unsupported JPEG ({JPEG_UNSUPPORTED.get(int(status), status)})")
+
+
+class JpegInfo:
+    """What ``jpeg_probe`` found: ``status`` 0 = the device decoder takes the file (then H, W, ``sampling`` 0 / 1 / 2 = 4:4:4 / 4:2:2 /
+    4:2:0 and the number of int16 coefficients are set), > 0 = unsupported."""
+
+    def __init__(self, status, H, W, sampling, n_coeffs):
+        self.status, self.H, self.W, self.sampling, self.n_coeffs = status, H, W, sampling, n_coeffs
+
+    @property
+    def supported(self) -> bool:
+        return self.status == 0
+
+    def __repr__(self):
+        return f"JpegInfo(status={self.status}, H={self.H}, W={self.W}, sampling={self.sampling}, n_coeffs={self.n_coeffs})"
+
+
+def _jpeg_malformed(status: int, index: Optional[int] = None) -> ValueError:
+    where = "" if index is None else f"file {index}: "
+    return ValueError(f"{where}malformed JPEG (status {status}: {JPEG_MALFORMED.get(int(status), 'unknown')})")
+
+
+def _jpeg_probe_raw(lib, data: bytes) -> JpegInfo:
+    H, W, samp, n = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+    rc = lib.tt_jpeg_probe(data, len(data), C.byref(H), C.byref(W), C.byref(samp), C.byref(n))
+    return JpegInfo(rc, H.value, W.value, samp.value, n.value)
+
+
+def jpeg_probe(data: bytes) -> JpegInfo:
+    """Classifies a JPEG file without decoding it.  A broken file raises ValueError; an unsupported one is a JpegInfo with status > 0."""
+    info = _jpeg_probe_raw(_lib.load(), bytes(data))
+    if info.status < 0:
+        raise _jpeg_malformed(info.status)
+    return info
+
+
+def jpeg_scan(data: bytes):
+    """Host only: (JpegInfo, coefficients int16 [n_coeffs], quantisation tables uint16 [3, 64]) of one supported file - the entropy layer
+    alone, for tests and tools.  Raises ValueError (broken file) or JpegUnsupported."""
+    lib = _lib.load()
+    data = bytes(data)
+    info = jpeg_probe(data)
+    if not info.supported:
+        raise JpegUnsupported(info.status)
+    coeffs, q = np.empty(info.n_coeffs, np.int16), np.empty((3, 64), np.uint16)
+    rc = lib.tt_jpeg_scan(data, len(data), coeffs.ctypes.data, coeffs.size, q.ctypes.data)
+    if rc < 0:
+        raise _jpeg_malformed(rc)
+    if rc > 0:
+        raise JpegUnsupported(rc)
+    return info, coeffs, q
+
+
+def _jpeg_grid(H: int, W: int, sampling: int, comp: int):
+    hmax, vmax = (1 if sampling == 0 else 2), (2 if sampling == 2 else 1)
+    mx, my = -(-W // (8 * hmax)), -(-H // (8 * vmax))
+    return (my * vmax, mx * hmax) if comp == 0 else (my, mx)
+
+
+class JpegHostBatch:
+    """The host half of a batch, ready for the device: pinned coefficients, pinned table + quantisation tables, and the output layout."""
+
+    def __init__(self, infos, coeffs, meta, n_coeffs, out_bytes, groups, where):
+        self.infos, self.coeffs, self.meta, self.n_coeffs, self.out_bytes, self.groups, self.where = infos, coeffs, meta, n_coeffs, out_bytes, groups, where
+
+
+_JPEG_POOLS: dict = {}
+
+
+def _jpeg_pool(workers: int):
+    """One thread pool per size, kept: starting 16 threads per batch costs as much as scanning a dozen frames."""
+    pool = _JPEG_POOLS.get(workers)
+    if pool is None:
+        from concurrent.futures import ThreadPoolExecutor
+
+        pool = _JPEG_POOLS[workers] = ThreadPoolExecutor(workers, thread_name_prefix="tt_jpeg")
+    return pool
+
+
+def jpeg_scan_batch(files: Sequence[bytes], threads: int = 8, pin: bool = True) -> JpegHostBatch:
+    """Probes and entropy-decodes every file in a pool of min(threads, 16) threads into ONE (pinned) coefficient buffer and builds the
+    descriptor table.  Raises JpegUnsupported for the first unsupported file and ValueError for the first broken one.  The pinned
+    buffers come from torch's caching host allocator: a steady stream of batches allocates nothing after the first."""
+    lib = _lib.load()
+    files = [bytes(f) for f in files]
+    n = len(files)
+    if n == 0:
+        raise ValueError("jpeg_scan_batch: no files")
+    workers = max(1, min(int(threads), JPEG_MAX_THREADS, n))
+    chunks = [range(k * n // workers, (k + 1) * n // workers) for k in range(workers)]   # one task per thread, not per file
+    run = (lambda fn: [fn(c) for c in chunks]) if workers == 1 else (lambda fn: list(_jpeg_pool(workers).map(fn, chunks)))
+
+    def probe(chunk):
+        return [_jpeg_probe_raw(lib, files[i]) for i in chunk]
+
+    infos = [info for part in run(probe) for info in part]
+    for i, info in enumerate(infos):
+        if info.status < 0:
+            raise _jpeg_malformed(info.status, i)
+        if not info.supported:
+            raise JpegUnsupported(info.status, i)
+    coeff_off = np.zeros(n + 1, np.int64)
+    np.cumsum([info.n_coeffs for info in infos], out=coeff_off[1:])
+    total = int(coeff_off[-1])
+    coeffs = torch.empty(total, dtype=torch.int16, pin_memory=pin)
+    meta = torch.zeros(n * (_JPEG_ROW * 8 + 3 * 64 * 2), dtype=torch.uint8, pin_memory=pin)    # the table, then the quantisation tables: one copy
+    table = meta.numpy()[:n * _JPEG_ROW * 8].view(np.int64).reshape(n, _JPEG_ROW)
+    q_base = meta.data_ptr() + n * _JPEG_ROW * 8
+    c_base = coeffs.data_ptr()
+
+    def scan(chunk):
+        return [lib.tt_jpeg_scan(files[i], len(files[i]), c_base + 2 * int(coeff_off[i]), infos[i].n_coeffs, q_base + i * 3 * 64 * 2) for i in chunk]
+
+    status = [rc for part in run(scan) for rc in part]
+    for i, rc in enumerate(status):
+        if rc < 0:
+            raise _jpeg_malformed(rc, i)
+        if rc > 0:
+            raise JpegUnsupported(rc, i)
+    # output layout: the frames of one size lie one after the other, so that they are views of one [k, H, W, 3] tensor
+    groups, where = {}, []
+    for i, info in enumerate(infos):
+        members = groups.setdefault((info.H, info.W), [])
+        where.append(((info.H, info.W), len(members)))
+        members.append(i)
+    out_bytes, group_base, plane_at = 0, {}, 0
+    for key, members in groups.items():
+        group_base[key] = out_bytes
+        out_bytes += -(-len(members) * key[0] * key[1] * 3 // 16) * 16
+    for i, info in enumerate(infos):
+        row = table[i]
+        row[0], row[1], row[2] = info.H, info.W, info.sampling
+        at = int(coeff_off[i])
+        for c in range(3):
+            rows, cols = _jpeg_grid(info.H, info.W, info.sampling, c)
+            row[3 + c], row[6 + c], row[9 + c] = at, 3 * i + c, plane_at
+            at += rows * cols * 64
+            plane_at += rows * cols * 64
+        key, k = where[i]
+        row[12] = group_base[key] + k * info.H * info.W * 3
+    return JpegHostBatch(infos, coeffs, meta, total, out_bytes, {k: (group_base[k], len(m)) for k, m in groups.items()}, where)
+
+
+def jpeg_decode_scanned(batch: JpegHostBatch, device=None):
+    """The device half: one host-to-device copy of the coefficients, one of the table and the quantisation tables, two launches on the
+    current stream.  Returns the frames as uint8 [H, W, 3] tensors in the order of the files; frames of one size are consecutive views
+    of one [k, H, W, 3] tensor (``frames_as_clip`` returns it without a copy)."""
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise _lib.HipLibraryError("decode_jpeg_batch: needs a GPU (the HIP path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    n = len(batch.infos)
+    table = batch.meta.numpy()[:n * _JPEG_ROW * 8]
+    ws_bytes = int(lib.tt_jpeg_decode_batch_workspace_bytes(table.ctypes.data, n))
+    if ws_bytes == 0:
+        raise ValueError("decode_jpeg_batch: the descriptor table holds a row that is not a frame")
+    with torch.cuda.device(dev):
+        coeffs = batch.coeffs.to(dev, non_blocking=True)
+        meta = batch.meta.to(dev, non_blocking=True)
+        out = torch.empty(max(batch.out_bytes, 16), dtype=torch.uint8, device=dev)
+        ws = _ws(ws_bytes, dev)
+        _lib.check(lib.tt_jpeg_decode_batch(_p(coeffs), batch.n_coeffs, meta.data_ptr() + n * _JPEG_ROW * 8, 3 * n, table.ctypes.data,
+                                            _p(meta), n, _p(out), out.numel(), _p(ws), ws.numel(), _stream()), "tt_jpeg_decode_batch")
+    stacks = {key: out[base:base + k * key[0] * key[1] * 3].view(k, key[0], key[1], 3) for key, (base, k) in batch.groups.items()}
+    return [stacks[key][k] for key, k in batch.where]
+
+
+def decode_jpeg_batch(files: Sequence[bytes], device=None, threads: int = 8):
+    """JPEG files -> uint8 [H, W, 3] GPU tensors, bit-equal to Pillow's decode.  The frames may differ in size and sampling; those of one
+    size come back as views of one [k, H, W, 3] tensor.  Unsupported files raise JpegUnsupported (no CPU fallback here), broken ones
+    ValueError."""
+    return jpeg_decode_scanned(jpeg_scan_batch(files, threads), device)
+
+
+def frames_as_clip(frames: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Frames of one size -> [k, H, W, 3]: the tensor they are consecutive views of where they are (``decode_jpeg_batch``), a stacked
+    copy otherwise."""
+    f0 = frames[0]
+    step = f0.numel()
+    same = all(f.shape == f0.shape and f.dtype == f0.dtype and f.is_contiguous() and f.device == f0.device and
+               f.untyped_storage().data_ptr() == f0.untyped_storage().data_ptr() and
+               f.storage_offset() == f0.storage_offset() + i * step for i, f in enumerate(frames))
+    if not same:
+        return torch.stack(list(frames))
+    H, W, ch = f0.shape
+    return f0.as_strided((len(frames), H, W, ch), (step, W * ch, ch, 1), f0.storage_offset())

@@ -4,7 +4,8 @@
 ``propagate_clip`` is the per-clip body of the evaluation loop (``:821-831``: extractor without head ->
 ``propagate_labels`` -> bilinear upsampling -> arg-max) and ``jaccard`` scores the propagated masks.  The evaluation
 driver reproduces the reference's flag set (``:849-871``, DAVIS protocol defaults ``--n_last_frames 4
---size_mask_neighborhood 12 --topk 5``); dataset readers are out of scope, so it runs on synthetic clips.
+--size_mask_neighborhood 12 --topk 5``); ``--dataset synthetic`` / ``synthetic_frames`` run on generated clips, any other name on
+the frames under ``--dataset_path`` (data_loader.py).
 
 Labels propagate on the frames' own token grid (H / P, W / P), so rectangular clips run at native size (``--frame_size H W``), and
 ``--size_mask_neighborhood 0`` is the unrestricted variant (``:422``).  Shapes the square entry accepts (``square_entry_accepts``) go to
@@ -461,8 +462,7 @@ def synthetic_davis_labels(T: int, H: int, W: int, num_objects: int, seed: int):
 
 def build_parser() -> argparse.ArgumentParser:
     """Flag names and defaults of ``mask_propagation.py:849-871`` (``type=bool`` flags keep the any-non-empty-string-is-True
-    quirk).  ``--dataset synthetic`` / ``synthetic_frames``, ``--raw_size``, ``--num_clips`` and ``--davis_metrics`` are additions: the
-    dataset readers are out of scope."""
+    quirk).  ``--dataset synthetic`` / ``synthetic_frames``, ``--raw_size``, ``--num_clips`` and ``--davis_metrics`` are additions."""
     p = argparse.ArgumentParser()
     p.add_argument("--architecture", type=str, default="dino-s16")
     p.add_argument("--model_path", type=str, default="../models/leopart_vits16.ckpt")
@@ -569,22 +569,34 @@ _FLOW_FRAME_MULTIPLE = 8
 
 
 def mask_propagation(args) -> float:
-    """The evaluation loop of ``mask_propagation.py:757-846`` on synthetic clips; returns the mean J over clips.  ``--dataset
-    synthetic`` renders normalised clips at the model's size; ``--dataset synthetic_frames`` renders raw uint8 frames with label maps at
-    ``--raw_size`` and takes them through the reference's pair transform first (``synthetic_frames_clip``).  With
+    """The evaluation loop of ``mask_propagation.py:757-846``; returns the mean J over clips.  ``--dataset synthetic`` renders normalised
+    clips at the model's size; ``--dataset synthetic_frames`` renders raw uint8 frames with label maps at ``--raw_size`` and takes them
+    through the reference's pair transform first (``synthetic_frames_clip``); any other name reads ``--dataset_path``
+    (``data_loader.make_loader``: JPEGImages/ and Annotations/, ``propagation_transforms``, ``SamplingMode.DENSE``, ``--num_frames``, batch 1,
+    one clip per video; the first frame's annotation is the seed).  With
     ``--davis_metrics`` it also prints the DAVIS statistics (``db_statistics`` over each object's frames) per clip and over all
     objects of all clips; the return value is the same.  ``--use_optical_flow`` runs the optical-flow baseline
     (``propagate_clip_optical_flow``) on the same clips, with the same scoring, and builds no backbone.  Both branches score predicted
     frame j against annotated frame j; the reference compares ``predictions[:, 1:]`` with ``annotations[:, 1:]``, one frame off."""
-    if args.dataset not in ("synthetic", "synthetic_frames"):
-        raise NotImplementedError("dataset readers (data_loader.py) are out of scope for this build; run with --dataset synthetic "
-                                  "or synthetic_frames")
     use_flow = bool(args.use_optical_flow)
     native = getattr(args, "frame_size", None) is not None
+    from_disk = args.dataset not in ("synthetic", "synthetic_frames")
     raw_frames = args.dataset == "synthetic_frames"
-    if raw_frames and native:
-        raise ValueError("--dataset synthetic_frames crops to --input_resolution as the reference's loader does; --frame_size does not apply")
+    if (raw_frames or from_disk) and native:
+        raise ValueError("--dataset synthetic_frames and the datasets on disk crop to --input_resolution as the reference's loader does; "
+                         "--frame_size does not apply")
     device = torch.device("cuda", 0)
+    disk_clips, disk_loader = None, None
+    if from_disk:   # <dataset_path>/JPEGImages + Annotations, decoded on the device (data_loader.py, N21); batch 1 (:775-790)
+        from . import data_loader as DL
+        from . import video_transformations as VT
+
+        disk_loader = DL.make_loader(args.dataset_path, args.num_frames, 1, 1, DL.SamplingMode.DENSE, frame_transform=None, target_transform=None,
+                                     video_transform=VT.propagation_transforms(args.input_resolution), shuffle=False,
+                                     num_workers=args.num_workers, device=device)
+        if not disk_loader.dataset.use_annotations:
+            raise FileNotFoundError(f"{args.dataset_path}/Annotations: the propagation evaluation needs the first frame's annotation")
+        disk_clips = iter(disk_loader)
     if use_flow:
         H, W = clip_size(args, _FLOW_FRAME_MULTIPLE)
         model = None
@@ -597,8 +609,11 @@ def mask_propagation(args) -> float:
         model = TimeT(fe, 200).to(device).eval()
     scores = []
     davis = []   # per object: (J_M, J_R, J_D, F_M, F_R, F_D)
-    for i in range(args.num_clips):
-        if raw_frames:
+    for i in range(len(disk_loader) if from_disk else args.num_clips):
+        if from_disk:
+            data, annotations, _ = next(disk_clips)
+            clip, masks = data[0, 0], annotations[0, 0].long()   # the first frame's annotation is the seed
+        elif raw_frames:
             clip, masks = synthetic_frames_clip(args, i, device)
         elif native:
             clip, masks = synthetic_tracking_clip(args.num_frames, H, seed=i + 1, width=W)
@@ -622,6 +637,8 @@ def mask_propagation(args) -> float:
             print(f"clip {i}: " + _davis_line(np.array(rows, np.float64)))
     mean = sum(scores) / len(scores)
     print(f"mean J over {len(scores)} clips: {mean:.4f}")
+    if from_disk:
+        print(f"frames decoded with Pillow on the host (files the device decoder does not take): {disk_loader.fallback_frames}")
     if davis:
         print(f"DAVIS over {len(davis)} objects of {len(scores)} clips: " + _davis_line(np.array(davis, np.float64)))
     return mean

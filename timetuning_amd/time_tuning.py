@@ -1034,8 +1034,8 @@ def build_parser() -> argparse.ArgumentParser:
     queue ON, as in the reference's README command); ``--epsilon --sinkhorn_iterations --n_last_frames --topk
     --size_mask_neighborhood --epochs --dataset_path --destination_path`` are parsed but never reach ``get_loss``,
     which uses its signature defaults (eps 0.05, 10 iterations, 7 frames, radius 6, top-5).
-    Added (not in the reference): ``--dataset synthetic`` / ``--steps_per_epoch`` / ``--eval_clips`` because the dataset
-    loaders are out of scope here, ``--eval_every`` (the reference hard-codes 4), ``--log_localization_every`` (the qualitative logs of
+    Added (not in the reference): ``--dataset synthetic`` / ``synthetic_frames`` / ``--steps_per_epoch`` / ``--eval_clips`` (generated
+    clips; the evaluation's Pascal VOC reader is out of scope), ``--eval_every`` (the reference hard-codes 4), ``--log_localization_every`` (the qualitative logs of
     :641-642, off by default), ``--unfreeze_layers`` (the reference hard-codes the two blocks, :574) and ``--precision`` (the arithmetic mode of the
     matrix products; the library-level default of ``hip_ops.set_gemm_precision`` stays "f32", the training driver's is "f16x3")."""
     p = argparse.ArgumentParser()
@@ -1203,8 +1203,10 @@ def seed_everything(seed: int = 1) -> None:
 
 def time_tuning(gpu=0, args=None):
     """One process per GPU (``time_tuning.py:508-666``): model, optimiser, epoch loop with the rank-0 evaluation every
-    ``--eval_every`` (reference: 4) epochs and the barrier behind it (:634-648).  Datasets are synthetic (the readers are out of
-    scope): training clips from the portable generator, evaluation frames with planted masks."""
+    ``--eval_every`` (reference: 4) epochs and the barrier behind it (:634-648).  ``--dataset synthetic`` / ``synthetic_frames`` train
+    on clips from the portable generator; any other name reads ``--dataset_path`` (``data_loader.make_loader``: JPEGImages/ and, when
+    present, Annotations/; ``training_transforms``, ``SamplingMode.Regular`` with ``--regular_step`` and ``--num_frames``, ``--num_workers``
+    host-decode threads).  The evaluation frames are synthetic, with planted masks (the Pascal VOC reader is out of scope)."""
     import torch.distributed as dist
 
     from .evaluation import Evaluator
@@ -1242,9 +1244,14 @@ def time_tuning(gpu=0, args=None):
         loader = SyntheticClips(args.batch_size, args.num_frames, args.input_resolution, args.steps_per_epoch, device, rank)
     elif args.dataset == "synthetic_frames":  # raw uint8 frames through the GPU input pipeline
         loader = SyntheticFrameClips(args.batch_size, args.num_frames, args.input_resolution, args.steps_per_epoch, device, rank)
-    else:
-        raise NotImplementedError("the dataset readers (data_loader.py: directory scanning, JPEG decoding) are out of scope for this "
-                                  "build; run with --dataset synthetic or --dataset synthetic_frames")
+    else:   # a dataset on disk: <dataset_path>/JPEGImages/<video>/*.jpg (+ Annotations/), decoded on the device (data_loader.py, N21)
+        from . import data_loader as DL
+        from . import video_transformations as VT
+
+        frame_transform, video_transform = VT.training_transforms(args.input_resolution)
+        loader = DL.make_loader(args.dataset_path, args.num_frames, args.batch_size, args.regular_step, DL.SamplingMode.Regular,
+                                frame_transform=frame_transform, target_transform=None, video_transform=video_transform, shuffle=True,
+                                num_workers=args.num_workers, world_size=world_size, rank=rank, device=device)
     num_itr = len(loader)
     opt = SwavOptimizer(model, "AdamW", args.use_projection_head, args.head_lr / 10, args.head_lr, args.lr_scheduler,
                         cosine_scheduler(0.04, 0.4, args.num_epochs, num_itr), num_itr, args.num_epochs)
@@ -1291,6 +1298,8 @@ def time_tuning(gpu=0, args=None):
         if world_size > 1:
             dist.barrier()                                                  # :647-648: the other ranks wait for rank 0
         model.train()
+        if hasattr(loader, "set_epoch"):
+            loader.set_epoch(epoch)
         for i, (data, annotations, label) in enumerate(loader):
             data = data.squeeze(1)
             if world_size > 1 and sk_exchange == "auto" and engine.EXCHANGE_CHOICE is None:
@@ -1308,6 +1317,9 @@ def time_tuning(gpu=0, args=None):
             if rank == 0:
                 print("Iteration: {}/{} loss {:.4f}".format(i, num_itr, loss.item()))
                 model.check_pair_range()   # the "f16x3" mode's range contract (the host has just synchronised for the loss)
+        if rank == 0 and hasattr(loader, "fallback_frames"):
+            print("Epoch: {} frames decoded with Pillow on the host so far (files the device decoder does not take): {}".format(
+                epoch, loader.fallback_frames))
     model.eval_scores = scores
     return model
 

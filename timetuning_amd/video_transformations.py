@@ -26,7 +26,7 @@ Reference quirks that are reproduced (and worth knowing):
 * ``RandomGrayscale`` draws from torch's generator, everything else from Python's ``random``.
 * ``CenterCrop`` rounds its origin with Python's round-half-even (``:596-597``).
 Not built: the numpy-array (cv2 / skimage) code paths, ``Normalize`` (its PIL branch returns nothing usable), bilinear resizing
-of annotation clips, and the dataset readers that decode the files.
+of annotation clips.  The files are read and decoded by ``data_loader.py``.
 """
 from __future__ import annotations
 
