@@ -1067,6 +1067,53 @@ int tt_jpeg_decode_batch(const int16_t* coeffs, long long n_coeffs, const uint16
                          const tt_jpeg_frame* frame_table_dev, int n_frames, uint8_t* out, long long out_bytes, void* workspace,
                          size_t workspace_bytes, tt_stream_t stream);
 
+/* ---- N22: ragged image kernels - the pixel work of the Pascal VOC reader (leoloader.py:241-264: Resize((S, S)) + ToTensor + Normalize of
+   the image, Resize((R, R), NEAREST) + ToTensor of the palette PNG) for a batch whose items DIFFER in size, one launch per batch; bit-equal
+   to Pillow like the tt_img_* entries above, whose arithmetic they share.
+   One row per item.  src_off: byte offset of the item's image in `in` - uint8 [H, W, 3] for the resize, [H, W] for the gather; ANY byte
+   value (a decoder's out_off, a packed buffer), no source read is wider than a byte.  (x0, y0, w, h): the crop box, inside the image.
+   flip: 0 / 1, the output row is written mirrored.  The *_off fields are offsets in int32 elements into one `pool`: hk_off / hb_off the
+   horizontal taps int32 [OW, hksize] and bounds int32 [OW, 2] (first column RELATIVE TO THE BOX and tap count, what
+   timetuning_amd.video_transformations.resample_coeffs(w, OW) builds), vk_off / vb_off / vksize the vertical ones for (h, OH); ytab_off /
+   xtab_off the gather's int32 [OH] / [OW] tables of ABSOLUTE source rows / columns (video_transformations.nearest_table with the crop offset
+   and the flip folded in; the gather does not look at the box beyond checking it, nor at flip).  Output item i is row i of the output. */
+typedef struct {
+  int64_t src_off, H, W;
+  int64_t x0, y0, w, h;
+  int64_t flip;
+  int64_t hk_off, hb_off, hksize;
+  int64_t vk_off, vb_off, vksize;
+  int64_t ytab_off, xtab_off;
+} tt_img_ragged_item;
+#define TT_IMG_RAGGED_BAND 16             /* output rows a workgroup of tt_img_resize_ragged owns */
+#define TT_IMG_RAGGED_LDS_BUDGET 65536    /* bytes of LDS per workgroup: two workgroups fit the 160 KiB of a CU */
+/* tt_img_resize_ragged   out[i] = crop(box_i).resize((OW, OH), BILINEAR) by Resample.c: 22-bit taps, uint8 rounding after the horizontal
+                          pass and again after the vertical pass; a pass with w == OW (h == OH) is the identity and its pool fields are not
+                          read.  Exactly one output: out_u8 [n, OH, OW, 3], or out_f32 [n, 3, OH, OW] = ((float)v / 255 - mean[c]) / std[c]
+                          with the arithmetic of tt_img_resample_v (mean3 / std3 HOST pointers to 3 floats).  A workgroup owns one item and
+                          a band of TT_IMG_RAGGED_BAND output rows; it runs the horizontal pass for the box rows min(bounds.ymin) ..
+                          max(bounds.ymin + cnt) of its band into LDS as uint8 [rows, OW, 3] and the vertical pass from there: the
+                          intermediate never reaches device memory.
+   tt_img_resize_ragged_lds_bytes   the largest band of an (h, w) box resized to (OH, OW) with Pillow's bounds, in bytes of LDS (0: a size
+                          outside 1 .. 32767); tt_img_resize_ragged_shape_ok: 1 when every size is inside 1 .. 32767 and that figure is within
+                          TT_IMG_RAGGED_LDS_BUDGET.  Pure host functions over one item's sizes, like tt_kmeans_fit_shape_ok.  Strong
+                          down-scaling of a wide image is what falls outside; the caller takes such an item through tt_img_resample_h / _v.
+   tt_img_gather_nearest_ragged   out[i, y, x] = in_i[ytab_i[y], xtab_i[x]] on label maps: out_u8 [n, OH, OW], or out_f32 [n, 1, OH, OW] =
+                          (float)v / 255 as one IEEE fp32 division (the C = 1 rule of tt_img_gather_nearest).
+   `items` and `pool` are the HOST copies and are checked in full before anything is launched - 1 <= n_items <= 65535, sizes and outputs in
+   1 .. 32767, every image inside in_bytes, every box inside its image, flip 0 / 1, every used pool range inside pool_len, every
+   bounds[...] >= 0 with cnt <= ksize and bounds + cnt inside the box's line, the LDS need of every band (from the vertical bounds handed
+   in) within the budget, every table entry inside its image: TT_EINVAL with a message naming the item, nothing launched.  items_dev /
+   pool_dev are the same data in device memory, which the kernels read and trust.  Both calls are one launch and allocate nothing. */
+size_t tt_img_resize_ragged_lds_bytes(int h, int w, int OH, int OW);
+int tt_img_resize_ragged_shape_ok(int h, int w, int OH, int OW);
+int tt_img_resize_ragged(const uint8_t* in, long long in_bytes, const tt_img_ragged_item* items, const tt_img_ragged_item* items_dev,
+                         int n_items, const int32_t* pool, const int32_t* pool_dev, long long pool_len, uint8_t* out_u8, float* out_f32,
+                         int OH, int OW, const float* mean3, const float* std3, tt_stream_t stream);
+int tt_img_gather_nearest_ragged(const uint8_t* in, long long in_bytes, const tt_img_ragged_item* items, const tt_img_ragged_item* items_dev,
+                                 int n_items, const int32_t* pool, const int32_t* pool_dev, long long pool_len, uint8_t* out_u8,
+                                 float* out_f32, int OH, int OW, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

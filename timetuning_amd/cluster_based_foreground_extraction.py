@@ -309,8 +309,8 @@ def synthetic_cluster_maps(M: int, R: int, k: int, seed: int, cell: int = 10):
 # ---- the driver (:281-373) --------------------------------------------------------------------------------------------------------
 
 def build_parser() -> argparse.ArgumentParser:
-    """The reference's flags with its defaults (:352-371).  ``--dataset synthetic`` and ``--num_*_images`` are additions: the
-    dataset readers are out of scope."""
+    """The reference's flags with its defaults (:352-371).  ``--dataset synthetic`` and ``--num_*_images`` are additions, and
+    so is ``--dataset voc``: ``leoloader.pascal_loader`` on ``--dataset_path`` (the VOCSegmentation root), as :340-341 call it."""
     p = argparse.ArgumentParser()
     p.add_argument("--architecture", type=str, default="dino-s16", help="which back-bone architecture do you want to use?")
     p.add_argument("--model_path", type=str, default="/home/ssalehi/video/dino/outputs/checkpoint0080.pth")
@@ -350,21 +350,30 @@ def main(args=None) -> float:
 
     if args is None or isinstance(args, (list, tuple)):
         args = build_parser().parse_args(args)
-    if args.dataset != "synthetic":
-        raise NotImplementedError("dataset readers are out of scope for this build; run with --dataset synthetic")
+    if args.dataset not in ("synthetic", "voc"):
+        raise NotImplementedError("this build reads Pascal VOC through --dataset voc (leoloader.pascal_loader on --dataset_path, the "
+                                  "VOCSegmentation root) and generated data through --dataset synthetic")
+    eval_resolution = 100 if args.evaluation_protocol == "dataset-wise" else args.input_resolution
+    if args.dataset == "voc":                                                            # :340-341
+        from .leoloader import pascal_loader
+
+        train_loader = pascal_loader(args.batch_size, args.dataset_path, "trainaug", eval_resolution, train_size=args.input_resolution)
+        val_loader = pascal_loader(args.batch_size, args.dataset_path, "val", eval_resolution, train_size=args.input_resolution)
+        eval_batches = val_loader
+    else:
+        x_tr, y_tr = synthetic_segmentation(args.num_train_images, args.input_resolution, 21, seed=1)
+        x_va, y_va = synthetic_segmentation(args.num_val_images, args.input_resolution, 21, seed=2)
+        train_loader = _batches(x_tr, y_tr, args.batch_size)
+        val_loader = _batches(x_va, y_va.clone(), args.batch_size)
+        eval_batches = _batches(x_va, y_va, args.batch_size)
     torch.cuda.set_device(0)
     feature_extractor = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], return_attention=True)
     model = TimeT(feature_extractor, 200).cuda()
-    eval_resolution = 100 if args.evaluation_protocol == "dataset-wise" else args.input_resolution
-    x_tr, y_tr = synthetic_segmentation(args.num_train_images, args.input_resolution, 21, seed=1)
-    x_va, y_va = synthetic_segmentation(args.num_val_images, args.input_resolution, 21, seed=2)
-    train_loader = _batches(x_tr, y_tr, args.batch_size)
-    val_loader = _batches(x_va, y_va.clone(), args.batch_size)
     cbfe = ClusterBasedForegroundExtraction(model, args.k_fg_extraction, eval_resolution, 50, train_loader, val_loader,
                                             bf_score=args.bf_score)
     set_soft_masks, set_annotations, _ = cbfe.get_foreground_masks("val")
     # the Evaluator reads integer labels: the val annotations as process_data_group made them
-    eval_loader = [(x[:, None], (y * 255).long()) for x, y in _batches(x_va, y_va, args.batch_size)]
+    eval_loader = [(x[:, None], (y * 255).long()) for x, y in eval_batches]
     evaluator = Evaluator(model, eval_loader, num_prototypes=21, fg_masks=set_soft_masks)
     score = evaluator.evaluate(many_to_one=args.many_to_one, evaluation_protocol=args.evaluation_protocol, eval_resolution=eval_resolution,
                                num_clusters=21, use_annotations=False, use_mask=True, precision_based=args.precision_based)

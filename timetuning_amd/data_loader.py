@@ -18,7 +18,7 @@ What differs, on purpose:
   in the sorted list (the reference: its position in ``os.listdir``'s arbitrary order).
 * ``frame_transformation`` errors raise (the reference prints "Error in frame transformation" and goes on with the untransformed clip).
 Not reproduced (out of scope): the extraction of video files with cv2 and the ``mkdir`` / ``remove`` it performs (``:509-540``), the
-hard-coded per-host dataset roots, the ``meta.json`` category mapping of ``YVOSDataset``, ``Kinetics`` and the Pascal VOC readers.
+hard-coded per-host dataset roots, the ``meta.json`` category mapping of ``YVOSDataset``, ``Kinetics`` and the SBD reader ``pascalVOCLoader`` (Pascal VOC is read by ``leoloader.py``).
 
 ``ClipLoader`` stands in for ``make_loader``'s ``DataLoader`` + ``DistributedSampler`` (``:1047-1110``).
 """

@@ -199,9 +199,10 @@ class Evaluator:
 
 def build_parser() -> argparse.ArgumentParser:
     """Flag names, types and defaults of ``evaluation.py:544-566``.  The ``type=bool`` flags treat ANY non-empty string as True, as in
-    the reference (and in ``time_tuning.build_parser``): ``--many_to_one False`` turns many-to-one matching ON.  ``--dataset_path``,
-    ``--destination_path`` and ``--num_workers`` are parsed and unused (the dataset readers are out of scope).  Added: ``--dataset
-    synthetic`` and ``--eval_clips``; an EMPTY ``--model_path`` selects synthetic weights; ``--log_videos`` (off by default: an evaluation
+    the reference (and in ``time_tuning.build_parser``): ``--many_to_one False`` turns many-to-one matching ON.  ``--destination_path``
+    and ``--num_workers`` are parsed and unused (the video dataset readers are out of scope).  Added: ``--dataset synthetic`` and
+    ``--eval_clips``; ``--dataset voc`` (``leoloader.pascal_loader`` on ``--dataset_path``, the VOCSegmentation root: the "for Pascal VOC"
+    line of ``:537``); an EMPTY ``--model_path`` selects synthetic weights; ``--log_videos`` (off by default: an evaluation
     writes no file unless asked) makes ``--logging_directory`` live - the frame-wise and sample-wise protocols then write the GIFs of the
     matched maps there (``evaluate_localizations``)."""
     p = argparse.ArgumentParser()
@@ -234,9 +235,15 @@ def main(argv=None, vit_cfg=None) -> float:
     from .time_tuning import SyntheticEvalClips, TimeT
 
     args = build_parser().parse_args(argv)
-    if args.dataset != "synthetic":
-        raise NotImplementedError("the dataset readers (data_loader.py: directory scanning, JPEG decoding) are out of scope for this "
-                                  "build; run with --dataset synthetic")
+    if args.dataset not in ("synthetic", "voc"):
+        raise NotImplementedError("the video dataset readers are out of scope for this build; run with --dataset voc (Pascal VOC through "
+                                  "leoloader.pascal_loader on --dataset_path, the VOCSegmentation root) or --dataset synthetic")
+    eval_resolution = 112 if args.evaluation_protocol == "dataset-wise" else args.input_resolution   # :536
+    voc_loader = None
+    if args.dataset == "voc":                                                          # :537, the "for Pascal VOC" line
+        from .leoloader import EvaluatorLoader, pascal_loader
+
+        voc_loader = EvaluatorLoader(pascal_loader(args.batch_size, args.dataset_path, "val", eval_resolution, train_size=args.input_resolution))
     num_epochs, num_itr = 50, 1000                                                     # :491,513
     device = torch.device("cuda", 0)
     fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], vit_cfg=vit_cfg, return_attention=False)  # :520
@@ -245,8 +252,7 @@ def main(argv=None, vit_cfg=None) -> float:
         model.init_momentum_teacher()
         model.set_momentum_teacher_schedular_params(args.EMA_decay, 1.0, num_epochs, num_itr)
     model = model.to(device)
-    loader = SyntheticEvalClips(args.eval_clips, args.num_frames, args.input_resolution, args.batch_size, device)
-    eval_resolution = 112 if args.evaluation_protocol == "dataset-wise" else args.input_resolution   # :536
+    loader = voc_loader or SyntheticEvalClips(args.eval_clips, args.num_frames, args.input_resolution, args.batch_size, device)
     logging_directory = None
     if args.log_videos:
         logging_directory = args.logging_directory

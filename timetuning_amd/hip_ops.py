@@ -2588,3 +2588,211 @@ def frames_as_clip(frames: Sequence[torch.Tensor]) -> torch.Tensor:
         return torch.stack(list(frames))
     H, W, ch = f0.shape
     return f0.as_strided((len(frames), H, W, ch), (step, W * ch, ch, 1), f0.storage_offset())
+
+
+# ---- N22: ragged image kernels.  A batch of images (or label maps) of different sizes through ONE launch: a descriptor row per item and one
+# int32 pool of taps / bounds / index tables, each uploaded with one copy.
+_RAGGED_ROW = 16     # int64 words of one tt_img_ragged_item
+(_RG_SRC, _RG_H, _RG_W, _RG_X0, _RG_Y0, _RG_BW, _RG_BH, _RG_FLIP, _RG_HK, _RG_HB, _RG_HKS, _RG_VK, _RG_VB, _RG_VKS, _RG_YT, _RG_XT) = range(16)
+IMG_RAGGED_BAND, IMG_RAGGED_LDS_BUDGET = 16, 65536
+
+
+def img_resize_ragged_shape_ok(h: int, w: int, OH: int, OW: int) -> bool:
+    """Whether ``tt_img_resize_ragged`` takes an ``h x w`` box resized to ``OH x OW``: the source rows the widest band of 16 output rows
+    reaches, as uint8 [rows, OW, 3], fit 64 KiB of LDS (pure host function)."""
+    return bool(_lib.load().tt_img_resize_ragged_shape_ok(int(h), int(w), int(OH), int(OW)))
+
+
+def _ragged_size(size):
+    OH, OW = (size, size) if isinstance(size, int) else size
+    return int(OH), int(OW)
+
+
+def _ragged_source(items: Sequence[torch.Tensor], what: str, ndim: int):
+    """The items' common buffer without a copy where they are views of one storage (``decode_jpeg_batch``'s frames, slices of a packed mask
+    buffer), else ONE ``torch.cat`` of their flattened views: (keep-alive tensor, base pointer, bytes, byte offset of every item)."""
+    if len(items) == 0:
+        raise ValueError(f"{what}: no items")
+    for t in items:
+        _chk(t, what, torch.uint8)
+        if t.dim() != ndim or (ndim == 3 and t.shape[2] != 3) or t.numel() == 0:
+            raise ValueError(f"{what}: uint8 {'[H, W, 3]' if ndim == 3 else '[H, W]'} tensors are needed, got {tuple(t.shape)}")
+        if t.device != items[0].device:
+            raise ValueError(f"{what}: the items lie on different devices")
+    s0 = items[0].untyped_storage()
+    if all(t.untyped_storage().data_ptr() == s0.data_ptr() for t in items):
+        base = min(t.data_ptr() for t in items)
+        return list(items), base, max(t.data_ptr() + t.numel() for t in items) - base, [t.data_ptr() - base for t in items]
+    packed = torch.cat([t.reshape(-1) for t in items])
+    offs = np.zeros(len(items) + 1, np.int64)
+    np.cumsum([t.numel() for t in items], out=offs[1:])
+    return packed, packed.data_ptr(), packed.numel(), [int(o) for o in offs[:-1]]
+
+
+class _RaggedPool:
+    """The int32 pool of one call, deduplicated by key (``array``: the whole pool as one host array)."""
+
+    def __init__(self):
+        self.parts, self.where, self.length = [], {}, 0
+
+    def array(self) -> np.ndarray:
+        return np.concatenate(self.parts) if self.parts else np.zeros(0, np.int32)
+
+    def add(self, key, make):
+        hit = self.where.get(key)
+        if hit is None:
+            arrays = make()
+            hit = []
+            for a in arrays:
+                a = np.ascontiguousarray(a, np.int32).reshape(-1)
+                hit.append(self.length)
+                self.parts.append(a)
+                self.length += a.size
+            self.where[key] = hit
+        return hit
+
+
+def _ragged_upload(table: np.ndarray, pool: np.ndarray, device):
+    """The descriptor table and the pool, each written into one pinned buffer and uploaded with one copy: (host table, device table, host
+    pool, device pool).  The host copies are what the entry points validate."""
+    table_host = torch.empty(table.size, dtype=torch.int64, pin_memory=True)
+    table_host.numpy()[:] = table.reshape(-1)
+    pool_host = torch.zeros(max(pool.size, 1), dtype=torch.int32, pin_memory=True)
+    pool_host.numpy()[:pool.size] = pool
+    return table_host, table_host.to(device, non_blocking=True), pool_host, pool_host.to(device, non_blocking=True)
+
+
+def _ragged_boxes(dims, boxes, flips, what: str):
+    n = len(dims)
+    boxes = [None] * n if boxes is None else list(boxes)
+    flips = [False] * n if flips is None else list(flips)
+    if len(boxes) != n or len(flips) != n:
+        raise ValueError(f"{what}: {n} items but {len(boxes)} boxes / {len(flips)} flips")
+    out = []
+    for (H, W), box in zip(dims, boxes):
+        x0, y0, w, h = (0, 0, W, H) if box is None else (int(v) for v in box)
+        if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+            raise ValueError(f"{what}: box (x0 {x0}, y0 {y0}, w {w}, h {h}) outside its image {H} x {W}")
+        out.append((x0, y0, w, h))
+    return out, [bool(f) for f in flips]
+
+
+def _ragged_rows(dims, offsets, boxes, flips) -> np.ndarray:
+    table = np.zeros((len(dims), _RAGGED_ROW), np.int64)
+    for row, (H, W), off, (x0, y0, w, h), flip in zip(table, dims, offsets, boxes, flips):
+        row[_RG_SRC], row[_RG_H], row[_RG_W] = off, H, W
+        row[_RG_X0], row[_RG_Y0], row[_RG_BW], row[_RG_BH], row[_RG_FLIP] = x0, y0, w, h, int(flip)
+    return table
+
+
+def img_resize_ragged_plan(dims, offsets, size, boxes=None, flips=None):
+    """Host only: the descriptor table (int64 [n, 16], the words of ``tt_img_ragged_item``) and the int32 pool ``tt_img_resize_ragged``
+    takes for images of ``dims[i] = (H, W)`` at byte ``offsets[i]``.  The taps are ``video_transformations.resample_coeffs`` (pinned
+    against Pillow), one copy per (in, out) length; a pass of equal lengths gets none."""
+    from . import video_transformations as VT
+
+    OH, OW = _ragged_size(size)
+    boxes, flips = _ragged_boxes(dims, boxes, flips, "img_resize_ragged")
+    table, pool = _ragged_rows(dims, offsets, boxes, flips), _RaggedPool()
+
+    def taps(n_in, n_out):
+        kk, bounds = VT.resample_coeffs(n_in, n_out)
+        return pool.add(("taps", n_in, n_out), lambda: (kk.numpy(), bounds.numpy())) + [kk.shape[1]]
+
+    for row, (x0, y0, w, h) in zip(table, boxes):
+        if w != OW:
+            row[_RG_HK], row[_RG_HB], row[_RG_HKS] = taps(w, OW)
+        if h != OH:
+            row[_RG_VK], row[_RG_VB], row[_RG_VKS] = taps(h, OH)
+    return table, pool.array()
+
+
+def img_gather_nearest_ragged_plan(dims, offsets, size, boxes=None, flips=None):
+    """Host only: table and pool for ``tt_img_gather_nearest_ragged``; the tables are ``video_transformations.nearest_table`` with the crop
+    offset and the flip folded in, one copy per distinct table."""
+    from . import video_transformations as VT
+
+    OH, OW = _ragged_size(size)
+    boxes, flips = _ragged_boxes(dims, boxes, flips, "img_gather_nearest_ragged")
+    table, pool = _ragged_rows(dims, offsets, boxes, flips), _RaggedPool()
+    for row, (x0, y0, w, h), flip in zip(table, boxes, flips):
+        row[_RG_YT], = pool.add(("near", h, OH, y0, False), lambda: (VT.nearest_table(h, OH, y0),))
+        row[_RG_XT], = pool.add(("near", w, OW, x0, flip), lambda: (VT.nearest_table(w, OW, x0, flip),))
+    return table, pool.array()
+
+
+def img_resize_ragged(frames: Sequence[torch.Tensor], size, boxes=None, flips=None, to_tensor=None, out=None):
+    """``Image.crop(box).resize((OW, OH), BILINEAR)`` of every frame of a mixed-size batch in ONE launch.  ``frames``: uint8 [H, W, 3] GPU
+    tensors (the views ``decode_jpeg_batch`` returns are used where they lie, by byte offset); ``size``: S or (OH, OW); ``boxes``: per item
+    ``(x0, y0, w, h)`` or None = the whole image; ``flips``: per item, mirror the output row.  Returns uint8 [n, OH, OW, 3], or with
+    ``to_tensor=(mean, std)`` the finished float32 [n, 3, OH, OW].  An item ``img_resize_ragged_shape_ok`` refuses goes through
+    ``video_transformations.resized_crop`` into its row of the same output: the result does not depend on the route.  ``out``: an output
+    tensor of that shape and dtype to write into (tests)."""
+    from . import video_transformations as VT
+
+    lib = _lib.load()
+    OH, OW = _ragged_size(size)
+    keep, base, in_bytes, offs = _ragged_source(frames, "frames", 3)
+    dev = frames[0].device
+    n = len(frames)
+    dims = [(t.shape[0], t.shape[1]) for t in frames]
+    boxes, flips = _ragged_boxes(dims, boxes, flips, "img_resize_ragged")
+    shape = (n, OH, OW, 3) if to_tensor is None else (n, 3, OH, OW)
+    dtype = torch.uint8 if to_tensor is None else f32
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"img_resize_ragged: out must be a contiguous {dtype} tensor {shape} on {dev}")
+    fast = [i for i in range(n) if lib.tt_img_resize_ragged_shape_ok(boxes[i][3], boxes[i][2], OH, OW)]
+    m3 = s3 = None
+    if to_tensor is not None:
+        mean, std = to_tensor
+        m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    with torch.cuda.device(dev):
+        if fast:
+            table, pool = img_resize_ragged_plan([dims[i] for i in fast], [offs[i] for i in fast], (OH, OW), [boxes[i] for i in fast],
+                                                 [flips[i] for i in fast])
+            table_host, table_dev, pool_host, pool_dev = _ragged_upload(table, pool, dev)
+            whole = len(fast) == n
+            dst = out if whole else torch.empty((len(fast),) + shape[1:], dtype=dtype, device=dev)
+            _lib.check(lib.tt_img_resize_ragged(base, in_bytes, table_host.data_ptr(), _p(table_dev), len(fast), pool_host.data_ptr(), _p(pool_dev),
+                                                pool.size, _p(dst) if to_tensor is None else None, None if to_tensor is None else _p(dst),
+                                                OH, OW, m3, s3, _stream()), "tt_img_resize_ragged")
+            if not whole:
+                out[torch.as_tensor(fast, device=dev)] = dst
+        taken = set(fast)
+        for i in range(n):
+            if i in taken:
+                continue
+            x0, y0, w, h = boxes[i]
+            one = VT.resized_crop(frames[i][None], y0, x0, h, w, (OH, OW), to_tensor, flips[i])
+            if to_tensor is None and flips[i]:
+                one = one.flip(2)
+            out[i] = one[0]
+    del keep
+    return out
+
+
+def img_gather_nearest_ragged(maps: Sequence[torch.Tensor], size, boxes=None, flips=None, to_tensor: bool = False, out=None):
+    """``Image.crop(box).resize((OW, OH), NEAREST)`` of every label map of a mixed-size batch in ONE launch.  ``maps``: uint8 [H, W] GPU
+    tensors (slices of one packed buffer are used where they lie).  Returns uint8 [n, OH, OW], or with ``to_tensor`` float32
+    [n, 1, OH, OW] = v / 255.  The tables are ``video_transformations.nearest_table`` with the crop offset and the flip folded in."""
+    lib = _lib.load()
+    OH, OW = _ragged_size(size)
+    keep, base, in_bytes, offs = _ragged_source(maps, "maps", 2)
+    dev = maps[0].device
+    n = len(maps)
+    table, pool = img_gather_nearest_ragged_plan([(t.shape[0], t.shape[1]) for t in maps], offs, (OH, OW), boxes, flips)
+    shape = (n, 1, OH, OW) if to_tensor else (n, OH, OW)
+    dtype = f32 if to_tensor else torch.uint8
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"img_gather_nearest_ragged: out must be a contiguous {dtype} tensor {shape} on {dev}")
+    with torch.cuda.device(dev):
+        table_host, table_dev, pool_host, pool_dev = _ragged_upload(table, pool, dev)
+        _lib.check(lib.tt_img_gather_nearest_ragged(base, in_bytes, table_host.data_ptr(), _p(table_dev), n, pool_host.data_ptr(), _p(pool_dev),
+                                                    pool.size, None if to_tensor else _p(out), _p(out) if to_tensor else None, OH, OW,
+                                                    _stream()), "tt_img_gather_nearest_ragged")
+    del keep
+    return out

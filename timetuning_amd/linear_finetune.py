@@ -233,8 +233,8 @@ class FusedSGD(torch.optim.Optimizer):
 # ---- the training driver (linear_finetune.py:55-89) ---------------------------------------------------------------------------------
 
 def build_parser() -> argparse.ArgumentParser:
-    """The constants of ``linear_finetune.py:55-89`` as flags.  ``--dataset synthetic`` and the ``--num_*_images`` flags are additions:
-    the Pascal VOC reader (``leoloader.pascal_loader``) is out of scope."""
+    """The constants of ``linear_finetune.py:55-89`` as flags.  ``--dataset synthetic`` and the ``--num_*_images`` flags are additions,
+    and so is ``--dataset voc``: ``leoloader.pascal_loader`` on ``--dataset_path`` (the VOCSegmentation root), as ``:69-71`` calls it."""
     p = argparse.ArgumentParser()
     p.add_argument("--architecture", type=str, default="dino-s16")
     p.add_argument("--model_path", type=str, default="dino-s16.pth")
@@ -298,14 +298,21 @@ def _batches(x, y, batch_size):
 
 
 def main(argv: Optional[list] = None) -> float:
-    """``linear_finetune.py:55-89`` on synthetic data: validate, train one epoch with CrossEntropyLoss(ignore_index=255) and SGD +
+    """``linear_finetune.py:55-89`` on synthetic data or (``--dataset voc``) on a Pascal VOC tree: validate, train one epoch with CrossEntropyLoss(ignore_index=255) and SGD +
     StepLR, validate; returns the last mIoU."""
     from .models import FeatureExtractor
     from .time_tuning import TimeT
 
     args = build_parser().parse_args(argv)
-    if args.dataset != "synthetic":
-        raise NotImplementedError("dataset readers (leoloader.pascal_loader) are out of scope for this build; run with --dataset synthetic")
+    if args.dataset not in ("synthetic", "voc"):
+        raise NotImplementedError("this build reads Pascal VOC through --dataset voc (leoloader.pascal_loader on --dataset_path, the "
+                                  "VOCSegmentation root) and generated data through --dataset synthetic")
+    train_loader = val_loader = None
+    if args.dataset == "voc":                                                            # linear_finetune.py:69-71
+        from .leoloader import pascal_loader
+
+        train_loader = pascal_loader(args.batch_size, args.dataset_path, "trainaug", args.mask_size, train_size=args.input_resolution)
+        val_loader = pascal_loader(args.batch_size, args.dataset_path, "val", args.mask_size, train_size=args.input_resolution)
     torch.cuda.set_device(0)
     feature_extractor = FeatureExtractor(args.architecture, args.model_path, list(args.head_layers), return_attention=False)
     model = TimeT(feature_extractor, args.num_prototypes)
@@ -314,10 +321,11 @@ def main(argv: Optional[list] = None) -> float:
     model.train()
     optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=args.step_size, gamma=args.gamma)
-    x_tr, y_tr = synthetic_segmentation(args.num_train_images, args.input_resolution, args.num_classes, seed=1)
-    x_va, y_va = synthetic_segmentation(args.num_val_images, args.input_resolution, args.num_classes, seed=2)
-    train_loader = _batches(x_tr, y_tr, args.batch_size)
-    val_loader = _batches(x_va, y_va, args.batch_size)
+    if train_loader is None:
+        x_tr, y_tr = synthetic_segmentation(args.num_train_images, args.input_resolution, args.num_classes, seed=1)
+        x_va, y_va = synthetic_segmentation(args.num_val_images, args.input_resolution, args.num_classes, seed=2)
+        train_loader = _batches(x_tr, y_tr, args.batch_size)
+        val_loader = _batches(x_va, y_va, args.batch_size)
     print("train_loader", len(train_loader))
     print("val_loader", len(val_loader))
     miou = math.nan

@@ -1035,7 +1035,7 @@ def build_parser() -> argparse.ArgumentParser:
     --size_mask_neighborhood --epochs --dataset_path --destination_path`` are parsed but never reach ``get_loss``,
     which uses its signature defaults (eps 0.05, 10 iterations, 7 frames, radius 6, top-5).
     Added (not in the reference): ``--dataset synthetic`` / ``synthetic_frames`` / ``--steps_per_epoch`` / ``--eval_clips`` (generated
-    clips; the evaluation's Pascal VOC reader is out of scope), ``--eval_every`` (the reference hard-codes 4), ``--log_localization_every`` (the qualitative logs of
+    clips), ``--eval_dataset_path`` (the evaluation's Pascal VOC root; empty = generated clips), ``--eval_every`` (the reference hard-codes 4), ``--log_localization_every`` (the qualitative logs of
     :641-642, off by default), ``--unfreeze_layers`` (the reference hard-codes the two blocks, :574) and ``--precision`` (the arithmetic mode of the
     matrix products; the library-level default of ``hip_ops.set_gemm_precision`` stays "f32", the training driver's is "f16x3")."""
     p = argparse.ArgumentParser()
@@ -1081,6 +1081,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--steps_per_epoch", default=8, type=int, help="synthetic data only")
     p.add_argument("--eval_every", default=4, type=int, help="epochs between rank-0 evaluations (the reference hard-codes 4; 0 = never)")
     p.add_argument("--eval_clips", default=8, type=int, help="synthetic evaluation set size")
+    p.add_argument("--eval_dataset_path", default="", type=str,
+                   help="a Pascal VOC root (VOCSegmentation): rank 0 evaluates on leoloader.pascal_loader(60, path, 'val', 112, train_size=224) as "
+                        "the reference does (time_tuning.py:596); empty = the synthetic evaluation clips")
     p.add_argument("--log_localization_every", default=0, type=int,
                    help="at the rank-0 evaluations of the epochs divisible by N: the prototype assignment histogram's entropy (log_assignment_histogram) and the overlay "
                         "GIFs of the first evaluation batch in --visualization_directory (log_clip_localization); 0 = never")
@@ -1267,7 +1270,12 @@ def time_tuning(gpu=0, args=None):
     eval_model = model.get_non_ddp_model() if isinstance(model, DistributedDataParallelModel) else model
     evaluator = None
     if args.eval_every > 0 and rank == 0:
-        eval_loader = SyntheticEvalClips(args.eval_clips, 1, args.input_resolution, 4, device)
+        if getattr(args, "eval_dataset_path", ""):                                                              # :596
+            from .leoloader import EvaluatorLoader, pascal_loader
+
+            eval_loader = EvaluatorLoader(pascal_loader(60, args.eval_dataset_path, "val", 112, train_size=224, device=device))
+        else:
+            eval_loader = SyntheticEvalClips(args.eval_clips, 1, args.input_resolution, 4, device)
         evaluator = Evaluator(eval_model, eval_loader, 21, device, clustering_algorithm="k-means", uvos_flag=bool(args.uvos))
     eval_resolution = args.input_resolution // 2 if args.evaluation_protocol == "dataset-wise" else args.input_resolution  # :603
     previous_score, scores = 0.0, []
