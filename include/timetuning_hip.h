@@ -1114,6 +1114,32 @@ int tt_img_gather_nearest_ragged(const uint8_t* in, long long in_bytes, const tt
                                  int n_items, const int32_t* pool, const int32_t* pool_dev, long long pool_len, uint8_t* out_u8,
                                  float* out_f32, int OH, int OW, tt_stream_t stream);
 
+/* ---- N23: label maps as byte streams (csrc/label_map.hip) - which label values occur in a segment, and the YouTube-VOS remap of per-video
+   instance ids to dataset-wide category ids built on it (data_loader.py:453-464 make_categories_dict, :497-506 map_instances, :774-796
+   YVOSDataset; the per-frame torch.unique of clustering.py:95-103).  Segment s is elements s P ... s P + P - 1 of `labels`; neither P nor
+   the base pointer needs any alignment beyond the element's own.  No workgroup waits on another; nothing is allocated.
+   tt_label_presence_segments   labels: uint8 (elem_bytes 1) or int64 (elem_bytes 8).  words uint32 [S][8]: bit (v & 31) of word v >> 5 is
+                          set iff value v in 0 .. 255 occurs in segment s.  status int32 [S]: 1 where an int64 value lies outside 0 .. 255
+                          (it sets no bit; the caller then counts that segment some other way), else 0.  The entry zeroes words and status
+                          on the stream; one launch.
+   tt_map_instances       labels_out[e] = lut_s[labels_in[e]] on uint8 [S][P], two launches: the presence pass into words_ws
+                          (tt_map_instances_workspace_bytes(S) = 32 S bytes, 4-byte aligned), then the apply pass, whose workgroups each
+                          compose lut_s in LDS.  cat int32 [S][256]: the category of object id v of segment s's video, -1 = not in the meta
+                          file.  sequential = 1 reproduces the reference's in-place loop `frame[frame == obj] = category` over the ascending
+                          torch.unique of the clip: from the identity, for obj = 1 .. 255 in order, if obj occurs in the ORIGINAL segment
+                          every entry whose CURRENT value equals obj becomes cat[obj] - a pixel mapped onto a later, present object id is
+                          mapped again (the reference's chaining, kept as a quirk).  sequential = 0: v -> cat[v] for present v >= 1.  Value 0
+                          is never remapped.  A present object whose cat is outside 0 .. 255 makes status[s] the smallest such id and
+                          lut_s the identity (the segment is copied unmapped); else status[s] = 0.  lut_out uint8 [S][256] receives lut_s.
+                          The ranges of labels_in and labels_out must not overlap (workgroups of one segment read all of it for the
+                          presence pass while others would write): TT_EINVAL.
+   Refusals (null pointers, S or P < 1, another elem_bytes / sequential, overlap, a short or misaligned workspace) return TT_EINVAL with the
+   numbers in tt_last_error, and nothing is launched. */
+int tt_label_presence_segments(const void* labels, int elem_bytes, int S, long long P, uint32_t* words, int32_t* status, tt_stream_t stream);
+size_t tt_map_instances_workspace_bytes(int S);
+int tt_map_instances(const uint8_t* labels_in, uint8_t* labels_out, const int32_t* cat, int S, long long P, int sequential, uint8_t* lut_out,
+                     int32_t* status, void* words_ws, size_t words_ws_bytes, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,9 @@ SIGNATURES = {
     "tt_img_resize_ragged": (c_i, [c_vp, c_ll, c_vp, c_vp, c_i, c_vp, c_vp, c_ll, c_vp, c_vp, c_i, c_i, C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), c_vp]),
     "tt_img_gather_nearest_ragged": (c_i, [c_vp, c_ll, c_vp, c_vp, c_i, c_vp, c_vp, c_ll, c_vp, c_vp, c_i, c_i, c_vp]),
+    "tt_label_presence_segments": (c_i, [c_vp, c_i, c_i, c_ll, c_vp, c_vp, c_vp]),
+    "tt_map_instances_workspace_bytes": (c_sz, [c_i]),
+    "tt_map_instances": (c_i, [c_vp, c_vp, c_vp, c_i, c_ll, c_i, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

@@ -429,8 +429,19 @@ def _kmeans_maps_grouped(points: torch.Tensor, ks) -> torch.Tensor:
     return out
 
 
+def _annotation_counts(annotations: torch.Tensor, segments: int, device) -> list:
+    """``torch.unique(segment).shape[0]`` of each of ``segments`` equal parts of the annotations (the reference: one ``torch.unique`` and so
+    one host sync per frame, ``clustering.py:95-103``) from ONE presence launch and one read-back (``hip_ops.label_value_counts``; a part
+    holding a value outside 0 .. 255 is counted by ``torch.unique`` there)."""
+    a = annotations.to(device)
+    if a.dtype not in (torch.uint8, torch.int64):
+        a = a.long()
+    return ops.label_value_counts(a.reshape(segments, -1).contiguous())
+
+
 def cluster_features(features, num_clusters, feature_resolution, input_resolution, evaluation_protocol, annotations=None):
-    """``clustering.cluster_features``: features [bs, fs, num_patches, dim] -> cluster maps [bs, fs, R, R] int16."""
+    """``clustering.cluster_features``: features [bs, fs, num_patches, dim] -> cluster maps [bs, fs, R, R] int16.  With ``annotations``
+    ([bs, fs, ...] label maps) every k-means takes as many clusters as its frame / clip / dataset has label values."""
     bs, fs, num_patches, dim = features.shape
     feats = normalize_and_transform(features.reshape(bs * fs * num_patches, dim), 50)
     dim = feats.shape[1]
@@ -438,13 +449,13 @@ def cluster_features(features, num_clusters, feature_resolution, input_resolutio
     R = input_resolution
     up = ops.upsample_bilinear_tokens(feats, R).view(bs, fs, R * R, dim)      # what the reference builds frame by frame
     if evaluation_protocol == "frame-wise":   # one k-means per frame
-        ks = [torch.unique(annotations[i, j]).shape[0] if annotations is not None else num_clusters for i in range(bs) for j in range(fs)]
+        ks = _annotation_counts(annotations, bs * fs, features.device) if annotations is not None else [num_clusters] * (bs * fs)
         out = _kmeans_maps_grouped(up.view(bs * fs, R * R, dim), ks).view(bs, fs, R, R)
     elif evaluation_protocol == "sample-wise":   # one per clip
-        ks = [torch.unique(annotations[i]).shape[0] if annotations is not None else num_clusters for i in range(bs)]
+        ks = _annotation_counts(annotations, bs, features.device) if annotations is not None else [num_clusters] * bs
         out = _kmeans_maps_grouped(up.view(bs, fs * R * R, dim), ks).view(bs, fs, R, R)
     elif evaluation_protocol == "dataset-wise":
-        k = torch.unique(annotations).shape[0] if annotations is not None else num_clusters
+        k = _annotation_counts(annotations, 1, features.device)[0] if annotations is not None else num_clusters
         out = _kmeans_maps(up.reshape(bs * fs * R * R, dim), k).view(bs, fs, R, R)
     else:
         raise ValueError(f"unknown evaluation protocol {evaluation_protocol!r}")

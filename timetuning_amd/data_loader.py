@@ -17,8 +17,13 @@ What differs, on purpose:
 * A video's length is the number of its frame files (the reference counts every directory entry, ``:590-592``); its label is its position
   in the sorted list (the reference: its position in ``os.listdir``'s arbitrary order).
 * ``frame_transformation`` errors raise (the reference prints "Error in frame transformation" and goes on with the untransformed clip).
+* The ``meta.json`` category mapping of ``YVOSDataset`` (``:774-796``, N23) runs on the device, ONCE per batch on the stacked annotations
+  (``hip_ops.map_instances``: two launches), not once per sample on the host.  ``compose_instance_lut`` states its rule; by default it is
+  the reference's chained in-place loop (``map_instances``, ``:497-506``), ``sequential_category_map=False`` selects the plain
+  ``id -> category``.  ``make_categories_dict`` raises ``ValueError`` for a name other than ``"ytvos"`` (the reference: an unbound local),
+  and ``num_clips != 1`` with a meta file raises (the reference's loop re-maps the already mapped clip there).
 Not reproduced (out of scope): the extraction of video files with cv2 and the ``mkdir`` / ``remove`` it performs (``:509-540``), the
-hard-coded per-host dataset roots, the ``meta.json`` category mapping of ``YVOSDataset``, ``Kinetics`` and the SBD reader ``pascalVOCLoader`` (Pascal VOC is read by ``leoloader.py``).
+hard-coded per-host dataset roots, ``Kinetics`` and the SBD reader ``pascalVOCLoader`` (Pascal VOC is read by ``leoloader.py``).
 
 ``ClipLoader`` stands in for ``make_loader``'s ``DataLoader`` + ``DistributedSampler`` (``:1047-1110``).
 """
@@ -26,6 +31,7 @@ from __future__ import annotations
 
 import glob
 import io
+import json
 import os
 import random
 from concurrent.futures import ThreadPoolExecutor
@@ -100,6 +106,57 @@ def decode_frame_on_host(data: bytes) -> np.ndarray:
     return np.array(Image.open(io.BytesIO(data)).convert("RGB"), np.uint8)   # (a writable copy)
 
 
+def make_categories_dict(meta_dict, name):
+    """``make_categories_dict`` (``data_loader.py:453-464``): the categories of every object of every video, sorted, numbered from 1 -
+    0 stays the background.  Only ``name == "ytvos"`` is defined (the reference falls into an unbound local for any other)."""
+    if name != "ytvos":
+        raise ValueError(f"make_categories_dict: only the \"ytvos\" meta layout is defined, got {name!r}")
+    categories = {obj["category"] for video in meta_dict["videos"].values() for obj in video["objects"].values()}
+    return {k: v + 1 for v, k in enumerate(sorted(categories))}
+
+
+def video_category_table(meta_dict, category_dict, video: str) -> np.ndarray:
+    """int32 [256]: the category id of each object id of ``meta["videos"][video]["objects"]``, -1 where the meta file has none (a video
+    the file does not list has none at all)."""
+    table = np.full(256, -1, np.int32)
+    entry = meta_dict["videos"].get(video)
+    for key, obj in ({} if entry is None else entry["objects"]).items():
+        if not 0 <= int(key) <= 255:
+            raise ValueError(f"video {video}: object id {key} does not fit a uint8 annotation map")
+        table[int(key)] = category_dict[obj["category"]]
+    if table.max() > 255:
+        raise ValueError(f"{len(category_dict)} categories do not fit a uint8 annotation map")
+    return table
+
+
+def compose_instance_lut(present, cat, sequential: bool = True) -> np.ndarray:
+    """The 256-entry table ``tt_map_instances`` applies to one segment (uint8 [256]); the host statement of the kernel's rule.
+    ``present``: the values that occur in the ORIGINAL segment (any iterable of ints, or a bool [256] array); ``cat``: int [256], the
+    category of each object id, -1 = none.
+
+    ``sequential``: the reference's ``map_instances`` - ``frame[frame == obj] = category`` in place, for obj over the ascending
+    ``torch.unique`` of the clip taken BEFORE the loop.  From the identity, for obj = 1 .. 255 in order, if obj is present every entry
+    whose CURRENT value equals obj becomes ``cat[obj]``; a pixel mapped onto a later, present object id is mapped again.  Otherwise the
+    plain ``v -> cat[v]`` for present v >= 1.  0 is never remapped.  Raises ``KeyError(obj)`` for the smallest present object without a
+    category in 0 .. 255 (the kernel: ``status`` = obj and the identity)."""
+    cat = np.asarray(cat).astype(np.int64)
+    flags = np.asarray(present)
+    if flags.dtype != np.bool_ or flags.shape != (256,):
+        flags = np.zeros(256, np.bool_)
+        flags[np.asarray(list(present), np.int64)] = True
+    objs = [v for v in range(1, 256) if flags[v]]
+    for obj in objs:
+        if not 0 <= cat[obj] <= 255:
+            raise KeyError(obj)
+    lut = np.arange(256, dtype=np.int64)
+    for obj in objs:
+        if sequential:
+            lut[lut == obj] = cat[obj]
+        else:
+            lut[obj] = cat[obj]
+    return lut.astype(np.uint8)
+
+
 def _read(path: str) -> bytes:
     with open(path, "rb") as f:
         return f.read()
@@ -108,8 +165,8 @@ def _read(path: str) -> bytes:
 class _HostSample:
     """One video's clips as the host leaves them: the frame files' bytes and the decoded annotation maps, per clip."""
 
-    def __init__(self, frames, annotations, label):
-        self.frames, self.annotations, self.label = frames, annotations, label
+    def __init__(self, frames, annotations, label, index=None):
+        self.frames, self.annotations, self.label, self.index = frames, annotations, label, index
 
 
 class _HostBatch:
@@ -119,18 +176,34 @@ class _HostBatch:
 
 class VideoDataset:
     """``VideoDataset(classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, ...)`` (``:552``).  ``rng`` draws the
-    frame indices (default: the ``random`` module, as in the reference); ``device`` and ``threads`` belong to the decode."""
+    frame indices (default: the ``random`` module, as in the reference); ``device`` and ``threads`` belong to the decode.
+    ``meta_file_directory`` (``:563-573``): the path of a YouTube-VOS ``meta.json``; when the file exists the annotations' per-video
+    instance ids become dataset-wide category ids (``map_categories``), ``sequential_category_map`` choosing the rule of
+    ``compose_instance_lut``.  A path that does not exist prints "There is no meta file." and maps nothing, as in the reference."""
 
     def __init__(self, classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, num_labels=1, frame_transform=None,
-                 target_transform=None, video_transform=None, meta_file_directory=None, regular_step=1, device=None, threads=8, rng=None):
+                 target_transform=None, video_transform=None, meta_file_directory=None, regular_step=1, device=None, threads=8, rng=None,
+                 sequential_category_map=True):
         if num_labels != 1:
             raise NotImplementedError("nested class directories (num_labels > 1) are not reproduced")
+        self.meta_dict, self.category_dict, self.category_tables = None, None, None
+        self.sequential_category_map = bool(sequential_category_map)
         if meta_file_directory is not None:
-            raise NotImplementedError("the meta.json category mapping is out of scope")
+            if os.path.exists(meta_file_directory):
+                if num_clips != 1:
+                    raise NotImplementedError("the meta.json category mapping with num_clips != 1: the reference's loop maps the already "
+                                              "mapped clip again there, and make_loader never asks for it")
+                with open(meta_file_directory) as f:
+                    self.meta_dict = json.load(f)
+                self.category_dict = make_categories_dict(self.meta_dict, "ytvos")
+            else:
+                print("There is no meta file.")
         self.keys = list_videos(classes_directory)
         if len(self.keys) == 0:
             raise FileNotFoundError(f"no video directories under {classes_directory}")
         self.train_dict = {k: np.array([i]) for i, k in enumerate(self.keys)}
+        if self.meta_dict is not None:   # one int32 [256] table per video, by the directory's name
+            self.category_tables = np.stack([video_category_table(self.meta_dict, self.category_dict, os.path.basename(k)) for k in self.keys])
         self.files = {k: list_frames(k) for k in self.keys}
         self.train_dict_lenghts = {k: len(v) for k, v in self.files.items()}
         if annotations_directory and os.path.exists(annotations_directory):
@@ -164,7 +237,7 @@ class VideoDataset:
         if self.use_annotations:
             afiles = self.annotation_files[self.annotation_keys[idx]]
             annotations = [np.stack([decode_annotation(_read(afiles[j])) for j in clip]) for clip in clip_indices]
-        return _HostSample(frames, annotations, np.tile(self.train_dict[path], (self.num_clips,)))
+        return _HostSample(frames, annotations, np.tile(self.train_dict[path], (self.num_clips,)), idx)
 
     def scan_host(self, samples: List[_HostSample]) -> _HostBatch:
         """Classifies every frame of the samples, entropy-decodes the supported ones into one pinned buffer and decodes the others with
@@ -221,9 +294,38 @@ class VideoDataset:
             sampled = torch.empty(0)
         return data, sampled
 
+    def map_categories(self, annotations: torch.Tensor, indices) -> torch.Tensor:
+        """annotations uint8 [n, ...] of the videos ``indices`` (one clip each) -> the same with instance ids replaced by category ids:
+        ONE ``hip_ops.map_instances`` call for all n clips, each with its video's table.  Without a meta file, or without annotations,
+        the tensor comes back as it is.  A present object id the meta file does not list raises ``KeyError`` naming the video and the
+        id (the reference raises ``KeyError`` there too)."""
+        if self.category_tables is None or annotations.numel() == 0:
+            return annotations
+        if annotations.dtype != torch.uint8:
+            raise TypeError(f"the category mapping reads uint8 annotation maps, got {annotations.dtype}")
+        n = len(indices)
+        cat = torch.from_numpy(self.category_tables[np.asarray(indices, np.int64)]).to(annotations.device)
+        mapped, _, status = ops.map_instances(annotations.contiguous().view(n, -1), cat, self.sequential_category_map)
+        status = status.cpu()
+        for k in range(n):
+            if int(status[k]) != 0:
+                raise KeyError(f"video {os.path.basename(self.keys[indices[k]])}: object id {int(status[k])} is not in the meta file")
+        return mapped.view(annotations.shape)
+
     def __getitem__(self, idx):
         """(data [num_clips, fs, 3, R, R], annotations uint8 [num_clips, fs, R, R] or an empty tensor, label [num_clips])."""
-        return self.finish(self.scan_host([self.read_host(idx)]))[0]
+        data, annotations, label = self.finish(self.scan_host([self.read_host(idx)]))[0]
+        return data, self.map_categories(annotations, [idx]), label
+
+
+class YVOSDataset(VideoDataset):
+    """``YVOSDataset`` (``:774-796``): a ``VideoDataset`` whose ``meta_file_directory`` must hold a readable YouTube-VOS ``meta.json``
+    (the reference fails on ``None["videos"]`` without one)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.meta_dict is None:
+            raise FileNotFoundError("YVOSDataset needs meta_file_directory, the path of an existing meta.json")
 
 
 class ClipLoader:
@@ -287,7 +389,7 @@ class ClipLoader:
                     pending = pool.submit(self._host, batches[k + 1])
                 items = self.dataset.finish(host)
                 data = torch.stack([d for d, _, _ in items])
-                annotations = torch.stack([a for _, a, _ in items])
+                annotations = self.dataset.map_categories(torch.stack([a for _, a, _ in items]), [s.index for s in host.samples])
                 label = torch.stack([l for _, _, l in items])
                 yield data, annotations, label
         finally:
@@ -297,16 +399,19 @@ class ClipLoader:
 
 def make_loader(dataset_path: str, num_clip_frames: int, batch_size: int, regular_step: int = 1, sampling_mode: SamplingMode = SamplingMode.UNIFORM,
                 frame_transform=None, target_transform=None, video_transform=None, shuffle: bool = False, num_workers: int = 6, world_size: int = 1,
-                rank: int = 0, device=None, seed: int = 0) -> ClipLoader:
+                rank: int = 0, device=None, seed: int = 0, meta_file_directory=None, sequential_category_map: bool = True) -> ClipLoader:
     """``make_loader`` (``:1047``) for the layout every ``VideoDataset`` branch of it reads: frames under ``<dataset_path>/JPEGImages/``,
     annotations under ``<dataset_path>/Annotations/`` when present.  ``num_workers`` is the thread count of the host decode (at most 16
-    are used)."""
+    are used).  ``meta_file_directory``: the path of a YouTube-VOS ``meta.json`` - a ``YVOSDataset`` then maps instance ids to category
+    ids (the ``ytvos`` branches, ``:1073-1090``).  It is never looked for: without the argument a tree that holds one is read as before."""
     frames = os.path.join(dataset_path, "JPEGImages")
     if not os.path.isdir(frames):
         # (the reference maps a dataset NAME to a hard-coded root and a layout of its own per name, :1055-1104: not reproduced)
         raise NotImplementedError(f"dataset readers: only the layout <dataset_path>/JPEGImages/<video>/*.jpg (+ <dataset_path>/Annotations/"
                                   f"<video>/*.png) is read, and {frames} is not a directory; point --dataset_path at such a tree, or run "
                                   "with --dataset synthetic / synthetic_frames")
-    dataset = VideoDataset(frames, os.path.join(dataset_path, "Annotations"), sampling_mode, 1, num_clip_frames, 1, frame_transform,
-                           target_transform, video_transform, regular_step=regular_step, device=device, threads=num_workers)
+    cls = VideoDataset if meta_file_directory is None else YVOSDataset
+    dataset = cls(frames, os.path.join(dataset_path, "Annotations"), sampling_mode, 1, num_clip_frames, 1, frame_transform,
+                  target_transform, video_transform, meta_file_directory=meta_file_directory, regular_step=regular_step, device=device,
+                  threads=num_workers, sequential_category_map=sequential_category_map)
     return ClipLoader(dataset, batch_size, shuffle=shuffle, world_size=world_size, rank=rank, seed=seed)

@@ -1,7 +1,8 @@
 """Evaluator with the reference's surface (``evaluation.py:250-310,312-486``): features without head -> clustering ->
 matched mIoU, for the three protocols (frame-wise / sample-wise / dataset-wise), with the GIF logs of the matched maps
-(``evaluation.py:255-300``) on ``visualization``'s render launch.  Dataset readers and the wandb plumbing are out of scope; the
-loader is any iterable of ``(data, annotations[, label])`` batches.
+(``evaluation.py:255-300``) on ``visualization``'s render launch.  The wandb plumbing is out of scope; the loader is any iterable of
+``(data, annotations[, label])`` batches - ``main`` builds it from a video tree (``data_loader.make_loader``, with the YouTube-VOS category
+mapping where the tree has a ``meta.json``), from Pascal VOC or from synthetic clips.
 ``evaluate_localizations`` scores a whole batch from one segmented confusion-count launch (``PredsmIoU.compute_segments``);
 ``evaluate_propagation`` is the reference's (``evaluation.py:228-246``).
 
@@ -200,7 +201,11 @@ class Evaluator:
 def build_parser() -> argparse.ArgumentParser:
     """Flag names, types and defaults of ``evaluation.py:544-566``.  The ``type=bool`` flags treat ANY non-empty string as True, as in
     the reference (and in ``time_tuning.build_parser``): ``--many_to_one False`` turns many-to-one matching ON.  ``--destination_path``
-    and ``--num_workers`` are parsed and unused (the video dataset readers are out of scope).  Added: ``--dataset synthetic`` and
+    is parsed and unused; ``--num_workers`` is the thread count of the loader's host decode.  Any ``--dataset`` but ``synthetic`` / ``voc``
+    names a video dataset (``davis_val``, ``ytvos_val``, ...) read from ``--dataset_path`` - the tree ``<dataset_path>/JPEGImages/<video>/*.jpg``
+    + ``<dataset_path>/Annotations/<video>/*.png`` - through ``data_loader.make_loader`` with the reference's transforms (``:533``) and
+    ``SamplingMode.UNIFORM``; when the name contains ``ytvos`` and ``<dataset_path>/meta.json`` exists, instance ids become category ids
+    (``YVOSDataset``), by the reference's chained loop unless ``--plain_category_map`` is given.  Added: ``--dataset synthetic`` and
     ``--eval_clips``; ``--dataset voc`` (``leoloader.pascal_loader`` on ``--dataset_path``, the VOCSegmentation root: the "for Pascal VOC"
     line of ``:537``); an EMPTY ``--model_path`` selects synthetic weights; ``--log_videos`` (off by default: an evaluation
     writes no file unless asked) makes ``--logging_directory`` live - the frame-wise and sample-wise protocols then write the GIFs of the
@@ -225,6 +230,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--EMA_decay", type=float, default=0.999)
     p.add_argument("--eval_clips", type=int, default=8, help="synthetic evaluation set size")
     p.add_argument("--log_videos", action="store_true", help="write the matched-map GIFs into --logging_directory (frame-wise / sample-wise)")
+    p.add_argument("--plain_category_map", action="store_true",
+                   help="YouTube-VOS meta.json: map every object id straight to its category, not by the reference's chained in-place loop")
     return p
 
 
@@ -235,7 +242,8 @@ def main(argv=None, vit_cfg=None) -> float:
     from .time_tuning import SyntheticEvalClips, TimeT
 
     args = build_parser().parse_args(argv)
-    if args.dataset not in ("synthetic", "voc"):
+    video_dataset = args.dataset not in ("synthetic", "voc")
+    if video_dataset and not os.path.isdir(os.path.join(args.dataset_path, "JPEGImages")):
         raise NotImplementedError("the video dataset readers are out of scope for this build; run with --dataset voc (Pascal VOC through "
                                   "leoloader.pascal_loader on --dataset_path, the VOCSegmentation root) or --dataset synthetic")
     eval_resolution = 112 if args.evaluation_protocol == "dataset-wise" else args.input_resolution   # :536
@@ -252,7 +260,20 @@ def main(argv=None, vit_cfg=None) -> float:
         model.init_momentum_teacher()
         model.set_momentum_teacher_schedular_params(args.EMA_decay, 1.0, num_epochs, num_itr)
     model = model.to(device)
-    loader = voc_loader or SyntheticEvalClips(args.eval_clips, args.num_frames, args.input_resolution, args.batch_size, device)
+    if video_dataset:                                                                  # :533-535
+        from . import data_loader as DL
+        from . import video_transformations as VT
+
+        meta = os.path.join(args.dataset_path, "meta.json")
+        loader = DL.make_loader(args.dataset_path, args.num_frames, args.batch_size, sampling_mode=DL.SamplingMode.UNIFORM, frame_transform=None,
+                                target_transform=None, video_transform=VT.evaluation_transforms(args.input_resolution), shuffle=False,
+                                num_workers=args.num_workers, device=device,
+                                meta_file_directory=meta if "ytvos" in args.dataset and os.path.isfile(meta) else None,
+                                sequential_category_map=not args.plain_category_map)
+        if not loader.dataset.use_annotations:
+            raise FileNotFoundError(f"{args.dataset_path}/Annotations: the evaluation needs annotation maps")
+    else:
+        loader = voc_loader or SyntheticEvalClips(args.eval_clips, args.num_frames, args.input_resolution, args.batch_size, device)
     logging_directory = None
     if args.log_videos:
         logging_directory = args.logging_directory
@@ -262,6 +283,8 @@ def main(argv=None, vit_cfg=None) -> float:
     score = float(evaluator.evaluate(many_to_one=args.many_to_one, evaluation_protocol=args.evaluation_protocol,
                                      eval_resolution=eval_resolution, num_clusters=args.num_clusters, use_annotations=False,
                                      use_mask=False, precision_based=args.precision_based))
+    if video_dataset:
+        print(f"Frames decoded on the host (fallback): {loader.fallback_frames}")
     print(f"Dataset score is {score}")
     return score
 

@@ -2796,3 +2796,82 @@ def img_gather_nearest_ragged(maps: Sequence[torch.Tensor], size, boxes=None, fl
                                                     _stream()), "tt_img_gather_nearest_ragged")
     del keep
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# N23: label maps as byte streams (csrc/label_map.hip)
+# ------------------------------------------------------------------------------------------------
+
+_LABEL_MAP_BYTES = {torch.uint8: 1, torch.int64: 8}
+
+
+def _chk_label_segments(labels: torch.Tensor, name: str, dtypes) -> torch.Tensor:
+    if labels.dtype not in dtypes:
+        raise TypeError(f"{name}: expected {' or '.join(str(d) for d in dtypes)}, got {labels.dtype}")
+    _chk(labels, name, labels.dtype)
+    if labels.dim() != 2 or labels.shape[0] < 1 or labels.shape[1] < 1:
+        raise ValueError(f"{name}: expected [S, P] with S, P >= 1, got {tuple(labels.shape)}")
+    return labels
+
+
+def _label_presence_into(labels: torch.Tensor, words: torch.Tensor, status: torch.Tensor) -> None:
+    S, P = labels.shape
+    with torch.cuda.device(labels.device):
+        _lib.check(_lib.load().tt_label_presence_segments(_p(labels), _LABEL_MAP_BYTES[labels.dtype], S, P, _p(words), _p(status), _stream()),
+                   "tt_label_presence_segments")
+
+
+def label_presence(labels: torch.Tensor):
+    """labels uint8 or int64 [S, P] -> (words int32 [S, 8], status int32 [S]), one launch: bit ``v & 31`` of ``words[s, v >> 5]`` (read as
+    unsigned) is set iff value v in 0 .. 255 occurs in row s; ``status[s]`` is 1 where an int64 value lies outside 0 .. 255."""
+    _chk_label_segments(labels, "labels", _LABEL_MAP_BYTES)
+    S = labels.shape[0]
+    words = torch.empty((S, 8), dtype=torch.int32, device=labels.device)
+    status = torch.empty((S,), dtype=torch.int32, device=labels.device)
+    _label_presence_into(labels, words, status)
+    return words, status
+
+
+def presence_values(words_row) -> list:
+    """Host only: the ascending values whose bit is set in one row of ``label_presence``'s words (8 integers, signed or unsigned)."""
+    return [32 * k + b for k, w in enumerate(words_row) for b in range(32) if (int(w) >> b) & 1]
+
+
+def label_value_counts(labels: torch.Tensor) -> list:
+    """``[torch.unique(row).shape[0] for row in labels]`` for label maps uint8 or int64 [S, P]: one presence launch and ONE read-back (the 32
+    bytes of presence bits and the status word of every row), popcount on the host.  A row whose status is set - an int64 value outside
+    0 .. 255 - is counted by ``torch.unique`` instead."""
+    _chk_label_segments(labels, "labels", _LABEL_MAP_BYTES)
+    S = labels.shape[0]
+    packed = torch.empty((S * 9,), dtype=torch.int32, device=labels.device)   # words [S, 8], then status [S]: one copy brings both
+    _label_presence_into(labels, packed[: S * 8], packed[S * 8:])
+    host = packed.cpu().numpy()
+    words, status = host[: S * 8].view(np.uint8).reshape(S, 32), host[S * 8:]
+    counts = np.unpackbits(words, axis=1).sum(axis=1)
+    return [int(counts[s]) if status[s] == 0 else int(torch.unique(labels[s]).shape[0]) for s in range(S)]
+
+
+def map_instances(labels: torch.Tensor, cat: torch.Tensor, sequential: bool = True, out: Optional[torch.Tensor] = None):
+    """The YouTube-VOS instance -> category remap (``data_loader.map_instances``, reference ``:497-506``) of S clips in two launches.
+    labels uint8 [S, P]; cat int32 [S, 256], the category of each object id of row s's video, -1 = not in the meta file.  Returns
+    ``(mapped uint8 [S, P], lut uint8 [S, 256], status int32 [S])``; the table is ``data_loader.compose_instance_lut``'s: ``sequential``
+    reproduces the reference's chained in-place loop, otherwise ``v -> cat[v]``.  ``status[s]`` != 0: the smallest present object id without
+    a category; that row is copied unmapped.  ``out``: a uint8 tensor of labels' shape to write into, not overlapping labels (tests)."""
+    lib = _lib.load()
+    _chk_label_segments(labels, "labels", (torch.uint8,))
+    _chk(cat, "cat", torch.int32)
+    S, P = labels.shape
+    if tuple(cat.shape) != (S, 256):
+        raise ValueError(f"cat: expected [{S}, 256], got {tuple(cat.shape)}")
+    if out is None:
+        out = torch.empty_like(labels)
+    elif out.shape != labels.shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != labels.device:
+        raise ValueError(f"map_instances: out must be a contiguous uint8 tensor {tuple(labels.shape)} on {labels.device}")
+    lut = torch.empty((S, 256), dtype=torch.uint8, device=labels.device)
+    status = torch.empty((S,), dtype=torch.int32, device=labels.device)
+    ws_bytes = int(lib.tt_map_instances_workspace_bytes(S))
+    ws = _ws(ws_bytes, labels.device)
+    with torch.cuda.device(labels.device):
+        _lib.check(lib.tt_map_instances(_p(labels), _p(out), _p(cat), S, P, 1 if sequential else 0, _p(lut), _p(status), _p(ws), ws_bytes,
+                                        _stream()), "tt_map_instances")
+    return out, lut, status
