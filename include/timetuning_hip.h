@@ -1067,6 +1067,46 @@ int tt_jpeg_decode_batch(const int16_t* coeffs, long long n_coeffs, const uint16
                          const tt_jpeg_frame* frame_table_dev, int n_frames, uint8_t* out, long long out_bytes, void* workspace,
                          size_t workspace_bytes, tt_stream_t stream);
 
+/* ---- N24: the Huffman streams decoded on the device.  tt_jpeg_prepare (host, jpeg_scan.cpp: no state, no allocation, every read and
+   write checked) copies a file's scan once without decoding it - stuffing and fill bytes dropped, cut at the RSTn markers, every restart
+   segment on a 4-byte boundary - behind the DHT bytes of its six tables; tt_jpeg_entropy_batch (jpeg_entropy.hip) turns the streams of
+   a batch into the SAME int16 coefficients tt_jpeg_scan writes, which tt_jpeg_decode_batch reads where they lie.  The scheme, its
+   bounds and the status rules: csrc/jpeg_huff.hpp, DESIGN.md N24.
+   One row per frame.  scan_off / huff_off: bytes into `scan` (multiples of 4) of the frame's clean stream (scan_len bytes) and of its
+   tables (6 x 272 bytes: 16 counts + 256 values of the DC, AC table of component 0, 1, 2).  Rows seg_off ... seg_off + n_segments - 1 of
+   the segment table (uint32 [n][2]) hold each segment's start in bytes from scan_off (a multiple of 4) and its length in bits.
+   restart: MCUs per segment, 0 = no DRI.  coeff_off: as in tt_jpeg_frame. */
+typedef struct {
+  int64_t H, W, sampling, restart;
+  int64_t scan_off, scan_len, huff_off;
+  int64_t seg_off, n_segments;
+  int64_t coeff_off[3];
+  int64_t reserved[4];
+} tt_jpeg_stream;
+/* The capacities tt_jpeg_prepare needs for a file of `len` bytes, from len alone: bytes of `scan`, rows of `segs`. */
+int tt_jpeg_prepare_bytes(size_t len, size_t* scan_bytes, size_t* n_segments);
+/* Status as tt_jpeg_scan's (a missing or misnumbered RSTn: TT_JPEG_ERESTART; a capacity too small: TT_JPEG_EARGUMENT).  Writes the
+   tables at scan[0], the stream behind them, the segment rows from segs[0], the row with offsets RELATIVE to these two (huff_off 0,
+   scan_off 1632, seg_off 0, coeff_off from 0: the caller adds where it put them) and qtables as tt_jpeg_scan does. */
+int tt_jpeg_prepare(const uint8_t* data, size_t len, uint8_t* scan, size_t scan_capacity, uint32_t* segs, size_t seg_capacity,
+                    tt_jpeg_stream* row, uint16_t* qtables);
+/* Bytes of workspace of a batch (per frame four int32 of statistics: rounds, tiles, subsequences, the first failing subsequence or -1);
+   0: bad arguments.  Pure host function. */
+size_t tt_jpeg_entropy_batch_workspace_bytes(const tt_jpeg_stream* stream_table, int n_frames, int subseq_bits);
+/* One workgroup per frame, one launch behind a memset of `coeffs` (all n_coeffs).  The HOST copies of the segment table and the stream
+   table are checked in full against scan_bytes, n_segs, n_coeffs and workspace_bytes before anything is launched (TT_EINVAL, no launch,
+   nothing written); the kernel reads the device copies.  subseq_bits: a multiple of 32 in [128, 4096].  status: device int32 [n_frames],
+   0 or the TT_JPEG_E* code of the frame's first error; a failed frame's coefficients are unspecified, the others' are not affected.
+   scan 4-byte, coeffs 16-byte aligned.  Allocates nothing, synchronises nothing. */
+int tt_jpeg_entropy_batch(const uint8_t* scan, long long scan_bytes, const uint32_t* segs_host, const uint32_t* segs_dev, long long n_segs,
+                          const tt_jpeg_stream* stream_table_host, const tt_jpeg_stream* stream_table_dev, int n_frames, int subseq_bits,
+                          int16_t* coeffs, long long n_coeffs, int32_t* status, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+/* The same arguments as host pointers (the *_dev ones and `stream` are not looked at): the emulation of the kernel, lane by lane through
+   the same header, bit-equal to it in coefficients, status and statistics.  No GPU call. */
+int tt_jpeg_entropy_host(const uint8_t* scan, long long scan_bytes, const uint32_t* segs_host, const uint32_t* segs_dev, long long n_segs,
+                         const tt_jpeg_stream* stream_table_host, const tt_jpeg_stream* stream_table_dev, int n_frames, int subseq_bits,
+                         int16_t* coeffs, long long n_coeffs, int32_t* status, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+
 /* ---- N22: ragged image kernels - the pixel work of the Pascal VOC reader (leoloader.py:241-264: Resize((S, S)) + ToTensor + Normalize of
    the image, Resize((R, R), NEAREST) + ToTensor of the palette PNG) for a batch whose items DIFFER in size, one launch per batch; bit-equal
    to Pillow like the tt_img_* entries above, whose arithmetic they share.

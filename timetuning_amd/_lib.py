@@ -211,6 +211,11 @@ SIGNATURES = {
     "tt_jpeg_scan": (c_i, [c_vp, c_sz, c_vp, c_ll, c_vp]),
     "tt_jpeg_decode_batch_workspace_bytes": (c_sz, [c_vp, c_i]),
     "tt_jpeg_decode_batch": (c_i, [c_vp, c_ll, c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_ll, c_vp, c_sz, c_vp]),
+    "tt_jpeg_prepare_bytes": (c_i, [c_sz, C.POINTER(c_sz), C.POINTER(c_sz)]),
+    "tt_jpeg_prepare": (c_i, [c_vp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp]),
+    "tt_jpeg_entropy_batch_workspace_bytes": (c_sz, [c_vp, c_i, c_i]),
+    "tt_jpeg_entropy_batch": (c_i, [c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_vp, c_i, c_i, c_vp, c_ll, c_vp, c_vp, c_sz, c_vp]),
+    "tt_jpeg_entropy_host": (c_i, [c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_vp, c_i, c_i, c_vp, c_ll, c_vp, c_vp, c_sz, c_vp]),
     "tt_img_resize_ragged_lds_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "tt_img_resize_ragged_shape_ok": (c_i, [c_i, c_i, c_i, c_i]),
     "tt_img_resize_ragged": (c_i, [c_vp, c_ll, c_vp, c_vp, c_i, c_vp, c_vp, c_ll, c_vp, c_vp, c_i, c_i, C.POINTER(C.c_float),

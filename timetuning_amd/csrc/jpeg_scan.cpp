@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "../../include/timetuning_hip.h"
+#include "jpeg_huff.hpp"
 
 namespace {
 
@@ -26,6 +27,8 @@ constexpr int kLook = 9;   // bits of the Huffman look-ahead table
 
 struct Huff {
   bool present = false;
+  uint8_t counts[16];           // the DHT segment's own bytes, for tt_jpeg_prepare
+  int nvals = 0;
   uint8_t vals[256];
   int32_t maxcode[18];          // largest code of each length, -1 = none
   int32_t valptr[17];           // vals index of the first code of each length
@@ -49,6 +52,8 @@ inline int rd16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 // false: the counts do not describe a prefix code
 bool build_huff(Huff& t, const uint8_t* bits, const uint8_t* vals, int n) {
   std::memcpy(t.vals, vals, (size_t)n);
+  std::memcpy(t.counts, bits, 16);
+  t.nvals = n;
   std::memset(t.look, 0, sizeof(t.look));
   int code = 0, k = 0;
   for (int len = 1; len <= 16; ++len) {
@@ -378,4 +383,219 @@ extern "C" int tt_jpeg_scan(const uint8_t* data, size_t len, int16_t* coeffs, lo
     }
   }
   return TT_JPEG_OK;
+}
+
+// ---- N24: the host half of the device entropy decode.  tt_jpeg_prepare copies the scan ONCE without decoding a bit (the runs between FF bytes whole: memchr, then memcpy):
+// stuffing and fill bytes dropped, cut at the RSTn markers (whose numbering it checks), every segment on a 4-byte boundary.  In front of
+// the stream it puts the DHT bytes of the six tables in use (jh::kHuffBytes).  tt_jpeg_entropy_host is the emulation of jpeg_entropy.hip:
+// the same phases through the same header (jpeg_huff.hpp), with loops over the lanes.
+extern "C" int tt_jpeg_prepare_bytes(size_t len, size_t* scan_bytes, size_t* n_segments) {
+  // every boundary drops a 2-byte marker and pads at most 3 bytes: at most len / 2 boundaries, one byte more each
+  if (scan_bytes) *scan_bytes = ((size_t)tt::jh::kHuffBytes + len + len / 2 + 8 + 3) / 4 * 4;
+  if (n_segments) *n_segments = len / 2 + 1;
+  return TT_JPEG_OK;
+}
+
+extern "C" int tt_jpeg_prepare(const uint8_t* data, size_t len, uint8_t* scan, size_t scan_capacity, uint32_t* segs, size_t seg_capacity,
+                               tt_jpeg_stream* row, uint16_t* qtables) {
+  namespace jh = tt::jh;
+  Header hd;
+  const int rc = parse_header(data, len, hd);
+  if (rc != 0) return rc;
+  if (!scan || !segs || !row || !qtables || scan_capacity < (size_t)jh::kHuffBytes) return TT_JPEG_EARGUMENT;
+  std::memset(row, 0, sizeof(*row));
+  row->H = hd.H;
+  row->W = hd.W;
+  row->sampling = hd.sampling;
+  row->restart = hd.restart;
+  long long total = 0;
+  for (int c = 0; c < 3; ++c) {
+    long long r, q;
+    grid(hd, c, &r, &q);
+    row->coeff_off[c] = total;
+    total += r * q * 64;
+    std::memcpy(qtables + 64 * c, hd.q[hd.tq[c]], sizeof(uint16_t) * 64);
+    const Huff* two[2] = {&hd.dc[hd.td[c]], &hd.ac[hd.ta[c]]};
+    for (int k = 0; k < 2; ++k) {
+      uint8_t* dst = scan + (2 * c + k) * jh::kDht;
+      std::memset(dst, 0, (size_t)jh::kDht);
+      std::memcpy(dst, two[k]->counts, 16);
+      std::memcpy(dst + 16, two[k]->vals, (size_t)two[k]->nvals);
+    }
+  }
+  const jh::Frame f = jh::make_frame(*row);
+  if ((size_t)f.n_segments > seg_capacity) return TT_JPEG_EARGUMENT;
+  row->huff_off = 0;
+  row->scan_off = jh::kHuffBytes;
+  row->seg_off = 0;
+  row->n_segments = f.n_segments;
+  uint8_t* out = scan + jh::kHuffBytes;
+  const size_t cap = scan_capacity - (size_t)jh::kHuffBytes;
+  size_t w = 0, seg_start = 0, pos = hd.scan_pos;
+  uint32_t seg = 0;
+  bool closed = false;
+  while (!closed) {
+    int marker = -1;   // -1 none, 0 the data ended
+    if (pos >= len) {
+      marker = 0;
+    } else {
+      const uint8_t b = data[pos];
+      if (b != 0xFF) {   // the run up to the next FF in one copy
+        const void* ff = std::memchr(data + pos, 0xFF, len - pos);
+        const size_t run = ff ? (size_t)(static_cast<const uint8_t*>(ff) - (data + pos)) : len - pos;
+        if (run > cap - w) return TT_JPEG_EARGUMENT;
+        std::memcpy(out + w, data + pos, run);
+        w += run;
+        pos += run;
+      } else if (pos + 1 >= len) {
+        marker = 0;
+      } else if (data[pos + 1] == 0x00) {   // a stuffed FF
+        if (w >= cap) return TT_JPEG_EARGUMENT;
+        out[w++] = 0xFF;
+        pos += 2;
+      } else if (data[pos + 1] == 0xFF) {   // a fill byte
+        ++pos;
+      } else {
+        marker = data[pos + 1];
+      }
+    }
+    if (marker < 0) continue;
+    if ((w - seg_start) * 8 > (size_t)jh::kMaxSegBits) return TT_JPEG_EARGUMENT;
+    segs[2 * seg] = (uint32_t)seg_start;
+    segs[2 * seg + 1] = (uint32_t)((w - seg_start) * 8);
+    while (w % 4) {
+      if (w >= cap) return TT_JPEG_EARGUMENT;
+      out[w++] = 0;
+    }
+    if (seg + 1 == f.n_segments) {
+      closed = true;   // whatever follows the last interval is not looked at, as in tt_jpeg_scan
+    } else {
+      if (marker == 0) return TT_JPEG_ETRUNCATED;
+      if (marker != 0xD0 + (int)(seg & 7u)) return TT_JPEG_ERESTART;
+      pos += 2;
+      ++seg;
+      seg_start = w;
+      if (seg_start > 0xfffffff0u) return TT_JPEG_EARGUMENT;
+    }
+  }
+  row->scan_len = (int64_t)w;
+  return TT_JPEG_OK;
+}
+
+namespace {
+
+// One frame, as one workgroup of jh::kTile lanes runs it (jpeg_entropy.hip: the same steps, the loops over i are its lanes).
+int entropy_frame(const uint8_t* scan, const uint32_t* segs, const tt_jpeg_stream& row, uint32_t S, int16_t* coeffs, int32_t* stats) {
+  namespace jh = tt::jh;
+  constexpr int T = jh::kTile;
+  const jh::Frame f = jh::make_frame(row);
+  static_assert(sizeof(jh::Table) * 6 < 16384, "the tables fit the stack");
+  jh::Table tabs[6];
+  const uint8_t* dht = scan + row.huff_off;
+  for (int t = 0; t < 6; ++t) {
+    std::memcpy(tabs[t].vals, dht + t * jh::kDht + 16, 256);
+    jh::build_codes(tabs[t], dht + t * jh::kDht);
+    for (int v = 0; v < (1 << jh::kLook); ++v) tabs[t].look[v] = jh::look_entry(tabs[t], v);
+  }
+  const uint32_t* stream = reinterpret_cast<const uint32_t*>(scan + row.scan_off);
+  const uint32_t* sg = segs + 2 * row.seg_off;
+  uint32_t cur_seg = 0, cur_sub = 0, carry_p = 0, carry_q = 0, carry_blocks = 0;
+  int status = 0, rounds = 0, tiles = 0, first_bad = -1;
+  long long subs = 0;
+  uint32_t l_seg[T], l_sub[T], ex_p[T], ex_q[T], l_cnt[T], l_n0[T];
+  jh::State entry[T];
+  bool dirty[T];
+  while (cur_seg < f.n_segments && status == 0) {
+    int n = 0;
+    while (n < T && cur_seg < f.n_segments) {
+      l_seg[n] = cur_seg;
+      l_sub[n] = cur_sub;
+      ++n;
+      if (++cur_sub >= jh::subsequences(sg[2 * cur_seg + 1], S)) {
+        ++cur_seg;
+        cur_sub = 0;
+      }
+    }
+    for (int i = 0; i < n; ++i) {
+      entry[i] = l_sub[i] == 0 ? jh::State{0, 0, 0, 0} : (i == 0 ? jh::unpack(carry_p, carry_q) : jh::State{l_sub[i] * S, 0, 0, 0});
+      dirty[i] = true;
+    }
+    for (int round = 0; round <= T; ++round) {
+      for (int i = 0; i < n; ++i) {
+        if (!dirty[i]) continue;
+        const uint32_t bits = sg[2 * l_seg[i] + 1], end = (l_sub[i] + 1) * S < bits ? (l_sub[i] + 1) * S : bits;
+        jh::State s = entry[i];
+        l_cnt[i] = jh::run_count(tabs, f, stream + sg[2 * l_seg[i]] / 4, bits, s, end, l_seg[i]);
+        ex_p[i] = s.p;
+        ex_q[i] = jh::pack(s);
+      }
+      bool any = false;
+      for (int i = 0; i < n; ++i) {
+        dirty[i] = false;
+        if (i == 0 || l_sub[i] == 0) continue;
+        if (ex_p[i - 1] != entry[i].p || ex_q[i - 1] != jh::pack(entry[i])) {
+          entry[i] = jh::unpack(ex_p[i - 1], ex_q[i - 1]);
+          dirty[i] = any = true;
+        }
+      }
+      if (!any) break;
+      ++rounds;
+    }
+    for (int i = 0; i < n; ++i) {
+      uint32_t n0 = 0;
+      int u = i - 1;
+      for (; u >= 0 && l_seg[u] == l_seg[i]; --u) n0 += l_cnt[u];
+      if (u < 0 && l_sub[i] > (uint32_t)i) n0 += carry_blocks;
+      l_n0[i] = n0;
+    }
+    for (int i = 0; i < n; ++i) {
+      const uint32_t bits = sg[2 * l_seg[i] + 1], end = (l_sub[i] + 1) * S < bits ? (l_sub[i] + 1) * S : bits;
+      const int e = jh::run_write(tabs, f, stream + sg[2 * l_seg[i]] / 4, bits, entry[i], end, l_seg[i], l_n0[i], coeffs);
+      if (e && status == 0) {
+        status = e;
+        first_bad = (int)(subs + i);
+      }
+    }
+    carry_p = ex_p[n - 1];
+    carry_q = ex_q[n - 1];
+    carry_blocks = l_n0[n - 1] + l_cnt[n - 1];
+    subs += n;
+    ++tiles;
+  }
+  if (status == 0)
+    for (int c = 0; c < 3; ++c) jh::dc_apply(f, coeffs, c, 0, jh::dc_blocks(f, c), 0);
+  if (stats) {
+    stats[0] = rounds;
+    stats[1] = tiles;
+    stats[2] = (int32_t)subs;
+    stats[3] = first_bad;
+  }
+  return status;
+}
+
+}  // namespace
+
+// (a pure host function, so it lives here: the sanitizer program links this file alone)
+extern "C" size_t tt_jpeg_entropy_batch_workspace_bytes(const tt_jpeg_stream* stream_table, int n_frames, int subseq_bits) {
+  namespace jh = tt::jh;
+  if (!stream_table || n_frames < 1 || n_frames > 65535 || subseq_bits < jh::kMinSubseq || subseq_bits > jh::kMaxSubseq || subseq_bits % 32) return 0;
+  return jh::workspace_bytes(n_frames);
+}
+
+extern "C" int tt_jpeg_entropy_host(const uint8_t* scan, long long scan_bytes, const uint32_t* segs, const uint32_t* segs_again, long long n_segs,
+                                    const tt_jpeg_stream* stream_table, const tt_jpeg_stream* stream_table_again, int n_frames, int subseq_bits,
+                                    int16_t* coeffs, long long n_coeffs, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  (void)segs_again;
+  (void)stream_table_again;
+  (void)stream;
+  char msg[256];
+  if (!scan || !coeffs || !status || !workspace || (reinterpret_cast<uintptr_t>(scan) & 3u) || (reinterpret_cast<uintptr_t>(workspace) & 3u))
+    return TT_EINVAL;
+  if (tt::jh::validate(scan_bytes, segs, n_segs, stream_table, n_frames, subseq_bits, n_coeffs, msg, sizeof(msg)) != 0) return TT_EINVAL;
+  if (workspace_bytes < tt::jh::workspace_bytes(n_frames)) return TT_EINVAL;
+  std::memset(coeffs, 0, sizeof(int16_t) * (size_t)n_coeffs);
+  int32_t* stats = static_cast<int32_t*>(workspace);
+  for (int i = 0; i < n_frames; ++i)
+    status[i] = entropy_frame(scan, segs, stream_table[i], (uint32_t)subseq_bits, coeffs, stats + i * tt::jh::kStatWords);
+  return TT_OK;
 }

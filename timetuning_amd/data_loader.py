@@ -176,14 +176,19 @@ class _HostBatch:
 
 class VideoDataset:
     """``VideoDataset(classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, ...)`` (``:552``).  ``rng`` draws the
-    frame indices (default: the ``random`` module, as in the reference); ``device`` and ``threads`` belong to the decode.
+    frame indices (default: the ``random`` module, as in the reference); ``device`` and ``threads`` belong to the decode, and so does
+    ``jpeg_entropy``: "host" undoes the Huffman coding in the thread pool (``hip_ops.jpeg_scan_batch``), "device" copies the compressed
+    scans and undoes it in one launch (``hip_ops.jpeg_prepare_batch`` / ``jpeg_decode_prepared``) - the same pixels either way.
     ``meta_file_directory`` (``:563-573``): the path of a YouTube-VOS ``meta.json``; when the file exists the annotations' per-video
     instance ids become dataset-wide category ids (``map_categories``), ``sequential_category_map`` choosing the rule of
     ``compose_instance_lut``.  A path that does not exist prints "There is no meta file." and maps nothing, as in the reference."""
 
     def __init__(self, classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, num_labels=1, frame_transform=None,
                  target_transform=None, video_transform=None, meta_file_directory=None, regular_step=1, device=None, threads=8, rng=None,
-                 sequential_category_map=True):
+                 sequential_category_map=True, jpeg_entropy="host"):
+        if jpeg_entropy not in ("host", "device"):
+            raise ValueError(f"jpeg_entropy must be 'host' or 'device', not {jpeg_entropy!r}")
+        self.jpeg_entropy = jpeg_entropy
         if num_labels != 1:
             raise NotImplementedError("nested class directories (num_labels > 1) are not reproduced")
         self.meta_dict, self.category_dict, self.category_tables = None, None, None
@@ -239,7 +244,7 @@ class VideoDataset:
             annotations = [np.stack([decode_annotation(_read(afiles[j])) for j in clip]) for clip in clip_indices]
         return _HostSample(frames, annotations, np.tile(self.train_dict[path], (self.num_clips,)), idx)
 
-    def scan_host(self, samples: List[_HostSample]) -> _HostBatch:
+    def scan_host(self, samples: List[_HostSample], jpeg_entropy: Optional[str] = None) -> _HostBatch:
         """Classifies every frame of the samples, entropy-decodes the supported ones into one pinned buffer and decodes the others with
         Pillow."""
         flat = [f for s in samples for clip in s.frames for f in clip]
@@ -250,7 +255,8 @@ class VideoDataset:
                 supported.append(data)
             else:
                 host_frames[k] = decode_frame_on_host(data)
-        scanned = ops.jpeg_scan_batch(supported, self.threads) if supported else None
+        scan = ops.jpeg_prepare_batch if (jpeg_entropy or self.jpeg_entropy) == "device" else ops.jpeg_scan_batch   # a loader may choose for itself
+        scanned = scan(supported, self.threads) if supported else None
         return _HostBatch(samples, scanned, device_slots, host_frames)
 
     # ---- device half: reconstruction, transforms
@@ -258,7 +264,8 @@ class VideoDataset:
         """-> per sample (data, annotations, label) as ``__getitem__`` returns them."""
         flat = [None] * (len(batch.device_slots) + len(batch.host_frames))
         if batch.scanned is not None:
-            for k, f in zip(batch.device_slots, ops.jpeg_decode_scanned(batch.scanned, self.device)):
+            decode = ops.jpeg_decode_prepared if isinstance(batch.scanned, ops.JpegStreamBatch) else ops.jpeg_decode_scanned
+            for k, f in zip(batch.device_slots, decode(batch.scanned, self.device)):
                 flat[k] = f
         for k, arr in batch.host_frames.items():
             flat[k] = torch.from_numpy(arr).to(self.device)
@@ -337,7 +344,10 @@ class ClipLoader:
     (``drop_last=False``, the DataLoader default)."""
 
     def __init__(self, dataset: VideoDataset, batch_size: int, shuffle: bool = False, world_size: int = 1, rank: int = 0, seed: int = 0,
-                 prefetch: bool = True):
+                 prefetch: bool = True, jpeg_entropy: Optional[str] = None):
+        if jpeg_entropy not in (None, "host", "device"):
+            raise ValueError(f"jpeg_entropy must be 'host' or 'device', not {jpeg_entropy!r}")
+        self.jpeg_entropy = dataset.jpeg_entropy if jpeg_entropy is None else jpeg_entropy   # the loader's own: the dataset is not touched
         self.dataset, self.batch_size, self.shuffle, self.world_size, self.rank, self.seed = dataset, int(batch_size), shuffle, world_size, rank, seed
         self.prefetch, self.epoch = prefetch, 0
         self.rng = random.Random(seed * 1000003 + rank)
@@ -372,8 +382,8 @@ class ClipLoader:
         dev = self.dataset.device
         if dev is not None and torch.device(dev).type == "cuda":
             with torch.cuda.device(dev):   # a new thread starts on device 0: the pinned buffers belong to this rank's device
-                return self.dataset.scan_host([self.dataset.read_host(i, self.rng) for i in indices])
-        return self.dataset.scan_host([self.dataset.read_host(i, self.rng) for i in indices])
+                return self.dataset.scan_host([self.dataset.read_host(i, self.rng) for i in indices], self.jpeg_entropy)
+        return self.dataset.scan_host([self.dataset.read_host(i, self.rng) for i in indices], self.jpeg_entropy)
 
     def __iter__(self):
         order = self._order()
@@ -399,10 +409,11 @@ class ClipLoader:
 
 def make_loader(dataset_path: str, num_clip_frames: int, batch_size: int, regular_step: int = 1, sampling_mode: SamplingMode = SamplingMode.UNIFORM,
                 frame_transform=None, target_transform=None, video_transform=None, shuffle: bool = False, num_workers: int = 6, world_size: int = 1,
-                rank: int = 0, device=None, seed: int = 0, meta_file_directory=None, sequential_category_map: bool = True) -> ClipLoader:
+                rank: int = 0, device=None, seed: int = 0, meta_file_directory=None, sequential_category_map: bool = True,
+                jpeg_entropy: str = "host") -> ClipLoader:
     """``make_loader`` (``:1047``) for the layout every ``VideoDataset`` branch of it reads: frames under ``<dataset_path>/JPEGImages/``,
     annotations under ``<dataset_path>/Annotations/`` when present.  ``num_workers`` is the thread count of the host decode (at most 16
-    are used).  ``meta_file_directory``: the path of a YouTube-VOS ``meta.json`` - a ``YVOSDataset`` then maps instance ids to category
+    are used); ``jpeg_entropy`` "host" / "device": where the frames' Huffman coding is undone (``VideoDataset``).  ``meta_file_directory``: the path of a YouTube-VOS ``meta.json`` - a ``YVOSDataset`` then maps instance ids to category
     ids (the ``ytvos`` branches, ``:1073-1090``).  It is never looked for: without the argument a tree that holds one is read as before."""
     frames = os.path.join(dataset_path, "JPEGImages")
     if not os.path.isdir(frames):
@@ -413,5 +424,5 @@ def make_loader(dataset_path: str, num_clip_frames: int, batch_size: int, regula
     cls = VideoDataset if meta_file_directory is None else YVOSDataset
     dataset = cls(frames, os.path.join(dataset_path, "Annotations"), sampling_mode, 1, num_clip_frames, 1, frame_transform,
                   target_transform, video_transform, meta_file_directory=meta_file_directory, regular_step=regular_step, device=device,
-                  threads=num_workers, sequential_category_map=sequential_category_map)
+                  threads=num_workers, sequential_category_map=sequential_category_map, jpeg_entropy=jpeg_entropy)
     return ClipLoader(dataset, batch_size, shuffle=shuffle, world_size=world_size, rank=rank, seed=seed)

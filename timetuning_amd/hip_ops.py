@@ -2569,11 +2569,186 @@ def jpeg_decode_scanned(batch: JpegHostBatch, device=None):
     return [stacks[key][k] for key, k in batch.where]
 
 
-def decode_jpeg_batch(files: Sequence[bytes], device=None, threads: int = 8):
+# ---- N24: the Huffman streams decoded on the device.  The host copies each scan once (tt_jpeg_prepare, in the same pool), what crosses
+# PCIe is the compressed stream, and tt_jpeg_entropy_batch leaves the coefficients where tt_jpeg_decode_batch reads them.
+JPEG_SUBSEQ_BITS = 2048   # bits of stream per lane: the default ``subseq_bits`` (profiles/n24_jpeg_entropy.txt); an argument, not a state
+_JPEG_STREAM_ROW = 16     # int64 words of one tt_jpeg_stream
+
+
+class JpegStreamBatch:
+    """The host half of a batch for the device entropy decode: ONE pinned buffer (``meta``: the stream table, the frame table, the
+    quantisation tables, the segment table, then every file's Huffman tables and clean stream) and the output layout."""
+
+    def __init__(self, infos, meta, layout, n_segs, n_coeffs, out_bytes, groups, where):
+        self.infos, self.meta, self.layout, self.n_segs, self.n_coeffs = infos, meta, layout, n_segs, n_coeffs
+        self.out_bytes, self.groups, self.where = out_bytes, groups, where
+
+    def part(self, name):
+        """A uint8 NumPy view of one part of the pinned buffer: 'streams', 'frames', 'qtables', 'segs' or 'scan'."""
+        at, size = self.layout[name]
+        return self.meta.numpy()[at:at + size]
+
+
+def jpeg_prepare_batch(files: Sequence[bytes], threads: int = 8, pin: bool = True) -> JpegStreamBatch:
+    """Probes every file and copies its scan, cleaned and cut at the restart markers, into ONE (pinned) buffer in a pool of min(threads,
+    16) threads - the pool and the pinned-buffer scheme of ``jpeg_scan_batch``; nothing is decoded.  Raises JpegUnsupported for the
+    first unsupported file and ValueError for the first broken one (markers and restart numbering; the codes themselves are the
+    device's to judge)."""
+    lib = _lib.load()
+    files = [bytes(f) for f in files]
+    n = len(files)
+    if n == 0:
+        raise ValueError("jpeg_prepare_batch: no files")
+    workers = max(1, min(int(threads), JPEG_MAX_THREADS, n))
+    chunks = [range(k * n // workers, (k + 1) * n // workers) for k in range(workers)]
+    run = (lambda fn: [fn(c) for c in chunks]) if workers == 1 else (lambda fn: list(_jpeg_pool(workers).map(fn, chunks)))
+    infos = [info for part in run(lambda chunk: [_jpeg_probe_raw(lib, files[i]) for i in chunk]) for info in part]
+    for i, info in enumerate(infos):
+        if info.status < 0:
+            raise _jpeg_malformed(info.status, i)
+        if not info.supported:
+            raise JpegUnsupported(info.status, i)
+    scan_cap, seg_cap = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+    a, b = C.c_size_t(), C.c_size_t()
+    for i, f in enumerate(files):
+        lib.tt_jpeg_prepare_bytes(len(f), C.byref(a), C.byref(b))
+        hmax, vmax = (1 if infos[i].sampling == 0 else 2), (2 if infos[i].sampling == 2 else 1)
+        mcus = -(-infos[i].W // (8 * hmax)) * -(-infos[i].H // (8 * vmax))
+        # a frame has at most one segment per MCU, and a boundary costs the stream at most one byte: tighter than the bound from len alone
+        scan_cap[i + 1], seg_cap[i + 1] = min(a.value, -(-(1632 + len(f) + mcus + 8) // 4) * 4), min(b.value, mcus)
+    np.cumsum(scan_cap, out=scan_cap)
+    np.cumsum(seg_cap, out=seg_cap)
+    layout, at = {}, 0
+    for name, size in (("streams", n * _JPEG_STREAM_ROW * 8), ("frames", n * _JPEG_ROW * 8), ("qtables", n * 3 * 64 * 2),
+                       ("segs", int(seg_cap[-1]) * 8), ("scan", int(scan_cap[-1]))):
+        layout[name] = (at, size)
+        at += -(-size // 16) * 16
+    meta = torch.zeros(at, dtype=torch.uint8, pin_memory=pin)
+    base = meta.data_ptr()
+    streams = meta.numpy()[layout["streams"][0]:layout["streams"][0] + layout["streams"][1]].view(np.int64).reshape(n, _JPEG_STREAM_ROW)
+    table = meta.numpy()[layout["frames"][0]:layout["frames"][0] + layout["frames"][1]].view(np.int64).reshape(n, _JPEG_ROW)
+    scan_at, segs_at, q_at, rows_at = base + layout["scan"][0], base + layout["segs"][0], base + layout["qtables"][0], base + layout["streams"][0]
+    sc, sg = scan_cap.tolist(), seg_cap.tolist()      # plain ints: the loop below runs once per file
+
+    def prepare(chunk):
+        return [lib.tt_jpeg_prepare(files[i], len(files[i]), scan_at + sc[i], sc[i + 1] - sc[i], segs_at + 8 * sg[i], sg[i + 1] - sg[i],
+                                    rows_at + i * _JPEG_STREAM_ROW * 8, q_at + i * 3 * 64 * 2) for i in chunk]
+
+    for i, rc in enumerate(rc for part in run(prepare) for rc in part):
+        if rc < 0:
+            raise _jpeg_malformed(rc, i)
+        if rc > 0:
+            raise JpegUnsupported(rc, i)
+    coeff_off = np.zeros(n + 1, np.int64)
+    np.cumsum([info.n_coeffs for info in infos], out=coeff_off[1:])
+    groups, where = {}, []
+    for i, info in enumerate(infos):
+        members = groups.setdefault((info.H, info.W), [])
+        where.append(((info.H, info.W), len(members)))
+        members.append(i)
+    out_bytes, group_base, plane_at = 0, {}, 0
+    for key, members in groups.items():
+        group_base[key] = out_bytes
+        out_bytes += -(-len(members) * key[0] * key[1] * 3 // 16) * 16
+    for i, info in enumerate(infos):
+        srow, row = streams[i], table[i]
+        srow[4] += scan_cap[i]       # scan_off, huff_off, seg_off: from the file's slot to the buffers
+        srow[6] += scan_cap[i]
+        srow[7] += seg_cap[i]
+        srow[9:12] += coeff_off[i]
+        row[0], row[1], row[2] = info.H, info.W, info.sampling
+        for c in range(3):
+            rows, cols = _jpeg_grid(info.H, info.W, info.sampling, c)
+            row[3 + c], row[6 + c], row[9 + c] = srow[9 + c], 3 * i + c, plane_at
+            plane_at += rows * cols * 64
+        key, k = where[i]
+        row[12] = group_base[key] + k * info.H * info.W * 3
+    return JpegStreamBatch(infos, meta, layout, int(seg_cap[-1]), int(coeff_off[-1]), out_bytes,
+                           {k: (group_base[k], len(m)) for k, m in groups.items()}, where)
+
+
+def _jpeg_subseq_bits(subseq_bits) -> int:
+    bits = JPEG_SUBSEQ_BITS if subseq_bits is None else int(subseq_bits)
+    if bits % 32 or not 128 <= bits <= 4096:
+        raise ValueError(f"jpeg entropy decode: subseq_bits {bits} is not a multiple of 32 in [128, 4096]")
+    return bits
+
+
+def jpeg_entropy_host(batch: JpegStreamBatch, subseq_bits=None):
+    """The host emulation of the device entropy decode (tt_jpeg_entropy_host: the kernel's phases lane by lane through the same header),
+    for tests and tools: (coefficients int16 [n_coeffs], status int32 [n], statistics int32 [n, 4] = rounds, tiles, subsequences, the
+    first failing subsequence).  Raises nothing for a broken stream: the status says it."""
+    lib, n, bits = _lib.load(), len(batch.infos), _jpeg_subseq_bits(subseq_bits)
+    coeffs, status = np.empty(max(batch.n_coeffs, 1), np.int16), np.zeros(n, np.int32)
+    streams, segs, scan = batch.part("streams"), batch.part("segs"), batch.part("scan")
+    ws = np.zeros(int(lib.tt_jpeg_entropy_batch_workspace_bytes(streams.ctypes.data, n, bits)) // 4, np.int32)
+    _lib.check(lib.tt_jpeg_entropy_host(scan.ctypes.data, scan.size, segs.ctypes.data, segs.ctypes.data, batch.n_segs, streams.ctypes.data,
+                                        streams.ctypes.data, n, bits, coeffs.ctypes.data, batch.n_coeffs, status.ctypes.data, ws.ctypes.data,
+                                        ws.nbytes, None), "tt_jpeg_entropy_host")
+    return coeffs[:batch.n_coeffs], status, ws[:4 * n].reshape(n, 4)
+
+
+def jpeg_entropy_decode(batch: JpegStreamBatch, device=None, subseq_bits=None, stats: bool = False):
+    """The device entropy decode: one host-to-device copy of the batch's buffer (the compressed streams and their tables), a memset and
+    one launch on the current stream, then ONE read-back of 4 n bytes - the frames' status.  Returns (coefficients int16 [n_coeffs] on the
+    device, in the layout of the batch's frame table; status int32 [n] on the host; the batch's buffer on the device).  A negative status
+    raises ValueError naming the file.  ``stats``: the per-frame statistics (rounds, tiles, subsequences, -1) as a fourth item."""
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise _lib.HipLibraryError("jpeg_entropy_decode: needs a GPU (the HIP path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    n, bits = len(batch.infos), _jpeg_subseq_bits(subseq_bits)
+    streams, segs = batch.part("streams"), batch.part("segs")
+    ws_bytes = int(lib.tt_jpeg_entropy_batch_workspace_bytes(streams.ctypes.data, n, bits))
+    with torch.cuda.device(dev):
+        meta = batch.meta.to(dev, non_blocking=True)
+        coeffs = torch.empty(max(batch.n_coeffs, 8), dtype=torch.int16, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if stats else _ws(ws_bytes, dev)
+        at = lambda name: meta.data_ptr() + batch.layout[name][0]
+        _lib.check(lib.tt_jpeg_entropy_batch(at("scan"), batch.layout["scan"][1], segs.ctypes.data, at("segs"), batch.n_segs, streams.ctypes.data,
+                                             at("streams"), n, bits, _p(coeffs), batch.n_coeffs, _p(status), _p(ws), ws.numel(), _stream()),
+                   "tt_jpeg_entropy_batch")
+        host_status = status.cpu().numpy()
+    for i, rc in enumerate(host_status):
+        if rc < 0:
+            raise _jpeg_malformed(int(rc), i)
+    if stats:
+        return coeffs, host_status, meta, ws[:16 * n].view(torch.int32).view(n, 4).cpu().numpy()
+    return coeffs, host_status, meta
+
+
+def jpeg_decode_prepared(batch: JpegStreamBatch, device=None, subseq_bits=None):
+    """prepare's batch -> frames: the entropy launch, then tt_jpeg_decode_batch on the device-resident coefficients (no coefficient
+    copy).  The frames come back as ``jpeg_decode_scanned`` returns them."""
+    lib = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    n = len(batch.infos)
+    table = batch.part("frames")
+    ws_bytes = int(lib.tt_jpeg_decode_batch_workspace_bytes(table.ctypes.data, n))
+    if ws_bytes == 0:
+        raise ValueError("decode_jpeg_batch: the descriptor table holds a row that is not a frame")
+    coeffs, _, meta = jpeg_entropy_decode(batch, dev, subseq_bits)
+    with torch.cuda.device(dev):
+        out = torch.empty(max(batch.out_bytes, 16), dtype=torch.uint8, device=dev)
+        ws = _ws(ws_bytes, dev)
+        _lib.check(lib.tt_jpeg_decode_batch(_p(coeffs), batch.n_coeffs, meta.data_ptr() + batch.layout["qtables"][0], 3 * n, table.ctypes.data,
+                                            meta.data_ptr() + batch.layout["frames"][0], n, _p(out), out.numel(), _p(ws), ws.numel(), _stream()),
+                   "tt_jpeg_decode_batch")
+    stacks = {key: out[base:base + k * key[0] * key[1] * 3].view(k, key[0], key[1], 3) for key, (base, k) in batch.groups.items()}
+    return [stacks[key][k] for key, k in batch.where]
+
+
+def decode_jpeg_batch(files: Sequence[bytes], device=None, threads: int = 8, entropy: str = "host", subseq_bits=None):
     """JPEG files -> uint8 [H, W, 3] GPU tensors, bit-equal to Pillow's decode.  The frames may differ in size and sampling; those of one
     size come back as views of one [k, H, W, 3] tensor.  Unsupported files raise JpegUnsupported (no CPU fallback here), broken ones
-    ValueError."""
-    return jpeg_decode_scanned(jpeg_scan_batch(files, threads), device)
+    ValueError.  ``entropy``: "host" undoes the Huffman coding in the thread pool and copies coefficients; "device" copies the compressed
+    scans and undoes it in one launch (``subseq_bits``: bits of stream per lane, None = JPEG_SUBSEQ_BITS)."""
+    if entropy == "host":
+        return jpeg_decode_scanned(jpeg_scan_batch(files, threads), device)
+    if entropy != "device":
+        raise ValueError(f"decode_jpeg_batch: entropy must be 'host' or 'device', not {entropy!r}")
+    return jpeg_decode_prepared(jpeg_prepare_batch(files, threads), device, subseq_bits)
 
 
 def frames_as_clip(frames: Sequence[torch.Tensor]) -> torch.Tensor:

@@ -160,10 +160,13 @@ def train_transforms(train_size: int) -> Compose:
 class VOCDataset:
     """The reference's file layout and errors: ``root/images/<name>.jpg``, ``root/SegmentationClassAug/<name>.png`` for ``train`` /
     ``trainaug`` and ``root/SegmentationClass/<name>.png`` for ``val``, names from ``root/sets/<image_set>.txt`` in the file's order.
-    ``device`` and ``threads`` belong to the decode."""
+    ``device``, ``threads`` and ``jpeg_entropy`` ("host" / "device": where the Huffman coding is undone) belong to the decode."""
 
     def __init__(self, root: str, image_set: str = "trainaug", transform=None, target_transform=None, transforms=None, return_masks: bool = False,
-                 device=None, threads: int = 8):
+                 device=None, threads: int = 8, jpeg_entropy: str = "host"):
+        if jpeg_entropy not in ("host", "device"):
+            raise ValueError(f"jpeg_entropy must be 'host' or 'device', not {jpeg_entropy!r}")
+        self.jpeg_entropy = jpeg_entropy
         self.root, self.image_set = root, image_set
         if image_set == "trainaug" or image_set == "train":
             seg_folder = "SegmentationClassAug"
@@ -230,7 +233,8 @@ class VOCLoader:
             else:
                 host_frames[k] = decode_frame_on_host(data)
                 dims[k] = host_frames[k].shape[:2]
-        scanned = ops.jpeg_scan_batch(supported, ds.threads) if supported else None
+        scan = ops.jpeg_prepare_batch if ds.jpeg_entropy == "device" else ops.jpeg_scan_batch
+        scanned = scan(supported, ds.threads) if supported else None
         for k, info in zip(device_slots, scanned.infos if scanned else []):
             dims[k] = (info.H, info.W)
         masks = [decode_annotation(_read(ds.masks[i])) for i in indices]
@@ -256,7 +260,8 @@ class VOCLoader:
             raise ops._lib.HipLibraryError("pascal_loader: needs a GPU (the HIP path has no CPU fallback)")
         frames = [None] * host.n
         if host.scanned is not None:
-            for k, f in zip(host.device_slots, ops.jpeg_decode_scanned(host.scanned, ds.device)):
+            decode = ops.jpeg_decode_prepared if isinstance(host.scanned, ops.JpegStreamBatch) else ops.jpeg_decode_scanned
+            for k, f in zip(host.device_slots, decode(host.scanned, ds.device)):
                 frames[k] = f
         for k, arr in host.host_frames.items():
             frames[k] = torch.from_numpy(arr).to(ds.device)
@@ -295,10 +300,10 @@ class VOCLoader:
                 pool.shutdown(wait=True)
 
 
-def pascal_loader(batch_size, root, split, val_size, train_size=448, device=None, threads=8) -> VOCLoader:
+def pascal_loader(batch_size, root, split, val_size, train_size=448, device=None, threads=8, jpeg_entropy="host") -> VOCLoader:
     """``leoloader.pascal_loader`` (``:241-264``): both of its branches apply the same image and target transforms, so both splits read
     through one path; ``train_transforms`` is built and unused there, and is not used here."""
-    dataset = VOCDataset(root=root, image_set=split, return_masks=(split == 'trainaug'), device=device, threads=threads)
+    dataset = VOCDataset(root=root, image_set=split, return_masks=(split == 'trainaug'), device=device, threads=threads, jpeg_entropy=jpeg_entropy)
     return VOCLoader(dataset, batch_size, val_size, train_size)
 
 
