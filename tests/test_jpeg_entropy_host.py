@@ -68,6 +68,26 @@ def test_every_supported_file_equals_the_host_scan(files, scans, subseq_bits):
         assert sum(subs[n] == 1 for n in grid) > len(grid) // 2
 
 
+def test_both_builders_produce_the_same_tables(files):
+    """jpeg_scan_batch and jpeg_prepare_batch describe one batch alike: the frame table and the quantisation tables byte for byte, the
+    output layout, and the stream rows' coefficient offsets - what tt_jpeg_prepare wrote, moved to the file's place - equal to the frame
+    rows'.  Every sampling at a ragged size, a 1 x 1 file, restart intervals, and a group of two frames."""
+    names = list(load_files(ENTROPY)) + ["clip_v0_f0", "clip_v0_f1"] + [f"grid_9x15_{s}_q75_std" for s in ("444", "422", "420")] + ["grid_1x1_420_q75_std"]
+    data, n = [files[k] for k in names], len(names)
+    host, dev = hip_ops.jpeg_scan_batch(data, threads=2, pin=False), hip_ops.jpeg_prepare_batch(data, threads=2, pin=False)
+    assert (host.route, dev.route) == ("host", "device") and host.n_segs == 0 and dev.coeffs is None and host.coeffs.numel() == host.n_coeffs
+    assert host.part("frames").size == n * 128 and host.part("qtables").size == n * 3 * 64 * 2 and host.meta.numel() == n * (128 + 384)
+    for part in ("frames", "qtables"):
+        assert np.array_equal(host.part(part), dev.part(part)), part
+    assert host.groups == dev.groups and host.where == dev.where
+    assert host.out_bytes == dev.out_bytes and host.n_coeffs == dev.n_coeffs == sum(hip_ops.jpeg_probe(d).n_coeffs for d in data)
+    clip = hip_ops.jpeg_probe(files["clip_v0_f0"])
+    assert host.groups[(clip.H, clip.W)][1] >= 2 and host.where[6][1] == host.where[5][1] + 1
+    frames = host.part("frames").view(np.int64).reshape(n, 16)
+    assert np.array_equal(stream_rows(dev)[:, 9:12], frames[:, 3:6])
+    assert frames[:, 3].tolist() == np.cumsum([0] + [hip_ops.jpeg_probe(d).n_coeffs for d in data])[:-1].tolist()
+
+
 # ---- tt_jpeg_prepare
 def scan_start(data):
     """Offset of the first entropy-coded byte: behind the SOS segment."""

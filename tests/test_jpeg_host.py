@@ -211,6 +211,29 @@ def test_generate_indices_follows_the_reference(size, num_frames, step):
         assert len(idx) == num_frames and idx == sorted(idx) and max(idx) < size
 
 
+@pytest.mark.parametrize("entropy", ["host", "device"])
+def test_scan_frames_sorts_files_between_the_device_and_pillow(fx, entropy):
+    """The loaders' host half: supported frames into one batch of the route asked for, an unsupported JPEG and a PNG to Pillow, the
+    (H, W) of every slot without a decode of the supported ones; a supported file cut short raises."""
+    Image = pytest.importorskip("PIL.Image")
+    from timetuning_amd.data_loader import decode_frame_on_host, scan_frames
+
+    png = io.BytesIO()
+    Image.fromarray(np.arange(5 * 7 * 3, dtype=np.uint8).reshape(5, 7, 3)).save(png, "PNG")
+    first, last = fx[0]["clip_v0_f0"][0], fx[0]["grid_9x15_420_q75_std"][0]
+    files = [first, fx[0]["prog_48x64_420_q90"][0], png.getvalue(), last]
+    assert hip_ops.jpeg_probe(files[1]).status > 0
+    host = scan_frames(files, 2, entropy, pin=False)
+    assert host.device_slots == [0, 3] and set(host.host_frames) == {1, 2}
+    for k in (1, 2):
+        assert np.array_equal(host.host_frames[k], decode_frame_on_host(files[k]))
+    assert host.host_frames[2].tolist() == np.arange(5 * 7 * 3).reshape(5, 7, 3).tolist()
+    assert [tuple(d) for d in host.dims] == [fx[0]["clip_v0_f0"][1].shape[:2], (48, 64), (5, 7), (9, 15)]
+    assert host.scanned.route == entropy and [(i.H, i.W) for i in host.scanned.infos] == [host.dims[0], host.dims[3]]
+    with pytest.raises(ValueError):
+        scan_frames(files[:3] + [last[:len(last) // 2]], 2, entropy, pin=False)
+
+
 def test_loader_pairs_directories_by_position_and_orders_files(fx, tmp_path):
     pytest.importorskip("PIL.Image")
     from timetuning_amd.data_loader import ClipLoader, SamplingMode, VideoDataset, list_frames, make_loader

@@ -22,6 +22,7 @@
 //     allows, byte by byte at ragged edges and unaligned rows.
 // Plain C++, vector loads and stores only; 32-bit integer arithmetic suffices for 8-bit baseline data.
 #include "common.hpp"
+#include "jpeg_huff.hpp"   // jh::grid: the block grid, stated once for the scan, the entropy kernels and these
 
 namespace tt {
 
@@ -31,14 +32,6 @@ constexpr int JP_TILE_ROW = 9, JP_TILE = 8 * JP_TILE_ROW;   // words
 constexpr int JP_MAX_FRAMES = 65535 / 3;                    // (frame, component) rides on gridDim.y
 constexpr long long JP_MAX_DIM = 65535;                     // a JPEG frame's largest side
 constexpr size_t JP_ALIGN = 256;
-
-struct JpGrid { long long rows, cols; };   // blocks
-
-__host__ __device__ inline JpGrid jp_grid(long long H, long long W, int sampling, int comp) {
-  const int hmax = sampling == TT_JPEG_444 ? 1 : 2, vmax = sampling == TT_JPEG_420 ? 2 : 1;
-  const long long mx = (W + 8 * hmax - 1) / (8 * hmax), my = (H + 8 * vmax - 1) / (8 * vmax);
-  return comp == 0 ? JpGrid{my * vmax, mx * hmax} : JpGrid{my, mx};
-}
 
 // One 1-D pass (Loeffler-Ligtenberg-Moschytz, CONST_BITS = 13), descaled by `shift` bits.
 template <int SHIFT>
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_idct_kernel(const int16_t* __
   __shared__ int tile[JP_BLOCKS_PER_WG * JP_TILE];
   const int frame = blockIdx.y / 3, comp = blockIdx.y % 3;
   const tt_jpeg_frame& f = table[frame];
-  const JpGrid g = jp_grid(f.H, f.W, (int)f.sampling, comp);
+  const jh::Grid g = jh::grid(f.H, f.W, (int)f.sampling, comp);
   const long long nblocks = g.rows * g.cols;
   if ((long long)blockIdx.x * JP_BLOCKS_PER_WG >= nblocks) return;   // uniform over the workgroup
   const int b = threadIdx.x >> 3, j = threadIdx.x & 7;
@@ -172,7 +165,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_colour_kernel(const tt_jpeg_f
   const long long item = (long long)blockIdx.x * JP_THREADS + threadIdx.x;
   if (item >= groups * pairs) return;
   const long long r = item / groups, x0 = (item % groups) * 4;
-  const JpGrid gy = jp_grid(H, W, sampling, 0), gc = jp_grid(H, W, sampling, 1);
+  const jh::Grid gy = jh::grid(H, W, sampling, 0), gc = jh::grid(H, W, sampling, 1);
   const long long ystride = gy.cols * 8, cstride = gc.cols * 8;
   const int hmax = sampling == TT_JPEG_444 ? 1 : 2, vmax = sampling == TT_JPEG_420 ? 2 : 1;
   const long long dw = (W + hmax - 1) / hmax, dh = (H + vmax - 1) / vmax;
@@ -218,7 +211,7 @@ static long long jp_plane_extent(const tt_jpeg_frame* table, int n_frames) {
     const tt_jpeg_frame& f = table[i];
     if (f.H < 1 || f.W < 1 || f.H > JP_MAX_DIM || f.W > JP_MAX_DIM || f.sampling < TT_JPEG_444 || f.sampling > TT_JPEG_420) return -1;
     for (int c = 0; c < 3; ++c) {
-      const JpGrid g = jp_grid(f.H, f.W, (int)f.sampling, c);
+      const jh::Grid g = jh::grid(f.H, f.W, (int)f.sampling, c);
       if (f.plane_off[c] < 0 || f.plane_off[c] > (1ll << 46)) return -1;
       const long long end = f.plane_off[c] + g.rows * g.cols * 64;
       if (end > extent) extent = end;
@@ -253,7 +246,7 @@ extern "C" int tt_jpeg_decode_batch(const int16_t* coeffs, long long n_coeffs, c
                (long long)f.W);
     TT_REQUIRE(f.sampling >= TT_JPEG_444 && f.sampling <= TT_JPEG_420, "jpeg_decode_batch: frame %d has sampling code %lld", i, (long long)f.sampling);
     for (int c = 0; c < 3; ++c) {
-      const JpGrid g = jp_grid(f.H, f.W, (int)f.sampling, c);
+      const jh::Grid g = jh::grid(f.H, f.W, (int)f.sampling, c);
       const long long nblocks = g.rows * g.cols;
       TT_REQUIRE(f.coeff_off[c] >= 0 && f.coeff_off[c] % 8 == 0 && f.coeff_off[c] <= n_coeffs && nblocks * 64 <= n_coeffs - f.coeff_off[c],
                  "jpeg_decode_batch: frame %d component %d: %lld coefficients at offset %lld do not lie 16-byte aligned inside the %lld given", i, c,

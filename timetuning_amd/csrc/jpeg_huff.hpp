@@ -1,6 +1,7 @@
 // N24: the Huffman layer of a baseline JPEG scan as a state step - shared by the kernels of jpeg_entropy.hip and by the host emulation
 // tt_jpeg_entropy_host (jpeg_scan.cpp), which is what the CPU tests and the sanitizer program run.  No HIP include: with the host compiler
-// alone the qualifiers are empty.
+// alone the qualifiers are empty.  It is also the one home of what every JPEG source states alike: the code table (Table), kLook, kZigzag,
+// extend and the block grid (grid) - the sequential parser of jpeg_scan.cpp and the kernels of jpeg.hip read them from here.
 //
 // The scheme (self-synchronising subsequence decode).  tt_jpeg_prepare has cut the scan into restart segments of clean bytes (no
 // stuffing, no markers), each starting on a 4-byte boundary.  A segment is cut into subsequences of S bits; one lane owns one.  A decoder's
@@ -35,7 +36,7 @@ namespace tt {
 namespace jh {
 
 constexpr int kTile = 256;           // lanes of a workgroup = subsequences of a tile
-constexpr int kLook = 9;             // bits of the look table, as in jpeg_scan.cpp
+constexpr int kLook = 9;             // bits of the Huffman look-ahead table
 constexpr int kDht = 272;            // bytes of one shipped table: 16 counts, 256 values
 constexpr int kHuffBytes = 6 * kDht; // DC, AC of component 0, 1, 2
 constexpr int kMinSubseq = 128, kMaxSubseq = 4096;
@@ -47,7 +48,17 @@ constexpr uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25,
                                  30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 JH_HD int zigzag(int k) { return kZigzag[k & 63]; }
 
-// The host's form (Huff in jpeg_scan.cpp): a 9-bit look table, mincode / maxcode / valptr for longer codes.  1556 bytes.
+// The block grid of component `comp` (0 luma, else chroma, which is 1 x 1) of an H x W frame: ceil(H / (8 vmax)) v rows of
+// ceil(W / (8 hmax)) h blocks.  THE statement of where tt_jpeg_scan places blocks; the chroma grid is the grid of MCUs.
+struct Grid { long long rows, cols; };   // blocks
+JH_HD Grid grid(long long H, long long W, int sampling, int comp) {
+  const int hmax = sampling == TT_JPEG_444 ? 1 : 2, vmax = sampling == TT_JPEG_420 ? 2 : 1;
+  const long long mx = (W + 8 * hmax - 1) / (8 * hmax), my = (H + 8 * vmax - 1) / (8 * vmax);
+  return comp == 0 ? Grid{my * vmax, mx * hmax} : Grid{my, mx};
+}
+
+// A 9-bit look table, mincode / maxcode / valptr for longer codes.  1556 bytes.  The sequential parser (Huff in jpeg_scan.cpp) holds one
+// per DHT table, the kernel six in LDS.
 struct Table {
   uint16_t look[1 << kLook];   // (length << 8) | value, 0 = a longer code
   int32_t maxcode[18];         // -1 = no code of this length
@@ -121,9 +132,9 @@ JH_HD Frame make_frame(const tt_jpeg_stream& s) {
   f.h0 = s.sampling == TT_JPEG_444 ? 1 : 2;
   f.v0 = s.sampling == TT_JPEG_420 ? 2 : 1;
   f.bpm = f.h0 * f.v0 + 2;
-  f.mx = (uint32_t)((s.W + 8 * f.h0 - 1) / (8 * f.h0));
-  const uint32_t my = (uint32_t)((s.H + 8 * f.v0 - 1) / (8 * f.v0));
-  f.mcus = f.mx * my;
+  const Grid mcu = grid(s.H, s.W, (int)s.sampling, 1);
+  f.mx = (uint32_t)mcu.cols;
+  f.mcus = f.mx * (uint32_t)mcu.rows;
   f.restart = s.restart > 0 && s.restart < (long long)f.mcus ? (uint32_t)s.restart : f.mcus;
   f.n_segments = (f.mcus + f.restart - 1) / f.restart;
   f.coeff0 = s.coeff_off[0];

@@ -3,7 +3,7 @@
 // and the quantisation table of each component; dequantisation, IDCT, up-sampling and colour run on the device (jpeg.hip).
 //
 // Plain C++17 with no HIP include: the file also compiles with the host compiler alone (tools/jpeg_scan_check.cpp builds it under
-// AddressSanitizer).  Both entries are pure functions: no state, no allocation (the tables live on the stack, about 5 KB), no GPU call, so
+// AddressSanitizer).  Both entries are pure functions: no state, no allocation (the tables live on the stack, about 13 KB), no GPU call, so
 // a thread pool may run them side by side.  EVERY read is checked against the buffer's length and every write against the caller's
 // capacity; a file is data from outside.
 //
@@ -19,21 +19,16 @@
 
 namespace {
 
-constexpr uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+namespace jh = tt::jh;
+using jh::kLook;
+using jh::kZigzag;
 
-constexpr int kLook = 9;   // bits of the Huffman look-ahead table
-
+// What the parser keeps of a DHT table beyond the code table the device decode shares
 struct Huff {
   bool present = false;
   uint8_t counts[16];           // the DHT segment's own bytes, for tt_jpeg_prepare
   int nvals = 0;
-  uint8_t vals[256];
-  int32_t maxcode[18];          // largest code of each length, -1 = none
-  int32_t valptr[17];           // vals index of the first code of each length
-  int32_t mincode[17];
-  uint16_t look[1 << kLook];    // (length << 8) | value for codes of up to kLook bits, 0 = longer
+  jh::Table t;
 };
 
 struct Header {
@@ -50,28 +45,23 @@ struct Header {
 inline int rd16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
 // false: the counts do not describe a prefix code
-bool build_huff(Huff& t, const uint8_t* bits, const uint8_t* vals, int n) {
+bool build_huff(Huff& h, const uint8_t* bits, const uint8_t* vals, int n) {
+  for (int len = 1, code = 0; len <= 16; ++len, code <<= 1)
+    if ((code += bits[len - 1]) > (1 << len)) return false;
+  std::memcpy(h.counts, bits, 16);
+  h.nvals = n;
+  jh::Table& t = h.t;
   std::memcpy(t.vals, vals, (size_t)n);
-  std::memcpy(t.counts, bits, 16);
-  t.nvals = n;
+  jh::build_codes(t, bits);
+  // the look table by scatter (jh::look_entry gathers the same entries, at several compares per entry, and every file is parsed
+  // twice): a code of len bits owns the 2^(kLook - len) entries it is a prefix of, which the check above keeps inside the table
   std::memset(t.look, 0, sizeof(t.look));
-  int code = 0, k = 0;
-  for (int len = 1; len <= 16; ++len) {
-    t.valptr[len] = k;
-    t.mincode[len] = code;
-    const int cnt = bits[len - 1];
-    if (code + cnt > (1 << len)) return false;
-    for (int i = 0; i < cnt; ++i, ++k, ++code) {
-      if (len <= kLook) {
-        const int first = code << (kLook - len);
-        for (int j = 0; j < (1 << (kLook - len)); ++j) t.look[first + j] = (uint16_t)((len << 8) | t.vals[k]);
-      }
+  for (int len = 1; len <= kLook; ++len)
+    for (int code = t.mincode[len]; code <= t.maxcode[len]; ++code) {
+      const uint16_t e = (uint16_t)((len << 8) | t.vals[t.valptr[len] + code - t.mincode[len]]);
+      for (int j = 0; j < (1 << (kLook - len)); ++j) t.look[(code << (kLook - len)) + j] = e;
     }
-    t.maxcode[len] = cnt ? code - 1 : -1;
-    code <<= 1;
-  }
-  t.maxcode[17] = 0x7fffffff;
-  t.present = true;
+  h.present = true;
   return true;
 }
 
@@ -205,10 +195,18 @@ int parse_header(const uint8_t* d, size_t len, Header& hd) {
   }
 }
 
-inline void grid(const Header& hd, int c, long long* rows, long long* cols) {
-  const long long mx = (hd.W + 8 * hd.h[0] - 1) / (8 * hd.h[0]), my = (hd.H + 8 * hd.v[0] - 1) / (8 * hd.v[0]);
-  *rows = my * hd.v[c];
-  *cols = mx * hd.h[c];
+// of a supported header: its sampling code says what h[] and v[] say
+inline jh::Grid grid(const Header& hd, int c) { return jh::grid(hd.H, hd.W, hd.sampling, c); }
+
+// int16 elements of the frame's coefficients; base[c]: where component c's begin
+inline long long coeff_layout(const Header& hd, long long* base) {
+  long long total = 0;
+  for (int c = 0; c < 3; ++c) {
+    const jh::Grid g = grid(hd, c);
+    if (base) base[c] = total;
+    total += g.rows * g.cols * 64;
+  }
+  return total;
 }
 
 struct Bits {
@@ -263,7 +261,7 @@ struct Bits {
     return true;
   }
   // one Huffman symbol.  0 ok, TT_JPEG_ETRUNCATED, TT_JPEG_EHUFFMAN
-  int symbol(const Huff& t, int* out) {
+  int symbol(const jh::Table& t, int* out) {
     if (cnt < 16) fill();
     const unsigned peek = (unsigned)(acc >> (64 - kLook));
     const uint16_t e = t.look[peek];
@@ -290,8 +288,6 @@ struct Bits {
   }
 };
 
-inline int extend(int v, int s) { return s && v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
-
 }  // namespace
 
 extern "C" int tt_jpeg_probe(const uint8_t* data, size_t len, int* H, int* W, int* sampling, long long* n_coeffs) {
@@ -300,15 +296,7 @@ extern "C" int tt_jpeg_probe(const uint8_t* data, size_t len, int* H, int* W, in
   if (H) *H = rc == 0 ? hd.H : 0;
   if (W) *W = rc == 0 ? hd.W : 0;
   if (sampling) *sampling = rc == 0 ? hd.sampling : -1;
-  long long total = 0;
-  if (rc == 0) {
-    for (int c = 0; c < 3; ++c) {
-      long long r, q;
-      grid(hd, c, &r, &q);
-      total += r * q * 64;
-    }
-  }
-  if (n_coeffs) *n_coeffs = total;
+  if (n_coeffs) *n_coeffs = rc == 0 ? coeff_layout(hd, nullptr) : 0;
   return rc;
 }
 
@@ -317,17 +305,14 @@ extern "C" int tt_jpeg_scan(const uint8_t* data, size_t len, int16_t* coeffs, lo
   const int rc = parse_header(data, len, hd);
   if (rc != 0) return rc;
   if (!coeffs || !qtables) return TT_JPEG_EARGUMENT;
-  long long rows[3], cols[3], base[3], total = 0;
-  for (int c = 0; c < 3; ++c) {
-    grid(hd, c, &rows[c], &cols[c]);
-    base[c] = total;
-    total += rows[c] * cols[c] * 64;
-  }
+  long long base[3];
+  const long long total = coeff_layout(hd, base);
   if (coeffs_capacity < total) return TT_JPEG_EARGUMENT;
   std::memset(coeffs, 0, sizeof(int16_t) * (size_t)total);
   for (int c = 0; c < 3; ++c) std::memcpy(qtables + 64 * c, hd.q[hd.tq[c]], sizeof(uint16_t) * 64);
 
-  const long long mx = cols[0] / hd.h[0], my = rows[0] / hd.v[0], mcus = mx * my;
+  const long long cols[3] = {grid(hd, 0).cols, grid(hd, 1).cols, grid(hd, 2).cols};
+  const long long mx = cols[1], mcus = mx * grid(hd, 1).rows;   // the chroma grid is the grid of MCUs
   Bits br{data, hd.scan_pos, len};
   int pred[3] = {0, 0, 0};
   long long until_restart = hd.restart ? hd.restart : mcus;
@@ -349,8 +334,8 @@ extern "C" int tt_jpeg_scan(const uint8_t* data, size_t len, int16_t* coeffs, lo
     --until_restart;
     const long long my_i = mcu / mx, mx_i = mcu % mx;
     for (int c = 0; c < 3; ++c) {
-      const Huff& dc = hd.dc[hd.td[c]];
-      const Huff& ac = hd.ac[hd.ta[c]];
+      const jh::Table& dc = hd.dc[hd.td[c]].t;
+      const jh::Table& ac = hd.ac[hd.ta[c]].t;
       for (int y = 0; y < hd.v[c]; ++y) {
         for (int x = 0; x < hd.h[c]; ++x) {
           int16_t* blk = coeffs + base[c] + ((my_i * hd.v[c] + y) * cols[c] + (mx_i * hd.h[c] + x)) * 64;
@@ -358,7 +343,7 @@ extern "C" int tt_jpeg_scan(const uint8_t* data, size_t len, int16_t* coeffs, lo
           if ((e = br.symbol(dc, &s)) != 0) return e;
           if (s > 11) return TT_JPEG_EHUFFMAN;   // a DC category an 8-bit file cannot hold
           if (!br.get(s, &bits)) return TT_JPEG_ETRUNCATED;
-          pred[c] += extend(bits, s);
+          pred[c] += jh::extend(bits, s);
           blk[0] = (int16_t)pred[c];
           int k = 1;
           while (k < 64) {
@@ -375,7 +360,7 @@ extern "C" int tt_jpeg_scan(const uint8_t* data, size_t len, int16_t* coeffs, lo
             k += r;
             if (k > 63) return TT_JPEG_ERUN;
             if (!br.get(s, &bits)) return TT_JPEG_ETRUNCATED;
-            blk[kZigzag[k]] = (int16_t)extend(bits, s);
+            blk[kZigzag[k]] = (int16_t)jh::extend(bits, s);
             ++k;
           }
         }
@@ -398,7 +383,6 @@ extern "C" int tt_jpeg_prepare_bytes(size_t len, size_t* scan_bytes, size_t* n_s
 
 extern "C" int tt_jpeg_prepare(const uint8_t* data, size_t len, uint8_t* scan, size_t scan_capacity, uint32_t* segs, size_t seg_capacity,
                                tt_jpeg_stream* row, uint16_t* qtables) {
-  namespace jh = tt::jh;
   Header hd;
   const int rc = parse_header(data, len, hd);
   if (rc != 0) return rc;
@@ -408,19 +392,17 @@ extern "C" int tt_jpeg_prepare(const uint8_t* data, size_t len, uint8_t* scan, s
   row->W = hd.W;
   row->sampling = hd.sampling;
   row->restart = hd.restart;
-  long long total = 0;
+  long long base[3];
+  coeff_layout(hd, base);
   for (int c = 0; c < 3; ++c) {
-    long long r, q;
-    grid(hd, c, &r, &q);
-    row->coeff_off[c] = total;
-    total += r * q * 64;
+    row->coeff_off[c] = base[c];
     std::memcpy(qtables + 64 * c, hd.q[hd.tq[c]], sizeof(uint16_t) * 64);
     const Huff* two[2] = {&hd.dc[hd.td[c]], &hd.ac[hd.ta[c]]};
     for (int k = 0; k < 2; ++k) {
       uint8_t* dst = scan + (2 * c + k) * jh::kDht;
       std::memset(dst, 0, (size_t)jh::kDht);
       std::memcpy(dst, two[k]->counts, 16);
-      std::memcpy(dst + 16, two[k]->vals, (size_t)two[k]->nvals);
+      std::memcpy(dst + 16, two[k]->t.vals, (size_t)two[k]->nvals);
     }
   }
   const jh::Frame f = jh::make_frame(*row);
@@ -486,7 +468,6 @@ namespace {
 
 // One frame, as one workgroup of jh::kTile lanes runs it (jpeg_entropy.hip: the same steps, the loops over i are its lanes).
 int entropy_frame(const uint8_t* scan, const uint32_t* segs, const tt_jpeg_stream& row, uint32_t S, int16_t* coeffs, int32_t* stats) {
-  namespace jh = tt::jh;
   constexpr int T = jh::kTile;
   const jh::Frame f = jh::make_frame(row);
   static_assert(sizeof(jh::Table) * 6 < 16384, "the tables fit the stack");
@@ -577,7 +558,6 @@ int entropy_frame(const uint8_t* scan, const uint32_t* segs, const tt_jpeg_strea
 
 // (a pure host function, so it lives here: the sanitizer program links this file alone)
 extern "C" size_t tt_jpeg_entropy_batch_workspace_bytes(const tt_jpeg_stream* stream_table, int n_frames, int subseq_bits) {
-  namespace jh = tt::jh;
   if (!stream_table || n_frames < 1 || n_frames > 65535 || subseq_bits < jh::kMinSubseq || subseq_bits > jh::kMaxSubseq || subseq_bits % 32) return 0;
   return jh::workspace_bytes(n_frames);
 }

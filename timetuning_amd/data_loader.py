@@ -169,16 +169,55 @@ class _HostSample:
         self.frames, self.annotations, self.label, self.index = frames, annotations, label, index
 
 
+class HostFrames:
+    """The host half of a list of frame files: ``scanned`` - the ``hip_ops.JpegBatch`` of the files the device decoder takes, None
+    without any -, ``device_slots`` their places in the list, ``host_frames`` {slot: uint8 [H, W, 3]} the Pillow decode of every other
+    file, ``dims`` the (H, W) of every slot."""
+
+    def __init__(self, scanned, device_slots, host_frames, dims):
+        self.scanned, self.device_slots, self.host_frames, self.dims = scanned, device_slots, host_frames, dims
+
+
+def scan_frames(files, threads: int, entropy: str = "host", pin: bool = True) -> HostFrames:
+    """Classifies every file and builds the batch of the supported ones on the ``entropy`` route ("host": ``hip_ops.jpeg_scan_batch``,
+    "device": ``jpeg_prepare_batch``); an unsupported file or one that is not a JPEG is decoded with Pillow.  A broken JPEG raises
+    ``ValueError``.  No GPU call: a background thread may run it."""
+    device_slots, host_frames, dims = [], {}, [None] * len(files)
+    for k, data in enumerate(files):
+        info = ops.jpeg_probe(data) if data[:2] == b"\xff\xd8" else None     # a broken JPEG raises here
+        if info is not None and info.supported:
+            device_slots.append(k)
+            dims[k] = (info.H, info.W)
+        else:
+            host_frames[k] = decode_frame_on_host(data)
+            dims[k] = host_frames[k].shape[:2]
+    build = ops.jpeg_prepare_batch if entropy == "device" else ops.jpeg_scan_batch
+    scanned = build([files[k] for k in device_slots], threads, pin) if device_slots else None
+    return HostFrames(scanned, device_slots, host_frames, dims)
+
+
+def finish_frames(host: HostFrames, device):
+    """The device half of ``scan_frames``: (the frames as uint8 [H, W, 3] tensors on ``device`` in file order, the number of them that
+    Pillow decoded - the fall-backs a loader counts)."""
+    frames = [None] * len(host.dims)
+    if host.scanned is not None:
+        for k, f in zip(host.device_slots, ops.jpeg_decode(host.scanned, device)):
+            frames[k] = f
+    for k, arr in host.host_frames.items():
+        frames[k] = torch.from_numpy(arr).to(device)
+    return frames, len(host.host_frames)
+
+
 class _HostBatch:
-    def __init__(self, samples, scanned, device_slots, host_frames):
-        self.samples, self.scanned, self.device_slots, self.host_frames = samples, scanned, device_slots, host_frames
+    def __init__(self, samples, frames: HostFrames):
+        self.samples, self.frames = samples, frames
 
 
 class VideoDataset:
     """``VideoDataset(classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, ...)`` (``:552``).  ``rng`` draws the
     frame indices (default: the ``random`` module, as in the reference); ``device`` and ``threads`` belong to the decode, and so does
     ``jpeg_entropy``: "host" undoes the Huffman coding in the thread pool (``hip_ops.jpeg_scan_batch``), "device" copies the compressed
-    scans and undoes it in one launch (``hip_ops.jpeg_prepare_batch`` / ``jpeg_decode_prepared``) - the same pixels either way.
+    scans and undoes it in one launch (``hip_ops.jpeg_prepare_batch``) - the same pixels either way.
     ``meta_file_directory`` (``:563-573``): the path of a YouTube-VOS ``meta.json``; when the file exists the annotations' per-video
     instance ids become dataset-wide category ids (``map_categories``), ``sequential_category_map`` choosing the rule of
     ``compose_instance_lut``.  A path that does not exist prints "There is no meta file." and maps nothing, as in the reference."""
@@ -248,28 +287,13 @@ class VideoDataset:
         """Classifies every frame of the samples, entropy-decodes the supported ones into one pinned buffer and decodes the others with
         Pillow."""
         flat = [f for s in samples for clip in s.frames for f in clip]
-        device_slots, host_frames, supported = [], {}, []
-        for k, data in enumerate(flat):
-            if data[:2] == b"\xff\xd8" and ops.jpeg_probe(data).supported:   # a broken JPEG raises here
-                device_slots.append(k)
-                supported.append(data)
-            else:
-                host_frames[k] = decode_frame_on_host(data)
-        scan = ops.jpeg_prepare_batch if (jpeg_entropy or self.jpeg_entropy) == "device" else ops.jpeg_scan_batch   # a loader may choose for itself
-        scanned = scan(supported, self.threads) if supported else None
-        return _HostBatch(samples, scanned, device_slots, host_frames)
+        return _HostBatch(samples, scan_frames(flat, self.threads, jpeg_entropy or self.jpeg_entropy))   # a loader may choose for itself
 
     # ---- device half: reconstruction, transforms
     def finish(self, batch: _HostBatch):
         """-> per sample (data, annotations, label) as ``__getitem__`` returns them."""
-        flat = [None] * (len(batch.device_slots) + len(batch.host_frames))
-        if batch.scanned is not None:
-            decode = ops.jpeg_decode_prepared if isinstance(batch.scanned, ops.JpegStreamBatch) else ops.jpeg_decode_scanned
-            for k, f in zip(batch.device_slots, decode(batch.scanned, self.device)):
-                flat[k] = f
-        for k, arr in batch.host_frames.items():
-            flat[k] = torch.from_numpy(arr).to(self.device)
-        self.fallback_frames += len(batch.host_frames)
+        flat, fallbacks = finish_frames(batch.frames, self.device)
+        self.fallback_frames += fallbacks
         out, at = [], 0
         for s in batch.samples:
             clips = []

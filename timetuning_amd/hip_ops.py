@@ -2383,15 +2383,21 @@ def remap_nearest_labels(first, flows, scale: float = 1.0):
     return out
 
 
-# ---- N21: JPEG frames.  The host half (tt_jpeg_probe / tt_jpeg_scan: markers and Huffman codes, pure host functions that ctypes runs
-# without the GIL) in a thread pool, the arithmetic half (tt_jpeg_decode_batch) in two launches for the whole batch.
+# ---- N21, N24: JPEG frames.  The host half (tt_jpeg_probe, then tt_jpeg_scan: markers and Huffman codes - or, on the "device" route,
+# tt_jpeg_prepare: markers only; pure host functions that ctypes runs without the GIL) in a thread pool, the arithmetic half
+# (tt_jpeg_decode_batch) in two launches for the whole batch, behind tt_jpeg_entropy_batch on the "device" route.
 JPEG_MAX_THREADS = 16
 JPEG_UNSUPPORTED = {1: "progressive, lossless or hierarchical frame", 2: "arithmetic coding", 3: "not three components", 4: "12-bit samples",
                     5: "sampling factors other than 4:4:4 / 4:2:2 / 4:2:0", 6: "more than one scan", 7: "16-bit quantisation tables",
                     8: "RGB stored without a colour transform"}
 JPEG_MALFORMED = {-1: "broken markers, segment lengths or tables", -2: "the scan data ends early", -3: "a Huffman code no table holds",
                   -4: "a run past coefficient 63", -5: "a missing or misnumbered restart marker", -6: "bad argument"}
-_JPEG_ROW = 16     # int64 words of one tt_jpeg_frame
+# the rows of the two descriptor tables (include/timetuning_hip.h), 128 bytes each: their fields are named here and nowhere else
+_JPEG_FRAME = np.dtype([("H", "<i8"), ("W", "<i8"), ("sampling", "<i8"), ("coeff_off", "<i8", 3), ("qslot", "<i8", 3), ("plane_off", "<i8", 3),
+                        ("out_off", "<i8"), ("reserved", "<i8", 3)])                                                  # tt_jpeg_frame
+_JPEG_STREAM = np.dtype([("H", "<i8"), ("W", "<i8"), ("sampling", "<i8"), ("restart", "<i8"), ("scan_off", "<i8"), ("scan_len", "<i8"),
+                         ("huff_off", "<i8"), ("seg_off", "<i8"), ("n_segments", "<i8"), ("coeff_off", "<i8", 3), ("reserved", "<i8", 4)])   # tt_jpeg_stream
+_JPEG_QTABLES = 3 * 64 * 2     # bytes of one file's quantisation tables: uint16 [3, 64]
 
 
 class JpegUnsupported(Exception):
@@ -2419,7 +2425,10 @@ class JpegInfo:
         return f"JpegInfo(status={self.status}, H={self.H}, W={self.W}, sampling={self.sampling}, n_coeffs={self.n_coeffs})"
 
 
-def _jpeg_malformed(status: int, index: Optional[int] = None) -> ValueError:
+def _jpeg_error(status: int, index: Optional[int] = None) -> Exception:
+    """The exception of a non-zero status: ValueError for a broken file (< 0), JpegUnsupported for one the device decoder does not take."""
+    if status > 0:
+        return JpegUnsupported(status, index)
     where = "" if index is None else f"file {index}: "
     return ValueError(f"{where}malformed JPEG (status {status}: {JPEG_MALFORMED.get(int(status), 'unknown')})")
 
@@ -2434,7 +2443,7 @@ def jpeg_probe(data: bytes) -> JpegInfo:
     """Classifies a JPEG file without decoding it.  A broken file raises ValueError; an unsupported one is a JpegInfo with status > 0."""
     info = _jpeg_probe_raw(_lib.load(), bytes(data))
     if info.status < 0:
-        raise _jpeg_malformed(info.status)
+        raise _jpeg_error(info.status)
     return info
 
 
@@ -2445,13 +2454,11 @@ def jpeg_scan(data: bytes):
     data = bytes(data)
     info = jpeg_probe(data)
     if not info.supported:
-        raise JpegUnsupported(info.status)
+        raise _jpeg_error(info.status)
     coeffs, q = np.empty(info.n_coeffs, np.int16), np.empty((3, 64), np.uint16)
     rc = lib.tt_jpeg_scan(data, len(data), coeffs.ctypes.data, coeffs.size, q.ctypes.data)
-    if rc < 0:
-        raise _jpeg_malformed(rc)
-    if rc > 0:
-        raise JpegUnsupported(rc)
+    if rc:
+        raise _jpeg_error(rc)
     return info, coeffs, q
 
 
@@ -2459,13 +2466,6 @@ def _jpeg_grid(H: int, W: int, sampling: int, comp: int):
     hmax, vmax = (1 if sampling == 0 else 2), (2 if sampling == 2 else 1)
     mx, my = -(-W // (8 * hmax)), -(-H // (8 * vmax))
     return (my * vmax, mx * hmax) if comp == 0 else (my, mx)
-
-
-class JpegHostBatch:
-    """The host half of a batch, ready for the device: pinned coefficients, pinned table + quantisation tables, and the output layout."""
-
-    def __init__(self, infos, coeffs, meta, n_coeffs, out_bytes, groups, where):
-        self.infos, self.coeffs, self.meta, self.n_coeffs, self.out_bytes, self.groups, self.where = infos, coeffs, meta, n_coeffs, out_bytes, groups, where
 
 
 _JPEG_POOLS: dict = {}
@@ -2481,190 +2481,119 @@ def _jpeg_pool(workers: int):
     return pool
 
 
-def jpeg_scan_batch(files: Sequence[bytes], threads: int = 8, pin: bool = True) -> JpegHostBatch:
-    """Probes and entropy-decodes every file in a pool of min(threads, 16) threads into ONE (pinned) coefficient buffer and builds the
-    descriptor table.  Raises JpegUnsupported for the first unsupported file and ValueError for the first broken one.  The pinned
-    buffers come from torch's caching host allocator: a steady stream of batches allocates nothing after the first."""
+class JpegBatch:
+    """The host half of a batch, ready for the device.  ``route`` "host" (N21): ``coeffs`` holds the int16 coefficients and ``meta`` the
+    frame table, then the quantisation tables.  ``route`` "device" (N24: the host copies each scan once, what crosses PCIe is the
+    compressed stream, and tt_jpeg_entropy_batch leaves the coefficients where tt_jpeg_decode_batch reads them): ``coeffs`` is None and
+    ``meta`` holds the stream table, the frame table, the quantisation tables, the segment table, then every file's Huffman tables and
+    clean stream.  Either way ONE pinned buffer per copy; ``layout``: name -> (offset, bytes) of ``meta``'s parts, each on a 16-byte
+    boundary; ``groups`` (size -> offset in the output, count), ``where`` (file -> size, place in its group) and ``out_bytes``: the output."""
+
+    def __init__(self, route, infos, meta, layout, coeffs, n_coeffs, n_segs, out_bytes, groups, where):
+        self.route, self.infos, self.meta, self.layout, self.coeffs, self.n_coeffs, self.n_segs = route, infos, meta, layout, coeffs, n_coeffs, n_segs
+        self.out_bytes, self.groups, self.where = out_bytes, groups, where
+
+    def part(self, name):
+        """A uint8 NumPy view of one part of ``meta``: 'frames' or 'qtables', on the device route also 'streams', 'segs' or 'scan'."""
+        at, size = self.layout[name]
+        return self.meta.numpy()[at:at + size]
+
+
+def _jpeg_batch(files: Sequence[bytes], threads: int, pin: bool, route: str) -> JpegBatch:
+    """What ``jpeg_scan_batch`` (route "host") and ``jpeg_prepare_batch`` ("device") share - the pool, the probes, the output layout and the
+    frame table - around what they do not: the buffers each fills and the host entry that fills them."""
     lib = _lib.load()
     files = [bytes(f) for f in files]
     n = len(files)
     if n == 0:
-        raise ValueError("jpeg_scan_batch: no files")
+        raise ValueError(f"jpeg_{'scan' if route == 'host' else 'prepare'}_batch: no files")
     workers = max(1, min(int(threads), JPEG_MAX_THREADS, n))
     chunks = [range(k * n // workers, (k + 1) * n // workers) for k in range(workers)]   # one task per thread, not per file
     run = (lambda fn: [fn(c) for c in chunks]) if workers == 1 else (lambda fn: list(_jpeg_pool(workers).map(fn, chunks)))
 
-    def probe(chunk):
-        return [_jpeg_probe_raw(lib, files[i]) for i in chunk]
+    def each(fn, status=int):
+        """fn(i) of every file, in the pool; then the first file in order whose status is not 0 raises"""
+        results = [r for part in run(lambda chunk: [fn(i) for i in chunk]) for r in part]
+        for i, r in enumerate(results):
+            if status(r):
+                raise _jpeg_error(status(r), i)
+        return results
 
-    infos = [info for part in run(probe) for info in part]
-    for i, info in enumerate(infos):
-        if info.status < 0:
-            raise _jpeg_malformed(info.status, i)
-        if not info.supported:
-            raise JpegUnsupported(info.status, i)
-    coeff_off = np.zeros(n + 1, np.int64)
-    np.cumsum([info.n_coeffs for info in infos], out=coeff_off[1:])
-    total = int(coeff_off[-1])
-    coeffs = torch.empty(total, dtype=torch.int16, pin_memory=pin)
-    meta = torch.zeros(n * (_JPEG_ROW * 8 + 3 * 64 * 2), dtype=torch.uint8, pin_memory=pin)    # the table, then the quantisation tables: one copy
-    table = meta.numpy()[:n * _JPEG_ROW * 8].view(np.int64).reshape(n, _JPEG_ROW)
-    q_base = meta.data_ptr() + n * _JPEG_ROW * 8
-    c_base = coeffs.data_ptr()
-
-    def scan(chunk):
-        return [lib.tt_jpeg_scan(files[i], len(files[i]), c_base + 2 * int(coeff_off[i]), infos[i].n_coeffs, q_base + i * 3 * 64 * 2) for i in chunk]
-
-    status = [rc for part in run(scan) for rc in part]
-    for i, rc in enumerate(status):
-        if rc < 0:
-            raise _jpeg_malformed(rc, i)
-        if rc > 0:
-            raise JpegUnsupported(rc, i)
+    infos = each(lambda i: _jpeg_probe_raw(lib, files[i]), lambda info: info.status)
+    # a component's int16 coefficients and the bytes of its plane are one number, so one running sum places both
+    sizes = np.array([[rows * cols * 64 for rows, cols in (_jpeg_grid(f.H, f.W, f.sampling, c) for c in range(3))] for f in infos], np.int64)
+    offs, total = (np.cumsum(sizes) - sizes.reshape(-1)).reshape(n, 3), int(sizes.sum())
     # output layout: the frames of one size lie one after the other, so that they are views of one [k, H, W, 3] tensor
     groups, where = {}, []
     for i, info in enumerate(infos):
         members = groups.setdefault((info.H, info.W), [])
         where.append(((info.H, info.W), len(members)))
         members.append(i)
-    out_bytes, group_base, plane_at = 0, {}, 0
+    out_bytes, group_base = 0, {}
     for key, members in groups.items():
         group_base[key] = out_bytes
         out_bytes += -(-len(members) * key[0] * key[1] * 3 // 16) * 16
-    for i, info in enumerate(infos):
-        row = table[i]
-        row[0], row[1], row[2] = info.H, info.W, info.sampling
-        at = int(coeff_off[i])
-        for c in range(3):
-            rows, cols = _jpeg_grid(info.H, info.W, info.sampling, c)
-            row[3 + c], row[6 + c], row[9 + c] = at, 3 * i + c, plane_at
-            at += rows * cols * 64
-            plane_at += rows * cols * 64
-        key, k = where[i]
-        row[12] = group_base[key] + k * info.H * info.W * 3
-    return JpegHostBatch(infos, coeffs, meta, total, out_bytes, {k: (group_base[k], len(m)) for k, m in groups.items()}, where)
-
-
-def jpeg_decode_scanned(batch: JpegHostBatch, device=None):
-    """The device half: one host-to-device copy of the coefficients, one of the table and the quantisation tables, two launches on the
-    current stream.  Returns the frames as uint8 [H, W, 3] tensors in the order of the files; frames of one size are consecutive views
-    of one [k, H, W, 3] tensor (``frames_as_clip`` returns it without a copy)."""
-    lib = _lib.load()
-    if not torch.cuda.is_available():
-        raise _lib.HipLibraryError("decode_jpeg_batch: needs a GPU (the HIP path has no CPU fallback)")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    n = len(batch.infos)
-    table = batch.meta.numpy()[:n * _JPEG_ROW * 8]
-    ws_bytes = int(lib.tt_jpeg_decode_batch_workspace_bytes(table.ctypes.data, n))
-    if ws_bytes == 0:
-        raise ValueError("decode_jpeg_batch: the descriptor table holds a row that is not a frame")
-    with torch.cuda.device(dev):
-        coeffs = batch.coeffs.to(dev, non_blocking=True)
-        meta = batch.meta.to(dev, non_blocking=True)
-        out = torch.empty(max(batch.out_bytes, 16), dtype=torch.uint8, device=dev)
-        ws = _ws(ws_bytes, dev)
-        _lib.check(lib.tt_jpeg_decode_batch(_p(coeffs), batch.n_coeffs, meta.data_ptr() + n * _JPEG_ROW * 8, 3 * n, table.ctypes.data,
-                                            _p(meta), n, _p(out), out.numel(), _p(ws), ws.numel(), _stream()), "tt_jpeg_decode_batch")
-    stacks = {key: out[base:base + k * key[0] * key[1] * 3].view(k, key[0], key[1], 3) for key, (base, k) in batch.groups.items()}
-    return [stacks[key][k] for key, k in batch.where]
-
-
-# ---- N24: the Huffman streams decoded on the device.  The host copies each scan once (tt_jpeg_prepare, in the same pool), what crosses
-# PCIe is the compressed stream, and tt_jpeg_entropy_batch leaves the coefficients where tt_jpeg_decode_batch reads them.
-JPEG_SUBSEQ_BITS = 2048   # bits of stream per lane: the default ``subseq_bits`` (profiles/n24_jpeg_entropy.txt); an argument, not a state
-_JPEG_STREAM_ROW = 16     # int64 words of one tt_jpeg_stream
-
-
-class JpegStreamBatch:
-    """The host half of a batch for the device entropy decode: ONE pinned buffer (``meta``: the stream table, the frame table, the
-    quantisation tables, the segment table, then every file's Huffman tables and clean stream) and the output layout."""
-
-    def __init__(self, infos, meta, layout, n_segs, n_coeffs, out_bytes, groups, where):
-        self.infos, self.meta, self.layout, self.n_segs, self.n_coeffs = infos, meta, layout, n_segs, n_coeffs
-        self.out_bytes, self.groups, self.where = out_bytes, groups, where
-
-    def part(self, name):
-        """A uint8 NumPy view of one part of the pinned buffer: 'streams', 'frames', 'qtables', 'segs' or 'scan'."""
-        at, size = self.layout[name]
-        return self.meta.numpy()[at:at + size]
-
-
-def jpeg_prepare_batch(files: Sequence[bytes], threads: int = 8, pin: bool = True) -> JpegStreamBatch:
-    """Probes every file and copies its scan, cleaned and cut at the restart markers, into ONE (pinned) buffer in a pool of min(threads,
-    16) threads - the pool and the pinned-buffer scheme of ``jpeg_scan_batch``; nothing is decoded.  Raises JpegUnsupported for the
-    first unsupported file and ValueError for the first broken one (markers and restart numbering; the codes themselves are the
-    device's to judge)."""
-    lib = _lib.load()
-    files = [bytes(f) for f in files]
-    n = len(files)
-    if n == 0:
-        raise ValueError("jpeg_prepare_batch: no files")
-    workers = max(1, min(int(threads), JPEG_MAX_THREADS, n))
-    chunks = [range(k * n // workers, (k + 1) * n // workers) for k in range(workers)]
-    run = (lambda fn: [fn(c) for c in chunks]) if workers == 1 else (lambda fn: list(_jpeg_pool(workers).map(fn, chunks)))
-    infos = [info for part in run(lambda chunk: [_jpeg_probe_raw(lib, files[i]) for i in chunk]) for info in part]
-    for i, info in enumerate(infos):
-        if info.status < 0:
-            raise _jpeg_malformed(info.status, i)
-        if not info.supported:
-            raise JpegUnsupported(info.status, i)
-    scan_cap, seg_cap = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
-    a, b = C.c_size_t(), C.c_size_t()
-    for i, f in enumerate(files):
-        lib.tt_jpeg_prepare_bytes(len(f), C.byref(a), C.byref(b))
-        hmax, vmax = (1 if infos[i].sampling == 0 else 2), (2 if infos[i].sampling == 2 else 1)
-        mcus = -(-infos[i].W // (8 * hmax)) * -(-infos[i].H // (8 * vmax))
-        # a frame has at most one segment per MCU, and a boundary costs the stream at most one byte: tighter than the bound from len alone
-        scan_cap[i + 1], seg_cap[i + 1] = min(a.value, -(-(1632 + len(f) + mcus + 8) // 4) * 4), min(b.value, mcus)
-    np.cumsum(scan_cap, out=scan_cap)
-    np.cumsum(seg_cap, out=seg_cap)
+    parts, coeffs = [("frames", n * _JPEG_FRAME.itemsize), ("qtables", n * _JPEG_QTABLES)], None
+    if route == "host":
+        coeffs = torch.empty(total, dtype=torch.int16, pin_memory=pin)
+    else:
+        scan_cap, seg_cap = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        a, b = C.c_size_t(), C.c_size_t()
+        for i, (f, info) in enumerate(zip(files, infos)):
+            lib.tt_jpeg_prepare_bytes(len(f), C.byref(a), C.byref(b))
+            rows, cols = _jpeg_grid(info.H, info.W, info.sampling, 1)
+            mcus = rows * cols     # (the chroma grid is the grid of MCUs)
+            # a frame has at most one segment per MCU, and a boundary costs the stream at most one byte: tighter than the bound from len alone
+            scan_cap[i + 1], seg_cap[i + 1] = min(a.value, -(-(1632 + len(f) + mcus + 8) // 4) * 4), min(b.value, mcus)
+        np.cumsum(scan_cap, out=scan_cap)
+        np.cumsum(seg_cap, out=seg_cap)
+        parts = [("streams", n * _JPEG_STREAM.itemsize)] + parts + [("segs", int(seg_cap[-1]) * 8), ("scan", int(scan_cap[-1]))]
     layout, at = {}, 0
-    for name, size in (("streams", n * _JPEG_STREAM_ROW * 8), ("frames", n * _JPEG_ROW * 8), ("qtables", n * 3 * 64 * 2),
-                       ("segs", int(seg_cap[-1]) * 8), ("scan", int(scan_cap[-1]))):
+    for name, size in parts:
         layout[name] = (at, size)
         at += -(-size // 16) * 16
-    meta = torch.zeros(at, dtype=torch.uint8, pin_memory=pin)
-    base = meta.data_ptr()
-    streams = meta.numpy()[layout["streams"][0]:layout["streams"][0] + layout["streams"][1]].view(np.int64).reshape(n, _JPEG_STREAM_ROW)
-    table = meta.numpy()[layout["frames"][0]:layout["frames"][0] + layout["frames"][1]].view(np.int64).reshape(n, _JPEG_ROW)
-    scan_at, segs_at, q_at, rows_at = base + layout["scan"][0], base + layout["segs"][0], base + layout["qtables"][0], base + layout["streams"][0]
-    sc, sg = scan_cap.tolist(), seg_cap.tolist()      # plain ints: the loop below runs once per file
+    meta = torch.zeros(at, dtype=torch.uint8, pin_memory=pin)    # every table and stream of the batch: one copy
+    batch = JpegBatch(route, infos, meta, layout, coeffs, total, 0 if route == "host" else int(seg_cap[-1]), out_bytes,
+                      {k: (group_base[k], len(m)) for k, m in groups.items()}, where)
+    q_at = meta.data_ptr() + layout["qtables"][0]
+    if route == "host":
+        c_base, first = coeffs.data_ptr(), offs[:, 0].tolist()      # plain ints: the calls below run once per file
+        each(lambda i: lib.tt_jpeg_scan(files[i], len(files[i]), c_base + 2 * first[i], infos[i].n_coeffs, q_at + i * _JPEG_QTABLES))
+    else:
+        scan_at, segs_at, rows_at = (meta.data_ptr() + layout[name][0] for name in ("scan", "segs", "streams"))
+        sc, sg = scan_cap.tolist(), seg_cap.tolist()
+        each(lambda i: lib.tt_jpeg_prepare(files[i], len(files[i]), scan_at + sc[i], sc[i + 1] - sc[i], segs_at + 8 * sg[i], sg[i + 1] - sg[i],
+                                           rows_at + i * _JPEG_STREAM.itemsize, q_at + i * _JPEG_QTABLES))
+        streams = batch.part("streams").view(_JPEG_STREAM)     # tt_jpeg_prepare counts from the file's own slots: now from the buffers
+        streams["scan_off"] += scan_cap[:-1]
+        streams["huff_off"] += scan_cap[:-1]
+        streams["seg_off"] += seg_cap[:-1]
+        streams["coeff_off"] += offs[:, :1]
+    frames = batch.part("frames").view(_JPEG_FRAME)
+    for name in ("H", "W", "sampling"):
+        frames[name] = [getattr(info, name) for info in infos]
+    frames["coeff_off"] = frames["plane_off"] = offs
+    frames["qslot"] = np.arange(3 * n).reshape(n, 3)
+    frames["out_off"] = [group_base[key] + k * key[0] * key[1] * 3 for key, k in where]
+    return batch
 
-    def prepare(chunk):
-        return [lib.tt_jpeg_prepare(files[i], len(files[i]), scan_at + sc[i], sc[i + 1] - sc[i], segs_at + 8 * sg[i], sg[i + 1] - sg[i],
-                                    rows_at + i * _JPEG_STREAM_ROW * 8, q_at + i * 3 * 64 * 2) for i in chunk]
 
-    for i, rc in enumerate(rc for part in run(prepare) for rc in part):
-        if rc < 0:
-            raise _jpeg_malformed(rc, i)
-        if rc > 0:
-            raise JpegUnsupported(rc, i)
-    coeff_off = np.zeros(n + 1, np.int64)
-    np.cumsum([info.n_coeffs for info in infos], out=coeff_off[1:])
-    groups, where = {}, []
-    for i, info in enumerate(infos):
-        members = groups.setdefault((info.H, info.W), [])
-        where.append(((info.H, info.W), len(members)))
-        members.append(i)
-    out_bytes, group_base, plane_at = 0, {}, 0
-    for key, members in groups.items():
-        group_base[key] = out_bytes
-        out_bytes += -(-len(members) * key[0] * key[1] * 3 // 16) * 16
-    for i, info in enumerate(infos):
-        srow, row = streams[i], table[i]
-        srow[4] += scan_cap[i]       # scan_off, huff_off, seg_off: from the file's slot to the buffers
-        srow[6] += scan_cap[i]
-        srow[7] += seg_cap[i]
-        srow[9:12] += coeff_off[i]
-        row[0], row[1], row[2] = info.H, info.W, info.sampling
-        for c in range(3):
-            rows, cols = _jpeg_grid(info.H, info.W, info.sampling, c)
-            row[3 + c], row[6 + c], row[9 + c] = srow[9 + c], 3 * i + c, plane_at
-            plane_at += rows * cols * 64
-        key, k = where[i]
-        row[12] = group_base[key] + k * info.H * info.W * 3
-    return JpegStreamBatch(infos, meta, layout, int(seg_cap[-1]), int(coeff_off[-1]), out_bytes,
-                           {k: (group_base[k], len(m)) for k, m in groups.items()}, where)
+def jpeg_scan_batch(files: Sequence[bytes], threads: int = 8, pin: bool = True) -> JpegBatch:
+    """The host route.  Probes and entropy-decodes every file in a pool of min(threads, 16) threads into ONE (pinned) coefficient buffer and
+    builds the descriptor table.  Raises JpegUnsupported for the first unsupported file and ValueError for the first broken one.  The
+    pinned buffers come from torch's caching host allocator: a steady stream of batches allocates nothing after the first."""
+    return _jpeg_batch(files, threads, pin, "host")
+
+
+def jpeg_prepare_batch(files: Sequence[bytes], threads: int = 8, pin: bool = True) -> JpegBatch:
+    """The device route.  Probes every file and copies its scan, cleaned and cut at the restart markers, into ONE (pinned) buffer in the
+    same pool; nothing is decoded.  Raises JpegUnsupported for the first unsupported file and ValueError for the first broken one
+    (markers and restart numbering; the codes themselves are the device's to judge)."""
+    return _jpeg_batch(files, threads, pin, "device")
+
+
+# ---- N24: the Huffman streams of a device-route batch decoded on the device (tt_jpeg_entropy_batch) or, for tests, by its host emulation.
+JPEG_SUBSEQ_BITS = 2048   # bits of stream per lane: the default ``subseq_bits`` (profiles/n24_jpeg_entropy.txt); an argument, not a state
 
 
 def _jpeg_subseq_bits(subseq_bits) -> int:
@@ -2674,7 +2603,7 @@ def _jpeg_subseq_bits(subseq_bits) -> int:
     return bits
 
 
-def jpeg_entropy_host(batch: JpegStreamBatch, subseq_bits=None):
+def jpeg_entropy_host(batch: JpegBatch, subseq_bits=None):
     """The host emulation of the device entropy decode (tt_jpeg_entropy_host: the kernel's phases lane by lane through the same header),
     for tests and tools: (coefficients int16 [n_coeffs], status int32 [n], statistics int32 [n, 4] = rounds, tiles, subsequences, the
     first failing subsequence).  Raises nothing for a broken stream: the status says it."""
@@ -2688,7 +2617,7 @@ def jpeg_entropy_host(batch: JpegStreamBatch, subseq_bits=None):
     return coeffs[:batch.n_coeffs], status, ws[:4 * n].reshape(n, 4)
 
 
-def jpeg_entropy_decode(batch: JpegStreamBatch, device=None, subseq_bits=None, stats: bool = False):
+def jpeg_entropy_decode(batch: JpegBatch, device=None, subseq_bits=None, stats: bool = False):
     """The device entropy decode: one host-to-device copy of the batch's buffer (the compressed streams and their tables), a memset and
     one launch on the current stream, then ONE read-back of 4 n bytes - the frames' status.  Returns (coefficients int16 [n_coeffs] on the
     device, in the layout of the batch's frame table; status int32 [n] on the host; the batch's buffer on the device).  A negative status
@@ -2712,24 +2641,31 @@ def jpeg_entropy_decode(batch: JpegStreamBatch, device=None, subseq_bits=None, s
         host_status = status.cpu().numpy()
     for i, rc in enumerate(host_status):
         if rc < 0:
-            raise _jpeg_malformed(int(rc), i)
+            raise _jpeg_error(int(rc), i)
     if stats:
         return coeffs, host_status, meta, ws[:16 * n].view(torch.int32).view(n, 4).cpu().numpy()
     return coeffs, host_status, meta
 
 
-def jpeg_decode_prepared(batch: JpegStreamBatch, device=None, subseq_bits=None):
-    """prepare's batch -> frames: the entropy launch, then tt_jpeg_decode_batch on the device-resident coefficients (no coefficient
-    copy).  The frames come back as ``jpeg_decode_scanned`` returns them."""
+def jpeg_decode(batch: JpegBatch, device=None, subseq_bits=None):
+    """The device half.  Host route: one host-to-device copy of the coefficients, one of the tables, two launches on the current stream.
+    Device route: ``jpeg_entropy_decode`` (``subseq_bits`` is its), then the same two launches on the device-resident coefficients.
+    Returns the frames as uint8 [H, W, 3] tensors in the order of the files; frames of one size are consecutive views of one
+    [k, H, W, 3] tensor (``frames_as_clip`` returns it without a copy)."""
     lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise _lib.HipLibraryError("decode_jpeg_batch: needs a GPU (the HIP path has no CPU fallback)")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     n = len(batch.infos)
     table = batch.part("frames")
     ws_bytes = int(lib.tt_jpeg_decode_batch_workspace_bytes(table.ctypes.data, n))
     if ws_bytes == 0:
         raise ValueError("decode_jpeg_batch: the descriptor table holds a row that is not a frame")
-    coeffs, _, meta = jpeg_entropy_decode(batch, dev, subseq_bits)
     with torch.cuda.device(dev):
+        if batch.route == "device":
+            coeffs, _, meta = jpeg_entropy_decode(batch, dev, subseq_bits)
+        else:
+            coeffs, meta = batch.coeffs.to(dev, non_blocking=True), batch.meta.to(dev, non_blocking=True)
         out = torch.empty(max(batch.out_bytes, 16), dtype=torch.uint8, device=dev)
         ws = _ws(ws_bytes, dev)
         _lib.check(lib.tt_jpeg_decode_batch(_p(coeffs), batch.n_coeffs, meta.data_ptr() + batch.layout["qtables"][0], 3 * n, table.ctypes.data,
@@ -2744,11 +2680,9 @@ def decode_jpeg_batch(files: Sequence[bytes], device=None, threads: int = 8, ent
     size come back as views of one [k, H, W, 3] tensor.  Unsupported files raise JpegUnsupported (no CPU fallback here), broken ones
     ValueError.  ``entropy``: "host" undoes the Huffman coding in the thread pool and copies coefficients; "device" copies the compressed
     scans and undoes it in one launch (``subseq_bits``: bits of stream per lane, None = JPEG_SUBSEQ_BITS)."""
-    if entropy == "host":
-        return jpeg_decode_scanned(jpeg_scan_batch(files, threads), device)
-    if entropy != "device":
+    if entropy not in ("host", "device"):
         raise ValueError(f"decode_jpeg_batch: entropy must be 'host' or 'device', not {entropy!r}")
-    return jpeg_decode_prepared(jpeg_prepare_batch(files, threads), device, subseq_bits)
+    return jpeg_decode(_jpeg_batch(files, threads, True, entropy), device, subseq_bits)
 
 
 def frames_as_clip(frames: Sequence[torch.Tensor]) -> torch.Tensor:

@@ -7,8 +7,8 @@ Both of its branches yield ``(x float32 [b, 3, S, S], y float32 [b, 1, R, R])``:
 reference overrides ``shuffle`` to ``False``, ``:263``), the last batch partial.
 
 Here a batch is two host steps and three device steps.  Host (may run one batch ahead in a background thread, as ``data_loader.ClipLoader``
-does): the files are read, the JPEGs entropy-decoded into one pinned buffer (``hip_ops.jpeg_scan_batch``) and the PNGs decoded with Pillow
-(``data_loader.decode_annotation``) into ONE packed pinned buffer.  Device: ``hip_ops.jpeg_decode_scanned`` reconstructs the frames, then
+does): the files are read, the JPEGs entropy-decoded into one pinned buffer (``data_loader.scan_frames``) and the PNGs decoded with Pillow
+(``data_loader.decode_annotation``) into ONE packed pinned buffer.  Device: ``data_loader.finish_frames`` reconstructs the frames, then
 ONE ``tt_img_resize_ragged`` launch covers every image of the mixed-size batch and ONE ``tt_img_gather_nearest_ragged`` launch every mask.
 A JPEG the device decoder does not take (progressive, gray, ...) is decoded with Pillow and COUNTED (``fallback_frames``), by N21's rule; a
 supported file that fails to decode raises.  All of it is bit-equal to the reference's Pillow chain.
@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import hip_ops as ops
-from .data_loader import _read, decode_annotation, decode_frame_on_host
+from .data_loader import _read, decode_annotation, finish_frames, scan_frames
 
 CLASS_IDX_TO_NAME = ['background', 'aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair',
                      'cow', 'diningtable', 'dog', 'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa',
@@ -197,9 +197,8 @@ class VOCDataset:
 
 
 class _VOCHostBatch:
-    def __init__(self, n, scanned, device_slots, host_frames, dims, mask_buf, mask_offs, mask_dims):
-        self.n, self.scanned, self.device_slots, self.host_frames, self.dims = n, scanned, device_slots, host_frames, dims
-        self.mask_buf, self.mask_offs, self.mask_dims = mask_buf, mask_offs, mask_dims
+    def __init__(self, frames, mask_buf, mask_offs, mask_dims):
+        self.frames, self.mask_buf, self.mask_offs, self.mask_dims = frames, mask_buf, mask_offs, mask_dims
 
 
 class VOCLoader:
@@ -224,19 +223,7 @@ class VOCLoader:
     # ---- host half: file reads, entropy decode, PNG decode (no launch: a background thread may run it)
     def _host_on(self, indices) -> _VOCHostBatch:
         ds = self.dataset
-        files = [_read(ds.images[i]) for i in indices]
-        device_slots, host_frames, supported, dims = [], {}, [], [None] * len(files)
-        for k, data in enumerate(files):
-            if data[:2] == b"\xff\xd8" and ops.jpeg_probe(data).supported:   # a broken JPEG raises here
-                device_slots.append(k)
-                supported.append(data)
-            else:
-                host_frames[k] = decode_frame_on_host(data)
-                dims[k] = host_frames[k].shape[:2]
-        scan = ops.jpeg_prepare_batch if ds.jpeg_entropy == "device" else ops.jpeg_scan_batch
-        scanned = scan(supported, ds.threads) if supported else None
-        for k, info in zip(device_slots, scanned.infos if scanned else []):
-            dims[k] = (info.H, info.W)
+        frames = scan_frames([_read(ds.images[i]) for i in indices], ds.threads, ds.jpeg_entropy)
         masks = [decode_annotation(_read(ds.masks[i])) for i in indices]
         offs = np.zeros(len(masks) + 1, np.int64)
         np.cumsum([m.size for m in masks], out=offs[1:])
@@ -244,7 +231,7 @@ class VOCLoader:
         view = mask_buf.numpy()
         for m, o in zip(masks, offs):
             view[o:o + m.size] = m.reshape(-1)
-        return _VOCHostBatch(len(files), scanned, device_slots, host_frames, dims, mask_buf, [int(o) for o in offs[:-1]], [m.shape for m in masks])
+        return _VOCHostBatch(frames, mask_buf, [int(o) for o in offs[:-1]], [m.shape for m in masks])
 
     def _host(self, indices) -> _VOCHostBatch:
         dev = self.dataset.device
@@ -258,21 +245,15 @@ class VOCLoader:
         ds = self.dataset
         if ds.device is None:
             raise ops._lib.HipLibraryError("pascal_loader: needs a GPU (the HIP path has no CPU fallback)")
-        frames = [None] * host.n
-        if host.scanned is not None:
-            decode = ops.jpeg_decode_prepared if isinstance(host.scanned, ops.JpegStreamBatch) else ops.jpeg_decode_scanned
-            for k, f in zip(host.device_slots, decode(host.scanned, ds.device)):
-                frames[k] = f
-        for k, arr in host.host_frames.items():
-            frames[k] = torch.from_numpy(arr).to(ds.device)
-        ds.fallback_frames += len(host.host_frames)
+        frames, fallbacks = finish_frames(host.frames, ds.device)
+        ds.fallback_frames += fallbacks
         buf = host.mask_buf.to(ds.device, non_blocking=True)
         maps = [buf[o:o + h * w].view(h, w) for o, (h, w) in zip(host.mask_offs, host.mask_dims)]
         S, R, boxes, flips, mean_std, target_float = self.train_size, self.val_size, None, None, (MEAN, STD), True
         if self.transforms is not None:
-            if any(tuple(d) != tuple(m) for d, m in zip(host.dims, host.mask_dims)):
+            if any(tuple(d) != tuple(m) for d, m in zip(host.frames.dims, host.mask_dims)):
                 raise ValueError("pair transforms need every mask at its image's size")
-            plan = self.transforms(host.dims, self.rng)
+            plan = self.transforms(host.frames.dims, self.rng)
             boxes, flips = plan.boxes, plan.flips
             if plan.size is not None:
                 S = R = plan.size

@@ -104,7 +104,7 @@ def main():
                 lines.append(f"{what}: pixels equal Pillow's on all {a.frames} frames (sum check): {[int(f.sum().item()) for f in frames] == sums}")
             lines.append(f"{what}: pixels equal Pillow's bit for bit on every 16th frame: {all(np.array_equal(frames[i].cpu().numpy(), w) for i, w in want.items())}")
 
-    n, row = a.frames, 16 * 8
+    n = a.frames
     ev = lambda: torch.cuda.Event(enable_timing=True)
     stream = lambda: torch.cuda.current_stream().cuda_stream
 
@@ -113,7 +113,7 @@ def main():
         w0 = time.perf_counter()
         batch = hip_ops.jpeg_scan_batch(files, a.threads)
         w1 = time.perf_counter()
-        table = batch.meta.numpy()[:n * row]
+        table = batch.part("frames")
         ws_bytes = int(lib.tt_jpeg_decode_batch_workspace_bytes(table.ctypes.data, n))
         out = torch.empty(batch.out_bytes, dtype=torch.uint8, device=dev)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -122,8 +122,9 @@ def main():
         coeffs = batch.coeffs.to(dev, non_blocking=True)
         meta = batch.meta.to(dev, non_blocking=True)
         e1.record()
-        rc = lib.tt_jpeg_decode_batch(coeffs.data_ptr(), batch.n_coeffs, meta.data_ptr() + n * row, 3 * n, table.ctypes.data, meta.data_ptr(), n,
-                                      out.data_ptr(), out.numel(), ws.data_ptr(), ws.numel(), stream())
+        at = lambda name: meta.data_ptr() + batch.layout[name][0]
+        rc = lib.tt_jpeg_decode_batch(coeffs.data_ptr(), batch.n_coeffs, at("qtables"), 3 * n, table.ctypes.data, at("frames"), n, out.data_ptr(),
+                                      out.numel(), ws.data_ptr(), ws.numel(), stream())
         assert rc == 0
         e2.record()
         torch.cuda.synchronize()
