@@ -1180,6 +1180,69 @@ size_t tt_map_instances_workspace_bytes(int S);
 int tt_map_instances(const uint8_t* labels_in, uint8_t* labels_out, const int32_t* cat, int S, long long P, int sequential, uint8_t* lut_out,
                      int32_t* status, void* words_ws, size_t words_ws_bytes, tt_stream_t stream);
 
+/* ---- N26: annotation PNGs decoded on the device - what Image.open does for the label maps in the reference's readers
+   (data_loader.py:595-614 read_clips, leoloader.py:220-235 VOCDataset.__getitem__), bit-equal to np.asarray(Image.open(...)).
+   The HOST half (png_scan.cpp: no HIP, no state, no allocation, re-entrant; every read checked against `len`, every write against the
+   caller's capacity) walks the chunks, checks the CRC-32 of the critical ones and concatenates the IDAT payloads; the DEVICE half
+   (png_decode.hip) inflates, checks the Adler-32, undoes the row filters and unpacks, one wave per file.  The scheme, its bounds and the
+   status rules: csrc/png_inflate.hpp, DESIGN.md N26.
+   Supported: non-interlaced palette maps at depth 1 / 2 / 4 / 8 (the output is the index) and gray maps at depth 8.
+   Status: TT_PNG_OK; > 0 a well-formed file this decoder does not take (the caller falls back); < 0 a broken file or a bad argument. */
+#define TT_PNG_OK 0
+#define TT_PNG_UNSUPPORTED_INTERLACE 1     /* Adam7 */
+#define TT_PNG_UNSUPPORTED_COLOUR 2        /* a colour type other than 3 (palette) or 0 (gray) */
+#define TT_PNG_UNSUPPORTED_GRAY_DEPTH 3    /* gray below 8 bits: Pillow rescales those */
+#define TT_PNG_UNSUPPORTED_16BIT 4
+#define TT_PNG_UNSUPPORTED_SIZE 5          /* a side above 32767: more than the kernels that read the maps take */
+#define TT_PNG_EMALFORMED (-1)             /* signature, IHDR, chunk order, zlib header; stored-block length check, reserved block type */
+#define TT_PNG_ETRUNCATED (-2)             /* a chunk past the end of the file; the stream or the output ends early */
+#define TT_PNG_EHUFFMAN (-3)               /* a refused code-length set or a code no table holds */
+#define TT_PNG_EDISTANCE (-4)              /* a back-reference before the first byte */
+#define TT_PNG_EOVERRUN (-5)               /* more than H (1 + row_bytes) inflated bytes */
+#define TT_PNG_ECHECKSUM (-6)              /* CRC-32 of a critical chunk (host), Adler-32 of the inflated bytes (device) */
+#define TT_PNG_EFILTER (-7)                /* a filter byte above 4 */
+#define TT_PNG_EARGUMENT (-8)              /* null pointer, capacity too small, a table row that is no file */
+int tt_png_probe(const uint8_t* data, size_t len, int* H, int* W, int* bit_depth, int* color_type);
+/* One row per file.  row_bytes = ceil(W depth / 8).  stream_off: bytes into `streams` (a multiple of 4) of the file's deflate stream from
+   its first block on, stream_len bytes, the Adler-32 trailer included.  out_off: bytes into `out` of the file's uint8 [H, W] map.  ws_off:
+   bytes into the workspace of the file's H (1 + row_bytes) inflated bytes. */
+typedef struct {
+  int64_t H, W, depth, color_type, row_bytes;
+  int64_t stream_off, stream_len;
+  int64_t out_off, ws_off;
+  int64_t reserved[7];
+} tt_png_stream;
+/* The capacity tt_png_prepare needs for a file of `len` bytes, from len alone. */
+int tt_png_prepare_bytes(size_t len, size_t* stream_bytes);
+/* Status as tt_png_probe's (a wrong CRC-32 in IHDR / PLTE / IDAT / IEND: TT_PNG_ECHECKSUM; a capacity too small: TT_PNG_EARGUMENT).  Writes
+   the stream behind its two-byte zlib header (checked: method 8, window <= 32 KB, check bits, no preset dictionary) at stream[0], zero-padded
+   to 4 bytes, and the row with stream_off, out_off and ws_off 0: the caller sets where it put them. */
+int tt_png_prepare(const uint8_t* data, size_t len, uint8_t* stream, size_t stream_capacity, tt_png_stream* row);
+/* Bytes of workspace of a batch: the slices the table's ws_off place, rounded to 16, then per file eight int32 of statistics (block kinds
+   seen as a bit mask, longest literal/length and distance code used, smallest and largest distance, longest match, filters seen as a bit
+   mask, inflated bytes); 0: a row is not a file.  Pure host function. */
+size_t tt_png_decode_batch_workspace_bytes(const tt_png_stream* table, int n_files);
+/* One wave per file, one launch.  table_host is checked in full against stream_bytes, out_bytes and workspace_bytes - offsets, extents,
+   4-byte stream alignment, overlapping outputs or slices - before anything is launched (TT_EINVAL, no launch, nothing written); the kernel
+   reads table_dev.  status: device int32 [n_files], 0 or the TT_PNG_E* code of the file's first error; a failed file's pixels are
+   unspecified inside its own slice, the others' are not affected.  streams and workspace 4-byte aligned.  Allocates nothing, synchronises
+   nothing. */
+int tt_png_decode_batch(const uint8_t* streams, long long stream_bytes, const tt_png_stream* table_host, const tt_png_stream* table_dev,
+                        int n_files, uint8_t* out, long long out_bytes, void* workspace, size_t workspace_bytes, int32_t* status_dev,
+                        tt_stream_t stream);
+/* The same arguments as host pointers (table_dev and `stream` are not looked at): the sequential loop over the same csrc/png_inflate.hpp
+   steps, with the same status codes and statistics.  No GPU call. */
+int tt_png_decode_host(const uint8_t* streams, long long stream_bytes, const tt_png_stream* table_host, const tt_png_stream* table_dev,
+                       int n_files, uint8_t* out, long long out_bytes, void* workspace, size_t workspace_bytes, int32_t* status,
+                       tt_stream_t stream);
+/* The same again with the kernel's 64 lanes: 64 host threads run the shared inflate side by side behind a barrier, so that the pending
+   literals, the lane-strided copies, the table fill and the Adler partial sums run on the CPU as on the device (lane 0 then runs the
+   sequential unfilter).  Same status codes and statistics.  A testing aid for the no-GPU tests and the sanitizer program: it starts
+   threads, and a barrier per match makes it slow on large files. */
+int tt_png_decode_host_wave(const uint8_t* streams, long long stream_bytes, const tt_png_stream* table_host, const tt_png_stream* table_dev,
+                            int n_files, uint8_t* out, long long out_bytes, void* workspace, size_t workspace_bytes, int32_t* status,
+                            tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

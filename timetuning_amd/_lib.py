@@ -224,6 +224,13 @@ SIGNATURES = {
     "tt_label_presence_segments": (c_i, [c_vp, c_i, c_i, c_ll, c_vp, c_vp, c_vp]),
     "tt_map_instances_workspace_bytes": (c_sz, [c_i]),
     "tt_map_instances": (c_i, [c_vp, c_vp, c_vp, c_i, c_ll, c_i, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "tt_png_probe": (c_i, [c_vp, c_sz, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i)]),
+    "tt_png_prepare_bytes": (c_i, [c_sz, C.POINTER(c_sz)]),
+    "tt_png_prepare": (c_i, [c_vp, c_sz, c_vp, c_sz, c_vp]),
+    "tt_png_decode_batch_workspace_bytes": (c_sz, [c_vp, c_i]),
+    "tt_png_decode_batch": (c_i, [c_vp, c_ll, c_vp, c_vp, c_i, c_vp, c_ll, c_vp, c_sz, c_vp, c_vp]),
+    "tt_png_decode_host": (c_i, [c_vp, c_ll, c_vp, c_vp, c_i, c_vp, c_ll, c_vp, c_sz, c_vp, c_vp]),
+    "tt_png_decode_host_wave": (c_i, [c_vp, c_ll, c_vp, c_vp, c_i, c_vp, c_ll, c_vp, c_sz, c_vp, c_vp]),
 }
 
 _lib = None

@@ -316,6 +316,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--model_path", type=str, default="/home/ssalehi/video/dino/outputs/checkpoint0080.pth")
     p.add_argument("--dataset", type=str, default="davis")
     p.add_argument("--dataset_path", type=str, default="../data")
+    p.add_argument("--png_decode", choices=["host", "device"], default="host",
+                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
     p.add_argument("--destination_path", type=str, default="ytvos")
     p.add_argument("--evaluation_protocol", type=str, default="dataset-wise")
     p.add_argument("--logging_directory", type=str, default="visualizations")
@@ -357,8 +359,8 @@ def main(args=None) -> float:
     if args.dataset == "voc":                                                            # :340-341
         from .leoloader import pascal_loader
 
-        train_loader = pascal_loader(args.batch_size, args.dataset_path, "trainaug", eval_resolution, train_size=args.input_resolution)
-        val_loader = pascal_loader(args.batch_size, args.dataset_path, "val", eval_resolution, train_size=args.input_resolution)
+        train_loader = pascal_loader(args.batch_size, args.dataset_path, "trainaug", eval_resolution, train_size=args.input_resolution, png=args.png_decode)
+        val_loader = pascal_loader(args.batch_size, args.dataset_path, "val", eval_resolution, train_size=args.input_resolution, png=args.png_decode)
         eval_batches = val_loader
     else:
         x_tr, y_tr = synthetic_segmentation(args.num_train_images, args.input_resolution, 21, seed=1)

@@ -12,8 +12,10 @@ What differs, on purpose:
   A file ``hip_ops.jpeg_probe`` reports as unsupported (progressive, grayscale, CMYK, ...) - or a frame that is not a JPEG at all - is
   decoded with Pillow on the host and uploaded, and COUNTED (``fallback_frames``).  A supported file that fails to decode raises: the
   fallback never hides a decoder failure.
-* Annotation PNGs (mode ``P`` / ``L`` -> indices) are decoded with Pillow on the host and uploaded as ``uint8 [fs, H, W]``: they are small
-  and carry no arithmetic.
+* Annotation PNGs (mode ``P`` / ``L`` -> indices) become ``uint8 [fs, H, W]`` on the device.  ``png="host"`` (the default): Pillow in the
+  loader's thread pool (its decoder releases the GIL), one upload per clip.  ``png="device"`` (N26): the compressed IDAT streams of the whole
+  batch cross PCIe once and ``hip_ops.png_decode`` inflates and unfilters them in one launch; a file ``hip_ops.png_probe`` reports as
+  unsupported (interlaced, RGB, 16-bit, ...) is decoded with Pillow and COUNTED (``fallback_annotations``), a broken one raises.
 * A video's length is the number of its frame files (the reference counts every directory entry, ``:590-592``); its label is its position
   in the sorted list (the reference: its position in ``os.listdir``'s arbitrary order).
 * ``frame_transformation`` errors raise (the reference prints "Error in frame transformation" and goes on with the untransformed clip).
@@ -99,6 +101,66 @@ def decode_annotation(data: bytes) -> np.ndarray:
     return np.asarray(im, np.uint8)
 
 
+def decode_annotations(files, threads: int = 1) -> List[np.ndarray]:
+    """``decode_annotation`` of every file, in the pool the JPEG batches use (at most 16 threads; Pillow's decoder releases the GIL): the
+    list a serial loop gives."""
+    files = list(files)
+    workers = max(1, min(int(threads), ops.JPEG_MAX_THREADS, len(files)))
+    if workers == 1:
+        return [decode_annotation(f) for f in files]
+    return list(ops._jpeg_pool(workers).map(decode_annotation, files))
+
+
+class HostAnnotations:
+    """The host half of a list of annotation files on the ``png="device"`` route: ``prepared`` - the ``hip_ops.PngBatch`` of the files the
+    device decoder takes, None without any -, ``device_slots`` their places in the list, ``host_maps`` {slot: uint8 [H, W]} the Pillow
+    decode of every other file."""
+
+    def __init__(self, prepared, device_slots, host_maps, n):
+        self.prepared, self.device_slots, self.host_maps, self.n = prepared, device_slots, host_maps, n
+
+
+def scan_annotations(files, threads: int, pin: Optional[bool] = None) -> HostAnnotations:
+    """Classifies every annotation file and prepares the supported ones (``hip_ops.png_prepare_batch``); an unsupported file is decoded
+    with Pillow.  A broken PNG raises ``ValueError``.  No GPU call: a background thread may run it."""
+    device_slots, host_maps = [], {}
+    for k, data in enumerate(files):
+        if ops.png_probe(data).supported:     # a broken file raises here
+            device_slots.append(k)
+        else:
+            host_maps[k] = decode_annotation(data)
+    pin = torch.cuda.is_available() if pin is None else pin
+    prepared = ops.png_prepare_batch([files[k] for k in device_slots], threads, pin) if device_slots else None
+    return HostAnnotations(prepared, device_slots, host_maps, len(files))
+
+
+def finish_annotations(host: HostAnnotations, device):
+    """The device half of ``scan_annotations``: (the maps as uint8 [H, W] tensors on ``device`` in file order - the device-decoded ones
+    views of ONE flat buffer, consecutive files one after the other -, the number of maps Pillow decoded)."""
+    maps = [None] * host.n
+    if host.prepared is not None:
+        decoded, _ = ops.png_decode(host.prepared, device)      # a non-zero status raises, naming the file
+        for k, m in zip(host.device_slots, decoded):
+            maps[k] = m
+    for k, arr in host.host_maps.items():
+        maps[k] = torch.from_numpy(np.array(arr)).to(device)     # (Pillow's array is read-only)
+    return maps, len(host.host_maps)
+
+
+def maps_as_clip(maps) -> torch.Tensor:
+    """Label maps of one size -> [k, H, W]: the tensor they are consecutive views of where they are (``hip_ops.png_decode``), a stacked
+    copy otherwise."""
+    m0 = maps[0]
+    step = m0.numel()
+    same = all(m.shape == m0.shape and m.is_contiguous() and m.device == m0.device and
+               m.untyped_storage().data_ptr() == m0.untyped_storage().data_ptr() and
+               m.storage_offset() == m0.storage_offset() + i * step for i, m in enumerate(maps))
+    if not same:
+        return torch.stack(list(maps))
+    H, W = m0.shape
+    return m0.as_strided((len(maps), H, W), (step, W, 1), m0.storage_offset())
+
+
 def decode_frame_on_host(data: bytes) -> np.ndarray:
     """The counted fallback: Pillow's decode, uint8 [H, W, 3]."""
     from PIL import Image
@@ -165,8 +227,9 @@ def _read(path: str) -> bytes:
 class _HostSample:
     """One video's clips as the host leaves them: the frame files' bytes and the decoded annotation maps, per clip."""
 
-    def __init__(self, frames, annotations, label, index=None):
+    def __init__(self, frames, annotations, label, index=None, annotation_files=None):
         self.frames, self.annotations, self.label, self.index = frames, annotations, label, index
+        self.annotation_files = annotation_files      # png="device": the files' bytes per clip, and ``annotations`` is None
 
 
 class HostFrames:
@@ -209,25 +272,29 @@ def finish_frames(host: HostFrames, device):
 
 
 class _HostBatch:
-    def __init__(self, samples, frames: HostFrames):
-        self.samples, self.frames = samples, frames
+    def __init__(self, samples, frames: HostFrames, annotations: Optional[HostAnnotations] = None):
+        self.samples, self.frames, self.annotations = samples, frames, annotations
 
 
 class VideoDataset:
     """``VideoDataset(classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, ...)`` (``:552``).  ``rng`` draws the
     frame indices (default: the ``random`` module, as in the reference); ``device`` and ``threads`` belong to the decode, and so does
     ``jpeg_entropy``: "host" undoes the Huffman coding in the thread pool (``hip_ops.jpeg_scan_batch``), "device" copies the compressed
-    scans and undoes it in one launch (``hip_ops.jpeg_prepare_batch``) - the same pixels either way.
+    scans and undoes it in one launch (``hip_ops.jpeg_prepare_batch``) - the same pixels either way.  ``png``: "host" decodes the
+    annotation PNGs with Pillow in the thread pool, "device" inflates and unfilters them in one launch per batch
+    (``hip_ops.png_decode``) - the same maps either way.
     ``meta_file_directory`` (``:563-573``): the path of a YouTube-VOS ``meta.json``; when the file exists the annotations' per-video
     instance ids become dataset-wide category ids (``map_categories``), ``sequential_category_map`` choosing the rule of
     ``compose_instance_lut``.  A path that does not exist prints "There is no meta file." and maps nothing, as in the reference."""
 
     def __init__(self, classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, num_labels=1, frame_transform=None,
                  target_transform=None, video_transform=None, meta_file_directory=None, regular_step=1, device=None, threads=8, rng=None,
-                 sequential_category_map=True, jpeg_entropy="host"):
+                 sequential_category_map=True, jpeg_entropy="host", png="host"):
         if jpeg_entropy not in ("host", "device"):
             raise ValueError(f"jpeg_entropy must be 'host' or 'device', not {jpeg_entropy!r}")
-        self.jpeg_entropy = jpeg_entropy
+        if png not in ("host", "device"):
+            raise ValueError(f"png must be 'host' or 'device', not {png!r}")
+        self.jpeg_entropy, self.png = jpeg_entropy, png
         if num_labels != 1:
             raise NotImplementedError("nested class directories (num_labels > 1) are not reproduced")
         self.meta_dict, self.category_dict, self.category_tables = None, None, None
@@ -264,6 +331,7 @@ class VideoDataset:
         self.threads = int(threads)
         self.rng = random if rng is None else rng
         self.fallback_frames = 0
+        self.fallback_annotations = 0
 
     def __len__(self):
         return len(self.keys)
@@ -272,28 +340,45 @@ class VideoDataset:
         return generate_indices(size, sampling_num, self.sampling_mode, self.num_clips, self.regular_step, self.rng if rng is None else rng)
 
     # ---- host half: index draws, file reads, annotation decode (no GPU call: a background thread may run it)
-    def read_host(self, idx: int, rng=None) -> _HostSample:
+    def read_host(self, idx: int, rng=None, png: Optional[str] = None, decode: bool = True) -> _HostSample:
+        """The index draws and file reads of one video.  Its annotation files are decoded here on the "host" route (in the thread pool)
+        unless ``decode`` is False: a loader leaves them as bytes for ``scan_host``, which pools over the whole BATCH."""
         path = self.keys[idx]
         clip_indices = self.generate_indices(self.train_dict_lenghts[path], self.num_frames, rng)
         files = self.files[path]
         frames = [[_read(files[j]) for j in clip] for clip in clip_indices]
-        annotations = None
+        annotations, raw = None, None
         if self.use_annotations:
             afiles = self.annotation_files[self.annotation_keys[idx]]
-            annotations = [np.stack([decode_annotation(_read(afiles[j])) for j in clip]) for clip in clip_indices]
-        return _HostSample(frames, annotations, np.tile(self.train_dict[path], (self.num_clips,)), idx)
+            raw = [[_read(afiles[j]) for j in clip] for clip in clip_indices]
+            if (png or self.png) == "host" and decode:
+                decoded = iter(decode_annotations([f for clip in raw for f in clip], self.threads))
+                annotations, raw = [np.stack([next(decoded) for _ in clip]) for clip in raw], None
+        return _HostSample(frames, annotations, np.tile(self.train_dict[path], (self.num_clips,)), idx, raw)
 
-    def scan_host(self, samples: List[_HostSample], jpeg_entropy: Optional[str] = None) -> _HostBatch:
+    def scan_host(self, samples: List[_HostSample], jpeg_entropy: Optional[str] = None, png: Optional[str] = None) -> _HostBatch:
         """Classifies every frame of the samples, entropy-decodes the supported ones into one pinned buffer and decodes the others with
-        Pillow."""
+        Pillow.  The annotation files the samples still carry as bytes are, on the "host" route, decoded in the thread pool - all files
+        of the batch in one go - and on the "device" route prepared for ONE device decode."""
         flat = [f for s in samples for clip in s.frames for f in clip]
-        return _HostBatch(samples, scan_frames(flat, self.threads, jpeg_entropy or self.jpeg_entropy))   # a loader may choose for itself
+        pending = [s for s in samples if s.annotation_files is not None]
+        if pending and (png or self.png) == "host":
+            decoded = iter(decode_annotations([f for s in pending for clip in s.annotation_files for f in clip], self.threads))
+            for s in pending:
+                s.annotations, s.annotation_files = [np.stack([next(decoded) for _ in clip]) for clip in s.annotation_files], None
+        ann = [f for s in samples if s.annotation_files is not None for clip in s.annotation_files for f in clip]
+        return _HostBatch(samples, scan_frames(flat, self.threads, jpeg_entropy or self.jpeg_entropy),    # a loader may choose for itself
+                          scan_annotations(ann, self.threads) if ann else None)
 
     # ---- device half: reconstruction, transforms
     def finish(self, batch: _HostBatch):
         """-> per sample (data, annotations, label) as ``__getitem__`` returns them."""
         flat, fallbacks = finish_frames(batch.frames, self.device)
         self.fallback_frames += fallbacks
+        maps, m_at = None, 0
+        if batch.annotations is not None:
+            maps, fallbacks = finish_annotations(batch.annotations, self.device)
+            self.fallback_annotations += fallbacks
         out, at = [], 0
         for s in batch.samples:
             clips = []
@@ -301,6 +386,11 @@ class VideoDataset:
                 clips.append(ops.frames_as_clip(flat[at:at + len(clip)]))
                 at += len(clip)
             ann = None if s.annotations is None else [torch.from_numpy(a).to(self.device) for a in s.annotations]
+            if s.annotation_files is not None:
+                ann = []
+                for clip in s.annotation_files:
+                    ann.append(maps_as_clip(maps[m_at:m_at + len(clip)]))
+                    m_at += len(clip)
             out.append(self._transform(clips, ann) + (torch.Tensor(s.label),))
         return out
 
@@ -368,10 +458,13 @@ class ClipLoader:
     (``drop_last=False``, the DataLoader default)."""
 
     def __init__(self, dataset: VideoDataset, batch_size: int, shuffle: bool = False, world_size: int = 1, rank: int = 0, seed: int = 0,
-                 prefetch: bool = True, jpeg_entropy: Optional[str] = None):
+                 prefetch: bool = True, jpeg_entropy: Optional[str] = None, png: Optional[str] = None):
         if jpeg_entropy not in (None, "host", "device"):
             raise ValueError(f"jpeg_entropy must be 'host' or 'device', not {jpeg_entropy!r}")
+        if png not in (None, "host", "device"):
+            raise ValueError(f"png must be 'host' or 'device', not {png!r}")
         self.jpeg_entropy = dataset.jpeg_entropy if jpeg_entropy is None else jpeg_entropy   # the loader's own: the dataset is not touched
+        self.png = dataset.png if png is None else png
         self.dataset, self.batch_size, self.shuffle, self.world_size, self.rank, self.seed = dataset, int(batch_size), shuffle, world_size, rank, seed
         self.prefetch, self.epoch = prefetch, 0
         self.rng = random.Random(seed * 1000003 + rank)
@@ -379,6 +472,10 @@ class ClipLoader:
     @property
     def fallback_frames(self) -> int:
         return self.dataset.fallback_frames
+
+    @property
+    def fallback_annotations(self) -> int:
+        return self.dataset.fallback_annotations
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
@@ -406,8 +503,8 @@ class ClipLoader:
         dev = self.dataset.device
         if dev is not None and torch.device(dev).type == "cuda":
             with torch.cuda.device(dev):   # a new thread starts on device 0: the pinned buffers belong to this rank's device
-                return self.dataset.scan_host([self.dataset.read_host(i, self.rng) for i in indices], self.jpeg_entropy)
-        return self.dataset.scan_host([self.dataset.read_host(i, self.rng) for i in indices], self.jpeg_entropy)
+                return self.dataset.scan_host([self.dataset.read_host(i, self.rng, self.png, decode=False) for i in indices], self.jpeg_entropy, self.png)
+        return self.dataset.scan_host([self.dataset.read_host(i, self.rng, self.png, decode=False) for i in indices], self.jpeg_entropy, self.png)
 
     def __iter__(self):
         order = self._order()
@@ -434,10 +531,11 @@ class ClipLoader:
 def make_loader(dataset_path: str, num_clip_frames: int, batch_size: int, regular_step: int = 1, sampling_mode: SamplingMode = SamplingMode.UNIFORM,
                 frame_transform=None, target_transform=None, video_transform=None, shuffle: bool = False, num_workers: int = 6, world_size: int = 1,
                 rank: int = 0, device=None, seed: int = 0, meta_file_directory=None, sequential_category_map: bool = True,
-                jpeg_entropy: str = "host") -> ClipLoader:
+                jpeg_entropy: str = "host", png: str = "host") -> ClipLoader:
     """``make_loader`` (``:1047``) for the layout every ``VideoDataset`` branch of it reads: frames under ``<dataset_path>/JPEGImages/``,
     annotations under ``<dataset_path>/Annotations/`` when present.  ``num_workers`` is the thread count of the host decode (at most 16
-    are used); ``jpeg_entropy`` "host" / "device": where the frames' Huffman coding is undone (``VideoDataset``).  ``meta_file_directory``: the path of a YouTube-VOS ``meta.json`` - a ``YVOSDataset`` then maps instance ids to category
+    are used); ``jpeg_entropy`` "host" / "device": where the frames' Huffman coding is undone, ``png`` "host" /
+    "device": where the annotation PNGs are inflated (``VideoDataset``).  ``meta_file_directory``: the path of a YouTube-VOS ``meta.json`` - a ``YVOSDataset`` then maps instance ids to category
     ids (the ``ytvos`` branches, ``:1073-1090``).  It is never looked for: without the argument a tree that holds one is read as before."""
     frames = os.path.join(dataset_path, "JPEGImages")
     if not os.path.isdir(frames):
@@ -448,5 +546,5 @@ def make_loader(dataset_path: str, num_clip_frames: int, batch_size: int, regula
     cls = VideoDataset if meta_file_directory is None else YVOSDataset
     dataset = cls(frames, os.path.join(dataset_path, "Annotations"), sampling_mode, 1, num_clip_frames, 1, frame_transform,
                   target_transform, video_transform, meta_file_directory=meta_file_directory, regular_step=regular_step, device=device,
-                  threads=num_workers, sequential_category_map=sequential_category_map, jpeg_entropy=jpeg_entropy)
+                  threads=num_workers, sequential_category_map=sequential_category_map, jpeg_entropy=jpeg_entropy, png=png)
     return ClipLoader(dataset, batch_size, shuffle=shuffle, world_size=world_size, rank=rank, seed=seed)

@@ -222,6 +222,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_workers", type=int, default=3)
     p.add_argument("--jpeg_entropy", choices=["host", "device"], default="host",
                    help="where the frames' Huffman coding is undone: in the host thread pool, or on the device from the compressed scans (N24)")
+    p.add_argument("--png_decode", choices=["host", "device"], default="host",
+                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
     p.add_argument("--num_clusters", type=int, default=10)
     p.add_argument("--input_resolution", type=int, default=224)
     p.add_argument("--many_to_one", type=bool, default=False)
@@ -254,7 +256,7 @@ def main(argv=None, vit_cfg=None) -> float:
         from .leoloader import EvaluatorLoader, pascal_loader
 
         voc_loader = EvaluatorLoader(pascal_loader(args.batch_size, args.dataset_path, "val", eval_resolution, train_size=args.input_resolution,
-                                                       jpeg_entropy=args.jpeg_entropy))
+                                                       jpeg_entropy=args.jpeg_entropy, png=args.png_decode))
     num_epochs, num_itr = 50, 1000                                                     # :491,513
     device = torch.device("cuda", 0)
     fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], vit_cfg=vit_cfg, return_attention=False)  # :520
@@ -270,7 +272,7 @@ def main(argv=None, vit_cfg=None) -> float:
         meta = os.path.join(args.dataset_path, "meta.json")
         loader = DL.make_loader(args.dataset_path, args.num_frames, args.batch_size, sampling_mode=DL.SamplingMode.UNIFORM, frame_transform=None,
                                 target_transform=None, video_transform=VT.evaluation_transforms(args.input_resolution), shuffle=False,
-                                num_workers=args.num_workers, device=device, jpeg_entropy=args.jpeg_entropy,
+                                num_workers=args.num_workers, device=device, jpeg_entropy=args.jpeg_entropy, png=args.png_decode,
                                 meta_file_directory=meta if "ytvos" in args.dataset and os.path.isfile(meta) else None,
                                 sequential_category_map=not args.plain_category_map)
         if not loader.dataset.use_annotations:

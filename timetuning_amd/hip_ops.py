@@ -2984,3 +2984,172 @@ def map_instances(labels: torch.Tensor, cat: torch.Tensor, sequential: bool = Tr
         _lib.check(lib.tt_map_instances(_p(labels), _p(out), _p(cat), S, P, 1 if sequential else 0, _p(lut), _p(status), _p(ws), ws_bytes,
                                         _stream()), "tt_map_instances")
     return out, lut, status
+
+
+# ---- N26: annotation PNGs.  The host half (tt_png_probe, tt_png_prepare: chunks and CRC-32 only, pure host functions that ctypes runs
+# without the GIL) in the thread pool of the JPEG batches, the device half (tt_png_decode_batch: inflate, Adler-32, row filters, unpacking)
+# in one launch for the whole batch.
+PNG_UNSUPPORTED = {1: "Adam7 interlace", 2: "a colour type other than palette or gray", 3: "gray below 8 bits", 4: "16-bit samples",
+                   5: "a side above 32767"}
+PNG_MALFORMED = {-1: "broken signature, IHDR, zlib header or block header", -2: "the file, the stream or the output ends early",
+                 -3: "a refused code-length set or a code no table holds", -4: "a back-reference before the first byte",
+                 -5: "more inflated bytes than the header's rows hold", -6: "a wrong CRC-32 or Adler-32", -7: "a filter byte above 4",
+                 -8: "bad argument"}
+_PNG_STREAM = np.dtype([("H", "<i8"), ("W", "<i8"), ("depth", "<i8"), ("color_type", "<i8"), ("row_bytes", "<i8"), ("stream_off", "<i8"),
+                        ("stream_len", "<i8"), ("out_off", "<i8"), ("ws_off", "<i8"), ("reserved", "<i8", 7)])                # tt_png_stream
+PNG_STATS = ("kinds", "lit_bits", "dist_bits", "min_dist", "max_dist", "max_len", "filters", "bytes")   # the eight int32 per file
+
+
+class PngUnsupported(Exception):
+    """A well-formed PNG file the device decoder does not take (``status`` > 0: TT_PNG_UNSUPPORTED_*).  hip_ops has no CPU fallback;
+    the loaders decode such a file with Pillow and count it."""
+
+    def __init__(self, status: int, index: Optional[int] = None):
+        self.status, self.index = int(status), index
+        where = "" if index is None else f"file {index}: "
+        super().__init__(f"{where}unsupported PNG ({PNG_UNSUPPORTED.get(int(status), status)})")
+
+
+class PngInfo:
+    """What ``png_probe`` found: ``status`` 0 = the device decoder takes the file, > 0 = unsupported; H, W, bit depth, colour type."""
+
+    def __init__(self, status, H, W, depth, color_type):
+        self.status, self.H, self.W, self.depth, self.color_type = status, H, W, depth, color_type
+
+    @property
+    def supported(self) -> bool:
+        return self.status == 0
+
+    def __repr__(self):
+        return f"PngInfo(status={self.status}, H={self.H}, W={self.W}, depth={self.depth}, color_type={self.color_type})"
+
+
+def _png_error(status: int, index: Optional[int] = None) -> Exception:
+    if status > 0:
+        return PngUnsupported(status, index)
+    where = "" if index is None else f"file {index}: "
+    return ValueError(f"{where}malformed PNG (status {status}: {PNG_MALFORMED.get(int(status), 'unknown')})")
+
+
+def _png_probe_raw(lib, data: bytes) -> PngInfo:
+    H, W, depth, color = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = lib.tt_png_probe(data, len(data), C.byref(H), C.byref(W), C.byref(depth), C.byref(color))
+    return PngInfo(rc, H.value, W.value, depth.value, color.value)
+
+
+def png_probe(data: bytes) -> PngInfo:
+    """Classifies a PNG file without decoding it.  A broken file raises ValueError; an unsupported one is a PngInfo with status > 0."""
+    info = _png_probe_raw(_lib.load(), bytes(data))
+    if info.status < 0:
+        raise _png_error(info.status)
+    return info
+
+
+class PngBatch:
+    """The host half of a batch of annotation files, ready for the device: ONE (pinned) buffer ``meta`` holding the stream table, then
+    every file's deflate stream; ``layout``: name -> (offset, bytes) of its two parts 'table' and 'streams', each on a 16-byte boundary.
+    The maps lie one after the other in the output (``out_bytes`` in all), so consecutive files of one size are one [k, H, W] tensor."""
+
+    def __init__(self, infos, meta, layout, out_bytes, ws_bytes):
+        self.infos, self.meta, self.layout, self.out_bytes, self.ws_bytes = infos, meta, layout, out_bytes, ws_bytes
+
+    def part(self, name):
+        at, size = self.layout[name]
+        return self.meta.numpy()[at:at + size]
+
+    @property
+    def table(self):
+        return self.part("table").view(_PNG_STREAM)
+
+
+def png_prepare_batch(files: Sequence[bytes], threads: int = 8, pin: bool = True) -> PngBatch:
+    """Probes every file and copies its IDAT payloads, CRC-checked, into ONE (pinned) buffer in the thread pool; nothing is inflated.
+    Raises PngUnsupported for the first unsupported file and ValueError for the first broken one (chunks, CRC-32, zlib header: the
+    deflate stream itself is the device's to judge)."""
+    lib = _lib.load()
+    files = [bytes(f) for f in files]
+    n = len(files)
+    if n == 0:
+        raise ValueError("png_prepare_batch: no files")
+    workers = max(1, min(int(threads), JPEG_MAX_THREADS, n))
+    chunks = [range(k * n // workers, (k + 1) * n // workers) for k in range(workers)]
+    run = (lambda fn: [fn(c) for c in chunks]) if workers == 1 else (lambda fn: list(_jpeg_pool(workers).map(fn, chunks)))
+    cap = np.zeros(n + 1, np.int64)
+    a = C.c_size_t()
+    for i, f in enumerate(files):
+        lib.tt_png_prepare_bytes(len(f), C.byref(a))
+        cap[i + 1] = a.value
+    np.cumsum(cap, out=cap)
+    layout = {"table": (0, n * _PNG_STREAM.itemsize), "streams": (n * _PNG_STREAM.itemsize, int(cap[-1]))}   # 128-byte rows: aligned
+    meta = torch.zeros(n * _PNG_STREAM.itemsize + int(cap[-1]), dtype=torch.uint8, pin_memory=pin)
+    rows_at, streams_at, at = meta.data_ptr(), meta.data_ptr() + layout["streams"][0], cap.tolist()
+    results = [r for part in run(lambda chunk: [lib.tt_png_prepare(files[i], len(files[i]), streams_at + at[i], at[i + 1] - at[i],
+                                                                    rows_at + i * _PNG_STREAM.itemsize) for i in chunk]) for r in part]
+    for i, rc in enumerate(results):
+        if rc:
+            raise _png_error(rc, i)
+    table = meta.numpy()[:layout["table"][1]].view(_PNG_STREAM)
+    table["stream_off"] = cap[:-1]
+    pixels = table["H"] * table["W"]
+    slices = (table["H"] * (1 + table["row_bytes"]) + 15) // 16 * 16
+    table["out_off"] = np.cumsum(pixels) - pixels
+    table["ws_off"] = np.cumsum(slices) - slices
+    infos = [PngInfo(0, int(r["H"]), int(r["W"]), int(r["depth"]), int(r["color_type"])) for r in table]
+    return PngBatch(infos, meta, layout, int(pixels.sum()), int(lib.tt_png_decode_batch_workspace_bytes(table.ctypes.data, n)))
+
+
+def _png_views(flat, table):
+    return [flat[int(r["out_off"]):int(r["out_off"]) + int(r["H"]) * int(r["W"])].reshape(int(r["H"]), int(r["W"])) for r in table]
+
+
+def png_decode_host(batch: PngBatch, lanes: int = 1):
+    """The host emulation of the device decode (tt_png_decode_host: the sequential loop over the kernel's steps), for tests and tools:
+    (the maps as uint8 [H, W] NumPy views of one flat buffer, status int32 [n], statistics int32 [n, 8] in the order of PNG_STATS, the
+    inflated - and, where the status is 0, unfiltered - bytes of every file).  Raises nothing for a broken stream: the status says it.
+    ``lanes`` = 64: tt_png_decode_host_wave, the inflate with the kernel's 64 lanes as 64 threads behind a barrier (slow on large files)."""
+    if lanes not in (1, 64):
+        raise ValueError(f"png_decode_host: lanes must be 1 or 64, not {lanes}")
+    lib, n = _lib.load(), len(batch.infos)
+    table, streams = batch.table, batch.part("streams")
+    out, status = np.zeros(max(batch.out_bytes, 1), np.uint8), np.zeros(n, np.int32)
+    ws = np.zeros(batch.ws_bytes // 4 + 1, np.int32)
+    _lib.check((lib.tt_png_decode_host if lanes == 1 else lib.tt_png_decode_host_wave)(streams.ctypes.data, streams.size, table.ctypes.data, table.ctypes.data, n, out.ctypes.data, batch.out_bytes,
+                                      ws.ctypes.data, batch.ws_bytes, status.ctypes.data, None), "tt_png_decode_host")
+    raw = ws.view(np.uint8)
+    slices = [raw[int(r["ws_off"]):int(r["ws_off"]) + int(r["H"]) * (1 + int(r["row_bytes"]))] for r in table]
+    return _png_views(out, table), status, ws[(batch.ws_bytes - 32 * n) // 4:batch.ws_bytes // 4].reshape(n, 8), slices
+
+
+def png_decode(batch: PngBatch, device=None, out: Optional[torch.Tensor] = None, check: bool = True):
+    """The device half: one host-to-device copy of the batch's buffer, ONE launch on the current stream, one read-back of 4 n bytes - the
+    files' status.  Returns (the maps as uint8 [H, W] views of ONE flat device buffer in file order - ``out``, a contiguous uint8 tensor
+    of at least ``batch.out_bytes`` elements, when given -, status int32 [n] on the host).  A non-zero status raises ValueError naming
+    the file and the reason unless ``check`` is False."""
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise _lib.HipLibraryError("png_decode: needs a GPU (the HIP path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    n, table = len(batch.infos), batch.table
+    with torch.cuda.device(dev):
+        meta = batch.meta.to(dev, non_blocking=True)
+        if out is None:
+            out = torch.empty(max(batch.out_bytes, 16), dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() != 1 or out.numel() < batch.out_bytes or out.device != dev:
+            raise ValueError(f"png_decode: out must be a flat contiguous uint8 tensor of at least {batch.out_bytes} elements on {dev}")
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        ws = _ws(batch.ws_bytes, dev)
+        _lib.check(lib.tt_png_decode_batch(meta.data_ptr() + batch.layout["streams"][0], batch.layout["streams"][1], table.ctypes.data,
+                                           meta.data_ptr(), n, _p(out), out.numel(), _p(ws), ws.numel(), _p(status), _stream()),
+                   "tt_png_decode_batch")
+        host_status = status.cpu().numpy()
+    if check:
+        for i, rc in enumerate(host_status):
+            if rc != 0:
+                raise _png_error(int(rc), i)
+    return _png_views(out, table), host_status
+
+
+def decode_png_batch(files: Sequence[bytes], device=None, threads: int = 8):
+    """Annotation PNG files -> uint8 [H, W] GPU label maps, bit-equal to ``np.asarray(Image.open(...))``; views of one flat buffer in file
+    order.  Unsupported files raise PngUnsupported (no CPU fallback here), broken ones ValueError."""
+    return png_decode(png_prepare_batch(files, threads, True), device)[0]

@@ -8,7 +8,9 @@ reference overrides ``shuffle`` to ``False``, ``:263``), the last batch partial.
 
 Here a batch is two host steps and three device steps.  Host (may run one batch ahead in a background thread, as ``data_loader.ClipLoader``
 does): the files are read, the JPEGs entropy-decoded into one pinned buffer (``data_loader.scan_frames``) and the PNGs decoded with Pillow
-(``data_loader.decode_annotation``) into ONE packed pinned buffer.  Device: ``data_loader.finish_frames`` reconstructs the frames, then
+(``data_loader.decode_annotations``, in the thread pool) into ONE packed pinned buffer - or, with ``png="device"`` (N26), prepared for ONE
+``hip_ops.png_decode`` launch whose buffer and offsets the mask gather then reads (a PNG it does not take: Pillow, counted in
+``fallback_annotations``).  Device: ``data_loader.finish_frames`` reconstructs the frames, then
 ONE ``tt_img_resize_ragged`` launch covers every image of the mixed-size batch and ONE ``tt_img_gather_nearest_ragged`` launch every mask.
 A JPEG the device decoder does not take (progressive, gray, ...) is decoded with Pillow and COUNTED (``fallback_frames``), by N21's rule; a
 supported file that fails to decode raises.  All of it is bit-equal to the reference's Pillow chain.
@@ -30,7 +32,7 @@ import numpy as np
 import torch
 
 from . import hip_ops as ops
-from .data_loader import _read, decode_annotation, finish_frames, scan_frames
+from .data_loader import _read, decode_annotations, finish_annotations, finish_frames, scan_annotations, scan_frames
 
 CLASS_IDX_TO_NAME = ['background', 'aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair',
                      'cow', 'diningtable', 'dog', 'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa',
@@ -160,13 +162,16 @@ def train_transforms(train_size: int) -> Compose:
 class VOCDataset:
     """The reference's file layout and errors: ``root/images/<name>.jpg``, ``root/SegmentationClassAug/<name>.png`` for ``train`` /
     ``trainaug`` and ``root/SegmentationClass/<name>.png`` for ``val``, names from ``root/sets/<image_set>.txt`` in the file's order.
-    ``device``, ``threads`` and ``jpeg_entropy`` ("host" / "device": where the Huffman coding is undone) belong to the decode."""
+    ``device``, ``threads``, ``jpeg_entropy`` ("host" / "device": where the Huffman coding is undone) and ``png`` ("host" / "device": where
+    the mask PNGs are inflated) belong to the decode."""
 
     def __init__(self, root: str, image_set: str = "trainaug", transform=None, target_transform=None, transforms=None, return_masks: bool = False,
-                 device=None, threads: int = 8, jpeg_entropy: str = "host"):
+                 device=None, threads: int = 8, jpeg_entropy: str = "host", png: str = "host"):
         if jpeg_entropy not in ("host", "device"):
             raise ValueError(f"jpeg_entropy must be 'host' or 'device', not {jpeg_entropy!r}")
-        self.jpeg_entropy = jpeg_entropy
+        if png not in ("host", "device"):
+            raise ValueError(f"png must be 'host' or 'device', not {png!r}")
+        self.jpeg_entropy, self.png = jpeg_entropy, png
         self.root, self.image_set = root, image_set
         if image_set == "trainaug" or image_set == "train":
             seg_folder = "SegmentationClassAug"
@@ -191,14 +196,16 @@ class VOCDataset:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None and torch.cuda.is_available() else device
         self.threads = int(threads)
         self.fallback_frames = 0
+        self.fallback_annotations = 0
 
     def __len__(self) -> int:
         return len(self.images)
 
 
 class _VOCHostBatch:
-    def __init__(self, frames, mask_buf, mask_offs, mask_dims):
+    def __init__(self, frames, mask_buf, mask_offs, mask_dims, masks=None):
         self.frames, self.mask_buf, self.mask_offs, self.mask_dims = frames, mask_buf, mask_offs, mask_dims
+        self.masks = masks      # png="device": the ``HostAnnotations`` of the batch, and the three mask_* fields are None
 
 
 class VOCLoader:
@@ -217,6 +224,10 @@ class VOCLoader:
     def fallback_frames(self) -> int:
         return self.dataset.fallback_frames
 
+    @property
+    def fallback_annotations(self) -> int:
+        return self.dataset.fallback_annotations
+
     def __len__(self) -> int:
         return -(-len(self.dataset) // self.batch_size)
 
@@ -224,7 +235,9 @@ class VOCLoader:
     def _host_on(self, indices) -> _VOCHostBatch:
         ds = self.dataset
         frames = scan_frames([_read(ds.images[i]) for i in indices], ds.threads, ds.jpeg_entropy)
-        masks = [decode_annotation(_read(ds.masks[i])) for i in indices]
+        if ds.png == "device":
+            return _VOCHostBatch(frames, None, None, None, scan_annotations([_read(ds.masks[i]) for i in indices], ds.threads))
+        masks = decode_annotations([_read(ds.masks[i]) for i in indices], ds.threads)
         offs = np.zeros(len(masks) + 1, np.int64)
         np.cumsum([m.size for m in masks], out=offs[1:])
         mask_buf = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
@@ -247,8 +260,13 @@ class VOCLoader:
             raise ops._lib.HipLibraryError("pascal_loader: needs a GPU (the HIP path has no CPU fallback)")
         frames, fallbacks = finish_frames(host.frames, ds.device)
         ds.fallback_frames += fallbacks
-        buf = host.mask_buf.to(ds.device, non_blocking=True)
-        maps = [buf[o:o + h * w].view(h, w) for o, (h, w) in zip(host.mask_offs, host.mask_dims)]
+        if host.masks is not None:      # the maps, their buffer and their offsets come straight from the decode
+            maps, fallbacks = finish_annotations(host.masks, ds.device)
+            ds.fallback_annotations += fallbacks
+            host.mask_dims = [tuple(m.shape) for m in maps]
+        else:
+            buf = host.mask_buf.to(ds.device, non_blocking=True)
+            maps = [buf[o:o + h * w].view(h, w) for o, (h, w) in zip(host.mask_offs, host.mask_dims)]
         S, R, boxes, flips, mean_std, target_float = self.train_size, self.val_size, None, None, (MEAN, STD), True
         if self.transforms is not None:
             if any(tuple(d) != tuple(m) for d, m in zip(host.frames.dims, host.mask_dims)):
@@ -281,10 +299,11 @@ class VOCLoader:
                 pool.shutdown(wait=True)
 
 
-def pascal_loader(batch_size, root, split, val_size, train_size=448, device=None, threads=8, jpeg_entropy="host") -> VOCLoader:
+def pascal_loader(batch_size, root, split, val_size, train_size=448, device=None, threads=8, jpeg_entropy="host", png="host") -> VOCLoader:
     """``leoloader.pascal_loader`` (``:241-264``): both of its branches apply the same image and target transforms, so both splits read
     through one path; ``train_transforms`` is built and unused there, and is not used here."""
-    dataset = VOCDataset(root=root, image_set=split, return_masks=(split == 'trainaug'), device=device, threads=threads, jpeg_entropy=jpeg_entropy)
+    dataset = VOCDataset(root=root, image_set=split, return_masks=(split == 'trainaug'), device=device, threads=threads, jpeg_entropy=jpeg_entropy,
+                         png=png)
     return VOCLoader(dataset, batch_size, val_size, train_size)
 
 

@@ -252,6 +252,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--input_resolution", type=int, default=448)
     p.add_argument("--dataset", type=str, default="pascal")
     p.add_argument("--dataset_path", type=str, default="../../dataset/leopascal/VOCSegmentation")
+    p.add_argument("--png_decode", choices=["host", "device"], default="host",
+                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
     p.add_argument("--save_path", type=str, default="linear_finetune.pth", help="state_dict written after every epoch ('' = none)")
     p.add_argument("--num_train_images", type=int, default=120, help="synthetic data only")
     p.add_argument("--num_val_images", type=int, default=60, help="synthetic data only")
@@ -311,8 +313,8 @@ def main(argv: Optional[list] = None) -> float:
     if args.dataset == "voc":                                                            # linear_finetune.py:69-71
         from .leoloader import pascal_loader
 
-        train_loader = pascal_loader(args.batch_size, args.dataset_path, "trainaug", args.mask_size, train_size=args.input_resolution)
-        val_loader = pascal_loader(args.batch_size, args.dataset_path, "val", args.mask_size, train_size=args.input_resolution)
+        train_loader = pascal_loader(args.batch_size, args.dataset_path, "trainaug", args.mask_size, train_size=args.input_resolution, png=args.png_decode)
+        val_loader = pascal_loader(args.batch_size, args.dataset_path, "val", args.mask_size, train_size=args.input_resolution, png=args.png_decode)
     torch.cuda.set_device(0)
     feature_extractor = FeatureExtractor(args.architecture, args.model_path, list(args.head_layers), return_attention=False)
     model = TimeT(feature_extractor, args.num_prototypes)

@@ -475,6 +475,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_workers", type=int, default=10)
     p.add_argument("--jpeg_entropy", choices=["host", "device"], default="host",
                    help="where the frames' Huffman coding is undone: in the host thread pool, or on the device from the compressed scans (N24)")
+    p.add_argument("--png_decode", choices=["host", "device"], default="host",
+                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
     p.add_argument("--num_clusters", type=int, default=10)
     p.add_argument("--input_resolution", type=int, default=224)
     p.add_argument("--many_to_one", type=bool, default=False)
@@ -595,7 +597,7 @@ def mask_propagation(args) -> float:
 
         disk_loader = DL.make_loader(args.dataset_path, args.num_frames, 1, 1, DL.SamplingMode.DENSE, frame_transform=None, target_transform=None,
                                      video_transform=VT.propagation_transforms(args.input_resolution), shuffle=False,
-                                     num_workers=args.num_workers, device=device, jpeg_entropy=args.jpeg_entropy)
+                                     num_workers=args.num_workers, device=device, jpeg_entropy=args.jpeg_entropy, png=args.png_decode)
         if not disk_loader.dataset.use_annotations:
             raise FileNotFoundError(f"{args.dataset_path}/Annotations: the propagation evaluation needs the first frame's annotation")
         disk_clips = iter(disk_loader)

@@ -1055,6 +1055,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_workers", type=int, default=10)
     p.add_argument("--jpeg_entropy", choices=["host", "device"], default="host",
                    help="where the frames' Huffman coding is undone: in the host thread pool, or on the device from the compressed scans (N24)")
+    p.add_argument("--png_decode", choices=["host", "device"], default="host",
+                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
     p.add_argument("--num_clusters", type=int, default=200)
     p.add_argument("--input_resolution", type=int, default=224)
     p.add_argument("--many_to_one", type=bool, default=False)
@@ -1256,7 +1258,7 @@ def time_tuning(gpu=0, args=None):
         frame_transform, video_transform = VT.training_transforms(args.input_resolution)
         loader = DL.make_loader(args.dataset_path, args.num_frames, args.batch_size, args.regular_step, DL.SamplingMode.Regular,
                                 frame_transform=frame_transform, target_transform=None, video_transform=video_transform, shuffle=True,
-                                num_workers=args.num_workers, world_size=world_size, rank=rank, device=device, jpeg_entropy=args.jpeg_entropy)
+                                num_workers=args.num_workers, world_size=world_size, rank=rank, device=device, jpeg_entropy=args.jpeg_entropy, png=args.png_decode)
     num_itr = len(loader)
     opt = SwavOptimizer(model, "AdamW", args.use_projection_head, args.head_lr / 10, args.head_lr, args.lr_scheduler,
                         cosine_scheduler(0.04, 0.4, args.num_epochs, num_itr), num_itr, args.num_epochs)
@@ -1276,7 +1278,7 @@ def time_tuning(gpu=0, args=None):
             from .leoloader import EvaluatorLoader, pascal_loader
 
             eval_loader = EvaluatorLoader(pascal_loader(60, args.eval_dataset_path, "val", 112, train_size=224, device=device,
-                                                        jpeg_entropy=args.jpeg_entropy))
+                                                        jpeg_entropy=args.jpeg_entropy, png=args.png_decode))
         else:
             eval_loader = SyntheticEvalClips(args.eval_clips, 1, args.input_resolution, 4, device)
         evaluator = Evaluator(eval_model, eval_loader, 21, device, clustering_algorithm="k-means", uvos_flag=bool(args.uvos))
