@@ -224,12 +224,12 @@ def test_scan_frames_sorts_files_between_the_device_and_pillow(fx, entropy):
     files = [first, fx[0]["prog_48x64_420_q90"][0], png.getvalue(), last]
     assert hip_ops.jpeg_probe(files[1]).status > 0
     host = scan_frames(files, 2, entropy, pin=False)
-    assert host.device_slots == [0, 3] and set(host.host_frames) == {1, 2}
+    assert host.device_slots == [0, 3] and set(host.host_items) == {1, 2}
     for k in (1, 2):
-        assert np.array_equal(host.host_frames[k], decode_frame_on_host(files[k]))
-    assert host.host_frames[2].tolist() == np.arange(5 * 7 * 3).reshape(5, 7, 3).tolist()
+        assert np.array_equal(host.host_items[k], decode_frame_on_host(files[k]))
+    assert host.host_items[2].tolist() == np.arange(5 * 7 * 3).reshape(5, 7, 3).tolist()
     assert [tuple(d) for d in host.dims] == [fx[0]["clip_v0_f0"][1].shape[:2], (48, 64), (5, 7), (9, 15)]
-    assert host.scanned.route == entropy and [(i.H, i.W) for i in host.scanned.infos] == [host.dims[0], host.dims[3]]
+    assert host.batch.route == entropy and [(i.H, i.W) for i in host.batch.infos] == [host.dims[0], host.dims[3]]
     with pytest.raises(ValueError):
         scan_frames(files[:3] + [last[:len(last) // 2]], 2, entropy, pin=False)
 
@@ -286,3 +286,178 @@ def test_loader_pairs_directories_by_position_and_orders_files(fx, tmp_path):
     assert make_loader(str(root), 2, 2, 2, SamplingMode.Regular, device="cpu").dataset.use_annotations
     with pytest.raises(NotImplementedError, match="JPEGImages"):
         make_loader(str(tmp_path / "nowhere"), 2, 2)
+
+
+# ---- N27: what the JPEG and PNG batches share (the PNG half of the vocabulary and of the layout: tests/test_png_host.py)
+def test_status_vocabulary_jpeg():
+    for index, where in ((None, ""), (3, "file 3: ")):
+        e = hip_ops._JPEG.error(1, index)
+        assert type(e) is hip_ops.JpegUnsupported and (e.status, e.index) == (1, index)
+        assert str(e) == where + "unsupported JPEG (progressive, lossless or hierarchical frame)"
+        e = hip_ops._JPEG.error(-2, index)
+        assert type(e) is ValueError and str(e) == where + "malformed JPEG (status -2: the scan data ends early)"
+    assert str(hip_ops.JpegUnsupported(99)) == "unsupported JPEG (99)" and str(hip_ops._JPEG.error(-99)) == "malformed JPEG (status -99: unknown)"
+    info = hip_ops.JpegInfo(0, 37, 53, 2, 5376)
+    assert repr(info) == "JpegInfo(status=0, H=37, W=53, sampling=2, n_coeffs=5376)" and info.supported
+    assert not hip_ops.JpegInfo(1, 0, 0, 0, 0).supported
+    assert not issubclass(hip_ops.JpegUnsupported, hip_ops.PngUnsupported) and not issubclass(hip_ops.PngUnsupported, hip_ops.JpegUnsupported)
+    with pytest.raises(ValueError, match=r"^malformed JPEG \(status -1: broken markers, segment lengths or tables\)$"):
+        hip_ops.jpeg_probe(b"\xff\xd8\xff\xd9")
+
+
+@pytest.mark.parametrize("threads", [1, 3, 16, 100])
+def test_the_per_file_runner(threads):
+    import threading
+
+    calls, lock = [], threading.Lock()
+
+    def fn(i):
+        with lock:
+            calls.append((i, threading.get_ident()))
+        return 10 * i
+
+    assert hip_ops._each_file(fn, 7, threads) == [0, 10, 20, 30, 40, 50, 60]
+    assert sorted(i for i, _ in calls) == list(range(7))                       # every item once
+    by_thread = {}
+    for i, t in calls:
+        by_thread.setdefault(t, []).append(i)
+    assert len(by_thread) <= min(threads, 16, 7)                               # a chunk runs on one thread: no more chunks than that
+    assert all(items == list(range(items[0], items[0] + len(items))) or len(by_thread) < min(threads, 16, 7)
+               for items in by_thread.values())                                # (a thread that took two chunks holds two runs)
+    if threads == 1:
+        assert set(by_thread) == {threading.get_ident()}                       # serial: no pool
+    statuses = [0, 0, -2, 5, 0]
+    with pytest.raises(ValueError, match=r"^file 2: malformed JPEG \(status -2"):
+        hip_ops._each_file(lambda i: statuses[i], 5, threads, hip_ops._JPEG.error)
+    with pytest.raises(hip_ops.PngUnsupported, match="^file 3: unsupported PNG"):
+        hip_ops._each_file(lambda i: {"rc": statuses[i]}, 5, threads, hip_ops._PNG.error, lambda r: max(r["rc"], 0))
+    assert hip_ops._each_file(fn, 0, threads) == []
+    assert hip_ops.FILE_MAX_THREADS == 16 and all(t.name.startswith("tt_files") for t in threading.enumerate() if t.ident in by_thread
+                                                  and t is not threading.current_thread())
+
+
+def test_the_layout_of_a_pinned_buffer(fx):
+    import torch
+
+    layout, total = hip_ops._layout([("a", 1), ("b", 16), ("c", 17), ("d", 0)])
+    assert layout == {"a": (0, 1), "b": (16, 16), "c": (32, 17), "d": (64, 0)} and total == 64
+    for batch in (hip_ops.jpeg_scan_batch([fx[0]["clip_v0_f0"][0]], 1, pin=False), hip_ops.jpeg_prepare_batch([fx[0]["clip_v0_f0"][0]], 1, pin=False)):
+        assert all(at % 16 == 0 for at, _ in batch.layout.values())
+        for name, (at, size) in batch.layout.items():
+            part = batch.part(name)
+            assert part.dtype == np.uint8 and part.size == size
+            if size:
+                assert part.ctypes.data == batch.meta.data_ptr() + at          # a view, not a copy
+                part[0] ^= 0xFF
+                assert int(batch.meta[at]) == int(part[0])
+                part[0] ^= 0xFF
+    assert isinstance(batch.meta, torch.Tensor)
+
+
+def _consecutive(shape, dtype=None):
+    import torch
+
+    step = int(np.prod(shape))
+    flat = torch.arange(7 * step, dtype=torch.int64).to(torch.uint8 if dtype is None else dtype)
+    return flat, [flat[(1 + i) * step:(2 + i) * step].view(*shape) for i in range(5)]
+
+
+@pytest.mark.parametrize("shape", [(2, 5), (2, 5, 3)])
+def test_consecutive_views_are_one_tensor(shape):
+    import torch
+    from timetuning_amd.data_loader import maps_as_clip
+
+    step = int(np.prod(shape))
+    flat, views = _consecutive(shape)
+    other, _ = _consecutive(shape)
+    for fn in (hip_ops.frames_as_clip, maps_as_clip):
+        one = fn(views)
+        assert one.shape == (5,) + shape and one.is_contiguous() and torch.equal(one, torch.stack(views))
+        assert one.data_ptr() == flat.data_ptr() + step and one.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr()
+        lists = {"gap": views[:2] + views[3:], "order": [views[1], views[0]] + views[2:],
+                 "storages": views[:4] + [other[5 * step:6 * step].view(*shape)], "dtype": views[:4] + [views[4].to(torch.int16)]}
+        for name, items in lists.items():
+            got = fn(items)
+            assert got.shape == (len(items),) + shape and got.untyped_storage().data_ptr() != flat.untyped_storage().data_ptr(), name
+            assert all(torch.equal(g.to(torch.int64), v.to(torch.int64)) for g, v in zip(got, items)), name
+    assert torch.equal(hip_ops.frames_as_clip(lists["gap"]), maps_as_clip(lists["gap"]))
+
+
+def test_the_route_check_at_all_six_sites(tmp_path):
+    from types import SimpleNamespace
+
+    from timetuning_amd import data_loader as DL, leoloader as LL
+
+    ds = SimpleNamespace(jpeg_entropy="host", png="device")
+    sites = {"VideoDataset": lambda **k: DL.VideoDataset(str(tmp_path), None, DL.SamplingMode.Full, 1, 4, **k),
+             "ClipLoader": lambda **k: DL.ClipLoader(ds, 2, **k), "VOCDataset": lambda **k: LL.VOCDataset(str(tmp_path), **k)}
+    for site, make in sites.items():
+        for name in ("jpeg_entropy", "png"):
+            with pytest.raises(ValueError, match=f"^{name} must be 'host' or 'device', not 'gpu'$"):
+                make(**{name: "gpu"})
+            if site != "ClipLoader":
+                with pytest.raises(ValueError, match=f"^{name} must be 'host' or 'device', not None$"):
+                    make(**{name: None})
+    loader = DL.ClipLoader(ds, 2, jpeg_entropy=None, png=None)
+    assert (loader.jpeg_entropy, loader.png) == ("host", "device")
+    loader = DL.ClipLoader(ds, 2, jpeg_entropy="device", png="host")
+    assert (loader.jpeg_entropy, loader.png) == ("device", "host") and (ds.jpeg_entropy, ds.png) == ("host", "device")
+
+
+def _prefetch_threads():
+    import threading
+
+    return [t for t in threading.enumerate() if t.name.startswith("tt_prefetch")]
+
+
+def test_the_prefetch_loop():
+    import threading
+
+    from timetuning_amd.data_loader import prefetched
+
+    batches = [[0, 1], [2, 3], [4, 5], [6]]
+    for prefetch in (True, False):
+        log, seen, logged = [], [], {b[0]: threading.Event() for b in batches}
+        host = lambda indices: (log.append(indices), logged[indices[0]].set(), tuple(indices))[2]
+        gen = prefetched(batches, host, None, prefetch)
+        for k, item in enumerate(gen):
+            if prefetch and k + 1 < len(batches):
+                assert logged[batches[k + 1][0]].wait(10)       # submitted before batch k was handed out: it runs without our asking for it
+                assert log == batches[:k + 2]
+            else:
+                assert log == batches[:k + 1]
+            seen.append(item)
+        assert seen == [tuple(b) for b in batches] and log == batches and not _prefetch_threads()
+    assert list(prefetched([], host, None, True)) == [] and list(prefetched([], host, None, False)) == []
+    gen = prefetched(batches, host, None, True)
+    assert next(gen) == (0, 1) and len(_prefetch_threads()) == 1
+    gen.close()
+    assert not _prefetch_threads()
+
+    def failing(indices):
+        if indices == [2, 3]:
+            raise KeyError("batch 1")
+        return indices
+
+    for prefetch in (True, False):
+        gen = prefetched(batches, failing, "cpu", prefetch)
+        assert next(gen) == [0, 1]
+        with pytest.raises(KeyError, match="batch 1"):
+            next(gen)
+        assert not _prefetch_threads()
+
+
+def test_the_drivers_decode_flags():
+    import importlib
+
+    for name, jpeg in (("time_tuning", True), ("evaluation", True), ("mask_propagation", True), ("linear_finetune", False),
+                       ("cluster_based_foreground_extraction", False)):
+        parser = importlib.import_module("timetuning_amd." + name).build_parser()
+        flags = ["--jpeg_entropy", "--png_decode"] if jpeg else ["--png_decode"]
+        assert ("--jpeg_entropy" in parser._option_string_actions) == jpeg and "--png_decode" in parser._option_string_actions, name
+        args = parser.parse_args([])
+        assert all(getattr(args, f[2:]) == "host" for f in flags), name
+        for f in flags:
+            assert getattr(parser.parse_args([f, "device"]), f[2:]) == "device", name
+            with pytest.raises(SystemExit):
+                parser.parse_args([f, "gpu"])

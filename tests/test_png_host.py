@@ -184,8 +184,8 @@ def test_host_loader_logic(fx, tmp_path):
         pooled = DL.decode_annotations(files, threads)
         assert len(pooled) == len(serial) and all(a.dtype == np.uint8 and np.array_equal(a, b) for a, b in zip(pooled, serial))
     host = DL.scan_annotations(files, 4, pin=False)
-    assert host.device_slots == list(range(12)) and list(host.host_maps) == [12] and len(host.prepared.infos) == 12
-    assert np.array_equal(host.host_maps[12], serial[12])
+    assert host.device_slots == list(range(12)) and list(host.host_items) == [12] and len(host.batch.infos) == 12
+    assert np.array_equal(host.host_items[12], serial[12])
     with pytest.raises(ValueError, match="malformed PNG"):
         DL.scan_annotations([files[0], files[0][:50]], 1, pin=False)
     maps = P.write_video_tree(str(tmp_path / "set"))
@@ -211,3 +211,38 @@ def test_host_loader_logic(fx, tmp_path):
     assert calls == [8] and host.annotations is None
     for v, s in enumerate(host.samples):
         assert s.annotation_files is None and np.array_equal(s.annotations[0], np.stack([maps[(v, f)] for f in range(4)]))
+
+
+# ---- N27: the PNG half of what the two codecs share (the rest: tests/test_jpeg_host.py)
+def test_status_vocabulary_png(fx):
+    for index, where in ((None, ""), (3, "file 3: ")):
+        e = hip_ops._PNG.error(1, index)
+        assert type(e) is hip_ops.PngUnsupported and (e.status, e.index) == (1, index)
+        assert str(e) == where + "unsupported PNG (Adam7 interlace)"
+        e = hip_ops._PNG.error(-6, index)
+        assert type(e) is ValueError and str(e) == where + "malformed PNG (status -6: a wrong CRC-32 or Adler-32)"
+    assert str(hip_ops.PngUnsupported(99)) == "unsupported PNG (99)" and str(hip_ops._PNG.error(-99)) == "malformed PNG (status -99: unknown)"
+    info = hip_ops.PngInfo(0, 480, 854, 8, 3)
+    assert repr(info) == "PngInfo(status=0, H=480, W=854, depth=8, color_type=3)" and info.supported
+    assert not hip_ops.PngInfo(2, 0, 0, 0, 0).supported
+    assert not isinstance(hip_ops._PNG.error(1), hip_ops.JpegUnsupported) and not isinstance(hip_ops._JPEG.error(1), hip_ops.PngUnsupported)
+    good = fx[0][list(fx[0])[0]]
+    with pytest.raises(hip_ops.PngUnsupported, match=r"^file 3: unsupported PNG \(Adam7 interlace\)$") as e:
+        hip_ops.png_prepare_batch([good] * 3 + [fx[2]["interlaced"][1], good[:50]], threads=2, pin=False)
+    assert (e.value.status, e.value.index) == (1, 3)
+    with pytest.raises(ValueError, match=r"^file 1: malformed PNG \(status -"):
+        hip_ops.png_prepare_batch([good, good[:50]], threads=2, pin=False)
+    with pytest.raises(ValueError, match=r"^malformed PNG \(status -"):
+        hip_ops.png_probe(good[:50])
+    with pytest.raises(ValueError, match="^png_prepare_batch: no files$"):
+        hip_ops.png_prepare_batch([], pin=False)
+
+
+def test_the_layout_of_a_png_batch(fx):
+    files = [fx[0][n] for n in list(fx[0])[:3]]
+    batch = hip_ops.png_prepare_batch(files, threads=2, pin=False)
+    assert batch.layout["table"] == (0, 3 * 128) and batch.layout["streams"][0] == 3 * 128
+    assert batch.meta.numel() == 3 * 128 + batch.layout["streams"][1] == 3 * 128 + sum((len(f) + 3) // 4 * 4 + 4 for f in files)
+    for name, (at, size) in batch.layout.items():
+        assert batch.part(name).ctypes.data == batch.meta.data_ptr() + at and batch.part(name).size == size      # views, not copies
+    assert batch.table.ctypes.data == batch.meta.data_ptr()

@@ -35,6 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
+from .data_loader import add_decode_arguments
 from .bfscore import evaluate_bf_score
 from .clustering import Kmeans, nearest_index_table, normalize_and_transform
 from .models import FeatureExtractor, process_attentions
@@ -316,8 +317,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--model_path", type=str, default="/home/ssalehi/video/dino/outputs/checkpoint0080.pth")
     p.add_argument("--dataset", type=str, default="davis")
     p.add_argument("--dataset_path", type=str, default="../data")
-    p.add_argument("--png_decode", choices=["host", "device"], default="host",
-                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
+    add_decode_arguments(p, jpeg=False)
     p.add_argument("--destination_path", type=str, default="ytvos")
     p.add_argument("--evaluation_protocol", type=str, default="dataset-wise")
     p.add_argument("--logging_directory", type=str, default="visualizations")

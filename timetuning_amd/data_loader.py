@@ -37,6 +37,7 @@ import json
 import os
 import random
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import nullcontext
 from enum import Enum
 from typing import List, Optional
 
@@ -102,63 +103,10 @@ def decode_annotation(data: bytes) -> np.ndarray:
 
 
 def decode_annotations(files, threads: int = 1) -> List[np.ndarray]:
-    """``decode_annotation`` of every file, in the pool the JPEG batches use (at most 16 threads; Pillow's decoder releases the GIL): the
+    """``decode_annotation`` of every file, in the pool the file batches use (at most 16 threads; Pillow's decoder releases the GIL): the
     list a serial loop gives."""
     files = list(files)
-    workers = max(1, min(int(threads), ops.JPEG_MAX_THREADS, len(files)))
-    if workers == 1:
-        return [decode_annotation(f) for f in files]
-    return list(ops._jpeg_pool(workers).map(decode_annotation, files))
-
-
-class HostAnnotations:
-    """The host half of a list of annotation files on the ``png="device"`` route: ``prepared`` - the ``hip_ops.PngBatch`` of the files the
-    device decoder takes, None without any -, ``device_slots`` their places in the list, ``host_maps`` {slot: uint8 [H, W]} the Pillow
-    decode of every other file."""
-
-    def __init__(self, prepared, device_slots, host_maps, n):
-        self.prepared, self.device_slots, self.host_maps, self.n = prepared, device_slots, host_maps, n
-
-
-def scan_annotations(files, threads: int, pin: Optional[bool] = None) -> HostAnnotations:
-    """Classifies every annotation file and prepares the supported ones (``hip_ops.png_prepare_batch``); an unsupported file is decoded
-    with Pillow.  A broken PNG raises ``ValueError``.  No GPU call: a background thread may run it."""
-    device_slots, host_maps = [], {}
-    for k, data in enumerate(files):
-        if ops.png_probe(data).supported:     # a broken file raises here
-            device_slots.append(k)
-        else:
-            host_maps[k] = decode_annotation(data)
-    pin = torch.cuda.is_available() if pin is None else pin
-    prepared = ops.png_prepare_batch([files[k] for k in device_slots], threads, pin) if device_slots else None
-    return HostAnnotations(prepared, device_slots, host_maps, len(files))
-
-
-def finish_annotations(host: HostAnnotations, device):
-    """The device half of ``scan_annotations``: (the maps as uint8 [H, W] tensors on ``device`` in file order - the device-decoded ones
-    views of ONE flat buffer, consecutive files one after the other -, the number of maps Pillow decoded)."""
-    maps = [None] * host.n
-    if host.prepared is not None:
-        decoded, _ = ops.png_decode(host.prepared, device)      # a non-zero status raises, naming the file
-        for k, m in zip(host.device_slots, decoded):
-            maps[k] = m
-    for k, arr in host.host_maps.items():
-        maps[k] = torch.from_numpy(np.array(arr)).to(device)     # (Pillow's array is read-only)
-    return maps, len(host.host_maps)
-
-
-def maps_as_clip(maps) -> torch.Tensor:
-    """Label maps of one size -> [k, H, W]: the tensor they are consecutive views of where they are (``hip_ops.png_decode``), a stacked
-    copy otherwise."""
-    m0 = maps[0]
-    step = m0.numel()
-    same = all(m.shape == m0.shape and m.is_contiguous() and m.device == m0.device and
-               m.untyped_storage().data_ptr() == m0.untyped_storage().data_ptr() and
-               m.storage_offset() == m0.storage_offset() + i * step for i, m in enumerate(maps))
-    if not same:
-        return torch.stack(list(maps))
-    H, W = m0.shape
-    return m0.as_strided((len(maps), H, W), (step, W, 1), m0.storage_offset())
+    return ops._each_file(lambda i: decode_annotation(files[i]), len(files), threads)
 
 
 def decode_frame_on_host(data: bytes) -> np.ndarray:
@@ -166,6 +114,115 @@ def decode_frame_on_host(data: bytes) -> np.ndarray:
     from PIL import Image
 
     return np.array(Image.open(io.BytesIO(data)).convert("RGB"), np.uint8)   # (a writable copy)
+
+
+maps_as_clip = ops.frames_as_clip     # label maps of one size -> [k, H, W]: one rule for every rank
+
+
+class HostFiles:
+    """The host half of a list of files, frames or annotation maps: ``batch`` - the ``hip_ops.JpegBatch`` / ``PngBatch`` of the files the
+    device decoder takes, None without any -, ``device_slots`` their places in the list, ``host_items`` {slot: uint8 [H, W, 3] or [H, W]}
+    the Pillow decode of every other file, ``dims`` the (H, W) of every slot and ``n`` their number."""
+
+    def __init__(self, batch, device_slots, host_items, dims):
+        self.batch, self.device_slots, self.host_items, self.dims, self.n = batch, device_slots, host_items, dims, len(dims)
+
+
+def _scan_files(files, probe, fallback, build, threads: int, pin: Optional[bool]) -> HostFiles:
+    """Classifies every file (``probe``: its info, None = not this codec's; a broken file raises there), builds the batch of the supported
+    ones (``build``) and decodes the others with Pillow (``fallback``).  ``pin`` None: where there is a GPU."""
+    device_slots, host_items, dims = [], {}, [None] * len(files)
+    for k, data in enumerate(files):
+        info = probe(data)
+        if info is not None and info.supported:
+            device_slots.append(k)
+            dims[k] = (info.H, info.W)
+        else:
+            host_items[k] = fallback(data)
+            dims[k] = host_items[k].shape[:2]
+    pin = torch.cuda.is_available() if pin is None else pin
+    return HostFiles(build([files[k] for k in device_slots], threads, pin) if device_slots else None, device_slots, host_items, dims)
+
+
+def _finish_files(host: HostFiles, decode, device):
+    """(every file as a tensor on ``device`` in file order - ``decode(batch, device)`` of the batch, an upload of the others -, the number
+    of files Pillow decoded: the fall-backs a loader counts)"""
+    items = [None] * host.n
+    if host.batch is not None:
+        for k, t in zip(host.device_slots, decode(host.batch, device)):
+            items[k] = t
+    for k, arr in host.host_items.items():
+        items[k] = torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(device)     # (Pillow's label maps are read-only)
+    return items, len(host.host_items)
+
+
+def scan_frames(files, threads: int, entropy: str = "host", pin: Optional[bool] = None) -> HostFiles:
+    """Classifies every file and builds the batch of the supported ones on the ``entropy`` route ("host": ``hip_ops.jpeg_scan_batch``,
+    "device": ``jpeg_prepare_batch``); an unsupported file or one that is not a JPEG is decoded with Pillow.  A broken JPEG raises
+    ``ValueError``.  No GPU call: a background thread may run it."""
+    return _scan_files(files, lambda data: ops.jpeg_probe(data) if data[:2] == b"\xff\xd8" else None, decode_frame_on_host,
+                       ops.jpeg_prepare_batch if entropy == "device" else ops.jpeg_scan_batch, threads, pin)
+
+
+def finish_frames(host: HostFiles, device):
+    """The device half of ``scan_frames``: (the frames as uint8 [H, W, 3] tensors on ``device`` in file order, the number of them that
+    Pillow decoded)."""
+    return _finish_files(host, ops.jpeg_decode, device)
+
+
+def scan_annotations(files, threads: int, pin: Optional[bool] = None) -> HostFiles:
+    """Classifies every annotation file and prepares the supported ones (``hip_ops.png_prepare_batch``); an unsupported file is decoded
+    with Pillow.  A broken PNG raises ``ValueError``.  No GPU call: a background thread may run it."""
+    return _scan_files(files, ops.png_probe, decode_annotation, ops.png_prepare_batch, threads, pin)
+
+
+def finish_annotations(host: HostFiles, device):
+    """The device half of ``scan_annotations``: (the maps as uint8 [H, W] tensors on ``device`` in file order - the device-decoded ones
+    views of ONE flat buffer, consecutive files one after the other -, the number of maps Pillow decoded).  A non-zero status raises,
+    naming the file."""
+    return _finish_files(host, lambda batch, dev: ops.png_decode(batch, dev)[0], device)
+
+
+def _route(name: str, value, optional: bool = False):
+    """``value`` where it names a decode route ("host" / "device"; None too where ``optional``), else ValueError naming the argument."""
+    if value not in ("host", "device") and not (optional and value is None):
+        raise ValueError(f"{name} must be 'host' or 'device', not {value!r}")
+    return value
+
+
+def prefetched(batches, host, device=None, prefetch: bool = True):
+    """``host(indices)`` of every index batch, in order.  With ``prefetch`` a background thread works on batch k + 1 while the caller has
+    batch k.  ``host`` runs under ``torch.cuda.device(device)`` where that is a GPU: a new thread starts on device 0, and the pinned
+    buffers belong to the loader's device."""
+    on_gpu = device is not None and torch.device(device).type == "cuda"
+
+    def run(indices):
+        with torch.cuda.device(device) if on_gpu else nullcontext():
+            return host(indices)
+
+    if not (prefetch and batches):
+        yield from map(run, batches)
+        return
+    pool = ThreadPoolExecutor(1, thread_name_prefix="tt_prefetch")
+    try:
+        pending = pool.submit(run, batches[0])
+        for k in range(len(batches)):
+            item = pending.result()
+            if k + 1 < len(batches):
+                pending = pool.submit(run, batches[k + 1])
+            yield item
+    finally:
+        pool.shutdown(wait=True)
+
+
+def add_decode_arguments(parser, jpeg: bool = True, png: bool = True) -> None:
+    """The drivers' ``--jpeg_entropy`` and ``--png_decode``."""
+    if jpeg:
+        parser.add_argument("--jpeg_entropy", choices=["host", "device"], default="host",
+                            help="where the frames' Huffman coding is undone: in the host thread pool, or on the device from the compressed scans (N24)")
+    if png:
+        parser.add_argument("--png_decode", choices=["host", "device"], default="host",
+                            help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
 
 
 def make_categories_dict(meta_dict, name):
@@ -232,47 +289,8 @@ class _HostSample:
         self.annotation_files = annotation_files      # png="device": the files' bytes per clip, and ``annotations`` is None
 
 
-class HostFrames:
-    """The host half of a list of frame files: ``scanned`` - the ``hip_ops.JpegBatch`` of the files the device decoder takes, None
-    without any -, ``device_slots`` their places in the list, ``host_frames`` {slot: uint8 [H, W, 3]} the Pillow decode of every other
-    file, ``dims`` the (H, W) of every slot."""
-
-    def __init__(self, scanned, device_slots, host_frames, dims):
-        self.scanned, self.device_slots, self.host_frames, self.dims = scanned, device_slots, host_frames, dims
-
-
-def scan_frames(files, threads: int, entropy: str = "host", pin: bool = True) -> HostFrames:
-    """Classifies every file and builds the batch of the supported ones on the ``entropy`` route ("host": ``hip_ops.jpeg_scan_batch``,
-    "device": ``jpeg_prepare_batch``); an unsupported file or one that is not a JPEG is decoded with Pillow.  A broken JPEG raises
-    ``ValueError``.  No GPU call: a background thread may run it."""
-    device_slots, host_frames, dims = [], {}, [None] * len(files)
-    for k, data in enumerate(files):
-        info = ops.jpeg_probe(data) if data[:2] == b"\xff\xd8" else None     # a broken JPEG raises here
-        if info is not None and info.supported:
-            device_slots.append(k)
-            dims[k] = (info.H, info.W)
-        else:
-            host_frames[k] = decode_frame_on_host(data)
-            dims[k] = host_frames[k].shape[:2]
-    build = ops.jpeg_prepare_batch if entropy == "device" else ops.jpeg_scan_batch
-    scanned = build([files[k] for k in device_slots], threads, pin) if device_slots else None
-    return HostFrames(scanned, device_slots, host_frames, dims)
-
-
-def finish_frames(host: HostFrames, device):
-    """The device half of ``scan_frames``: (the frames as uint8 [H, W, 3] tensors on ``device`` in file order, the number of them that
-    Pillow decoded - the fall-backs a loader counts)."""
-    frames = [None] * len(host.dims)
-    if host.scanned is not None:
-        for k, f in zip(host.device_slots, ops.jpeg_decode(host.scanned, device)):
-            frames[k] = f
-    for k, arr in host.host_frames.items():
-        frames[k] = torch.from_numpy(arr).to(device)
-    return frames, len(host.host_frames)
-
-
 class _HostBatch:
-    def __init__(self, samples, frames: HostFrames, annotations: Optional[HostAnnotations] = None):
+    def __init__(self, samples, frames: HostFiles, annotations: Optional[HostFiles] = None):
         self.samples, self.frames, self.annotations = samples, frames, annotations
 
 
@@ -290,11 +308,7 @@ class VideoDataset:
     def __init__(self, classes_directory, annotations_directory, sampling_mode, num_clips, num_frames, num_labels=1, frame_transform=None,
                  target_transform=None, video_transform=None, meta_file_directory=None, regular_step=1, device=None, threads=8, rng=None,
                  sequential_category_map=True, jpeg_entropy="host", png="host"):
-        if jpeg_entropy not in ("host", "device"):
-            raise ValueError(f"jpeg_entropy must be 'host' or 'device', not {jpeg_entropy!r}")
-        if png not in ("host", "device"):
-            raise ValueError(f"png must be 'host' or 'device', not {png!r}")
-        self.jpeg_entropy, self.png = jpeg_entropy, png
+        self.jpeg_entropy, self.png = _route("jpeg_entropy", jpeg_entropy), _route("png", png)
         if num_labels != 1:
             raise NotImplementedError("nested class directories (num_labels > 1) are not reproduced")
         self.meta_dict, self.category_dict, self.category_tables = None, None, None
@@ -375,22 +389,16 @@ class VideoDataset:
         """-> per sample (data, annotations, label) as ``__getitem__`` returns them."""
         flat, fallbacks = finish_frames(batch.frames, self.device)
         self.fallback_frames += fallbacks
-        maps, m_at = None, 0
+        maps = []
         if batch.annotations is not None:
             maps, fallbacks = finish_annotations(batch.annotations, self.device)
             self.fallback_annotations += fallbacks
-        out, at = [], 0
-        for s in batch.samples:
-            clips = []
-            for clip in s.frames:
-                clips.append(ops.frames_as_clip(flat[at:at + len(clip)]))
-                at += len(clip)
+        flat, maps, out = iter(flat), iter(maps), []
+        for s in batch.samples:     # the files of the batch in the order scan_host listed them: sample by sample, clip by clip
+            clips = [ops.frames_as_clip([next(flat) for _ in clip]) for clip in s.frames]
             ann = None if s.annotations is None else [torch.from_numpy(a).to(self.device) for a in s.annotations]
             if s.annotation_files is not None:
-                ann = []
-                for clip in s.annotation_files:
-                    ann.append(maps_as_clip(maps[m_at:m_at + len(clip)]))
-                    m_at += len(clip)
+                ann = [maps_as_clip([next(maps) for _ in clip]) for clip in s.annotation_files]
             out.append(self._transform(clips, ann) + (torch.Tensor(s.label),))
         return out
 
@@ -459,12 +467,8 @@ class ClipLoader:
 
     def __init__(self, dataset: VideoDataset, batch_size: int, shuffle: bool = False, world_size: int = 1, rank: int = 0, seed: int = 0,
                  prefetch: bool = True, jpeg_entropy: Optional[str] = None, png: Optional[str] = None):
-        if jpeg_entropy not in (None, "host", "device"):
-            raise ValueError(f"jpeg_entropy must be 'host' or 'device', not {jpeg_entropy!r}")
-        if png not in (None, "host", "device"):
-            raise ValueError(f"png must be 'host' or 'device', not {png!r}")
-        self.jpeg_entropy = dataset.jpeg_entropy if jpeg_entropy is None else jpeg_entropy   # the loader's own: the dataset is not touched
-        self.png = dataset.png if png is None else png
+        self.jpeg_entropy = _route("jpeg_entropy", jpeg_entropy, optional=True) or dataset.jpeg_entropy   # the loader's own: the dataset is not touched
+        self.png = _route("png", png, optional=True) or dataset.png
         self.dataset, self.batch_size, self.shuffle, self.world_size, self.rank, self.seed = dataset, int(batch_size), shuffle, world_size, rank, seed
         self.prefetch, self.epoch = prefetch, 0
         self.rng = random.Random(seed * 1000003 + rank)
@@ -500,32 +504,17 @@ class ClipLoader:
         return -(-local // self.batch_size)
 
     def _host(self, indices) -> _HostBatch:
-        dev = self.dataset.device
-        if dev is not None and torch.device(dev).type == "cuda":
-            with torch.cuda.device(dev):   # a new thread starts on device 0: the pinned buffers belong to this rank's device
-                return self.dataset.scan_host([self.dataset.read_host(i, self.rng, self.png, decode=False) for i in indices], self.jpeg_entropy, self.png)
         return self.dataset.scan_host([self.dataset.read_host(i, self.rng, self.png, decode=False) for i in indices], self.jpeg_entropy, self.png)
 
     def __iter__(self):
         order = self._order()
         batches = [order[i:i + self.batch_size] for i in range(0, len(order), self.batch_size)]
-        if not batches:
-            return
-        pool = ThreadPoolExecutor(1) if self.prefetch else None
-        try:
-            pending = pool.submit(self._host, batches[0]) if pool else None
-            for k in range(len(batches)):
-                host = pending.result() if pool else self._host(batches[k])
-                if pool and k + 1 < len(batches):
-                    pending = pool.submit(self._host, batches[k + 1])
-                items = self.dataset.finish(host)
-                data = torch.stack([d for d, _, _ in items])
-                annotations = self.dataset.map_categories(torch.stack([a for _, a, _ in items]), [s.index for s in host.samples])
-                label = torch.stack([l for _, _, l in items])
-                yield data, annotations, label
-        finally:
-            if pool:
-                pool.shutdown(wait=True)
+        for host in prefetched(batches, self._host, self.dataset.device, self.prefetch):
+            items = self.dataset.finish(host)
+            data = torch.stack([d for d, _, _ in items])
+            annotations = self.dataset.map_categories(torch.stack([a for _, a, _ in items]), [s.index for s in host.samples])
+            label = torch.stack([l for _, _, l in items])
+            yield data, annotations, label
 
 
 def make_loader(dataset_path: str, num_clip_frames: int, batch_size: int, regular_step: int = 1, sampling_mode: SamplingMode = SamplingMode.UNIFORM,

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip_ops as ops
+from .data_loader import add_decode_arguments
 from .clustering import cluster_features, nearest_index_table, proto_clustering
 from .metrics import PredsmIoU
 from .models import FeatureExtractor, apply_attention_mask
@@ -220,10 +221,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--logging_directory", type=str, default="visualizations")
     p.add_argument("--batch_size", type=int, default=16)
     p.add_argument("--num_workers", type=int, default=3)
-    p.add_argument("--jpeg_entropy", choices=["host", "device"], default="host",
-                   help="where the frames' Huffman coding is undone: in the host thread pool, or on the device from the compressed scans (N24)")
-    p.add_argument("--png_decode", choices=["host", "device"], default="host",
-                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
+    add_decode_arguments(p)
     p.add_argument("--num_clusters", type=int, default=10)
     p.add_argument("--input_resolution", type=int, default=224)
     p.add_argument("--many_to_one", type=bool, default=False)

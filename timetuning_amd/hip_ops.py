@@ -2383,10 +2383,122 @@ def remap_nearest_labels(first, flows, scale: float = 1.0):
     return out
 
 
+# ---- N27: what a batch of compressed files is, whatever the codec (JPEG frames and annotation PNGs below): the thread pool of the host
+# half, the status vocabulary, the one pinned buffer with its parts, the device-side preamble and the read-back of the files' status.
+FILE_MAX_THREADS = 16
+_FILE_POOLS: dict = {}
+
+
+def _file_pool(workers: int):
+    """One thread pool per size, kept: starting 16 threads per batch costs as much as scanning a dozen frames."""
+    pool = _FILE_POOLS.get(workers)
+    if pool is None:
+        from concurrent.futures import ThreadPoolExecutor
+
+        pool = _FILE_POOLS[workers] = ThreadPoolExecutor(workers, thread_name_prefix="tt_files")
+    return pool
+
+
+def _file_list(files: Sequence[bytes], who: str) -> list:
+    files = [bytes(f) for f in files]
+    if not files:
+        raise ValueError(f"{who}: no files")
+    return files
+
+
+def _each_file(fn, n: int, threads: int, error=None, status=int) -> list:
+    """[fn(i) for i in range(n)] in min(threads, 16, n) threads - one task per thread, not per file; serial at one.  With ``error``: then
+    the first file in order whose ``status(result)`` is not 0 raises ``error(status, i)``."""
+    workers = max(1, min(int(threads), FILE_MAX_THREADS, n))
+    chunks = [range(k * n // workers, (k + 1) * n // workers) for k in range(workers)]
+    work = lambda chunk: [fn(i) for i in chunk]
+    results = [r for part in ([work(chunks[0])] if workers == 1 else _file_pool(workers).map(work, chunks)) for r in part]
+    if error is not None:
+        for i, r in enumerate(results):
+            if status(r):
+                raise error(status(r), i)
+    return results
+
+
+class _Codec:
+    """The status vocabulary of one codec: its word, the reasons of its positive (unsupported) and negative (malformed) statuses, the
+    fields ``probe`` fills, and - set where that class is declared - the exception of a file the device decoder does not take."""
+
+    def __init__(self, word, unsupported, malformed, fields):
+        self.word, self.unsupported, self.malformed, self.fields = word, unsupported, malformed, fields
+
+    def error(self, status: int, index: Optional[int] = None) -> Exception:
+        """The exception of a non-zero status: ValueError for a broken file (< 0), the codec's ``*Unsupported`` for one the device decoder
+        does not take."""
+        if status > 0:
+            return self.unsupported_class(status, index)
+        where = "" if index is None else f"file {index}: "
+        return ValueError(f"{where}malformed {self.word} (status {status}: {self.malformed.get(int(status), 'unknown')})")
+
+    def probed(self, info):
+        """``info`` as ``*_probe`` returns it: a broken file raises"""
+        if info.status < 0:
+            raise self.error(info.status)
+        return info
+
+
+class _FileUnsupported(Exception):
+    def __init_subclass__(cls, codec):
+        cls.codec, codec.unsupported_class = codec, cls
+
+    def __init__(self, status: int, index: Optional[int] = None):
+        self.status, self.index = int(status), index
+        where = "" if index is None else f"file {index}: "
+        super().__init__(f"{where}unsupported {self.codec.word} ({self.codec.unsupported.get(int(status), status)})")
+
+
+class _FileInfo:
+    def __init_subclass__(cls, codec):
+        cls.codec = codec
+
+    @property
+    def supported(self) -> bool:
+        return self.status == 0
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(f'{k}={getattr(self, k)}' for k in ('status',) + self.codec.fields)})"
+
+
+def _layout(parts):
+    """[(name, bytes), ...] -> ({name: (offset, bytes)}, the bytes of the whole): every part on a 16-byte boundary"""
+    layout, at = {}, 0
+    for name, size in parts:
+        layout[name] = (at, size)
+        at += -(-size // 16) * 16
+    return layout, at
+
+
+class _FileBatch:
+    def part(self, name):
+        """A uint8 NumPy view of one part of ``meta``, by its name in ``layout``."""
+        at, size = self.layout[name]
+        return self.meta.numpy()[at:at + size]
+
+
+def _need_gpu(who: str, device) -> torch.device:
+    if not torch.cuda.is_available():
+        raise _lib.HipLibraryError(f"{who}: needs a GPU (the HIP path has no CPU fallback)")
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def _file_status(status: torch.Tensor, codec: _Codec, bad=None) -> np.ndarray:
+    """ONE read-back of the files' status (int32 [n] on the device); the first file in order whose status ``bad`` holds for raises."""
+    host = status.cpu().numpy()
+    if bad is not None:
+        for i, rc in enumerate(host):
+            if bad(rc):
+                raise codec.error(int(rc), i)
+    return host
+
+
 # ---- N21, N24: JPEG frames.  The host half (tt_jpeg_probe, then tt_jpeg_scan: markers and Huffman codes - or, on the "device" route,
 # tt_jpeg_prepare: markers only; pure host functions that ctypes runs without the GIL) in a thread pool, the arithmetic half
 # (tt_jpeg_decode_batch) in two launches for the whole batch, behind tt_jpeg_entropy_batch on the "device" route.
-JPEG_MAX_THREADS = 16
 JPEG_UNSUPPORTED = {1: "progressive, lossless or hierarchical frame", 2: "arithmetic coding", 3: "not three components", 4: "12-bit samples",
                     5: "sampling factors other than 4:4:4 / 4:2:2 / 4:2:0", 6: "more than one scan", 7: "16-bit quantisation tables",
                     8: "RGB stored without a colour transform"}
@@ -2398,39 +2510,20 @@ _JPEG_FRAME = np.dtype([("H", "<i8"), ("W", "<i8"), ("sampling", "<i8"), ("coeff
 _JPEG_STREAM = np.dtype([("H", "<i8"), ("W", "<i8"), ("sampling", "<i8"), ("restart", "<i8"), ("scan_off", "<i8"), ("scan_len", "<i8"),
                          ("huff_off", "<i8"), ("seg_off", "<i8"), ("n_segments", "<i8"), ("coeff_off", "<i8", 3), ("reserved", "<i8", 4)])   # tt_jpeg_stream
 _JPEG_QTABLES = 3 * 64 * 2     # bytes of one file's quantisation tables: uint16 [3, 64]
+_JPEG = _Codec("JPEG", JPEG_UNSUPPORTED, JPEG_MALFORMED, ("H", "W", "sampling", "n_coeffs"))
 
 
-class JpegUnsupported(Exception):
+class JpegUnsupported(_FileUnsupported, codec=_JPEG):
     """A well-formed JPEG file the device decoder does not take (``status`` > 0: TT_JPEG_UNSUPPORTED_*).  hip_ops has no CPU fallback;
     data_loader decodes such a file with Pillow and counts it."""
 
-    def __init__(self, status: int, index: Optional[int] = None):
-        self.status, self.index = int(status), index
-        where = "" if index is None else f"file {index}: "
-        super().__init__(f"{where}unsupported JPEG ({JPEG_UNSUPPORTED.get(int(status), status)})")
 
-
-class JpegInfo:
+class JpegInfo(_FileInfo, codec=_JPEG):
     """What ``jpeg_probe`` found: ``status`` 0 = the device decoder takes the file (then H, W, ``sampling`` 0 / 1 / 2 = 4:4:4 / 4:2:2 /
     4:2:0 and the number of int16 coefficients are set), > 0 = unsupported."""
 
     def __init__(self, status, H, W, sampling, n_coeffs):
         self.status, self.H, self.W, self.sampling, self.n_coeffs = status, H, W, sampling, n_coeffs
-
-    @property
-    def supported(self) -> bool:
-        return self.status == 0
-
-    def __repr__(self):
-        return f"JpegInfo(status={self.status}, H={self.H}, W={self.W}, sampling={self.sampling}, n_coeffs={self.n_coeffs})"
-
-
-def _jpeg_error(status: int, index: Optional[int] = None) -> Exception:
-    """The exception of a non-zero status: ValueError for a broken file (< 0), JpegUnsupported for one the device decoder does not take."""
-    if status > 0:
-        return JpegUnsupported(status, index)
-    where = "" if index is None else f"file {index}: "
-    return ValueError(f"{where}malformed JPEG (status {status}: {JPEG_MALFORMED.get(int(status), 'unknown')})")
 
 
 def _jpeg_probe_raw(lib, data: bytes) -> JpegInfo:
@@ -2441,10 +2534,7 @@ def _jpeg_probe_raw(lib, data: bytes) -> JpegInfo:
 
 def jpeg_probe(data: bytes) -> JpegInfo:
     """Classifies a JPEG file without decoding it.  A broken file raises ValueError; an unsupported one is a JpegInfo with status > 0."""
-    info = _jpeg_probe_raw(_lib.load(), bytes(data))
-    if info.status < 0:
-        raise _jpeg_error(info.status)
-    return info
+    return _JPEG.probed(_jpeg_probe_raw(_lib.load(), bytes(data)))
 
 
 def jpeg_scan(data: bytes):
@@ -2454,11 +2544,11 @@ def jpeg_scan(data: bytes):
     data = bytes(data)
     info = jpeg_probe(data)
     if not info.supported:
-        raise _jpeg_error(info.status)
+        raise _JPEG.error(info.status)
     coeffs, q = np.empty(info.n_coeffs, np.int16), np.empty((3, 64), np.uint16)
     rc = lib.tt_jpeg_scan(data, len(data), coeffs.ctypes.data, coeffs.size, q.ctypes.data)
     if rc:
-        raise _jpeg_error(rc)
+        raise _JPEG.error(rc)
     return info, coeffs, q
 
 
@@ -2468,57 +2558,27 @@ def _jpeg_grid(H: int, W: int, sampling: int, comp: int):
     return (my * vmax, mx * hmax) if comp == 0 else (my, mx)
 
 
-_JPEG_POOLS: dict = {}
-
-
-def _jpeg_pool(workers: int):
-    """One thread pool per size, kept: starting 16 threads per batch costs as much as scanning a dozen frames."""
-    pool = _JPEG_POOLS.get(workers)
-    if pool is None:
-        from concurrent.futures import ThreadPoolExecutor
-
-        pool = _JPEG_POOLS[workers] = ThreadPoolExecutor(workers, thread_name_prefix="tt_jpeg")
-    return pool
-
-
-class JpegBatch:
+class JpegBatch(_FileBatch):
     """The host half of a batch, ready for the device.  ``route`` "host" (N21): ``coeffs`` holds the int16 coefficients and ``meta`` the
     frame table, then the quantisation tables.  ``route`` "device" (N24: the host copies each scan once, what crosses PCIe is the
     compressed stream, and tt_jpeg_entropy_batch leaves the coefficients where tt_jpeg_decode_batch reads them): ``coeffs`` is None and
     ``meta`` holds the stream table, the frame table, the quantisation tables, the segment table, then every file's Huffman tables and
     clean stream.  Either way ONE pinned buffer per copy; ``layout``: name -> (offset, bytes) of ``meta``'s parts, each on a 16-byte
-    boundary; ``groups`` (size -> offset in the output, count), ``where`` (file -> size, place in its group) and ``out_bytes``: the output."""
+    boundary - 'frames' and 'qtables', on the device route also 'streams', 'segs' and 'scan'; ``groups`` (size -> offset in the output,
+    count), ``where`` (file -> size, place in its group) and ``out_bytes``: the output."""
 
     def __init__(self, route, infos, meta, layout, coeffs, n_coeffs, n_segs, out_bytes, groups, where):
         self.route, self.infos, self.meta, self.layout, self.coeffs, self.n_coeffs, self.n_segs = route, infos, meta, layout, coeffs, n_coeffs, n_segs
         self.out_bytes, self.groups, self.where = out_bytes, groups, where
-
-    def part(self, name):
-        """A uint8 NumPy view of one part of ``meta``: 'frames' or 'qtables', on the device route also 'streams', 'segs' or 'scan'."""
-        at, size = self.layout[name]
-        return self.meta.numpy()[at:at + size]
 
 
 def _jpeg_batch(files: Sequence[bytes], threads: int, pin: bool, route: str) -> JpegBatch:
     """What ``jpeg_scan_batch`` (route "host") and ``jpeg_prepare_batch`` ("device") share - the pool, the probes, the output layout and the
     frame table - around what they do not: the buffers each fills and the host entry that fills them."""
     lib = _lib.load()
-    files = [bytes(f) for f in files]
+    files = _file_list(files, f"jpeg_{'scan' if route == 'host' else 'prepare'}_batch")
     n = len(files)
-    if n == 0:
-        raise ValueError(f"jpeg_{'scan' if route == 'host' else 'prepare'}_batch: no files")
-    workers = max(1, min(int(threads), JPEG_MAX_THREADS, n))
-    chunks = [range(k * n // workers, (k + 1) * n // workers) for k in range(workers)]   # one task per thread, not per file
-    run = (lambda fn: [fn(c) for c in chunks]) if workers == 1 else (lambda fn: list(_jpeg_pool(workers).map(fn, chunks)))
-
-    def each(fn, status=int):
-        """fn(i) of every file, in the pool; then the first file in order whose status is not 0 raises"""
-        results = [r for part in run(lambda chunk: [fn(i) for i in chunk]) for r in part]
-        for i, r in enumerate(results):
-            if status(r):
-                raise _jpeg_error(status(r), i)
-        return results
-
+    each = lambda fn, status=int: _each_file(fn, n, threads, _JPEG.error, status)
     infos = each(lambda i: _jpeg_probe_raw(lib, files[i]), lambda info: info.status)
     # a component's int16 coefficients and the bytes of its plane are one number, so one running sum places both
     sizes = np.array([[rows * cols * 64 for rows, cols in (_jpeg_grid(f.H, f.W, f.sampling, c) for c in range(3))] for f in infos], np.int64)
@@ -2548,11 +2608,8 @@ def _jpeg_batch(files: Sequence[bytes], threads: int, pin: bool, route: str) -> 
         np.cumsum(scan_cap, out=scan_cap)
         np.cumsum(seg_cap, out=seg_cap)
         parts = [("streams", n * _JPEG_STREAM.itemsize)] + parts + [("segs", int(seg_cap[-1]) * 8), ("scan", int(scan_cap[-1]))]
-    layout, at = {}, 0
-    for name, size in parts:
-        layout[name] = (at, size)
-        at += -(-size // 16) * 16
-    meta = torch.zeros(at, dtype=torch.uint8, pin_memory=pin)    # every table and stream of the batch: one copy
+    layout, meta_bytes = _layout(parts)
+    meta = torch.zeros(meta_bytes, dtype=torch.uint8, pin_memory=pin)    # every table and stream of the batch: one copy
     batch = JpegBatch(route, infos, meta, layout, coeffs, total, 0 if route == "host" else int(seg_cap[-1]), out_bytes,
                       {k: (group_base[k], len(m)) for k, m in groups.items()}, where)
     q_at = meta.data_ptr() + layout["qtables"][0]
@@ -2622,10 +2679,7 @@ def jpeg_entropy_decode(batch: JpegBatch, device=None, subseq_bits=None, stats: 
     one launch on the current stream, then ONE read-back of 4 n bytes - the frames' status.  Returns (coefficients int16 [n_coeffs] on the
     device, in the layout of the batch's frame table; status int32 [n] on the host; the batch's buffer on the device).  A negative status
     raises ValueError naming the file.  ``stats``: the per-frame statistics (rounds, tiles, subsequences, -1) as a fourth item."""
-    lib = _lib.load()
-    if not torch.cuda.is_available():
-        raise _lib.HipLibraryError("jpeg_entropy_decode: needs a GPU (the HIP path has no CPU fallback)")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib, dev = _lib.load(), _need_gpu("jpeg_entropy_decode", device)
     n, bits = len(batch.infos), _jpeg_subseq_bits(subseq_bits)
     streams, segs = batch.part("streams"), batch.part("segs")
     ws_bytes = int(lib.tt_jpeg_entropy_batch_workspace_bytes(streams.ctypes.data, n, bits))
@@ -2638,10 +2692,7 @@ def jpeg_entropy_decode(batch: JpegBatch, device=None, subseq_bits=None, stats: 
         _lib.check(lib.tt_jpeg_entropy_batch(at("scan"), batch.layout["scan"][1], segs.ctypes.data, at("segs"), batch.n_segs, streams.ctypes.data,
                                              at("streams"), n, bits, _p(coeffs), batch.n_coeffs, _p(status), _p(ws), ws.numel(), _stream()),
                    "tt_jpeg_entropy_batch")
-        host_status = status.cpu().numpy()
-    for i, rc in enumerate(host_status):
-        if rc < 0:
-            raise _jpeg_error(int(rc), i)
+        host_status = _file_status(status, _JPEG, lambda rc: rc < 0)
     if stats:
         return coeffs, host_status, meta, ws[:16 * n].view(torch.int32).view(n, 4).cpu().numpy()
     return coeffs, host_status, meta
@@ -2652,10 +2703,7 @@ def jpeg_decode(batch: JpegBatch, device=None, subseq_bits=None):
     Device route: ``jpeg_entropy_decode`` (``subseq_bits`` is its), then the same two launches on the device-resident coefficients.
     Returns the frames as uint8 [H, W, 3] tensors in the order of the files; frames of one size are consecutive views of one
     [k, H, W, 3] tensor (``frames_as_clip`` returns it without a copy)."""
-    lib = _lib.load()
-    if not torch.cuda.is_available():
-        raise _lib.HipLibraryError("decode_jpeg_batch: needs a GPU (the HIP path has no CPU fallback)")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib, dev = _lib.load(), _need_gpu("decode_jpeg_batch", device)
     n = len(batch.infos)
     table = batch.part("frames")
     ws_bytes = int(lib.tt_jpeg_decode_batch_workspace_bytes(table.ctypes.data, n))
@@ -2686,8 +2734,8 @@ def decode_jpeg_batch(files: Sequence[bytes], device=None, threads: int = 8, ent
 
 
 def frames_as_clip(frames: Sequence[torch.Tensor]) -> torch.Tensor:
-    """Frames of one size -> [k, H, W, 3]: the tensor they are consecutive views of where they are (``decode_jpeg_batch``), a stacked
-    copy otherwise."""
+    """Frames [H, W, 3] - or label maps [H, W], or views of any one shape - -> [k, ...]: the tensor they are consecutive views of where
+    they are (``jpeg_decode``, ``png_decode``), a stacked copy otherwise."""
     f0 = frames[0]
     step = f0.numel()
     same = all(f.shape == f0.shape and f.dtype == f0.dtype and f.is_contiguous() and f.device == f0.device and
@@ -2695,8 +2743,7 @@ def frames_as_clip(frames: Sequence[torch.Tensor]) -> torch.Tensor:
                f.storage_offset() == f0.storage_offset() + i * step for i, f in enumerate(frames))
     if not same:
         return torch.stack(list(frames))
-    H, W, ch = f0.shape
-    return f0.as_strided((len(frames), H, W, ch), (step, W * ch, ch, 1), f0.storage_offset())
+    return f0.as_strided((len(frames) * step,), (1,), f0.storage_offset()).view(len(frames), *f0.shape)
 
 
 # ---- N22: ragged image kernels.  A batch of images (or label maps) of different sizes through ONE launch: a descriptor row per item and one
@@ -2987,7 +3034,7 @@ def map_instances(labels: torch.Tensor, cat: torch.Tensor, sequential: bool = Tr
 
 
 # ---- N26: annotation PNGs.  The host half (tt_png_probe, tt_png_prepare: chunks and CRC-32 only, pure host functions that ctypes runs
-# without the GIL) in the thread pool of the JPEG batches, the device half (tt_png_decode_batch: inflate, Adler-32, row filters, unpacking)
+# without the GIL) in the thread pool the JPEG batches use, the device half (tt_png_decode_batch: inflate, Adler-32, row filters, unpacking)
 # in one launch for the whole batch.
 PNG_UNSUPPORTED = {1: "Adam7 interlace", 2: "a colour type other than palette or gray", 3: "gray below 8 bits", 4: "16-bit samples",
                    5: "a side above 32767"}
@@ -2998,64 +3045,36 @@ PNG_MALFORMED = {-1: "broken signature, IHDR, zlib header or block header", -2: 
 _PNG_STREAM = np.dtype([("H", "<i8"), ("W", "<i8"), ("depth", "<i8"), ("color_type", "<i8"), ("row_bytes", "<i8"), ("stream_off", "<i8"),
                         ("stream_len", "<i8"), ("out_off", "<i8"), ("ws_off", "<i8"), ("reserved", "<i8", 7)])                # tt_png_stream
 PNG_STATS = ("kinds", "lit_bits", "dist_bits", "min_dist", "max_dist", "max_len", "filters", "bytes")   # the eight int32 per file
+_PNG = _Codec("PNG", PNG_UNSUPPORTED, PNG_MALFORMED, ("H", "W", "depth", "color_type"))
 
 
-class PngUnsupported(Exception):
+class PngUnsupported(_FileUnsupported, codec=_PNG):
     """A well-formed PNG file the device decoder does not take (``status`` > 0: TT_PNG_UNSUPPORTED_*).  hip_ops has no CPU fallback;
     the loaders decode such a file with Pillow and count it."""
 
-    def __init__(self, status: int, index: Optional[int] = None):
-        self.status, self.index = int(status), index
-        where = "" if index is None else f"file {index}: "
-        super().__init__(f"{where}unsupported PNG ({PNG_UNSUPPORTED.get(int(status), status)})")
 
-
-class PngInfo:
+class PngInfo(_FileInfo, codec=_PNG):
     """What ``png_probe`` found: ``status`` 0 = the device decoder takes the file, > 0 = unsupported; H, W, bit depth, colour type."""
 
     def __init__(self, status, H, W, depth, color_type):
         self.status, self.H, self.W, self.depth, self.color_type = status, H, W, depth, color_type
 
-    @property
-    def supported(self) -> bool:
-        return self.status == 0
-
-    def __repr__(self):
-        return f"PngInfo(status={self.status}, H={self.H}, W={self.W}, depth={self.depth}, color_type={self.color_type})"
-
-
-def _png_error(status: int, index: Optional[int] = None) -> Exception:
-    if status > 0:
-        return PngUnsupported(status, index)
-    where = "" if index is None else f"file {index}: "
-    return ValueError(f"{where}malformed PNG (status {status}: {PNG_MALFORMED.get(int(status), 'unknown')})")
-
-
-def _png_probe_raw(lib, data: bytes) -> PngInfo:
-    H, W, depth, color = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    rc = lib.tt_png_probe(data, len(data), C.byref(H), C.byref(W), C.byref(depth), C.byref(color))
-    return PngInfo(rc, H.value, W.value, depth.value, color.value)
-
 
 def png_probe(data: bytes) -> PngInfo:
     """Classifies a PNG file without decoding it.  A broken file raises ValueError; an unsupported one is a PngInfo with status > 0."""
-    info = _png_probe_raw(_lib.load(), bytes(data))
-    if info.status < 0:
-        raise _png_error(info.status)
-    return info
+    data = bytes(data)
+    H, W, depth, color = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = _lib.load().tt_png_probe(data, len(data), C.byref(H), C.byref(W), C.byref(depth), C.byref(color))
+    return _PNG.probed(PngInfo(rc, H.value, W.value, depth.value, color.value))
 
 
-class PngBatch:
+class PngBatch(_FileBatch):
     """The host half of a batch of annotation files, ready for the device: ONE (pinned) buffer ``meta`` holding the stream table, then
     every file's deflate stream; ``layout``: name -> (offset, bytes) of its two parts 'table' and 'streams', each on a 16-byte boundary.
     The maps lie one after the other in the output (``out_bytes`` in all), so consecutive files of one size are one [k, H, W] tensor."""
 
     def __init__(self, infos, meta, layout, out_bytes, ws_bytes):
         self.infos, self.meta, self.layout, self.out_bytes, self.ws_bytes = infos, meta, layout, out_bytes, ws_bytes
-
-    def part(self, name):
-        at, size = self.layout[name]
-        return self.meta.numpy()[at:at + size]
 
     @property
     def table(self):
@@ -3067,27 +3086,19 @@ def png_prepare_batch(files: Sequence[bytes], threads: int = 8, pin: bool = True
     Raises PngUnsupported for the first unsupported file and ValueError for the first broken one (chunks, CRC-32, zlib header: the
     deflate stream itself is the device's to judge)."""
     lib = _lib.load()
-    files = [bytes(f) for f in files]
+    files = _file_list(files, "png_prepare_batch")
     n = len(files)
-    if n == 0:
-        raise ValueError("png_prepare_batch: no files")
-    workers = max(1, min(int(threads), JPEG_MAX_THREADS, n))
-    chunks = [range(k * n // workers, (k + 1) * n // workers) for k in range(workers)]
-    run = (lambda fn: [fn(c) for c in chunks]) if workers == 1 else (lambda fn: list(_jpeg_pool(workers).map(fn, chunks)))
     cap = np.zeros(n + 1, np.int64)
     a = C.c_size_t()
     for i, f in enumerate(files):
         lib.tt_png_prepare_bytes(len(f), C.byref(a))
         cap[i + 1] = a.value
     np.cumsum(cap, out=cap)
-    layout = {"table": (0, n * _PNG_STREAM.itemsize), "streams": (n * _PNG_STREAM.itemsize, int(cap[-1]))}   # 128-byte rows: aligned
-    meta = torch.zeros(n * _PNG_STREAM.itemsize + int(cap[-1]), dtype=torch.uint8, pin_memory=pin)
+    layout, _ = _layout([("table", n * _PNG_STREAM.itemsize), ("streams", int(cap[-1]))])
+    meta = torch.zeros(sum(layout["streams"]), dtype=torch.uint8, pin_memory=pin)      # (ends with the last stream, not on a boundary)
     rows_at, streams_at, at = meta.data_ptr(), meta.data_ptr() + layout["streams"][0], cap.tolist()
-    results = [r for part in run(lambda chunk: [lib.tt_png_prepare(files[i], len(files[i]), streams_at + at[i], at[i + 1] - at[i],
-                                                                    rows_at + i * _PNG_STREAM.itemsize) for i in chunk]) for r in part]
-    for i, rc in enumerate(results):
-        if rc:
-            raise _png_error(rc, i)
+    _each_file(lambda i: lib.tt_png_prepare(files[i], len(files[i]), streams_at + at[i], at[i + 1] - at[i], rows_at + i * _PNG_STREAM.itemsize),
+               n, threads, _PNG.error)
     table = meta.numpy()[:layout["table"][1]].view(_PNG_STREAM)
     table["stream_off"] = cap[:-1]
     pixels = table["H"] * table["W"]
@@ -3113,8 +3124,9 @@ def png_decode_host(batch: PngBatch, lanes: int = 1):
     table, streams = batch.table, batch.part("streams")
     out, status = np.zeros(max(batch.out_bytes, 1), np.uint8), np.zeros(n, np.int32)
     ws = np.zeros(batch.ws_bytes // 4 + 1, np.int32)
-    _lib.check((lib.tt_png_decode_host if lanes == 1 else lib.tt_png_decode_host_wave)(streams.ctypes.data, streams.size, table.ctypes.data, table.ctypes.data, n, out.ctypes.data, batch.out_bytes,
-                                      ws.ctypes.data, batch.ws_bytes, status.ctypes.data, None), "tt_png_decode_host")
+    entry = "tt_png_decode_host" if lanes == 1 else "tt_png_decode_host_wave"
+    _lib.check(getattr(lib, entry)(streams.ctypes.data, streams.size, table.ctypes.data, table.ctypes.data, n, out.ctypes.data, batch.out_bytes,
+                                   ws.ctypes.data, batch.ws_bytes, status.ctypes.data, None), entry)
     raw = ws.view(np.uint8)
     slices = [raw[int(r["ws_off"]):int(r["ws_off"]) + int(r["H"]) * (1 + int(r["row_bytes"]))] for r in table]
     return _png_views(out, table), status, ws[(batch.ws_bytes - 32 * n) // 4:batch.ws_bytes // 4].reshape(n, 8), slices
@@ -3125,10 +3137,7 @@ def png_decode(batch: PngBatch, device=None, out: Optional[torch.Tensor] = None,
     files' status.  Returns (the maps as uint8 [H, W] views of ONE flat device buffer in file order - ``out``, a contiguous uint8 tensor
     of at least ``batch.out_bytes`` elements, when given -, status int32 [n] on the host).  A non-zero status raises ValueError naming
     the file and the reason unless ``check`` is False."""
-    lib = _lib.load()
-    if not torch.cuda.is_available():
-        raise _lib.HipLibraryError("png_decode: needs a GPU (the HIP path has no CPU fallback)")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib, dev = _lib.load(), _need_gpu("png_decode", device)
     n, table = len(batch.infos), batch.table
     with torch.cuda.device(dev):
         meta = batch.meta.to(dev, non_blocking=True)
@@ -3141,11 +3150,7 @@ def png_decode(batch: PngBatch, device=None, out: Optional[torch.Tensor] = None,
         _lib.check(lib.tt_png_decode_batch(meta.data_ptr() + batch.layout["streams"][0], batch.layout["streams"][1], table.ctypes.data,
                                            meta.data_ptr(), n, _p(out), out.numel(), _p(ws), ws.numel(), _p(status), _stream()),
                    "tt_png_decode_batch")
-        host_status = status.cpu().numpy()
-    if check:
-        for i, rc in enumerate(host_status):
-            if rc != 0:
-                raise _png_error(int(rc), i)
+        host_status = _file_status(status, _PNG, (lambda rc: rc != 0) if check else None)
     return _png_views(out, table), host_status
 
 

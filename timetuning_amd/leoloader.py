@@ -25,14 +25,14 @@ from __future__ import annotations
 import math
 import os
 import random
-from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
 
 import numpy as np
 import torch
 
 from . import hip_ops as ops
-from .data_loader import _read, decode_annotations, finish_annotations, finish_frames, scan_annotations, scan_frames
+from . import data_loader as DL     # (scan_frames and decode_annotations through the module: looked up when called, as ClipLoader does)
+from .data_loader import _read, _route, finish_annotations, finish_frames, prefetched, scan_annotations
 
 CLASS_IDX_TO_NAME = ['background', 'aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair',
                      'cow', 'diningtable', 'dog', 'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa',
@@ -167,11 +167,7 @@ class VOCDataset:
 
     def __init__(self, root: str, image_set: str = "trainaug", transform=None, target_transform=None, transforms=None, return_masks: bool = False,
                  device=None, threads: int = 8, jpeg_entropy: str = "host", png: str = "host"):
-        if jpeg_entropy not in ("host", "device"):
-            raise ValueError(f"jpeg_entropy must be 'host' or 'device', not {jpeg_entropy!r}")
-        if png not in ("host", "device"):
-            raise ValueError(f"png must be 'host' or 'device', not {png!r}")
-        self.jpeg_entropy, self.png = jpeg_entropy, png
+        self.jpeg_entropy, self.png = _route("jpeg_entropy", jpeg_entropy), _route("png", png)
         self.root, self.image_set = root, image_set
         if image_set == "trainaug" or image_set == "train":
             seg_folder = "SegmentationClassAug"
@@ -205,7 +201,7 @@ class VOCDataset:
 class _VOCHostBatch:
     def __init__(self, frames, mask_buf, mask_offs, mask_dims, masks=None):
         self.frames, self.mask_buf, self.mask_offs, self.mask_dims = frames, mask_buf, mask_offs, mask_dims
-        self.masks = masks      # png="device": the ``HostAnnotations`` of the batch, and the three mask_* fields are None
+        self.masks = masks      # png="device": the ``HostFiles`` of the batch, and the three mask_* fields are None
 
 
 class VOCLoader:
@@ -232,12 +228,12 @@ class VOCLoader:
         return -(-len(self.dataset) // self.batch_size)
 
     # ---- host half: file reads, entropy decode, PNG decode (no launch: a background thread may run it)
-    def _host_on(self, indices) -> _VOCHostBatch:
+    def _host(self, indices) -> _VOCHostBatch:
         ds = self.dataset
-        frames = scan_frames([_read(ds.images[i]) for i in indices], ds.threads, ds.jpeg_entropy)
+        frames = DL.scan_frames([_read(ds.images[i]) for i in indices], ds.threads, ds.jpeg_entropy)
         if ds.png == "device":
             return _VOCHostBatch(frames, None, None, None, scan_annotations([_read(ds.masks[i]) for i in indices], ds.threads))
-        masks = decode_annotations([_read(ds.masks[i]) for i in indices], ds.threads)
+        masks = DL.decode_annotations([_read(ds.masks[i]) for i in indices], ds.threads)
         offs = np.zeros(len(masks) + 1, np.int64)
         np.cumsum([m.size for m in masks], out=offs[1:])
         mask_buf = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
@@ -245,13 +241,6 @@ class VOCLoader:
         for m, o in zip(masks, offs):
             view[o:o + m.size] = m.reshape(-1)
         return _VOCHostBatch(frames, mask_buf, [int(o) for o in offs[:-1]], [m.shape for m in masks])
-
-    def _host(self, indices) -> _VOCHostBatch:
-        dev = self.dataset.device
-        if dev is not None and torch.device(dev).type == "cuda":
-            with torch.cuda.device(dev):   # a new thread starts on device 0: the pinned buffers belong to this loader's device
-                return self._host_on(indices)
-        return self._host_on(indices)
 
     # ---- device half: reconstruction and the two ragged launches
     def _finish(self, host: _VOCHostBatch):
@@ -263,7 +252,7 @@ class VOCLoader:
         if host.masks is not None:      # the maps, their buffer and their offsets come straight from the decode
             maps, fallbacks = finish_annotations(host.masks, ds.device)
             ds.fallback_annotations += fallbacks
-            host.mask_dims = [tuple(m.shape) for m in maps]
+            host.mask_dims = host.masks.dims
         else:
             buf = host.mask_buf.to(ds.device, non_blocking=True)
             maps = [buf[o:o + h * w].view(h, w) for o, (h, w) in zip(host.mask_offs, host.mask_dims)]
@@ -284,19 +273,8 @@ class VOCLoader:
     def __iter__(self):
         order = list(range(len(self.dataset)))
         batches = [order[i:i + self.batch_size] for i in range(0, len(order), self.batch_size)]
-        if not batches:
-            return
-        pool = ThreadPoolExecutor(1) if self.prefetch else None
-        try:
-            pending = pool.submit(self._host, batches[0]) if pool else None
-            for k in range(len(batches)):
-                host = pending.result() if pool else self._host(batches[k])
-                if pool and k + 1 < len(batches):
-                    pending = pool.submit(self._host, batches[k + 1])
-                yield self._finish(host)
-        finally:
-            if pool:
-                pool.shutdown(wait=True)
+        for host in prefetched(batches, self._host, self.dataset.device, self.prefetch):
+            yield self._finish(host)
 
 
 def pascal_loader(batch_size, root, split, val_size, train_size=448, device=None, threads=8, jpeg_entropy="host", png="host") -> VOCLoader:

@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
+from .data_loader import add_decode_arguments
 from .metrics import PredsmIoU
 
 MAX_D, MAX_C, MAX_G, MAX_R = 1024, 256, 64, 1024   # what the N5 kernels support (include/timetuning_hip.h)
@@ -252,8 +253,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--input_resolution", type=int, default=448)
     p.add_argument("--dataset", type=str, default="pascal")
     p.add_argument("--dataset_path", type=str, default="../../dataset/leopascal/VOCSegmentation")
-    p.add_argument("--png_decode", choices=["host", "device"], default="host",
-                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
+    add_decode_arguments(p, jpeg=False)
     p.add_argument("--save_path", type=str, default="linear_finetune.pth", help="state_dict written after every epoch ('' = none)")
     p.add_argument("--num_train_images", type=int, default=120, help="synthetic data only")
     p.add_argument("--num_val_images", type=int, default=60, help="synthetic data only")

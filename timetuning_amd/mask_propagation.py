@@ -34,6 +34,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip_ops as ops
+from .data_loader import add_decode_arguments
 
 
 def to_one_hot(y_tensor: torch.Tensor, n_dims: Optional[int] = None) -> torch.Tensor:
@@ -473,10 +474,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--logging_directory", type=str, default="visualizations")
     p.add_argument("--batch_size", type=int, default=1)
     p.add_argument("--num_workers", type=int, default=10)
-    p.add_argument("--jpeg_entropy", choices=["host", "device"], default="host",
-                   help="where the frames' Huffman coding is undone: in the host thread pool, or on the device from the compressed scans (N24)")
-    p.add_argument("--png_decode", choices=["host", "device"], default="host",
-                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
+    add_decode_arguments(p)
     p.add_argument("--num_clusters", type=int, default=10)
     p.add_argument("--input_resolution", type=int, default=224)
     p.add_argument("--many_to_one", type=bool, default=False)

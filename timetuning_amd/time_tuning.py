@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from . import engine
 from . import hip_ops as ops
+from .data_loader import add_decode_arguments
 from .models import DistributedDataParallelModel, FeatureExtractor
 from .my_utils import cosine_scheduler
 from .visualization import localize_clip, make_overlayed_grid  # noqa: F401  (time_tuning.py:322-341: the reference defines them here)
@@ -1053,10 +1054,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch_size", type=int, default=128)
     p.add_argument("--num_epochs", type=int, default=100)
     p.add_argument("--num_workers", type=int, default=10)
-    p.add_argument("--jpeg_entropy", choices=["host", "device"], default="host",
-                   help="where the frames' Huffman coding is undone: in the host thread pool, or on the device from the compressed scans (N24)")
-    p.add_argument("--png_decode", choices=["host", "device"], default="host",
-                   help="where the annotation PNGs are inflated: Pillow in the host thread pool, or on the device from the IDAT streams (N26)")
+    add_decode_arguments(p)
     p.add_argument("--num_clusters", type=int, default=200)
     p.add_argument("--input_resolution", type=int, default=224)
     p.add_argument("--many_to_one", type=bool, default=False)
