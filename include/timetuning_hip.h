@@ -796,6 +796,53 @@ int tt_kmeans_fit_batched_split(const float* x, const int32_t* init, const int32
                                 int32_t* status, int B, long long n, int d, int k, int nredo, int niter, void* workspace,
                                 size_t workspace_bytes, const double* draws, int n_draws, tt_stream_t stream);
 
+/* ---- N28: the large k-means fits as one enqueued device loop - the faiss.Kmeans(50, k, niter=50, nredo=5).train(x) of the dataset-wise
+ *      protocol (clustering.py:69-71; k = 500 in the over-clustering evaluation) and the faiss.Kmeans(dim, k_fg_extraction).train of
+ *      cluster-based foreground extraction (cluster_based_foreground_extraction.py:273-275, 384 raw feature columns), whose centroids
+ *      do not fit one workgroup's LDS (tt_kmeans_fit_shape_ok refuses them), so that they ran clustering.Kmeans._iterate: per Lloyd
+ *      iteration a dozen launches and two host synchronisations.
+ *   tt_kmeans_fit_loop         x [n, d], init int32 [nredo, k] (+ init_host, a HOST copy checked before the first launch) -> centroids
+ *                              [nredo, k, d], obj fp64 [nredo], status int32 [nredo].  Every redo and iteration is enqueued on
+ *                              `stream`: between the first launch and the caller's read-back of obj and status there is no host
+ *                              synchronisation, no read-back and no allocation (it can be captured into a graph).  Kernel
+ *                              boundaries are the only ordering between workgroups: no flag, no counter another workgroup spins on,
+ *                              no cooperative launch.  Per output number the arithmetic is that of the host loop over the N2 / N12
+ *                              entries, so a fit returns that loop's bits:
+ *                                assignment    the k-means contract (N2 above) - the resident kernel where tt_kmeans_shape_ok(d, k)
+ *                                              and tile_k == 0, else the tiled one (a tile_k given asks for it; the bits are the same) -
+ *                                              with the redo on a grid axis: every redo reads the ONE point set, its own centroids;
+ *                                accumulation  the k-means contract, the redo on a grid axis;
+ *                                update        c = (float)(sum / (double)count) where count > 0, the old centroid otherwise;
+ *                                split         after the update, once per (redo, iteration) whose counts hold a zero: the statement of
+ *                                              N18 above (the same device function), on an int copy of that iteration's counts that is
+ *                                              not carried on; at d > 64 lane j of the one wave owns columns j, j + 64, ..., each still
+ *                                              a single fp32 product of the old donor row.  draws == NULL or n_draws == 0: no split;
+ *                                objective     obj[r] = the LAST iteration's dist2 summed in fp64 in an order fixed by n alone; it
+ *                                              agrees with another fp64 summation order to about n * 2^-53 relative.
+ *                              status[r] = 0, or the 1-based iteration whose split would have read past the table (without a table:
+ *                              the first iteration with an empty cluster).  Every later launch leaves that redo alone (a uniform
+ *                              early exit on the status word); its centroids and obj are unspecified and the caller reruns the fit
+ *                              on the host loop.
+ *   redo_group                 how many redos ride one launch: 0 = all of them, fewer = several passes over the iterations.  The
+ *                              result does not depend on it; the workspace does.
+ *   tt_kmeans_loop_shape_ok    1 for the tiled pair's rule (1 <= d <= 1024, k >= 1, k * d < 2^31) with k <= n <= 2^31 - 1, else 0.
+ *   tt_kmeans_loop_workspace_bytes   for redo_group (0 = nredo) redos in flight: the accumulation's fp64 partials
+ *                              (tt_kmeans_accumulate_workspace_bytes each: 200 MB at n = 128 000, d = 50, k = 500), the folded sums
+ *                              and counts, the labels and the last dist2 (4 n bytes each), the split's counts; 0 for a refused shape,
+ *                              nredo outside 1 ... 65535 or redo_group < 0.
+ *   Refused with TT_EINVAL and a message naming the numbers, nothing launched: null pointers, niter < 1, nredo outside 1 ... 65535,
+ *   redo_group < 0, n_draws < 0 (or > 0 without a table), a shape beyond the rule, a tile_k outside 0 ... tt_kmeans_tile_centroids(d),
+ *   an init index outside [0, n), a workspace that is too small or not aligned to 8 bytes. */
+int tt_kmeans_loop_shape_ok(long long n, int d, int k);   /* pure host function, like tt_kmeans_fit_shape_ok */
+size_t tt_kmeans_loop_workspace_bytes(long long n, int d, int k, int nredo, int redo_group);
+int tt_kmeans_loop_last_offsets(long long n, int d, int k, int nredo, int redo_group, size_t* labels_offset,
+                                size_t* dist2_offset);   /* byte offsets, in a workspace of that query, of the last iteration's labels int32
+                                                            [g][n] and dist2 fp32 [g][n] of the LAST pass's g redos in flight (for tests
+                                                            and tools; the layout is the library's); 1, or 0 for what the query refuses */
+int tt_kmeans_fit_loop(const float* x, const int32_t* init, const int32_t* init_host, float* centroids, double* obj, int32_t* status,
+                       long long n, int d, int k, int nredo, int niter, int tile_k, int redo_group, const double* draws, int n_draws,
+                       void* workspace, size_t workspace_bytes, tt_stream_t stream);
+
 /* ---- N3(SURVEY.md 8(f)): the clip input pipeline - the pixel work of video_transformations.py as wired at
  *      time_tuning.py:588-593, bit-exact with Pillow (which the reference calls per frame on the host).
  *   Frames are interleaved uint8 RGB [F, H, W, 3] in device memory.

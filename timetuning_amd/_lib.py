@@ -171,6 +171,10 @@ SIGNATURES = {
     "tt_kmeans_fit_batched": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_ll, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
     "tt_kmeans_fit_batched_split": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_ll, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp, c_i, c_vp]),
     "tt_kmeans_assign_batched": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_ll, c_i, c_i, c_vp]),
+    "tt_kmeans_loop_shape_ok": (c_i, [c_ll, c_i, c_i]),
+    "tt_kmeans_loop_workspace_bytes": (c_sz, [c_ll, c_i, c_i, c_i, c_i]),
+    "tt_kmeans_loop_last_offsets": (c_i, [c_ll, c_i, c_i, c_i, c_i, c_vp, c_vp]),
+    "tt_kmeans_fit_loop": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_i, c_vp, c_sz, c_vp]),
     "tt_label_propagate_sims": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
     "tt_label_propagate_from_sims": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_vp, c_sz, c_vp]),
     "tt_label_propagate_maps": (c_i, [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp, c_sz, c_vp]),

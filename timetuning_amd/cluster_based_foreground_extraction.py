@@ -34,6 +34,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import clustering
 from . import hip_ops as ops
 from .data_loader import add_decode_arguments
 from .bfscore import evaluate_bf_score
@@ -41,6 +42,9 @@ from .clustering import Kmeans, nearest_index_table, normalize_and_transform
 from .models import FeatureExtractor, process_attentions
 
 ATTENTION_THRESHOLD = 0.65   # :242,252
+# What the over-clustering's device loop (clustering.Kmeans(loop="device")) may take for its redos in flight: one redo's partials at the
+# default k = 300 on 50 columns (73 MB) and no second - the host loop's footprint, which get_foreground_masks' memory bound was set with.
+LOOP_WORKSPACE_BYTES = 96 << 20
 
 
 class ScaleType:
@@ -262,12 +266,14 @@ class ClusterBasedForegroundExtraction(nn.Module):
             tokens, R = features.tokens, int(features.resolution)
             bs, fs, n, dim = tokens.shape
             tokens = tokens.reshape(bs * fs, n, dim)
-            km = Kmeans(dim, k, niter=50, nredo=5, seed=1)
+            km = Kmeans(dim, k, niter=50, nredo=5, seed=1, loop="device" if clustering.DEVICE_LOOP else "host",
+                        loop_workspace_bytes=LOOP_WORKSPACE_BYTES)
             km.train_upsampled(tokens, R)
             return km.assign_upsampled(tokens, R).view(bs, fs, R, R)
         bs, fs, dim, R, _ = features.shape
         points = features.permute(0, 1, 3, 4, 2).reshape(-1, dim)
-        km = Kmeans(dim, k, niter=50, nredo=5, seed=1)
+        km = Kmeans(dim, k, niter=50, nredo=5, seed=1, loop="device" if clustering.DEVICE_LOOP else "host",
+                        loop_workspace_bytes=LOOP_WORKSPACE_BYTES)
         km.train(points)
         return km.assign(points)[1].view(bs, fs, R, R)
 

@@ -22,6 +22,11 @@ The frame-wise and sample-wise protocols fit all their problems of one k in one 
 clusters draws from ``numpy.RandomState(1234)``, re-created at every call; ``split_draws`` holds that one sequence as a table, with which
 the fused kernel splits on the device (N18: ``KmeansBatch(split="device")``, ``split_empty_from_table`` is its host statement), so a
 masked evaluation batch, whose every fit meets empty clusters, stays off the host-driven loop.
+
+The large fits - the dataset-wise protocol, the over-clustering at k = 500, the over-clustering of cluster-based foreground extraction on
+384 raw columns - do not fit the fused kernel's LDS.  ``Kmeans(loop="device")`` (N28) enqueues their whole Lloyd loop, split included, on
+the stream (``ops.kmeans_fit_loop``: the loop's own kernels with the redo on a grid axis) and reads the objectives and status words
+back once; ``DEVICE_LOOP`` routes the callers.
 """
 from __future__ import annotations
 
@@ -89,12 +94,29 @@ def _redo_seeds(n: int, k: int, seed: int, nredo: int, init_indices=None) -> tor
 
 class Kmeans:
     """``faiss.Kmeans(d, k, niter=50, nredo=5, seed=1, verbose=False, gpu=False, spherical=False)`` surface: ``train(x)``,
-    ``centroids`` ([k, d] numpy, as faiss exposes them), ``assign(x) -> (dist2, labels)`` in place of ``index.search(x, 1)``."""
+    ``centroids`` ([k, d] numpy, as faiss exposes them), ``assign(x) -> (dist2, labels)`` in place of ``index.search(x, 1)``.
+
+    ``loop`` says who drives the Lloyd iterations.  ``"host"``: ``_iterate``, a dozen launches and two synchronisations per iteration.
+    ``"device"`` (N28): where ``ops.kmeans_loop_shape_ok`` takes the (subsampled) shape, every redo and iteration is enqueued at once
+    (``ops.kmeans_fit_loop``, empty clusters split from the table of ``split_draws``) and the objectives and status words are read
+    back once.  Per redo the arithmetic is ``_iterate``'s, so the centroids are the same bits - with one reservation: the per-redo
+    objective is the kernel's own fixed-order fp64 sum, not torch's reduction (they agree to about n * 2^-53 relative), so the redo
+    kept can differ where two DISTINCT objectives lie that close.  A fit in which any redo ended with a non-zero status (one split call
+    needed more draws than the table holds), or whose shape the rule refuses, runs the unchanged host loop on the same subsample and
+    seeds.  ``loop_workspace_bytes`` bounds the device loop's workspace: as many redos ride one launch as fit it, at least one (the
+    result does not depend on it; ``redo_group`` says how many did).  ``status`` [nredo] is the device loop's (None where it did not run), ``fallback`` whether the host loop fitted after it."""
 
     def __init__(self, d: int, k: int, niter: int = 50, nredo: int = 5, seed: int = 1, verbose: bool = False, gpu: bool = False,
-                 spherical: bool = False, max_points_per_centroid: int = 256):
+                 spherical: bool = False, max_points_per_centroid: int = 256, loop: str = "host", loop_workspace_bytes: Optional[int] = None):
         if spherical:
             raise NotImplementedError("spherical k-means is not used by the reference")
+        if loop not in ("host", "device"):
+            raise ValueError(f"Kmeans: loop = {loop!r}: expected 'host' or 'device'")
+        self.loop = loop
+        self.loop_workspace_bytes = loop_workspace_bytes   # None = LOOP_WORKSPACE_BYTES
+        self.status: Optional[np.ndarray] = None
+        self.fallback = False
+        self.redo_group: Optional[int] = None   # redos per launch of the last device loop
         self.d, self.k, self.niter, self.nredo, self.seed = d, k, niter, nredo, seed
         self.max_points_per_centroid = max_points_per_centroid
         self.centroids: Optional[np.ndarray] = None
@@ -164,8 +186,41 @@ class Kmeans:
                                            "take (1 <= d <= 1024, k >= 1, k * d < 2^31)")
         return ops.kmeans_assign_tiled, ops.kmeans_accumulate_tiled
 
-    def _fit(self, x: torch.Tensor, init_indices=None) -> float:
-        return self._iterate(x, init_indices, *self._kernels(x.shape[1]))
+    def _fit(self, x: torch.Tensor, init_indices=None, *, _draws: Optional[torch.Tensor] = None) -> float:
+        """The fit of the (subsampled) training points x [n, d].  ``_draws``: another table than ``split_draws()`` for ``loop="device"``
+        (testing aid: a table that is too short)."""
+        n, d = x.shape
+        self.status, self.fallback = None, False
+        if self.loop == "device" and ops.kmeans_loop_shape_ok(n, d, self.k):
+            if self._fit_device(x, init_indices, _draws):
+                return min(self.obj)
+            self.fallback = True
+        return self._iterate(x, init_indices, *self._kernels(d))
+
+    def _fit_device(self, x: torch.Tensor, init_indices, draws) -> bool:
+        """The device loop: fills ``centroids``, ``_centroids_dev``, ``obj`` and ``status``; False where a redo's status is non-zero."""
+        n, d = x.shape
+        init = _redo_seeds(n, self.k, self.seed, self.nredo, init_indices).to(torch.int32)
+        table = split_draws(device=x.device) if draws is None else draws
+        budget = LOOP_WORKSPACE_BYTES if self.loop_workspace_bytes is None else self.loop_workspace_bytes
+        group = self.nredo   # all redos in one pass where their workspace fits the budget, else as many as do, at least one
+        while group > 1 and ops.kmeans_loop_workspace_bytes(n, d, self.k, self.nredo, group) > budget:
+            group -= 1
+        self.redo_group = group
+        cent, obj, status = ops.kmeans_fit_loop(x, init, self.niter, table, redo_group=group)
+        host = torch.cat([obj, status.to(torch.float64)]).cpu().numpy()   # the one read-back
+        obj_h, status_h = host[: self.nredo], host[self.nredo:]
+        self.status = status_h.astype(np.int32)
+        if (status_h != 0).any():
+            return False
+        best, best_r = float("inf"), 0
+        for r in range(self.nredo):   # the loop's ``obj < best_obj``: the first redo with the strictly smallest objective
+            if float(obj_h[r]) < best:
+                best, best_r = float(obj_h[r]), r
+        self.obj = [float(o) for o in obj_h]
+        self._centroids_dev = cent[best_r].clone()
+        self.centroids = self._centroids_dev.cpu().numpy()
+        return True
 
     def _lloyd(self, x: torch.Tensor, init_indices=None) -> float:
         """The redos of Lloyd iterations on the (subsampled) training points x [n, d], on the resident pair only."""
@@ -254,6 +309,8 @@ class Kmeans:
 # on the host (the tests hold the two to each other), and kf_split_empty of csrc/kmeans_fit.hip is the same statement in the kernel.
 
 DEVICE_SPLIT = True          # _kmeans_maps_grouped builds KmeansBatch(split="device"); False forces the fall-back to the loop
+DEVICE_LOOP = True           # the dataset-wise fit and create_overclustering_maps build Kmeans(loop="device"); False = the host loop
+LOOP_WORKSPACE_BYTES = 1 << 30   # what the redos in flight of a device loop may take (200 MB each at n = 128 000, d = 50, k = 500)
 SPLIT_DRAWS = 4096           # ten times the most one _split_empty call was seen to draw at the evaluator's shapes (393, at k = 21)
 _split_tables: dict = {}
 
@@ -400,8 +457,8 @@ def nearest_index_table(g: int, R: int, device=None):
 # cluster_features / proto_clustering  (clustering.py:20-117)
 # ------------------------------------------------------------------------------------------------
 
-def _kmeans_maps(points: torch.Tensor, num_clusters: int) -> torch.Tensor:
-    km = Kmeans(points.shape[1], num_clusters, niter=50, nredo=5, seed=1)
+def _kmeans_maps(points: torch.Tensor, num_clusters: int, loop: str = "host") -> torch.Tensor:
+    km = Kmeans(points.shape[1], num_clusters, niter=50, nredo=5, seed=1, loop=loop)
     km.train(points)
     return km.assign(points)[1]
 
@@ -424,7 +481,7 @@ def _kmeans_maps_grouped(points: torch.Tensor, ks) -> torch.Tensor:
                 return labels
             out[torch.as_tensor(idx, device=points.device)] = labels
         else:
-            for b in idx:
+            for b in idx:   # (on the host loop: the route the N13 / N18 tests count; the large dataset-wise fit is the device loop's)
                 out[b] = _kmeans_maps(points[b], k)
     return out
 
@@ -456,7 +513,7 @@ def cluster_features(features, num_clusters, feature_resolution, input_resolutio
         out = _kmeans_maps_grouped(up.view(bs, fs * R * R, dim), ks).view(bs, fs, R, R)
     elif evaluation_protocol == "dataset-wise":
         k = _annotation_counts(annotations, 1, features.device)[0] if annotations is not None else num_clusters
-        out = _kmeans_maps(up.reshape(bs * fs * R * R, dim), k).view(bs, fs, R, R)
+        out = _kmeans_maps(up.reshape(bs * fs * R * R, dim), k, "device" if DEVICE_LOOP else "host").view(bs, fs, R, R)
     else:
         raise ValueError(f"unknown evaluation protocol {evaluation_protocol!r}")
     return out.to(torch.int16)

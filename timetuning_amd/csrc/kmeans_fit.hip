@@ -39,62 +39,7 @@ static int kf_fit_group(long long n, int d, int k) {
   return (int)(g > blocks ? blocks : g);
 }
 
-// ---- faiss' split of the empty clusters, clustering.Kmeans._split_empty statement for statement, run by ONE wave on a workgroup's LDS
-// centroids cs [k][d] and counts cnt [k] after the update (the host restatement is clustering.split_empty_from_table).  draws holds the
-// first n_draws values of numpy.random.RandomState(1234).random_sample(): the host re-creates that generator at every call, so every
-// call reads a prefix of one sequence and the index starts at 0 here.  Lane 0 decides - it alone reads and writes the counts and the
-// table - and hands each decision to the wave by a shuffle; lane j < d <= 64 owns column j of every row, so no lane reads what another
-// wrote.  Trip counts: k clusters, at most 64 k + 1 tries each and at most n_draws draws in all.  False: a draw beyond the table was
-// needed (cs and cnt are then part-way through the call and must not be used).
-__device__ __forceinline__ bool kf_split_empty(float* cs, int* cnt, int n, int d, int k, const double* __restrict__ draws, int n_draws,
-                                               int lane) {
-  constexpr int SKIP = -1, STOP = -2, SHORT = -3;
-  const float s = (lane & 1) ? 1.0f - 1.0f / 1024.0f : 1.0f + 1.0f / 1024.0f;   // both, and 2 - s, are exact in fp32
-  int next = 0;   // lane 0's index of the next draw
-  for (int ci = 0; ci < k; ++ci) {
-    int dec = SKIP;   // the donor cj >= 0, or one of the three above
-    if (lane == 0 && cnt[ci] == 0) {
-      int most = cnt[0], arg = 0;   // the first arg-max (numpy.argmax)
-      for (int j = 1; j < k; ++j)
-        if (cnt[j] > most) most = cnt[j], arg = j;
-      if (n <= k || most <= 1) {
-        dec = STOP;
-      } else {
-        const double span = (double)(n - k);
-        int cj = 0, tries = 0;
-        for (;;) {
-          if (next >= n_draws) {
-            dec = SHORT;
-            break;
-          }
-          if (draws[next++] < (double)(cnt[cj] - 1) / span) {
-            dec = cj;
-            break;
-          }
-          cj = cj + 1 == k ? 0 : cj + 1;
-          if (++tries > 64 * k) {   // vanishing acceptance: the largest cluster
-            dec = arg;
-            break;
-          }
-        }
-      }
-    }
-    dec = __shfl(dec, 0, 64);
-    if (dec == STOP) break;
-    if (dec == SHORT) return false;
-    if (dec == SKIP) continue;
-    if (lane < d) {   // single fp32 products, the new row from the OLD donor row
-      const float old = cs[dec * d + lane];
-      cs[ci * d + lane] = old * s;
-      cs[dec * d + lane] = old * (2.0f - s);
-    }
-    if (lane == 0) {
-      cnt[ci] = cnt[dec] / 2;
-      cnt[dec] -= cnt[ci];
-    }
-  }
-  return true;
-}
+// (faiss' split of the empty clusters, kf_split_empty, is kmeans.hpp's: the device loop of kmeans.hip runs the same statement.)
 
 // ---- the fused fit.  grid (nredo, B), KF_THREADS threads.  Per iteration:
 //   assignment    one thread per point (stride KF_THREADS); the row goes from global memory (L2 at these sizes) into registers, the

@@ -1307,6 +1307,56 @@ def kmeans_fit_batched(x, init, niter: int, split_draws=None):
     return cent, obj, status
 
 
+def kmeans_loop_shape_ok(n: int, d: int, k: int) -> bool:
+    """Whether ``kmeans_fit_loop`` takes a fit of n points, d columns and k clusters (tt_kmeans_loop_shape_ok)."""
+    return bool(_lib.load().tt_kmeans_loop_shape_ok(int(n), int(d), int(k)))
+
+
+def kmeans_loop_workspace_bytes(n: int, d: int, k: int, nredo: int, redo_group: int = 0) -> int:
+    """The workspace of ``kmeans_fit_loop`` with ``redo_group`` redos in flight (0 = all ``nredo``); 0 for a refused shape."""
+    return int(_lib.load().tt_kmeans_loop_workspace_bytes(int(n), int(d), int(k), int(nredo), int(redo_group)))
+
+
+def kmeans_fit_loop(x, init, niter: int, draws=None, tile_k: int = 0, redo_group: int = 0, return_last: bool = False):
+    """Every redo and Lloyd iteration of ONE fit enqueued on the current stream: x [n, d], init int32 [nredo, k] on the HOST (rows of x
+    that seed redo r) -> centroids [nredo, k, d], obj fp64 [nredo], status int32 [nredo] (0, or the 1-based iteration at which the redo
+    ended: its centroids and objective are then unspecified).  Nothing is read back here.  ``draws``: a float64 table on x's device
+    (``clustering.split_draws``) from which empty clusters are split as ``Kmeans._split_empty`` does; None = no split, the first empty
+    cluster ends the redo.  ``tile_k``: 0 = the resident kernels where they take (d, k), the tiled ones at their default tile otherwise;
+    a value asks for the tiled ones.  ``redo_group``: redos of one launch (0 = all; fewer = a smaller workspace, the same result).
+    ``return_last`` (testing aid, all redos in one pass only): also the last iteration's labels int32 [nredo, n] and dist2 [nredo, n]."""
+    lib = _lib.load()
+    _chk(x, "x")
+    if draws is not None:
+        _chk(draws, "draws", torch.float64)
+        if draws.dim() != 1 or draws.device != x.device:
+            raise ValueError(f"draws: expected a 1-d table on {x.device}, got {tuple(draws.shape)} on {draws.device}")
+    n, d = x.shape
+    init_h = torch.as_tensor(init, dtype=torch.int32).cpu().contiguous()
+    if init_h.dim() != 2:
+        raise ValueError(f"init: expected [nredo, k], got {tuple(init_h.shape)}")
+    nredo, k = init_h.shape
+    if return_last and 0 < int(redo_group) < nredo:
+        raise ValueError(f"return_last: the workspace holds the last pass only (redo_group = {redo_group} of {nredo} redos)")
+    init_d = init_h.to(x.device)
+    cent = torch.empty((nredo, k, d), dtype=f32, device=x.device)
+    obj = torch.empty(nredo, dtype=torch.float64, device=x.device)
+    status = torch.empty(nredo, dtype=torch.int32, device=x.device)
+    nb = lib.tt_kmeans_loop_workspace_bytes(n, d, k, nredo, int(redo_group))
+    ws = _ws(nb, x.device)
+    _lib.check(lib.tt_kmeans_fit_loop(_p(x), _p(init_d), _p(init_h), _p(cent), _p(obj), _p(status), n, d, k, nredo, int(niter), int(tile_k),
+                                      int(redo_group), _p(draws), 0 if draws is None else draws.numel(), _p(ws), nb, _stream()),
+               "tt_kmeans_fit_loop")
+    if not return_last:
+        return cent, obj, status
+    lab_off, d2_off = C.c_size_t(), C.c_size_t()   # where the library keeps them in its workspace
+    if not lib.tt_kmeans_loop_last_offsets(n, d, k, nredo, int(redo_group), C.addressof(lab_off), C.addressof(d2_off)):
+        raise _lib.HipLibraryError("tt_kmeans_loop_last_offsets refused the shape tt_kmeans_fit_loop took")
+    size = 4 * nredo * n
+    return (cent, obj, status, ws[lab_off.value: lab_off.value + size].view(torch.int32).view(nredo, n).clone(),
+            ws[d2_off.value: d2_off.value + size].view(f32).view(nredo, n).clone())
+
+
 def kmeans_assign_batched(x, centroids, return_dist=False):
     """x [B, N, d], centroids [B, k, d] -> labels int32 [B, N] (+ squared distances): ``kmeans_assign`` per problem, in one launch."""
     lib = _lib.load()
