@@ -1290,6 +1290,62 @@ int tt_png_decode_host_wave(const uint8_t* streams, long long stream_bytes, cons
                             int n_files, uint8_t* out, long long out_bytes, void* workspace, size_t workspace_bytes, int32_t* status,
                             tt_stream_t stream);
 
+/* ---- N29: label maps written as palette PNGs, deflated on the device - what the reference's my_utils.imwrite_indexed ("Save indexed
+   png for DAVIS", my_utils.py:72-79: Image.fromarray + putpalette + save) does for one map, for a batch of maps that never leave the
+   device as pixels.  The DEVICE half (png_encode.hip) filters every row with Up and deflates every band of rows ("chunk") of every map
+   in a workgroup of its own into one fixed-Huffman block closed by an empty stored block, so that a file's stream is the plain
+   concatenation of its chunks; a scan and a gather make ONE compact buffer of all streams.  The HOST half (png_scan.cpp) wraps a stream
+   into a file: signature, IHDR, PLTE, ONE IDAT, IEND.  The byte format, its bounds and the table rules: csrc/png_deflate.hpp, DESIGN.md
+   N29.  Pixel-equal to Pillow's file, not byte-equal: runs at distance 1 in the fixed code only, about four times Pillow's size.
+   8-bit maps uint8 [H, W], 1 <= H, W <= 32767.  Every refusal is TT_PNG_EARGUMENT. */
+/* One row per map.  data: the map's first byte (device memory for tt_png_encode_batch, host memory for tt_png_encode_host), rows
+   `pitch` >= W bytes apart.  first_chunk, n_chunks: its rows of the chunk table.  out_off: bytes into the slots of the workspace of its
+   first chunk's slot, which is also where its stream would begin in the output were every chunk at its capacity. */
+typedef struct {
+  const uint8_t* data;
+  int64_t H, W, pitch;
+  int64_t first_chunk, n_chunks, out_off;
+  int64_t reserved;
+} tt_png_map;
+/* One row per chunk: rows row0 .. row0 + rows - 1 of map `map`, deflated into the slot at slot_off of the workspace. */
+typedef struct {
+  int64_t map, row0, rows, slot_off;
+} tt_png_chunk;
+/* One row per map, written by the device: where its stream lies in the output, its length, and the Adler-32 of its filtered bytes. */
+typedef struct {
+  int64_t offset, length, adler;
+  int64_t reserved;
+} tt_png_result;
+/* Builds the tables from data, H, W and pitch of every map: fills first_chunk, n_chunks and out_off, and - with `chunks`, of
+   chunk_capacity rows - the chunk table.  *n_chunks: the rows of the chunk table; *out_capacity: the bytes the output must hold (every
+   chunk at its capacity of (9 n + 7) / 8 + 7 bytes for n filtered bytes, rounded up to 4).  Call it without `chunks` for the counts.
+   Pure host function. */
+int tt_png_encode_plan(tt_png_map* maps, int n_maps, tt_png_chunk* chunks, long long chunk_capacity, long long* n_chunks, long long* out_capacity);
+/* Bytes of workspace of a batch: one slot per chunk, then four int32 per chunk (stream bytes, Adler a, b, filtered bytes), then the
+   chunks' offsets in the output; 0: a row is not a map.  Pure host function. */
+size_t tt_png_encode_batch_workspace_bytes(const tt_png_map* maps, int n_maps);
+/* Three launches: one workgroup per chunk (filter, runs, bits), one workgroup for the scan of the chunk lengths and the files' Adler-32,
+   one workgroup per chunk for the gather.  The HOST tables are checked in full against the plan, out_bytes and workspace_bytes before
+   anything is launched (TT_PNG_EARGUMENT, no launch, nothing written); the kernels read maps_dev and chunks_dev.  out: device bytes, the
+   streams one behind the other in map order (no zlib header, no Adler-32 trailer); results_dev: device tt_png_result [n_maps].  The
+   workspace need not be cleared between calls.  workspace 16-byte, tables and results 8-byte aligned.  No workgroup waits for another;
+   allocates nothing, synchronises nothing. */
+int tt_png_encode_batch(const tt_png_map* maps_host, const tt_png_map* maps_dev, int n_maps, const tt_png_chunk* chunks_host,
+                        const tt_png_chunk* chunks_dev, long long n_chunks, uint8_t* out, long long out_bytes, tt_png_result* results_dev,
+                        void* workspace, size_t workspace_bytes, tt_stream_t stream);
+/* The same arguments as host pointers (maps_dev, chunks_dev and `stream` are not looked at): the sequential loop over the same
+   csrc/png_deflate.hpp steps, bit-equal to the kernels.  No GPU call. */
+int tt_png_encode_host(const tt_png_map* maps_host, const tt_png_map* maps_dev, int n_maps, const tt_png_chunk* chunks_host,
+                       const tt_png_chunk* chunks_dev, long long n_chunks, uint8_t* out, long long out_bytes, tt_png_result* results,
+                       void* workspace, size_t workspace_bytes, tt_stream_t stream);
+/* Bytes of the file around a stream of stream_len bytes with a palette of palette_entries colours (0: a gray file). */
+size_t tt_png_file_bytes(size_t stream_len, int palette_entries);
+/* The finished file around a device-made stream: signature, IHDR (W, H, depth 8, colour type 3 with a palette, 0 without), PLTE
+   (palette: 3 palette_entries bytes, 1..256 entries, or null and 0), ONE IDAT (78 01, the stream, `adler` big-endian), IEND, each with
+   its CRC-32.  TT_PNG_EARGUMENT: a null pointer, a side outside 1..32767, more than 256 entries, out_capacity below tt_png_file_bytes. */
+int tt_png_write_file(const uint8_t* stream, size_t stream_len, uint32_t adler, int H, int W, const uint8_t* palette, int palette_entries,
+                      uint8_t* out, size_t out_capacity, size_t* out_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,12 @@ SIGNATURES = {
     "tt_png_decode_batch": (c_i, [c_vp, c_ll, c_vp, c_vp, c_i, c_vp, c_ll, c_vp, c_sz, c_vp, c_vp]),
     "tt_png_decode_host": (c_i, [c_vp, c_ll, c_vp, c_vp, c_i, c_vp, c_ll, c_vp, c_sz, c_vp, c_vp]),
     "tt_png_decode_host_wave": (c_i, [c_vp, c_ll, c_vp, c_vp, c_i, c_vp, c_ll, c_vp, c_sz, c_vp, c_vp]),
+    "tt_png_encode_plan": (c_i, [c_vp, c_i, c_vp, c_ll, C.POINTER(c_ll), C.POINTER(c_ll)]),
+    "tt_png_encode_batch_workspace_bytes": (c_sz, [c_vp, c_i]),
+    "tt_png_encode_batch": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_sz, c_vp]),
+    "tt_png_encode_host": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_sz, c_vp]),
+    "tt_png_file_bytes": (c_sz, [c_sz, c_i]),
+    "tt_png_write_file": (c_i, [c_vp, c_sz, C.c_uint32, c_i, c_i, c_vp, c_i, c_vp, c_sz, C.POINTER(c_sz)]),
 }
 
 _lib = None

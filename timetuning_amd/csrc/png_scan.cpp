@@ -1,13 +1,16 @@
 // N26, host half: the chunk layer of an annotation PNG (tt_png_probe, tt_png_prepare) and the emulation of png_decode.hip
 // (tt_png_decode_host: the sequential loop over the steps of png_inflate.hpp).  Plain C++: no HIP include, no state, no allocation,
 // re-entrant; every read is checked against `len`, every write against the caller's capacity.  The one exception is the testing aid
-// tt_png_decode_host_wave at the end, which starts 64 threads.
+// tt_png_decode_host_wave, which starts 64 threads.
+// N29, host half, at the end: the file around a device-made stream (tt_png_file_bytes, tt_png_write_file), the tables of a batch
+// (tt_png_encode_plan) and the emulation of png_encode.hip (tt_png_encode_host: the sequential loop over the steps of png_deflate.hpp).
 #include <condition_variable>
 #include <cstring>
 #include <mutex>
 #include <thread>
 #include <vector>
 
+#include "png_deflate.hpp"
 #include "png_inflate.hpp"
 
 namespace {
@@ -248,5 +251,156 @@ extern "C" int tt_png_decode_host_wave(const uint8_t* streams, long long stream_
   for (int lane = 1; lane < pz::kLanes; ++lane) lanes.emplace_back(lane_main, lane);
   lane_main(0);
   for (std::thread& t : lanes) t.join();
+  return TT_OK;
+}
+
+// ---- N29: writing
+
+namespace {
+
+void put_be32(uint8_t* p, uint32_t v) {
+  p[0] = (uint8_t)(v >> 24);
+  p[1] = (uint8_t)(v >> 16);
+  p[2] = (uint8_t)(v >> 8);
+  p[3] = (uint8_t)v;
+}
+
+// Closes the chunk whose type starts at out[type_at] and whose data end at out[end]: length in front, CRC-32 behind; the next free byte.
+size_t close_chunk(uint8_t* out, size_t type_at, size_t end) {
+  put_be32(out + type_at - 4, (uint32_t)(end - type_at - 4));
+  put_be32(out + end, crc32(out + type_at, end - type_at));
+  return end + 4;
+}
+
+}  // namespace
+
+extern "C" size_t tt_png_file_bytes(size_t stream_len, int palette_entries) {
+  return 8 + (12 + 13) + (palette_entries > 0 ? 12 + 3 * (size_t)palette_entries : 0) + (12 + 2 + stream_len + 4) + 12;
+}
+
+extern "C" int tt_png_write_file(const uint8_t* stream, size_t stream_len, uint32_t adler, int H, int W, const uint8_t* palette, int palette_entries,
+                                 uint8_t* out, size_t out_capacity, size_t* out_len) {
+  if (!stream || !out || !out_len || H < 1 || W < 1 || H > pe::kMaxDim || W > pe::kMaxDim) return TT_PNG_EARGUMENT;
+  if (palette_entries < 0 || palette_entries > 256 || (palette_entries > 0) != (palette != nullptr)) return TT_PNG_EARGUMENT;
+  if (stream_len > 0x7ffffff0u || out_capacity < tt_png_file_bytes(stream_len, palette_entries)) return TT_PNG_EARGUMENT;
+  std::memcpy(out, kSignature, 8);
+  size_t at = 8 + 4;
+  std::memcpy(out + at, "IHDR", 4);
+  put_be32(out + at + 4, (uint32_t)W);
+  put_be32(out + at + 8, (uint32_t)H);
+  out[at + 12] = 8;
+  out[at + 13] = palette_entries > 0 ? 3 : 0;
+  out[at + 14] = out[at + 15] = out[at + 16] = 0;
+  at = close_chunk(out, at, at + 17) + 4;
+  if (palette_entries > 0) {
+    std::memcpy(out + at, "PLTE", 4);
+    std::memcpy(out + at + 4, palette, 3 * (size_t)palette_entries);
+    at = close_chunk(out, at, at + 4 + 3 * (size_t)palette_entries) + 4;
+  }
+  std::memcpy(out + at, "IDAT", 4);
+  out[at + 4] = 0x78;
+  out[at + 5] = 0x01;
+  std::memcpy(out + at + 6, stream, stream_len);
+  put_be32(out + at + 6 + stream_len, adler);
+  at = close_chunk(out, at, at + 6 + stream_len + 4) + 4;
+  std::memcpy(out + at, "IEND", 4);
+  at = close_chunk(out, at, at + 4);
+  *out_len = at;
+  return 0;
+}
+
+extern "C" int tt_png_encode_plan(tt_png_map* maps, int n_maps, tt_png_chunk* chunks, long long chunk_capacity, long long* n_chunks,
+                                  long long* out_capacity) {
+  if (!n_chunks || !out_capacity) return TT_PNG_EARGUMENT;
+  pe::Layout l;
+  const int rc = pe::plan(maps, n_maps, chunks, chunk_capacity, &l);
+  if (rc) return rc;
+  *n_chunks = l.n_chunks;
+  *out_capacity = l.slot_bytes;
+  return 0;
+}
+
+extern "C" size_t tt_png_encode_batch_workspace_bytes(const tt_png_map* maps, int n_maps) {
+  if (!maps || n_maps < 1 || n_maps > 65535) return 0;
+  pe::Layout l{0, 0};
+  for (int i = 0; i < n_maps; ++i) {
+    if (!pe::map_ok(maps[i])) return 0;
+    l.n_chunks += pe::chunk_count(maps[i].H, maps[i].W);
+    l.slot_bytes += pe::file_capacity(maps[i].H, maps[i].W);
+    if (l.slot_bytes > pe::kMaxBatchBytes) return 0;
+  }
+  return (size_t)pe::workspace_bytes(l);
+}
+
+extern "C" int tt_png_encode_host(const tt_png_map* maps, const tt_png_map*, int n_maps, const tt_png_chunk* chunks, const tt_png_chunk*,
+                                  long long n_chunks, uint8_t* out, long long out_bytes, tt_png_result* results, void* workspace,
+                                  size_t workspace_bytes, tt_stream_t) {
+  if (!maps || !chunks || !out || !results || !workspace) return TT_PNG_EARGUMENT;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15u) return TT_PNG_EARGUMENT;
+  pe::Layout l;
+  const char* why = "";
+  if (pe::validate(maps, n_maps, chunks, n_chunks, out_bytes, workspace_bytes, &l, &why) != 0) return TT_PNG_EARGUMENT;
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  int32_t* meta = reinterpret_cast<int32_t*>(ws + pe::meta_offset(l));
+  uint32_t* chunk_off = reinterpret_cast<uint32_t*>(ws + pe::offsets_offset(l));
+  // the chunks: what one workgroup does, with one thread that owns every position
+  for (long long c = 0; c < l.n_chunks; ++c) {
+    const tt_png_chunk& ck = chunks[c];
+    const tt_png_map& m = maps[ck.map];
+    const int W = (int)m.W, row0 = (int)ck.row0, n = (int)ck.rows * (W + 1);
+    auto F = [&](int p) { return pe::filtered(m.data, m.pitch, W, row0, p); };
+    uint32_t token_bits = 0;
+    pe::walk(F, 0, n, 0, n, [&](pe::Code code) { token_bits += (uint32_t)code.count; });
+    const int len = pe::chunk_bytes(token_bits), words = (len + 3) / 4;
+    if (words * 4 > pe::slot_stride(n)) return TT_PNG_EARGUMENT;   // the capacity rule, checked where the kernel relies on it
+    uint32_t* slot = reinterpret_cast<uint32_t*>(ws + ck.slot_off);
+    for (int k = 0; k < words; ++k) slot[k] = 0u;
+    auto or32 = [&](uint32_t word, uint32_t v) {
+      if (v != 0u && word < (uint32_t)words) slot[word] |= v;
+    };
+    uint32_t at = pe::kHeadBits;
+    pe::walk(F, 0, n, 0, n, [&](pe::Code code) {
+      pe::put_bits(or32, at, code.bits, code.count);
+      at += (uint32_t)code.count;
+    });
+    pe::put_frame(or32, token_bits, c == m.first_chunk + m.n_chunks - 1);
+    uint64_t sa = 0, sb = 0;
+    for (int p = 0; p < n; ++p) {
+      const uint32_t d = F(p);
+      sa += d;
+      sb += (uint64_t)(n - p) * d;
+    }
+    int32_t* o = meta + c * pe::kMetaWords;
+    o[0] = len;
+    o[1] = (int32_t)(sa % pe::kAdlerMod);
+    o[2] = (int32_t)(sb % pe::kAdlerMod);
+    o[3] = n;
+  }
+  // the scan
+  uint32_t total = 0;
+  for (long long c = 0; c < l.n_chunks; ++c) {
+    chunk_off[c] = total;
+    total += (uint32_t)meta[c * pe::kMetaWords];
+  }
+  for (int f = 0; f < n_maps; ++f) {
+    const tt_png_map& m = maps[f];
+    uint32_t A = 1, B = 0;
+    int64_t length = 0;
+    for (long long c = m.first_chunk; c < m.first_chunk + m.n_chunks; ++c) {
+      const int32_t* o = meta + c * pe::kMetaWords;
+      length += o[0];
+      pe::adler_append(A, B, (uint32_t)o[1], (uint32_t)o[2], (uint32_t)o[3]);
+    }
+    results[f].offset = chunk_off[m.first_chunk];
+    results[f].length = length;
+    results[f].adler = (int64_t)((B << 16) | A);
+    results[f].reserved = 0;
+  }
+  // the gather
+  for (long long c = 0; c < l.n_chunks; ++c) {
+    const int len = meta[c * pe::kMetaWords];
+    if ((long long)chunk_off[c] + len > out_bytes) return TT_PNG_EARGUMENT;
+    std::memcpy(out + chunk_off[c], ws + chunks[c].slot_off, (size_t)len);
+  }
   return TT_OK;
 }

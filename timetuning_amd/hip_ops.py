@@ -3208,3 +3208,205 @@ def decode_png_batch(files: Sequence[bytes], device=None, threads: int = 8):
     """Annotation PNG files -> uint8 [H, W] GPU label maps, bit-equal to ``np.asarray(Image.open(...))``; views of one flat buffer in file
     order.  Unsupported files raise PngUnsupported (no CPU fallback here), broken ones ValueError."""
     return png_decode(png_prepare_batch(files, threads, True), device)[0]
+
+
+# ---- N29: label maps written as palette PNGs.  The device half (tt_png_encode_batch: Up filter, run tokens, fixed-Huffman bits, one
+# workgroup per band of rows, then a scan and a gather) leaves ONE compact buffer of streams; the host half (tt_png_write_file: signature,
+# IHDR, PLTE, one IDAT, IEND - a pure host function that ctypes runs without the GIL) wraps them into files in the thread pool the decode
+# batches use.  The byte format: csrc/png_deflate.hpp.
+_PNG_MAP = np.dtype([("data", "<u8"), ("H", "<i8"), ("W", "<i8"), ("pitch", "<i8"), ("first_chunk", "<i8"), ("n_chunks", "<i8"),
+                     ("out_off", "<i8"), ("reserved", "<i8")])                                                          # tt_png_map
+_PNG_CHUNK = np.dtype([("map", "<i8"), ("row0", "<i8"), ("rows", "<i8"), ("slot_off", "<i8")])                        # tt_png_chunk
+_PNG_RESULT = np.dtype([("offset", "<i8"), ("length", "<i8"), ("adler", "<i8"), ("reserved", "<i8")])                 # tt_png_result
+
+
+class PngEncodePlan(_FileBatch):
+    """The tables of a batch of maps to encode: ONE (pinned) buffer ``meta`` with its parts 'maps' (tt_png_map rows) and 'chunks'
+    (tt_png_chunk rows); ``out_bytes``: the capacity the output needs, ``ws_bytes``: the workspace.  ``maps`` keeps the tensors or arrays
+    the rows point into."""
+
+    def __init__(self, maps, meta, layout, n_chunks, out_bytes, ws_bytes):
+        self.maps, self.meta, self.layout, self.n_chunks, self.out_bytes, self.ws_bytes = maps, meta, layout, n_chunks, out_bytes, ws_bytes
+
+    @property
+    def table(self):
+        return self.part("maps").view(_PNG_MAP)
+
+    @property
+    def chunks(self):
+        return self.part("chunks").view(_PNG_CHUNK)
+
+
+def _png_map_list(maps, who: str) -> list:
+    """One [k, H, W] / [H, W] tensor or array, or a sequence of [H, W] ones -> a list of 2-D maps (views)."""
+    if isinstance(maps, (torch.Tensor, np.ndarray)):
+        if maps.ndim == 2:
+            return [maps]
+        if maps.ndim != 3:
+            raise ValueError(f"{who}: expected [H, W] maps or one [k, H, W] stack, got {tuple(maps.shape)}")
+        maps = [maps[i] for i in range(maps.shape[0])]
+    maps = list(maps)
+    if not maps:
+        raise ValueError(f"{who}: no maps")
+    for i, m in enumerate(maps):
+        if not isinstance(m, (torch.Tensor, np.ndarray)) or m.ndim != 2:
+            raise ValueError(f"{who}: map {i} is not a 2-D tensor or array")
+        if m.shape[0] < 1 or m.shape[1] < 1 or m.shape[0] > 32767 or m.shape[1] > 32767:
+            raise ValueError(f"{who}: map {i} is {m.shape[0]} x {m.shape[1]}: both sides must be in 1..32767")
+    return maps
+
+
+def _png_rows(m):
+    """A uint8 [H, W] map whose rows are contiguous and at least W bytes apart (a view where it is one already), and that pitch."""
+    if isinstance(m, torch.Tensor):
+        s0, s1 = m.stride()
+        if (s1 != 1 and m.shape[1] > 1) or (s0 < m.shape[1] and m.shape[0] > 1):
+            m = m.contiguous()
+        return m, (int(m.stride(0)) if m.shape[0] > 1 else int(m.shape[1]))
+    s0, s1 = m.strides
+    if (s1 != 1 and m.shape[1] > 1) or (s0 < m.shape[1] and m.shape[0] > 1):
+        m = np.ascontiguousarray(m)
+    return m, (int(m.strides[0]) if m.shape[0] > 1 else int(m.shape[1]))
+
+
+def _png_uint8_maps(maps: list, who: str) -> list:
+    """Integer maps as uint8, by a CHECKED conversion: a value outside 0..255 raises ValueError naming the map (one read-back of the
+    extrema of the maps that are not uint8 already)."""
+    maps = list(maps)
+    wide = []            # the maps whose values have to be looked at: integer, not uint8, not bool
+    for i, m in enumerate(maps):
+        dt, tensor = m.dtype, isinstance(m, torch.Tensor)
+        if dt in (torch.uint8, np.dtype(np.uint8)):
+            continue
+        if (dt.is_floating_point or dt.is_complex) if tensor else dt.kind not in "iub":
+            raise TypeError(f"{who}: map {i} is {dt}: label maps must be integer")
+        if dt not in (torch.bool, np.dtype(bool)):
+            wide.append(i)
+    on_gpu = [i for i in wide if isinstance(maps[i], torch.Tensor)]
+    extrema = {i: (int(maps[i].min()), int(maps[i].max())) for i in wide if i not in on_gpu}
+    if on_gpu:
+        host = torch.stack([torch.stack([maps[i].min(), maps[i].max()]).long() for i in on_gpu]).cpu().tolist()
+        extrema.update(zip(on_gpu, host))
+    for i in wide:
+        lo, hi = extrema[i]
+        if lo < 0 or hi > 255:
+            raise ValueError(f"{who}: map {i} holds values in {lo}..{hi}: an 8-bit PNG takes 0..255")
+    return [m if m.dtype in (torch.uint8, np.dtype(np.uint8)) else (m.to(torch.uint8) if isinstance(m, torch.Tensor) else m.astype(np.uint8)) for m in maps]
+
+
+def png_encode_plan(maps, pin: bool = True) -> PngEncodePlan:
+    """The tables of tt_png_encode_plan for uint8 [H, W] maps (GPU tensors for ``png_encode``, NumPy arrays for ``png_encode_host``; a
+    pitched view - rows of a wider tensor - is taken as it is), in one (pinned) buffer."""
+    lib = _lib.load()
+    maps = _png_map_list(maps, "png_encode_plan")
+    rows = [_png_rows(m) for m in maps]
+    n = len(rows)
+    table = np.zeros(n, _PNG_MAP)
+    for i, (m, pitch) in enumerate(rows):
+        if m.dtype not in (torch.uint8, np.dtype(np.uint8)):
+            raise TypeError(f"png_encode_plan: map {i} is {m.dtype}, expected uint8")
+        table[i]["data"] = m.data_ptr() if isinstance(m, torch.Tensor) else m.ctypes.data
+        table[i]["H"], table[i]["W"], table[i]["pitch"] = m.shape[0], m.shape[1], pitch
+    n_chunks, cap = C.c_longlong(), C.c_longlong()
+    rc = lib.tt_png_encode_plan(table.ctypes.data, n, None, 0, C.byref(n_chunks), C.byref(cap))
+    if rc != 0:
+        raise ValueError(f"png_encode_plan: the maps were refused (status {rc}: {PNG_MALFORMED.get(rc, 'unknown')})")
+    layout, size = _layout([("maps", n * _PNG_MAP.itemsize), ("chunks", n_chunks.value * _PNG_CHUNK.itemsize)])
+    meta = torch.zeros(size, dtype=torch.uint8, pin_memory=pin)
+    host = meta.numpy()
+    host[:layout["maps"][1]] = table.view(np.uint8)
+    rc = lib.tt_png_encode_plan(meta.data_ptr(), n, meta.data_ptr() + layout["chunks"][0], n_chunks.value, C.byref(n_chunks), C.byref(cap))
+    assert rc == 0
+    ws_bytes = int(lib.tt_png_encode_batch_workspace_bytes(meta.data_ptr(), n))
+    return PngEncodePlan([m for m, _ in rows], meta, layout, int(n_chunks.value), int(cap.value), ws_bytes)
+
+
+def _png_streams(flat: np.ndarray, results: np.ndarray):
+    return [flat[int(r["offset"]):int(r["offset"]) + int(r["length"])] for r in results], results["adler"].astype(np.uint32)
+
+
+def png_encode_host(maps):
+    """The host emulation of the device encoder (tt_png_encode_host: the sequential loop over the kernels' steps) on NumPy maps, for tests
+    and tools: (the streams as uint8 views of one flat array in map order, their Adler-32 uint32 [n])."""
+    lib = _lib.load()
+    maps = _png_uint8_maps([np.asarray(m) for m in _png_map_list(maps, "png_encode_host")], "png_encode_host")
+    plan = png_encode_plan(maps, pin=False)
+    n = len(plan.maps)
+    table, chunks = plan.table, plan.chunks
+    out, results = np.zeros(max(plan.out_bytes, 1), np.uint8), np.zeros(n, _PNG_RESULT)
+    ws = np.zeros(plan.ws_bytes // 16 + 2, np.dtype("<u8, <u8"))
+    at = ws.ctypes.data + (-ws.ctypes.data) % 16
+    rc = lib.tt_png_encode_host(table.ctypes.data, None, n, chunks.ctypes.data, None, plan.n_chunks, out.ctypes.data, plan.out_bytes,
+                                results.ctypes.data, at, plan.ws_bytes, None)
+    if rc != 0:
+        raise ValueError(f"png_encode_host: refused (status {rc})")
+    return _png_streams(out, results)
+
+
+def png_encode(maps, device=None):
+    """The device half: uint8 [H, W] GPU maps (or one [k, H, W] stack; mixed sizes and pitched views in one call) -> (the deflate streams
+    as uint8 NumPy views of one flat array in map order, their Adler-32 uint32 [n]).  One host-to-device copy of the tables, the three
+    launches of tt_png_encode_batch on the current stream, and exactly TWO read-backs: the result table (32 bytes per map), then exactly
+    the streams' bytes - the maps themselves never cross the bus."""
+    lib = _lib.load()
+    maps = _png_map_list(maps, "png_encode")
+    for i, m in enumerate(maps):
+        if not isinstance(m, torch.Tensor) or not m.is_cuda:
+            raise _lib.HipLibraryError(f"png_encode: map {i}: expected a tensor in GPU memory (the HIP path has no CPU fallback)")
+    dev = _need_gpu("png_encode", maps[0].device if device is None else device)
+    if any(m.device != dev for m in maps):
+        raise ValueError(f"png_encode: every map must be on {dev}")
+    plan = png_encode_plan(_png_uint8_maps(maps, "png_encode"))
+    n = len(plan.maps)
+    with torch.cuda.device(dev):
+        meta = plan.meta.to(dev, non_blocking=True)
+        out = torch.empty(max(plan.out_bytes, 16), dtype=torch.uint8, device=dev)
+        results = torch.empty(n * _PNG_RESULT.itemsize, dtype=torch.uint8, device=dev)
+        ws = _ws(plan.ws_bytes, dev)
+        rc = lib.tt_png_encode_batch(plan.table.ctypes.data, meta.data_ptr() + plan.layout["maps"][0], n, plan.chunks.ctypes.data,
+                                     meta.data_ptr() + plan.layout["chunks"][0], plan.n_chunks, _p(out), out.numel(), _p(results), _p(ws),
+                                     ws.numel(), _stream())
+        _lib.check(rc, "tt_png_encode_batch")
+        table = results.cpu().numpy().view(_PNG_RESULT)                                   # read-back 1
+        total = int(table["offset"][-1] + table["length"][-1])
+        flat = out[:total].cpu().numpy()                                                  # read-back 2
+    return _png_streams(flat, table)
+
+
+def _png_palette(palette, who: str):
+    if palette is None:
+        return None
+    pal = np.ascontiguousarray(palette.cpu().numpy() if isinstance(palette, torch.Tensor) else np.asarray(palette))
+    if pal.ndim != 2 or pal.shape[1] != 3 or not 1 <= pal.shape[0] <= 256 or pal.dtype != np.uint8:
+        raise ValueError(f"{who}: the palette must be uint8 [n, 3] with 1 <= n <= 256, got {pal.dtype} {tuple(pal.shape)}")
+    return pal
+
+
+def png_wrap_files(streams, adlers, shapes, palette=None, threads: int = 8) -> list:
+    """The finished files around device-made streams (tt_png_write_file), in the thread pool: ``shapes`` [(H, W)] per stream; ``palette``
+    uint8 [n, 3] (mode P) or None (mode L)."""
+    lib = _lib.load()
+    pal = _png_palette(palette, "png_wrap_files")
+    entries = 0 if pal is None else pal.shape[0]
+    streams = [np.ascontiguousarray(s) for s in streams]
+
+    def wrap(i):
+        cap = int(lib.tt_png_file_bytes(streams[i].size, entries))
+        buf, n = np.empty(cap, np.uint8), C.c_size_t()
+        rc = lib.tt_png_write_file(streams[i].ctypes.data, streams[i].size, int(adlers[i]), int(shapes[i][0]), int(shapes[i][1]),
+                                   None if pal is None else pal.ctypes.data, entries, buf.ctypes.data, cap, C.byref(n))
+        return rc, buf[:n.value].tobytes()
+
+    done = _each_file(wrap, len(streams), threads, lambda rc, i: ValueError(f"png_wrap_files: file {i} was refused (status {rc})"), lambda r: r[0])
+    return [data for _, data in done]
+
+
+def encode_png_batch(maps, palette=None, device=None, threads: int = 8) -> list:
+    """Label maps on the GPU -> finished PNG files (``bytes``), one per map: palette files (mode P) with ``palette`` uint8 [n, 3], gray
+    files (mode L) without.  Maps: contiguous-row uint8 [H, W] GPU tensors of any mix of sizes, or one [k, H, W] tensor; other integer
+    dtypes convert (a value outside 0..255: ValueError naming the map).  Pixel-equal to what Pillow would write, not byte-equal.  CPU
+    tensors are refused."""
+    maps = _png_map_list(maps, "encode_png_batch")
+    _png_palette(palette, "encode_png_batch")
+    streams, adlers = png_encode(maps, device)
+    return png_wrap_files(streams, adlers, [tuple(m.shape) for m in maps], palette, threads)

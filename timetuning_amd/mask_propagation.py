@@ -24,6 +24,7 @@ held to an fp64 restatement of OpenCV's algorithm in the tests.
 from __future__ import annotations
 
 import argparse
+import os
 import sys
 import warnings
 from typing import List, Optional, Tuple
@@ -463,7 +464,8 @@ def synthetic_davis_labels(T: int, H: int, W: int, num_objects: int, seed: int):
 
 def build_parser() -> argparse.ArgumentParser:
     """Flag names and defaults of ``mask_propagation.py:849-871`` (``type=bool`` flags keep the any-non-empty-string-is-True
-    quirk).  ``--dataset synthetic`` / ``synthetic_frames``, ``--raw_size``, ``--num_clips`` and ``--davis_metrics`` are additions."""
+    quirk).  ``--dataset synthetic`` / ``synthetic_frames``, ``--raw_size``, ``--num_clips`` and ``--davis_metrics`` are additions; so is
+    ``--save_masks DIR``, which writes every clip's seed and predictions as palette PNGs (``my_utils.write_indexed_clip``)."""
     p = argparse.ArgumentParser()
     p.add_argument("--architecture", type=str, default="dino-s16")
     p.add_argument("--model_path", type=str, default="../models/leopart_vits16.ckpt")
@@ -494,6 +496,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--raw_size", type=int, nargs=2, default=(360, 480), metavar=("H", "W"),
                    help="--dataset synthetic_frames: size of the raw uint8 frames and label maps that go through the reference's "
                         "Resize -> RandomCrop -> ClipToTensor pair transform; multiples of 8 (addition)")
+    p.add_argument("--save_masks", type=str, default=None, metavar="DIR",
+                   help="write what is scored as palette PNGs, deflated on the device: DIR/<clip>/00000.png ... per clip - frame 0 the seed "
+                        "annotation as propagated from, frames 1.. the predictions, at the size they were predicted at; <clip> is the "
+                        "video directory's name, or clip_0000 ... for the synthetic datasets (addition)")
     p.add_argument("--frame_size", type=int, nargs=2, default=None, metavar=("H", "W"),
                    help="synthetic H x W clips propagated on their native token grid (H / P, W / P) and scored at H x W; multiples of "
                         "the patch size P (addition)")
@@ -570,7 +576,7 @@ def clip_size(args, patch_size: int) -> Tuple[int, int]:
 _FLOW_FRAME_MULTIPLE = 8
 
 
-def mask_propagation(args) -> float:
+def mask_propagation(args, vit_cfg: Optional[dict] = None) -> float:
     """The evaluation loop of ``mask_propagation.py:757-846``; returns the mean J over clips.  ``--dataset synthetic`` renders normalised
     clips at the model's size; ``--dataset synthetic_frames`` renders raw uint8 frames with label maps at ``--raw_size`` and takes them
     through the reference's pair transform first (``synthetic_frames_clip``); any other name reads ``--dataset_path``
@@ -578,9 +584,13 @@ def mask_propagation(args) -> float:
     one clip per video; the first frame's annotation is the seed).  With
     ``--davis_metrics`` it also prints the DAVIS statistics (``db_statistics`` over each object's frames) per clip and over all
     objects of all clips; the return value is the same.  ``--use_optical_flow`` runs the optical-flow baseline
-    (``propagate_clip_optical_flow``) on the same clips, with the same scoring, and builds no backbone.  Both branches score predicted
+    (``propagate_clip_optical_flow``) on the same clips, with the same scoring, and builds no backbone.  ``--save_masks DIR`` writes,
+    in both branches, one directory per clip with the seed annotation as frame 0 and the predictions behind it as palette PNGs deflated on
+    the device (``my_utils.write_indexed_clip``: the only writer this build has; one encode call per clip); printed scores and the return
+    value are unchanged.  ``vit_cfg`` replaces the architecture's dimensions (tests).  Both branches score predicted
     frame j against annotated frame j; the reference compares ``predictions[:, 1:]`` with ``annotations[:, 1:]``, one frame off."""
     use_flow = bool(args.use_optical_flow)
+    save_masks = getattr(args, "save_masks", None)
     native = getattr(args, "frame_size", None) is not None
     from_disk = args.dataset not in ("synthetic", "synthetic_frames")
     raw_frames = args.dataset == "synthetic_frames"
@@ -606,14 +616,14 @@ def mask_propagation(args) -> float:
         from .models import FeatureExtractor
         from .time_tuning import TimeT
 
-        fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], return_attention=False)  # "" = synthetic weights
+        fe = FeatureExtractor(args.architecture, args.model_path, [1024, 1024, 512, 256], return_attention=False, vit_cfg=vit_cfg)  # "" = synthetic weights
         H, W = clip_size(args, fe.backbone.patch_embed.patch_size)
         model = TimeT(fe, 200).to(device).eval()
     scores = []
     davis = []   # per object: (J_M, J_R, J_D, F_M, F_R, F_D)
     for i in range(len(disk_loader) if from_disk else args.num_clips):
         if from_disk:
-            data, annotations, _ = next(disk_clips)
+            data, annotations, label = next(disk_clips)
             clip, masks = data[0, 0], annotations[0, 0].long()   # the first frame's annotation is the seed
         elif raw_frames:
             clip, masks = synthetic_frames_clip(args, i, device)
@@ -629,6 +639,14 @@ def mask_propagation(args) -> float:
         else:
             pred = propagate_clip(model, clip.to(device), masks[0].to(device), args.n_last_frames, args.size_mask_neighborhood, args.topk,
                                   (H, W) if native else args.input_resolution, C)
+        if save_masks:   # what is scored, as files: the seed as propagated from, then the predictions (one encode call per clip)
+            from .my_utils import write_indexed_clip
+
+            name = os.path.basename(os.path.normpath(str(disk_loader.dataset.keys[int(label)]))) if from_disk else f"clip_{i:04d}"
+            seed = masks[0].to(device)
+            if seed.shape != pred.shape[1:]:
+                raise ValueError(f"--save_masks: the seed is {tuple(seed.shape)}, the predictions are {tuple(pred.shape[1:])}")
+            write_indexed_clip(os.path.join(save_masks, name), torch.cat([seed[None].to(pred.dtype), pred], 0))
         j, _ = jaccard(pred, masks[1:].to(device), C)
         scores.append(j)
         print(f"clip {i}: J = {j:.4f}")
