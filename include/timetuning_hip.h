@@ -449,7 +449,9 @@ int tt_label_propagate_from_sims(const float* xn, const float* seg0, int64_t* la
  *                            (mask_propagation.py:448-496): pmap_all [fs-1, bs, n, K] fp64.  Workspace as above.
  *   tt_upsample_argmax       nn.functional.interpolate(maps, (R,R), mode="bilinear", align_corners=False) followed by
  *                            torch.max(dim=1) (mask_propagation.py:828-829), fused: maps [M, n, K] fp64 ->
- *                            labels_out [M, R, R] int64; the upsampled fp64 tensor is never written.
+ *                            labels_out [M, R, R] int64; the upsampled fp64 tensor is never written.  One kernel template
+ *                            (csrc/upsample.hip) serves this entry, tt_upsample_argmax_hw (N9) and tt_upsample_argmax_f32 (N2);
+ *                            taps, weights and the first maximum are the shared rule of csrc/interp.hpp.
  *   tt_confusion_counts      counts[gt*C + pred] += 1 over n pixels (labels outside [0,C) ignored), uint64 [C,C],
  *                            C <= 4096: the confusion matrix from which the Jaccard index (J) of the propagated masks and
  *                            the evaluator's matched mIoU (metrics.py:357-432) follow.  An LDS histogram up to C = 96,
@@ -545,7 +547,7 @@ int tt_match_segments(const unsigned long long* counts, int S, int Cg, int Cp, i
  *   tt_upsample_argmax_hist_f32   maps [M, g * g, K] fp32 -> counts[k] += the number of the M * R * R output pixels whose bilinear arg-max
  *                     is k: the histogram of tt_upsample_argmax_f32's labels without the labels (time_tuning.py:354-375
  *                     get_similarity_histogram: proto_clustering's [N, 224, 224] map on the host, then torch.histc).  Per pixel the
- *                     statement of tt_upsample_argmax_f32 (same fp32 expressions, first maximum).  counts uint64 [K] is ADDED to: the
+ *                     device function tt_upsample_argmax_f32's kernel calls (csrc/upsample.hip): the same labels by construction.  counts uint64 [K] is ADDED to: the
  *                     caller zeroes it, and a loop over batches adds up.  A u32 histogram per workgroup in LDS, 64-bit integer atomics
  *                     for its non-zero bins: exact, independent of order and grid.  Refused with TT_EINVAL: null pointers, M, g, K, R
  *                     <= 0, K > 16384 (the LDS limit of tt_confusion_counts_segments), M > 65535, g or R > 32768, counts misaligned. */
@@ -676,7 +678,8 @@ int tt_foreground_mask_from_probs(const float* cls_probs, float* mask_out, float
  *      reference delegates to faiss.Kmeans(d, k, niter=50, nredo=5, seed=1).
  *   tt_col_moments              per-column mean and population variance (StandardScaler, my_utils.py:24-30), fp64.
  *   tt_upsample_bilinear_tokens token maps [M, g*g, C] -> [M, R*R, C] as nn.functional.interpolate(x.double(), (R,R),
- *                               mode="bilinear").float() (clustering.py:34-36).
+ *                               mode="bilinear").float() (clustering.py:34-36).  Its taps are csrc/interp.hpp's lin_tap in fp64,
+ *                               the function tt_bilinear_adjoint_tokens (N5) takes its own from.
  *   tt_upsample_argmax_f32      fp32 twin of tt_upsample_argmax for proto_clustering's prototype scores (clustering.py:101-104).
  *   tt_kmeans_assign            labels[p] = argmin_j |x_p - c_j|^2 (first minimum) over centroids [k, d]; dist2 optional.
  *   tt_kmeans_accumulate        sums[k, d] (fp64) and counts[k] of the points per label, deterministic (no atomics).

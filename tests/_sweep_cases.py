@@ -803,7 +803,7 @@ PINNED = {
     "sinkhorn_from_q": [dict(B=777, K=333, iters=5, transposed=0), dict(B=2049, K=256, iters=0, transposed=1), dict(B=65, K=511, iters=1, transposed=1)],
     "sinkhorn_local": [dict(B=777, K=333, iters=5), dict(B=2049, K=257, iters=0), dict(B=31, K=64, iters=1)],
     "queue_push": [dict(Q=40, D=32, m=1), dict(Q=40, D=32, m=40), dict(Q=1, D=128, m=1)],
-    # ---- second tier (cluster.hip, kmeans.hip, label_prop.hip, rowops.hip, attn_mask.hip)
+    # ---- second tier (cluster.hip, upsample.hip, kmeans.hip, label_prop.hip, rowops.hip, attn_mask.hip)
     "kmeans_assign": [
         # tt_kmeans_assign's dispatch: d <= 16 (16 registers), d <= 64 (64 registers), wider rows read in place - either side of each edge
         dict(P=300, d=1, k=7, dup=0), dict(P=5000, d=16, k=100, dup=0), dict(P=5000, d=17, k=100, dup=0), dict(P=20000, d=64, k=200, dup=0),

@@ -277,7 +277,7 @@ def test_col_moments_under_at_and_over_the_cap():
 
 
 def test_upsampling_every_ratio_and_workgroup_size():
-    threads = lambda C: 256 if C >= 256 else (128 if C > 64 else 64)   # cluster.hip, tt_upsample_bilinear_tokens
+    threads = lambda C: 256 if C >= 256 else (128 if C > 64 else 64)   # upsample.hip, tt_upsample_bilinear_tokens
     for op, key in (("upsample_tokens", "C"), ("upsample_argmax_f32", "K"), ("upsample_argmax", "K")):
         cases = _of(op)
         assert any(p["R"] < p["g"] for p in cases) and any(p["R"] == p["g"] for p in cases) and any(p["R"] > p["g"] for p in cases), op

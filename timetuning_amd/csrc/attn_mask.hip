@@ -15,6 +15,7 @@
 //   components-> sizes 1 and 2 are detectable locally: a pixel with no set neighbour, or a pair whose members have
 //                no other set neighbour.  No labelling pass, no host.
 #include "common.hpp"
+#include "interp.hpp"
 
 namespace tt {
 
@@ -197,17 +198,8 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(float* __restrict__ x, 
 
 // interpolate_pos_encoding (dino_vision_transformer.py:214-234) for inputs whose token grid is not the stored one:
 // nn.functional.interpolate(patch_pos_embed [1,D,g,g], scale_factor=(sh, sw), mode="bicubic") - align_corners False, the
-// coordinate scale is 1 / scale_factor (scale_factor given, not recomputed), cubic convolution with A = -0.75, taps
+// coordinate scale is 1 / scale_factor (scale_factor given, not recomputed), cubic convolution with A = -0.75 (interp.hpp cubic_coeffs), taps
 // clamped to the border - then the class row in front.  pos [1+g*g, D] -> out [1+gh*gw, D]; one thread per (token, 4 d's).
-__device__ __forceinline__ void cubic_coeffs(float t, float (&w)[4]) {
-  const float A = -0.75f;
-  const float x0 = t + 1.f, x3 = 2.f - t, u = 1.f - t;
-  w[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
-  w[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
-  w[2] = ((A + 2.f) * u - (A + 3.f)) * u * u + 1.f;
-  w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
-}
-
 __global__ __launch_bounds__(256) void pos_embed_bicubic_kernel(const float* __restrict__ pos, float* __restrict__ out, int g, int gh,
                                                                 int gw, int D, float rscale_h, float rscale_w) {
   const int d4 = D / 4;

@@ -14,7 +14,7 @@
 // Because at most a handful of sources survive per query, step 2 is a sparse gather, not a GEMM.  Frame t's
 // maps become context for frame t+1, so the frames are sequential; everything inside a frame is parallel.
 // The last frame also emits argmax_K (the hard labels the loss consumes, time_tuning.py:296).
-// N9 (tt_label_propagate_grid_maps, tt_upsample_argmax_hw): the evaluation propagation on a gh x gw grid - frames at native size -
+// N9 (tt_label_propagate_grid_maps): the evaluation propagation on a gh x gw grid - frames at native size -
 // with the same similarity GEMMs (lp_sims_chunk) and a per-query kernel that streams its candidates from the similarity rows, so
 // neither the window (radius 0: the whole grid) nor the number of context frames is bounded by registers or LDS.
 #include "common.hpp"
@@ -739,69 +739,7 @@ extern "C" int tt_label_propagate_grid_maps(const float* xn, const float* seg0, 
   return TT_OK;
 }
 
-// ---- evaluation tail of mask_propagation.py:826-829: bilinear upsample (align_corners=False) of the fp64 maps to the
-// input resolution, then argmax over the label channel - fused, so the [M, K, R, R] fp64 tensor (77 MB per 25-frame clip
-// at K = 8) is never written.
 namespace tt {
-__global__ __launch_bounds__(256) void upsample_argmax_kernel(const double* __restrict__ maps, int64_t* __restrict__ out, int g, int K,
-                                                              int R) {
-  const int pix = blockIdx.x * 256 + threadIdx.x;
-  if (pix >= R * R) return;
-  const int m = blockIdx.y, oy = pix / R, ox = pix - oy * R;
-  const double scale = (double)g / (double)R;  // area_pixel_compute_scale, align_corners = False
-  double sy = scale * (oy + 0.5) - 0.5, sx = scale * (ox + 0.5) - 0.5;
-  sy = sy < 0.0 ? 0.0 : sy;
-  sx = sx < 0.0 ? 0.0 : sx;
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int y1 = y0 + (y0 < g - 1 ? 1 : 0), x1 = x0 + (x0 < g - 1 ? 1 : 0);
-  const double ly = sy - y0, lx = sx - x0, hy = 1.0 - ly, hx = 1.0 - lx;
-  const double* base = maps + (long long)m * g * g * K;
-  const double* p00 = base + (long long)(y0 * g + x0) * K;
-  const double* p01 = base + (long long)(y0 * g + x1) * K;
-  const double* p10 = base + (long long)(y1 * g + x0) * K;
-  const double* p11 = base + (long long)(y1 * g + x1) * K;
-  double best = -INFINITY;
-  int besti = 0;
-  for (int k = 0; k < K; ++k) {
-    const double v = hy * (hx * p00[k] + lx * p01[k]) + ly * (hx * p10[k] + lx * p11[k]);
-    if (v > best) {  // torch.max: first index of the maximum
-      best = v;
-      besti = k;
-    }
-  }
-  out[(long long)m * R * R + pix] = besti;
-}
-
-// N9: the same for a gh x gw grid and an H x W output (rows and columns scale separately)
-__global__ __launch_bounds__(256) void upsample_argmax_hw_kernel(const double* __restrict__ maps, int64_t* __restrict__ out, int gh, int gw,
-                                                                 int K, int H, int W) {
-  const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (pix >= (long long)H * W) return;
-  const int m = blockIdx.y, oy = (int)(pix / W), ox = (int)(pix - (long long)oy * W);
-  // area_pixel_compute_scale, align_corners = False: input / output size per dimension
-  double sy = (double)gh / (double)H * (oy + 0.5) - 0.5, sx = (double)gw / (double)W * (ox + 0.5) - 0.5;
-  sy = sy < 0.0 ? 0.0 : sy;
-  sx = sx < 0.0 ? 0.0 : sx;
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int y1 = y0 + (y0 < gh - 1 ? 1 : 0), x1 = x0 + (x0 < gw - 1 ? 1 : 0);
-  const double ly = sy - y0, lx = sx - x0, hy = 1.0 - ly, hx = 1.0 - lx;
-  const double* base = maps + (long long)m * gh * gw * K;
-  const double* p00 = base + (long long)(y0 * gw + x0) * K;
-  const double* p01 = base + (long long)(y0 * gw + x1) * K;
-  const double* p10 = base + (long long)(y1 * gw + x0) * K;
-  const double* p11 = base + (long long)(y1 * gw + x1) * K;
-  double best = -INFINITY;
-  int besti = 0;
-  for (int k = 0; k < K; ++k) {
-    const double v = hy * (hx * p00[k] + lx * p01[k]) + ly * (hx * p10[k] + lx * p11[k]);
-    if (v > best) {  // torch.max: first index of the maximum
-      best = v;
-      besti = k;
-    }
-  }
-  out[(long long)m * H * W + pix] = besti;
-}
-
 // counts[gt * C + pred] += 1 over n pixels (labels outside [0, C) are ignored): the confusion matrix behind the
 // Jaccard index of the propagated masks
 __global__ __launch_bounds__(256) void confusion_kernel(const int64_t* __restrict__ pred, const int64_t* __restrict__ gt, long long n,
@@ -830,23 +768,6 @@ __global__ __launch_bounds__(256) void confusion_global_kernel(const int64_t* __
   }
 }
 }  // namespace tt
-
-extern "C" int tt_upsample_argmax(const double* maps, int64_t* labels_out, int M, int g, int K, int R, tt_stream_t stream) {
-  TT_REQUIRE(maps && labels_out && M > 0 && g > 0 && K > 0 && R > 0, "upsample_argmax: bad arguments");
-  TT_REQUIRE(M <= 65535 && R <= 32768, "upsample_argmax: %d maps of %dx%d exceed one launch (at most 65535 maps)", M, R, R);
-  hipLaunchKernelGGL(upsample_argmax_kernel, dim3((R * R + 255) / 256, M), dim3(256), 0, as_stream(stream), maps, labels_out, g, K, R);
-  TT_CHECK_LAUNCH("upsample_argmax");
-  return TT_OK;
-}
-
-extern "C" int tt_upsample_argmax_hw(const double* maps, int64_t* labels_out, int M, int gh, int gw, int K, int H, int W, tt_stream_t stream) {
-  TT_REQUIRE(maps && labels_out && M > 0 && gh > 0 && gw > 0 && K > 0 && H > 0 && W > 0, "upsample_argmax_hw: bad arguments");
-  TT_REQUIRE(M <= 65535 && (long long)H * W <= 0x7fffffffLL, "upsample_argmax_hw: %d maps of %dx%d exceed one launch", M, H, W);
-  hipLaunchKernelGGL(upsample_argmax_hw_kernel, dim3((unsigned)(((long long)H * W + 255) / 256), M), dim3(256), 0, as_stream(stream), maps,
-                     labels_out, gh, gw, K, H, W);
-  TT_CHECK_LAUNCH("upsample_argmax_hw");
-  return TT_OK;
-}
 
 extern "C" int tt_confusion_counts(const int64_t* pred, const int64_t* gt, long long n, int C, unsigned long long* counts,
                                    tt_stream_t stream) {

@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "interp.hpp"
 
 namespace tt {
 
@@ -110,21 +111,9 @@ __global__ __launch_bounds__(LP_THREADS) void probe_logits_kernel(const float* _
   }
 }
 
-// ---- bilinear source index, align_corners = False (ATen's area_pixel_compute_source_index: src = max(scale (dst + 0.5) - 0.5, 0),
-// scale = n_in / n_out), in fp64 as tt_upsample_bilinear_tokens, whose adjoint this must be; the weight is then rounded to fp32
-struct SrcIdx {
-  int i0, i1;
-  float l1;  // weight of i1; i0 gets 1 - l1
-};
-__device__ __forceinline__ SrcIdx src_index(int dst, double scale, int n_in) {
-  double s = scale * ((double)dst + 0.5) - 0.5;
-  s = s < 0.0 ? 0.0 : s;
-  SrcIdx r;
-  r.i0 = (int)s;
-  r.i1 = r.i0 + (r.i0 < n_in - 1 ? 1 : 0);
-  r.l1 = (float)(s - (double)r.i0);
-  return r;
-}
+// ---- bilinear source index, align_corners = False: interp.hpp's lin_tap in fp64, the very function tt_upsample_bilinear_tokens takes
+// its taps from (upsample.hip), whose adjoint this must be; the weight is then rounded to fp32
+// (l1: the weight of the second tap, i0 gets 1 - l1)
 
 // ---- the gather shared by tt_probe_upsample_ce (CE = true) and tt_bilinear_adjoint_tokens (CE = false).
 // Workgroup (i, b) owns low-res row i of image b: it walks the mask rows oy whose source rows include i, produces the mask-resolution
@@ -157,10 +146,10 @@ __global__ __launch_bounds__(LP_THREADS) void probe_gather_kernel(const float* _
   const int t = threadIdx.x, i = blockIdx.x, b = blockIdx.y;
   const double scale = (double)g / (double)R;
   for (int o = t; o < R; o += LP_THREADS) {
-    const SrcIdx s = src_index(o, scale, g);
+    const LinTap<double> s = lin_tap<double>(o, scale, g);
     x0s[o] = s.i0;
     x1s[o] = s.i1;
-    l1s[o] = s.l1;
+    l1s[o] = (float)s.l;
   }
   for (int e = t; e < g * C; e += LP_THREADS) acc[e] = 0.f;
   __syncthreads();
@@ -169,9 +158,10 @@ __global__ __launch_bounds__(LP_THREADS) void probe_gather_kernel(const float* _
   const float* img = src + (size_t)b * (CE ? (size_t)g * g : (size_t)R * R) * C;
   double loss = 0.0, nvalid = 0.0, ninvalid = 0.0;
   for (int oy = 0; oy < R; ++oy) {
-    const SrcIdx sy = src_index(oy, scale, g);
+    const LinTap<double> sy = lin_tap<double>(oy, scale, g);
     if (sy.i0 != i && sy.i1 != i) continue;  // uniform over the workgroup
-    const float wy = (sy.i0 == i ? 1.f - sy.l1 : 0.f) + (sy.i1 == i ? sy.l1 : 0.f);
+    const float ly = (float)sy.l;
+    const float wy = (sy.i0 == i ? 1.f - ly : 0.f) + (sy.i1 == i ? ly : 0.f);
     const bool owner = sy.i0 == i;
     for (int xa = 0; xa < R; xa += P) {
       const int ox = xa + slot;
@@ -179,7 +169,7 @@ __global__ __launch_bounds__(LP_THREADS) void probe_gather_kernel(const float* _
         float* dzp = dz + slot * C;
         if (CE) {
           const int x0 = x0s[ox], x1 = x1s[ox];
-          const float lx = l1s[ox], hx = 1.f - lx, ly = sy.l1, hy = 1.f - ly;
+          const float lx = l1s[ox], hx = 1.f - lx, hy = 1.f - ly;
           const float* p00 = img + (size_t)(sy.i0 * g + x0) * C;
           const float* p01 = img + (size_t)(sy.i0 * g + x1) * C;
           const float* p10 = img + (size_t)(sy.i1 * g + x0) * C;

@@ -9,6 +9,7 @@
 // (pos_embed_bicubic_bwd_kernel; forward: attn_mask.hip pos_embed_bicubic_kernel).
 // Every sum has a fixed order and no float atomics: two calls give the same bits.
 #include "common.hpp"
+#include "interp.hpp"
 
 namespace tt {
 
@@ -159,22 +160,13 @@ __global__ __launch_bounds__(256) void stem_fold_kernel(const float* __restrict_
   }
 }
 
-// The forward's weight function, restated (attn_mask.hip cubic_coeffs: cubic convolution, A = -0.75).
-__device__ __forceinline__ void stem_cubic_coeffs(float t, float (&w)[4]) {
-  const float A = -0.75f;
-  const float x0 = t + 1.f, x3 = 2.f - t, u = 1.f - t;
-  w[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
-  w[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
-  w[2] = ((A + 2.f) * u - (A + 3.f)) * u * u + 1.f;
-  w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
-}
 // Weight with which output coordinate o taps source cell s along one axis: the forward's four taps at clamp(floor(r) - 1 + i, 0, g - 1)
 // (several taps of a border output fall on the same cell: their weights add up, in tap order).
 __device__ __forceinline__ float stem_axis_weight(int o, int s, int g, float rscale) {
   const float rr = rscale * (o + 0.5f) - 0.5f;
   const float fl = floorf(rr);
   float w[4];
-  stem_cubic_coeffs(rr - fl, w);
+  cubic_coeffs(rr - fl, w);   // interp.hpp: the forward's weight function itself
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
