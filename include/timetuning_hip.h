@@ -1349,6 +1349,42 @@ size_t tt_png_file_bytes(size_t stream_len, int palette_entries);
 int tt_png_write_file(const uint8_t* stream, size_t stream_len, uint32_t adler, int H, int W, const uint8_t* palette, int palette_entries,
                       uint8_t* out, size_t out_capacity, size_t* out_len);
 
+/* ---- N31: dense nearest-neighbour retrieval (csrc/nn_retrieval.hip; timetuning_amd/nn_retrieval.py) - the evaluation of
+   Balazevic et al., 2023: every patch of a validation image retrieves its k nearest patches of a labelled memory bank by cosine similarity
+   and takes the softmax-weighted mean of their label distributions.  The similarities are tt_linear_fwd's, one block of the bank at a
+   time; these entries are the exact search step, the bank's label distributions and the weighted gather.  None of them allocates,
+   synchronises or frees; every refusal is TT_EINVAL with nothing launched and nothing written.
+   tt_topk_merge       sims fp32 [Q, Nc] with rows ld >= Nc floats apart: the similarities of Q queries to bank rows base .. base + Nc - 1.
+                       vals fp32 [Q, k], idx int64 [Q, k]: per query the k best seen so far, REPLACED by the k best of (list U block).
+                       The order is total: the larger similarity first, among equal similarities the smaller bank index first.  An
+                       empty list is k times (-inf, -1): init = 1 starts from it without reading vals / idx, init = 0 merges into them.
+                       A NaN is never selected, and neither is a -inf (it ties with the empty entry, whose index -1 is the smaller):
+                       the tail of a list that has seen fewer than k finite similarities stays (-inf, -1).  Lists are always sorted, so
+                       vals[q][k - 1] is the query's threshold.  The result is a function of the multiset of (similarity, index)
+                       offered so far: not of the cut into blocks, of their order or of the launch geometry.  Bank indices offered to
+                       one list must be distinct.  sims may start at any 4-byte address.  1 <= k <= tt_topk_merge_max_k() = 64;
+                       1 <= Q, Nc <= 2^31 - 1; ld <= 2^40; 0 <= base, base + Nc <= 2^62.  One wave per query, no LDS, no atomics.
+   tt_patch_label_counts   maps uint8 [M, R, R], a grid of g x g cells of (R / g)^2 pixels (R % g == 0): counts int32 [M, g g, C] the pixels
+                       of every class in every cell, valid int32 [M, g g] their sum.  A pixel equal to `ignore` (0 .. 255, or -1 for none)
+                       is counted nowhere.  A label >= C that is not `ignore` is counted nowhere either and lowers *status (device
+                       uint32, set to 0xffffffff by the call) to the index of its map: after the call *status is the FIRST such map, or
+                       0xffffffff.  C <= 256, R <= 16384, M g g <= 2^23.  Integer LDS atomics: exact and independent of order.  maps
+                       may start at any address.
+   tt_nn_label_aggregate   vals fp32 [Q, k], idx int64 [Q, k] (tt_topk_merge's), labels fp32 [N, C], beta > 0:
+                       out[q][c] = sum_j w_j labels[idx_j][c] with w = softmax(vals / beta) over the entries whose idx is a bank row
+                       (0 <= idx < N; the others are left out and never read).  The maximum is subtracted, j runs 0 .. k - 1 in order,
+                       fp32 throughout, no atomics; a query without a valid entry gets a zero row.  1 <= k <= 64, C <= 2^20. */
+int tt_topk_merge_max_k(void);
+int tt_topk_merge_shape_ok(long long Q, long long Nc, long long ld, int k);
+int tt_topk_merge(const float* sims, long long Q, long long Nc, long long ld, long long base, float* vals, int64_t* idx, int k, int init,
+                  tt_stream_t stream);
+int tt_patch_label_counts_shape_ok(int M, int R, int g, int C);
+int tt_patch_label_counts(const uint8_t* maps, int M, int R, int g, int C, int ignore, int32_t* counts, int32_t* valid, uint32_t* status,
+                          tt_stream_t stream);
+int tt_nn_label_aggregate_shape_ok(long long Q, int k, long long N, int C);
+int tt_nn_label_aggregate(const float* vals, const int64_t* idx, const float* labels, long long Q, int k, long long N, int C, float beta,
+                          float* out, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,13 @@ SIGNATURES = {
     "tt_png_encode_host": (c_i, [c_vp, c_vp, c_i, c_vp, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_sz, c_vp]),
     "tt_png_file_bytes": (c_sz, [c_sz, c_i]),
     "tt_png_write_file": (c_i, [c_vp, c_sz, C.c_uint32, c_i, c_i, c_vp, c_i, c_vp, c_sz, C.POINTER(c_sz)]),
+    "tt_topk_merge_max_k": (c_i, []),
+    "tt_topk_merge_shape_ok": (c_i, [c_ll, c_ll, c_ll, c_i]),
+    "tt_topk_merge": (c_i, [c_vp, c_ll, c_ll, c_ll, c_ll, c_vp, c_vp, c_i, c_i, c_vp]),
+    "tt_patch_label_counts_shape_ok": (c_i, [c_i, c_i, c_i, c_i]),
+    "tt_patch_label_counts": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
+    "tt_nn_label_aggregate_shape_ok": (c_i, [c_ll, c_i, c_ll, c_i]),
+    "tt_nn_label_aggregate": (c_i, [c_vp, c_vp, c_vp, c_ll, c_i, c_ll, c_i, c_f, c_vp, c_vp]),
 }
 
 _lib = None

@@ -3410,3 +3410,183 @@ def encode_png_batch(maps, palette=None, device=None, threads: int = 8) -> list:
     _png_palette(palette, "encode_png_batch")
     streams, adlers = png_encode(maps, device)
     return png_wrap_files(streams, adlers, [tuple(m.shape) for m in maps], palette, threads)
+
+
+# ------------------------------------------------------------------------------------------------
+# N31: dense nearest-neighbour retrieval (csrc/nn_retrieval.hip)
+# ------------------------------------------------------------------------------------------------
+
+NN_MAX_K = 64
+NN_SEARCH_WORKSPACE_BYTES = 64 << 20     # one block of similarities; DESIGN.md N31 has the measurement behind the default
+NN_SEARCH_QUERY_TILE = 4096              # queries per block: one wave each, enough of them to fill the device
+
+
+def _chk_topk_lists(vals, idx, Q: int, k: int, device, who: str) -> None:
+    _chk(vals, "vals"); _chk(idx, "idx", torch.int64)
+    if tuple(vals.shape) != (Q, k) or tuple(idx.shape) != (Q, k) or vals.device != device or idx.device != device:
+        raise ValueError(f"{who}: vals and idx must be [{Q}, {k}] on {device}, got {tuple(vals.shape)} and {tuple(idx.shape)}")
+
+
+def topk_merge(sims, base: int, vals=None, idx=None, k: Optional[int] = None, init: Optional[bool] = None):
+    """One step of the exact top-k search.  sims fp32 [Q, Nc] (rows may be pitched: ``stride(1) == 1``, any ``stride(0) >= Nc``, any
+    4-byte-aligned start): the similarities of Q queries to bank rows ``base .. base + Nc - 1``.  ``vals`` fp32 [Q, k] / ``idx`` int64
+    [Q, k]: the running lists, replaced IN PLACE by the k best of (list U block); without them (pass ``k``) the search starts from
+    empty lists, and so it does with ``init=True`` (the lists' contents are then not read).  Order: larger similarity first, then smaller bank index; NaN and -inf are never selected; a list that has seen fewer
+    than k finite candidates ends in (-inf, -1).  Returns ``(vals, idx)``."""
+    lib = _lib.load()
+    if sims.dim() != 2 or not sims.is_cuda or sims.dtype != f32 or sims.shape[0] < 1 or sims.shape[1] < 1:
+        raise ValueError("topk_merge: sims must be a non-empty 2-D fp32 GPU tensor")
+    Q, Nc = sims.shape
+    ld = sims.stride(0) if Q > 1 else max(sims.stride(0), Nc)
+    if sims.stride(1) != 1 or ld < Nc:
+        raise ValueError(f"topk_merge: sims must have unit inner stride and rows at least Nc = {Nc} apart, got strides {sims.stride()}")
+    fresh = vals is None and idx is None
+    init = fresh if init is None else bool(init)
+    if fresh:
+        if not init:
+            raise ValueError("topk_merge: init=False needs the running lists")
+        if k is None:
+            raise ValueError("topk_merge: pass the running lists (vals, idx), or k to start from empty ones")
+        k = int(k)
+        if not 1 <= k <= NN_MAX_K:
+            raise ValueError(f"topk_merge: k = {k} is outside 1 .. {NN_MAX_K}")
+        vals = torch.empty((Q, k), dtype=f32, device=sims.device)
+        idx = torch.empty((Q, k), dtype=torch.int64, device=sims.device)
+    elif vals is None or idx is None:
+        raise ValueError("topk_merge: vals and idx come together")
+    else:
+        if k is not None and int(k) != vals.shape[1]:
+            raise ValueError(f"topk_merge: k = {k}, the lists hold {vals.shape[1]} entries")
+        k = int(vals.shape[1])
+    _chk_topk_lists(vals, idx, Q, k, sims.device, "topk_merge")
+    with torch.cuda.device(sims.device):
+        _lib.check(lib.tt_topk_merge(_p(sims), Q, Nc, ld, int(base), _p(vals), _p(idx), k, 1 if init else 0, _stream()), "tt_topk_merge")
+    return vals, idx
+
+
+def patch_label_counts(maps, grid: int, num_classes: int, ignore: Optional[int] = 255, check: bool = True):
+    """maps uint8 [M, R, R] -> ``(counts int32 [M, g*g, C], valid int32 [M, g*g])``: the pixels of every class in every cell of the g x g grid,
+    and their sum.  Pixels equal to ``ignore`` (None: no such value) count nowhere.  A label >= C that is not ``ignore`` raises ValueError
+    naming the first such map (``check=True`` reads the status word: one device-to-host copy; ``check=False`` returns
+    ``(counts, valid, status)`` with the device word, 0xffffffff = -1 when every label was in range)."""
+    lib = _lib.load()
+    _chk(maps, "maps", torch.uint8)
+    if maps.dim() != 3 or maps.shape[1] != maps.shape[2]:
+        raise ValueError(f"patch_label_counts: expected uint8 [M, R, R], got {tuple(maps.shape)}")
+    M, R = int(maps.shape[0]), int(maps.shape[1])
+    g, Cn, ign = int(grid), int(num_classes), (-1 if ignore is None else int(ignore))
+    if not lib.tt_patch_label_counts_shape_ok(M, R, g, Cn):
+        raise ValueError(f"patch_label_counts: {M} maps of {R} x {R} on a grid of {g} with {Cn} classes are not supported "
+                         f"(need R % g == 0, R <= 16384, 1 <= C <= 256)")
+    counts = torch.empty((M, g * g, Cn), dtype=torch.int32, device=maps.device)
+    valid = torch.empty((M, g * g), dtype=torch.int32, device=maps.device)
+    status = torch.empty((1,), dtype=torch.int32, device=maps.device)
+    with torch.cuda.device(maps.device):
+        _lib.check(lib.tt_patch_label_counts(_p(maps), M, R, g, Cn, ign, _p(counts), _p(valid), _p(status), _stream()), "tt_patch_label_counts")
+    if not check:
+        return counts, valid, status
+    bad = int(status.item())
+    if bad >= 0:
+        raise ValueError(f"patch_label_counts: map {bad} holds a label outside [0, {Cn}) that is not the ignore value {ignore}")
+    return counts, valid
+
+
+def nn_label_aggregate(vals, idx, labels, beta: float, out=None):
+    """``out[q] = sum_j softmax(vals[q] / beta)_j * labels[idx[q, j]]`` over the entries with ``idx >= 0``: vals fp32 [Q, k], idx int64 [Q, k],
+    labels fp32 [N, C] -> fp32 [Q, C]; a query with no valid entry gets a zero row."""
+    lib = _lib.load()
+    _chk(labels, "labels")
+    if vals.dim() != 2 or labels.dim() != 2:
+        raise ValueError(f"nn_label_aggregate: expected vals [Q, k] and labels [N, C], got {tuple(vals.shape)} and {tuple(labels.shape)}")
+    Q, k = vals.shape
+    N, Cn = labels.shape
+    _chk_topk_lists(vals, idx, Q, k, labels.device, "nn_label_aggregate")
+    if not lib.tt_nn_label_aggregate_shape_ok(Q, k, N, Cn) or not float(beta) > 0:
+        raise ValueError(f"nn_label_aggregate: Q = {Q}, k = {k}, N = {N}, C = {Cn}, beta = {beta} are not supported (1 <= k <= {NN_MAX_K}, beta > 0)")
+    if out is None:
+        out = torch.empty((Q, Cn), dtype=f32, device=labels.device)
+    else:
+        _chk(out, "out")
+        if tuple(out.shape) != (Q, Cn):
+            raise ValueError(f"nn_label_aggregate: out must be [{Q}, {Cn}]")
+    with torch.cuda.device(labels.device):
+        _lib.check(lib.tt_nn_label_aggregate(_p(vals), _p(idx), _p(labels), Q, k, N, Cn, float(beta), _p(out), _stream()), "tt_nn_label_aggregate")
+    return out
+
+
+def nn_search_plan(Q: int, N: int, workspace_bytes: int = NN_SEARCH_WORKSPACE_BYTES, query_tile: int = NN_SEARCH_QUERY_TILE) -> list:
+    """Host only: the blocks ``(q0, q1, n0, n1)`` of ``nn_search``, in the order it runs them.  A block is at most ``query_tile`` queries by as
+    many bank rows as ``workspace_bytes`` of fp32 similarities hold beside them; every (query, bank row) pair lies in exactly one block."""
+    Q, N, floats = int(Q), int(N), int(workspace_bytes) // 4
+    if Q < 1 or N < 1 or floats < 1 or int(query_tile) < 1:
+        raise ValueError(f"nn_search_plan: Q = {Q}, N = {N}, workspace_bytes = {workspace_bytes}, query_tile = {query_tile}: need each >= 1 "
+                         "(the workspace at least one fp32)")
+    rows = min(Q, int(query_tile), floats)
+    cols = min(N, floats // rows, 2 ** 31 - 1)
+    return [(q0, min(q0 + rows, Q), n0, min(n0 + cols, N)) for q0 in range(0, Q, rows) for n0 in range(0, N, cols)]
+
+
+def _nn_select_torch(block, base: int, vals, idx, k: int):
+    """``select="torch"``: what a user of torch alone writes - top-k of the block, concatenated with the running list, top-k again."""
+    bv, bi = torch.topk(block, min(k, block.shape[1]), dim=1)
+    bi = bi + base
+    if vals is not None:
+        bv, bi = torch.cat([vals, bv], dim=1), torch.cat([idx, bi], dim=1)
+    if bv.shape[1] > k:
+        bv, at = torch.topk(bv, k, dim=1)
+        bi = torch.gather(bi, 1, at)
+    return bv, bi
+
+
+def _nn_canonical_torch(vals, idx, k: int):
+    """The torch route's lists in the order tt_topk_merge keeps: similarity descending, then index ascending; padded with (-inf, -1)."""
+    idx, order = torch.sort(idx, dim=1, stable=True)
+    vals = torch.gather(vals, 1, order)
+    vals, order = torch.sort(vals, dim=1, descending=True, stable=True)
+    idx = torch.gather(idx, 1, order)
+    if vals.shape[1] < k:
+        pad = k - vals.shape[1]
+        vals = torch.cat([vals, vals.new_full((vals.shape[0], pad), float("-inf"))], dim=1)
+        idx = torch.cat([idx, idx.new_full((idx.shape[0], pad), -1)], dim=1)
+    return vals.contiguous(), idx.contiguous()
+
+
+def nn_search(queries, bank, k: int, workspace_bytes: int = NN_SEARCH_WORKSPACE_BYTES, select: str = "hip", query_tile: int = NN_SEARCH_QUERY_TILE,
+              workspace=None):
+    """Exact k nearest bank rows of every query by inner product (cosine similarity on L2-normalised rows): queries fp32 [Q, D], bank fp32
+    [N, D] -> ``(vals fp32 [Q, k], idx int64 [Q, k])``, best first, ties by the smaller bank index.  The [Q, N] similarities are never held
+    whole: block by block (``nn_search_plan``) ``linear_fwd`` writes queries x bank-block^T into the workspace and the select merges it into
+    the running lists.  ``select="hip"``: tt_topk_merge.  ``select="torch"``: the same tiling with torch.topk on the block and
+    cat + topk for the merge - the A/B partner on finite similarities, not a fallback.  ``workspace``: a uint8 GPU tensor of at least
+    ``workspace_bytes`` to reuse between calls."""
+    _chk(queries, "queries"); _chk(bank, "bank")
+    if queries.dim() != 2 or bank.dim() != 2 or queries.shape[1] != bank.shape[1] or queries.device != bank.device:
+        raise ValueError(f"nn_search: expected queries [Q, D] and bank [N, D] on one device, got {tuple(queries.shape)} and {tuple(bank.shape)}")
+    if select not in ("hip", "torch"):
+        raise ValueError(f"nn_search: select = {select!r} is neither 'hip' nor 'torch'")
+    k = int(k)
+    if not 1 <= k <= NN_MAX_K:
+        raise ValueError(f"nn_search: k = {k} is outside 1 .. {NN_MAX_K}")
+    Q, N = int(queries.shape[0]), int(bank.shape[0])
+    plan = nn_search_plan(Q, N, workspace_bytes, query_tile)
+    need = 4 * max((q1 - q0) * (n1 - n0) for q0, q1, n0, n1 in plan)
+    if workspace is None:
+        workspace = _ws(need, queries.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() < need \
+            or workspace.data_ptr() % 16:
+        raise ValueError(f"nn_search: workspace must be a contiguous, 16-byte-aligned uint8 GPU tensor of at least {need} bytes")
+    floats = workspace[: need].view(f32)
+    vals = torch.empty((Q, k), dtype=f32, device=queries.device)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    done = None
+    for q0, q1, n0, n1 in plan:
+        block = linear_fwd(queries[q0:q1], bank[n0:n1], out=floats[: (q1 - q0) * (n1 - n0)].view(q1 - q0, n1 - n0))
+        first = n0 == 0
+        if select == "hip":
+            topk_merge(block, n0, vals[q0:q1], idx[q0:q1], init=first)
+        else:
+            done = _nn_select_torch(block, n0, None if first else done[0], None if first else done[1], k)
+            if n1 == N:
+                v, i = _nn_canonical_torch(done[0], done[1], k)
+                vals[q0:q1], idx[q0:q1] = v, i
+    return vals, idx
