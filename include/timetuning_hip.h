@@ -1385,6 +1385,40 @@ int tt_nn_label_aggregate_shape_ok(long long Q, int k, long long N, int C);
 int tt_nn_label_aggregate(const float* vals, const int64_t* idx, const float* labels, long long Q, int k, long long N, int C, float beta,
                           float* out, tt_stream_t stream);
 
+/* ---- N32: FCN-head fine-tuning (csrc/conv_tokens.hip; timetuning_amd/leopart.py, timetuning_amd/fcn_finetune.py) - the
+   FCNHead of leopart.py:83-147 (num_convs 3x3 conv + ReLU layers, an optional conv_cat over cat([x, convs(x)]), Dropout2d, a 1x1
+   conv_seg) on frozen token features, forward and backward.  Tokens are [B, gh*gw, C] (NHWC); a convolution is an implicit GEMM in fp32
+   on v_mfma_f32_32x32x2_f32 whose A operand is gathered from the neighbouring token rows, zeros off the grid.  None of these allocates,
+   synchronises or frees; no float atomics, every sum in a fixed order (two calls give the same bits); every refusal is TT_EINVAL with
+   tt_last_error() text, nothing launched and nothing written.  All tensor pointers except `weight`, `dw`, `db` and `dlogits` must be
+   16-byte aligned.  Limits: channel counts % 4 == 0 and <= 1024 per source (so Ca + Cb <= 2048), 1 <= gh, gw <= 64, B gh gw < 2^31.
+   The weight is nn.Conv2d's [Cout, Ca + Cb, 3, 3]; each call repacks it tap-major into its workspace (one launch).
+   tt_conv3x3_tokens_fwd          y[b, (i, j), co] = act(bias[co] + sum over ci, di, dj of w[co, ci, 1 + di, 1 + dj] x[b, (i + di, j + dj), ci])
+                                  * out_scale[b, co], zero padding.  x = channels of xa [B, gh gw, Ca] followed by those of xb
+                                  [B, gh gw, Cb] (null with Cb = 0: one source).  act 0 = none, 1 = ReLU; bias [Cout] or null; out_scale
+                                  [B, Cout] or null (Dropout2d as a multiplier).  2 launches.
+   tt_conv3x3_tokens_bwd_data     dx [B, gh gw, c_count] = the gradient with respect to input channels c_begin .. c_begin + c_count - 1
+                                  (c_count % 4 == 0, <= 1024) of dpre [B, gh gw, Cout], the gradient of the pre-activation: the
+                                  transposed, flipped convolution.  gate [B gh gw, c_count] or null: dx is zero where gate <= 0 (the
+                                  producing layer's ReLU, read from its saved output).  2 launches.
+   tt_conv3x3_tokens_bwd_weight   dw [Cout, Ca + Cb, 3, 3] = sum over the rows of dpre[row][co] x[row shifted by the tap][ci], db [Cout]
+                                  (or null) = the column sums of dpre, both times *scale_device if that is not null.  Rows are split
+                                  over workgroups and folded in slice order (db: the fold of every bias gradient here).  2 launches.
+   tt_fcn_head_grad               dpre [B gh gw, channels] = (dlogits [B gh gw, C] wseg [C, channels]) * out_scale[b, c] * [y > 0]: the
+                                  gradient entering the last convolution from the gradient of the token-resolution logits; out_scale
+                                  [B, channels] and y [B gh gw, channels] (that convolution's output) may be null.  C <= 256.  1 launch. */
+size_t tt_conv3x3_tokens_fwd_workspace_bytes(int Ca, int Cb, int Cout);
+int tt_conv3x3_tokens_fwd(const float* xa, const float* xb, const float* weight, const float* bias, const float* out_scale, float* y, int B,
+                          int gh, int gw, int Ca, int Cb, int Cout, int act, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+size_t tt_conv3x3_tokens_bwd_data_workspace_bytes(int Cout, int c_count);
+int tt_conv3x3_tokens_bwd_data(const float* dpre, const float* weight, const float* gate, float* dx, int B, int gh, int gw, int Cin, int Cout,
+                               int c_begin, int c_count, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+size_t tt_conv3x3_tokens_bwd_weight_workspace_bytes(long long rows, int Cin, int Cout);
+int tt_conv3x3_tokens_bwd_weight(const float* dpre, const float* xa, const float* xb, const float* scale_device, float* dw, float* db, int B,
+                                 int gh, int gw, int Ca, int Cb, int Cout, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+int tt_fcn_head_grad(const float* dlogits, const float* wseg, const float* out_scale, const float* y, float* dpre, int B, int gh, int gw,
+                     int C, int channels, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,13 @@ SIGNATURES = {
     "tt_patch_label_counts": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
     "tt_nn_label_aggregate_shape_ok": (c_i, [c_ll, c_i, c_ll, c_i]),
     "tt_nn_label_aggregate": (c_i, [c_vp, c_vp, c_vp, c_ll, c_i, c_ll, c_i, c_f, c_vp, c_vp]),
+    "tt_conv3x3_tokens_fwd_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "tt_conv3x3_tokens_fwd": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
+    "tt_conv3x3_tokens_bwd_data_workspace_bytes": (c_sz, [c_i, c_i]),
+    "tt_conv3x3_tokens_bwd_data": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
+    "tt_conv3x3_tokens_bwd_weight_workspace_bytes": (c_sz, [c_ll, c_i, c_i]),
+    "tt_conv3x3_tokens_bwd_weight": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
+    "tt_fcn_head_grad": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
 }
 
 _lib = None

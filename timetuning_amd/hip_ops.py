@@ -2127,6 +2127,121 @@ def sgd_step_(entries: Sequence[tuple], momentum: float = 0.0, first_step: bool 
         _lib.check(lib.tt_sgd_step(arr, len(chunk), float(momentum), int(bool(first_step)), _stream()), "tt_sgd_step")
 
 
+# ---- N32: FCN-head fine-tuning (leopart.py:83-147; include/timetuning_hip.h "N32") -------------------------------------------------------
+
+def _conv_sources(who: str, xa, xb, grid):
+    _chk(xa, "xa")
+    if xa.dim() != 3:
+        raise ValueError(f"{who}: xa must be [B, gh*gw, Ca], got {tuple(xa.shape)}")
+    B, n, Ca = xa.shape
+    gh, gw = _grid(grid, n, who)
+    Cb = 0
+    if xb is not None:
+        _chk(xb, "xb")
+        if xb.dim() != 3 or xb.shape[:2] != xa.shape[:2]:
+            raise ValueError(f"{who}: xb must be [B, gh*gw, Cb] on xa's tokens, got {tuple(xb.shape)}")
+        Cb = xb.shape[2]
+    return B, gh, gw, Ca, Cb
+
+
+def _conv_weight(who: str, weight, Cin=None):
+    _chk(weight, "weight")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or (Cin is not None and weight.shape[1] != Cin):
+        raise ValueError(f"{who}: weight must be [Cout, {'Cin' if Cin is None else Cin}, 3, 3], got {tuple(weight.shape)}")
+    return weight.shape[0], weight.shape[1]
+
+
+def conv3x3_tokens(xa, weight, bias=None, xb=None, grid=None, act: int = 0, out_scale=None):
+    """3x3 convolution, zero padding, over token-major features: xa [B, gh*gw, Ca] (and xb [B, gh*gw, Cb], the further input channels of
+    a concatenation that is never stored), weight [Cout, Ca + Cb, 3, 3] (nn.Conv2d's), bias [Cout] -> y [B, gh*gw, Cout] =
+    act(bias + conv) * out_scale[b, co]; act 0 / 1 (ReLU), out_scale [B, Cout] (Dropout2d as a multiplier)."""
+    lib = _lib.load()
+    who = "conv3x3_tokens"
+    B, gh, gw, Ca, Cb = _conv_sources(who, xa, xb, grid)
+    Cout, _ = _conv_weight(who, weight, Ca + Cb)
+    if bias is not None:
+        _chk(bias, "bias")
+        if bias.shape != (Cout,):
+            raise ValueError(f"{who}: bias must be [{Cout}], got {tuple(bias.shape)}")
+    if out_scale is not None:
+        _chk(out_scale, "out_scale")
+        if out_scale.shape != (B, Cout):
+            raise ValueError(f"{who}: out_scale must be [{B}, {Cout}], got {tuple(out_scale.shape)}")
+    y = torch.empty((B, gh * gw, Cout), dtype=f32, device=xa.device)
+    nb = lib.tt_conv3x3_tokens_fwd_workspace_bytes(Ca, Cb, Cout)
+    ws = _ws(nb, xa.device)
+    _lib.check(lib.tt_conv3x3_tokens_fwd(_p(xa), _p(xb), _p(weight), _p(bias), _p(out_scale), _p(y), B, gh, gw, Ca, Cb, Cout, int(act), _p(ws), nb,
+                                         _stream()), "tt_conv3x3_tokens_fwd")
+    return y
+
+
+def conv3x3_tokens_bwd_data(dpre, weight, grid, c_begin: int = 0, c_count: Optional[int] = None, gate=None):
+    """dpre [B, gh*gw, Cout] (the gradient of the pre-activation), weight [Cout, Cin, 3, 3] -> dx [B, gh*gw, c_count]: the gradient with
+    respect to input channels c_begin .. c_begin + c_count - 1 (default: all), zeroed where gate [B, gh*gw, c_count] <= 0."""
+    lib = _lib.load()
+    who = "conv3x3_tokens_bwd_data"
+    B, gh, gw, Cout, _ = _conv_sources(who, dpre, None, grid)
+    wo, Cin = _conv_weight(who, weight)
+    if wo != Cout:
+        raise ValueError(f"{who}: weight has {wo} output channels, dpre has {Cout}")
+    c_count = Cin - int(c_begin) if c_count is None else int(c_count)
+    if gate is not None:
+        _chk(gate, "gate")
+        if gate.numel() != B * gh * gw * c_count:
+            raise ValueError(f"{who}: gate must be [{B}, {gh * gw}, {c_count}], got {tuple(gate.shape)}")
+    dx = torch.empty((B, gh * gw, max(c_count, 0)), dtype=f32, device=dpre.device)
+    nb = lib.tt_conv3x3_tokens_bwd_data_workspace_bytes(Cout, c_count)
+    ws = _ws(nb, dpre.device)
+    _lib.check(lib.tt_conv3x3_tokens_bwd_data(_p(dpre), _p(weight), _p(gate), _p(dx), B, gh, gw, Cin, Cout, int(c_begin), c_count, _p(ws), nb,
+                                              _stream()), "tt_conv3x3_tokens_bwd_data")
+    return dx
+
+
+def conv3x3_tokens_bwd_weight(dpre, xa, xb=None, grid=None, scale=None, need_bias: bool = True):
+    """dpre [B, gh*gw, Cout], the sources of ``conv3x3_tokens`` -> (dw [Cout, Ca + Cb, 3, 3], db [Cout] or None), both times the
+    one-element device tensor ``scale`` if given."""
+    lib = _lib.load()
+    who = "conv3x3_tokens_bwd_weight"
+    B, gh, gw, Ca, Cb = _conv_sources(who, xa, xb, grid)
+    _chk(dpre, "dpre")
+    if dpre.dim() != 3 or dpre.shape[:2] != xa.shape[:2]:
+        raise ValueError(f"{who}: dpre must be [B, gh*gw, Cout] on xa's tokens, got {tuple(dpre.shape)}")
+    if scale is not None:
+        _chk(scale, "scale")
+    Cout = dpre.shape[2]
+    dev = xa.device
+    dw = torch.empty((Cout, Ca + Cb, 3, 3), dtype=f32, device=dev)
+    db = torch.empty((Cout,), dtype=f32, device=dev) if need_bias else None
+    nb = lib.tt_conv3x3_tokens_bwd_weight_workspace_bytes(B * gh * gw, Ca + Cb, Cout)
+    ws = _ws(nb, dev)
+    _lib.check(lib.tt_conv3x3_tokens_bwd_weight(_p(dpre), _p(xa), _p(xb), _p(scale), _p(dw), _p(db), B, gh, gw, Ca, Cb, Cout, _p(ws), nb, _stream()),
+               "tt_conv3x3_tokens_bwd_weight")
+    return dw, db
+
+
+def fcn_head_grad(dlogits, wseg, grid, out_scale=None, y=None):
+    """dlogits [B, gh*gw, C], wseg [C, channels] (conv_seg's weight as a matrix) -> dpre [B, gh*gw, channels] =
+    (dlogits wseg) * out_scale[b, c] * [y > 0]: the gradient entering the convolution whose output is y."""
+    lib = _lib.load()
+    who = "fcn_head_grad"
+    B, gh, gw, Cc, _ = _conv_sources(who, dlogits, None, grid)
+    _chk(wseg, "wseg")
+    if wseg.dim() != 2 or wseg.shape[0] != Cc:
+        raise ValueError(f"{who}: wseg must be [{Cc}, channels], got {tuple(wseg.shape)}")
+    ch = wseg.shape[1]
+    if out_scale is not None:
+        _chk(out_scale, "out_scale")
+        if out_scale.shape != (B, ch):
+            raise ValueError(f"{who}: out_scale must be [{B}, {ch}], got {tuple(out_scale.shape)}")
+    if y is not None:
+        _chk(y, "y")
+        if y.numel() != B * gh * gw * ch:
+            raise ValueError(f"{who}: y must be [{B}, {gh * gw}, {ch}], got {tuple(y.shape)}")
+    dpre = torch.empty((B, gh * gw, ch), dtype=f32, device=dlogits.device)
+    _lib.check(lib.tt_fcn_head_grad(_p(dlogits), _p(wseg), _p(out_scale), _p(y), _p(dpre), B, gh, gw, Cc, ch, _stream()), "tt_fcn_head_grad")
+    return dpre
+
+
 # ---- N6: cluster-based foreground extraction (cluster_based_foreground_extraction.py; include/timetuning_hip.h "N6") ------------------
 
 class ClusterRangeError(_lib.HipLibraryError):

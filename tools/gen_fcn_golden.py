@@ -1,0 +1,24 @@
+"""Writes tests/golden/fcn_head.npz: one FCN head's parameters, features, labels, dropout multipliers, loss, logits and every parameter
+gradient from the fp64 restatement tests/_fcn_ref.py, stored as fp32 (B = 2, g = 4, D = 16, channels = 8, C = 5, R = 9).
+
+    python tools/gen_fcn_golden.py
+"""
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
+
+import _fcn_ref  # noqa: E402
+
+
+def main():
+    path = os.path.join(REPO, "tests", "golden", "fcn_head.npz")
+    np.savez_compressed(path, **_fcn_ref.fixture_arrays())
+    print(path, os.path.getsize(path), "bytes")
+
+
+if __name__ == "__main__":
+    main()
