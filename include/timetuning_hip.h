@@ -1419,6 +1419,35 @@ int tt_conv3x3_tokens_bwd_weight(const float* dpre, const float* xa, const float
 int tt_fcn_head_grad(const float* dlogits, const float* wseg, const float* out_scale, const float* y, float* dpre, int B, int gh, int gw,
                      int C, int channels, tt_stream_t stream);
 
+/* ---- N33: batch normalisation of the FCN head's ConvModules (csrc/bn_tokens.hip; timetuning_amd/leopart.py norm_cfg) -
+   nn.BatchNorm2d over token-major tensors [rows = B gh gw, C] fp32, channel-contiguous (what the N32 convolutions read and write),
+   forward and backward, fused with the ReLU and the Dropout2d multiplier that follow it in a ConvModule.  The rules of N32 hold: no
+   allocation, synchronisation or free on a launch path; no float atomics; every column sum is taken in fp64 in a fixed order (per row
+   slice: each thread's rows ascending, the 16 row lanes of the workgroup in lane order; then the slices in slice order, as two halves),
+   so two calls give the same bits; every refusal is TT_EINVAL with tt_last_error() text, nothing launched and nothing written.
+   Limits: C % 4 == 0, 0 < C <= 1024, 0 < rows < 2^31 (rows >= 2 when training), eps > 0, 0 <= momentum <= 1, act 0 or 1 (ReLU);
+   z, y, g, dz, out_scale and the workspace 16-byte aligned.  The workspace holds the slice partials (fp64) and is needed by the
+   training forward and by the backward.
+   tt_bn_tokens_fwd   training = 1: mean[c], var[c] = the mean and the biased variance of column c of z (sums about the column's first row,
+                      as tt_col_moments: a small variance beside a large mean survives), rstd = 1 / sqrt(var + eps),
+                      y[r, c] = act((z[r, c] - mean[c]) * rstd[c] * gamma[c] + beta[c]) * out_scale[r / rows_per_image, c];
+                      save_mean, save_rstd [C] are written for the backward; running_mean = (1 - m) running_mean + m mean and
+                      running_var = (1 - m) running_var + m var rows / (rows - 1) (both may be null together: no running statistics).
+                      out_scale [rows / rows_per_image, C] or null (then rows_per_image is not read).  2 launches: slice partials; then
+                      a kernel whose workgroups fold the partials of their own 64 columns and apply.
+                      training = 0: mean = running_mean, var = running_var; only y is written; 1 launch, no workspace.
+   tt_bn_tokens_bwd   from g [rows, C], the gradient with respect to the BN output (already gated and scaled by its producer), z and the
+                      saved statistics: dbeta[c] = sum_r g, dgamma[c] = sum_r g xhat, dz = gamma rstd (g - dbeta / rows - xhat dgamma /
+                      rows) with xhat = (z - mean) rstd: the `dpre` of tt_conv3x3_tokens_bwd_weight / _bwd_data.  2 launches. */
+int tt_bn_tokens_shape_ok(long long rows, int C, int training);
+size_t tt_bn_tokens_fwd_workspace_bytes(long long rows, int C);
+int tt_bn_tokens_fwd(const float* z, const float* gamma, const float* beta, const float* out_scale, float* running_mean, float* running_var,
+                     float* y, float* save_mean, float* save_rstd, long long rows, long long rows_per_image, int C, int training, int act,
+                     double momentum, double eps, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+size_t tt_bn_tokens_bwd_workspace_bytes(long long rows, int C);
+int tt_bn_tokens_bwd(const float* g, const float* z, const float* save_mean, const float* save_rstd, const float* gamma, float* dz,
+                     float* dgamma, float* dbeta, long long rows, int C, void* workspace, size_t workspace_bytes, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

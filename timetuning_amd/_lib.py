@@ -255,6 +255,11 @@ SIGNATURES = {
     "tt_conv3x3_tokens_bwd_weight_workspace_bytes": (c_sz, [c_ll, c_i, c_i]),
     "tt_conv3x3_tokens_bwd_weight": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_sz, c_vp]),
     "tt_fcn_head_grad": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
+    "tt_bn_tokens_shape_ok": (c_i, [c_ll, c_i, c_i]),
+    "tt_bn_tokens_fwd_workspace_bytes": (c_sz, [c_ll, c_i]),
+    "tt_bn_tokens_fwd": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_ll, c_i, c_i, c_i, c_d, c_d, c_vp, c_sz, c_vp]),
+    "tt_bn_tokens_bwd_workspace_bytes": (c_sz, [c_ll, c_i]),
+    "tt_bn_tokens_bwd": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_i, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

@@ -7,7 +7,9 @@ the mask size, as in the linear probe.  ``forward`` returns 
 parameter; ``loss(x, y)`` is the fused step: convs -> tt_probe_logits -> tt_probe_upsample_ce -> tt_probe_wgrad -> the backward chain of
 ``leopart.head_backward``, with the gradients held and scaled by the incoming gradient, as ``linear_finetune._FusedProbeLoss`` does.
 Dropout2d is a per-(image, channel) multiplier drawn by torch from a module-owned ``torch.Generator`` (``rand(B, channels) >= p``,
-divided by ``1 - p``) and applied in the last convolution's epilogue; in ``eval()`` there is none.
+divided by ``1 - p``) and applied in the last convolution's epilogue; in ``eval()`` there is none.  ``norm_cfg`` (``--norm bn``) gives every
+ConvModule its BatchNorm2d (tt_bn_tokens_fwd / _bwd): batch statistics in ``train()``, running ones in ``eval()`` and in
+``predict``.
 """
 from __future__ import annotations
 
@@ -29,10 +31,12 @@ class _FusedHeadLoss(torch.autograd.Function):
     backward scales them by the incoming gradient (1 for ``loss.backward()``)."""
 
     @staticmethod
-    def forward(ctx, feats, labels, out_scale, grid, num_convs, concat_input, out: dict, *params):
-        acts, f, low = leopart.head_forward(feats, grid, params, num_convs, concat_input, out_scale)
+    def forward(ctx, feats, labels, out_scale, grid, num_convs, concat_input, norm, out: dict, *params):
+        leopart.check_norm_backward(norm, bool(num_convs or concat_input))
+        acts, f, low, saved = leopart.head_forward(feats, grid, params, num_convs, concat_input, out_scale, norm)
         loss, dlow, out["counts"] = ops.probe_upsample_ce(low, labels)
-        ctx.grads = [g.contiguous() for g in leopart.head_backward(feats, grid, params, num_convs, concat_input, out_scale, acts, f, dlow)]
+        ctx.grads = [g.contiguous() for g in leopart.head_backward(feats, grid, params, num_convs, concat_input, out_scale, acts, f, dlow,
+                                                                   saved)]
         return loss.view(())
 
     @staticmethod
@@ -41,13 +45,14 @@ class _FusedHeadLoss(torch.autograd.Function):
         if out is None:
             raise RuntimeError("the fused FCN-head loss was already back-propagated")
         ops.scale_tensors_(out, gout.reshape(1).to(torch.float32).contiguous())
-        return (None,) * 7 + tuple(out)
+        return (None,) * 8 + tuple(out)
 
 
 class FCNFinetune(nn.Module):
     """``FCNFinetune(model, num_classes, train_mask_size, channels=512, **head_args)``: a frozen backbone and an ``FCNHead`` on its
-    features.  ``head_args``: ``num_convs``, ``kernel_size``, ``concat_input``, ``dropout_ratio`` of ``leopart.FCNHead``; ``seed``
-    seeds the dropout generator."""
+    features.  ``head_args``: ``num_convs``, ``kernel_size``, ``concat_input``, ``dropout_ratio``, ``norm_cfg`` of ``leopart.FCNHead``;
+    ``seed`` seeds the dropout generator.  With a norm layer, ``train()`` normalises with batch statistics and updates the running ones;
+    ``eval()`` (``predict``, ``validate``) normalises with the running ones."""
 
     def __init__(self, model, num_classes, train_mask_size, channels=512, seed: int = 0, **head_args):
         super().__init__()
@@ -107,7 +112,7 @@ class FCNFinetune(nn.Module):
         if out_scale is None:
             out_scale = self.dropout_scale(B, feats.device)
         h = self.decode_head
-        hi = leopart.HeadFunction.apply(feats, out_scale, self._grid(feats), R, h.num_convs, h.concat_input, *params)
+        hi = leopart.HeadFunction.apply(feats, out_scale, self._grid(feats), R, h.num_convs, h.concat_input, h.head_norm(), *params)
         return hi.view(B, R, R, -1).permute(0, 3, 1, 2)
 
     def forward(self, x, use_head=False):
@@ -128,7 +133,8 @@ class FCNFinetune(nn.Module):
             out_scale = self.dropout_scale(B, feats.device)
         h = self.decode_head
         out: dict = {}
-        loss = _FusedHeadLoss.apply(feats, labels.view(B, R, R), out_scale, self._grid(feats), h.num_convs, h.concat_input, out, *params)
+        loss = _FusedHeadLoss.apply(feats, labels.view(B, R, R), out_scale, self._grid(feats), h.num_convs, h.concat_input, h.head_norm(), out,
+                                    *params)
         invalid = int(out["counts"][1])
         if invalid:
             raise ValueError(f"FCNFinetune.loss: {invalid} labels outside [0, {self.num_classes}) that are not the ignore index "
@@ -147,7 +153,10 @@ class FCNFinetune(nn.Module):
     @torch.no_grad()
     def head_predict(self, feats: torch.Tensor) -> torch.Tensor:
         h = self.decode_head
-        _, _, low = leopart.head_forward(feats, self._grid(feats), self._params(), h.num_convs, h.concat_input, None)
+        norm = h.head_norm()
+        if norm is not None:
+            norm.training = False   # a prediction normalises with the running statistics, whatever the module's mode
+        _, _, low, _ = leopart.head_forward(feats, self._grid(feats), self._params(), h.num_convs, h.concat_input, None, norm)
         return ops.upsample_argmax_f32(low, self.train_mask_size)
 
 
@@ -160,6 +169,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_convs", type=int, default=2)
     p.add_argument("--concat_input", action=argparse.BooleanOptionalAction, default=True)
     p.add_argument("--dropout_ratio", type=float, default=0.1)
+    p.add_argument("--norm", choices=("none", "bn"), default="none", help="bn: conv (no bias) -> BatchNorm2d -> ReLU in every ConvModule")
     p.set_defaults(save_path="fcn_finetune.pth")
     return p
 
@@ -184,7 +194,8 @@ def main(argv: Optional[list] = None) -> float:
     feature_extractor = FeatureExtractor(args.architecture, args.model_path, list(args.head_layers), return_attention=False)
     model = TimeT(feature_extractor, args.num_prototypes)
     model = FCNFinetune(model, args.num_classes, args.mask_size, channels=args.channels, num_convs=args.num_convs,
-                        concat_input=args.concat_input, dropout_ratio=args.dropout_ratio)
+                        concat_input=args.concat_input, dropout_ratio=args.dropout_ratio,
+                        norm_cfg=dict(type="BN", requires_grad=True) if args.norm == "bn" else None)
     model.cuda()
     model.train()
     optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)

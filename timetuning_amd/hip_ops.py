@@ -2242,6 +2242,86 @@ def fcn_head_grad(dlogits, wseg, grid, out_scale=None, y=None):
     return dpre
 
 
+# ---- N33: batch normalisation of the FCN head's ConvModules (leopart.py norm_cfg; include/timetuning_hip.h "N33") ---------------------------
+
+def _bn_rows(who: str, z):
+    _chk(z, "z")
+    if z.dim() not in (2, 3):
+        raise ValueError(f"{who}: z must be [B, gh*gw, C] or [rows, C], got {tuple(z.shape)}")
+    C = z.shape[-1]
+    rows = z.numel() // max(C, 1)
+    npix = z.shape[1] if z.dim() == 3 else rows
+    return rows, npix, C
+
+
+def _bn_vector(who: str, t, name: str, C: int):
+    _chk(t, name)
+    if t.shape != (C,):
+        raise ValueError(f"{who}: {name} must be [{C}], got {tuple(t.shape)}")
+    return t
+
+
+def bn_tokens(z, gamma, beta, running_mean, running_var, *, training: bool, momentum: float = 0.1, eps: float = 1e-5, act: int = 1,
+              out_scale=None):
+    """nn.BatchNorm2d over token-major z [B, gh*gw, C] (or [rows, C]), then ReLU (``act`` 1) and the Dropout2d multipliers out_scale
+    [B, C] -> (y, save_mean [C], save_rstd [C]).  ``training``: batch statistics, and running_mean / running_var (None: none kept) are
+    updated in place as nn.BatchNorm2d does; otherwise the running statistics normalise, nothing else is written and the two saved
+    vectors are None."""
+    lib = _lib.load()
+    who = "bn_tokens"
+    rows, npix, C = _bn_rows(who, z)
+    training = bool(training)
+    _bn_vector(who, gamma, "gamma", C)
+    _bn_vector(who, beta, "beta", C)
+    if (running_mean is None) != (running_var is None) or (running_mean is None and not training):
+        raise ValueError(f"{who}: running_mean and running_var go together, and eval mode needs them")
+    if running_mean is not None:
+        _bn_vector(who, running_mean, "running_mean", C)
+        _bn_vector(who, running_var, "running_var", C)
+    if not lib.tt_bn_tokens_shape_ok(rows, C, int(training)):
+        raise ValueError(f"{who}: {rows} rows of {C} channels are not supported (need C % 4 == 0, 0 < C <= 1024, 0 < rows < 2^31 and, "
+                         f"in training, rows >= 2)")
+    if out_scale is not None:
+        _chk(out_scale, "out_scale")
+        if z.dim() != 3 or out_scale.shape != (z.shape[0], C):
+            raise ValueError(f"{who}: out_scale must be [B, {C}] beside z [B, gh*gw, {C}], got {tuple(out_scale.shape)}")
+    if not float(eps) > 0.0 or not 0.0 <= float(momentum) <= 1.0 or act not in (0, 1):
+        raise ValueError(f"{who}: need eps > 0, 0 <= momentum <= 1 and act 0 or 1 (got {eps}, {momentum}, {act})")
+    y = torch.empty_like(z)
+    mean = torch.empty((C,), dtype=f32, device=z.device) if training else None
+    rstd = torch.empty((C,), dtype=f32, device=z.device) if training else None
+    nb = lib.tt_bn_tokens_fwd_workspace_bytes(rows, C) if training else 0
+    ws = _ws(nb, z.device) if training else None
+    _lib.check(lib.tt_bn_tokens_fwd(_p(z), _p(gamma), _p(beta), _p(out_scale), _p(running_mean), _p(running_var), _p(y), _p(mean), _p(rstd),
+                                    rows, npix, C, int(training), int(act), float(momentum), float(eps), _p(ws), nb, _stream()),
+               "tt_bn_tokens_fwd")
+    return y, mean, rstd
+
+
+def bn_tokens_bwd(g, z, save_mean, save_rstd, gamma):
+    """g (the gradient with respect to ``bn_tokens``' output before ReLU and out_scale: already gated and scaled by its producer), z and
+    the saved statistics -> (dz, dgamma [C], dbeta [C]); dz is the ``dpre`` of the convolution that produced z."""
+    lib = _lib.load()
+    who = "bn_tokens_bwd"
+    rows, _, C = _bn_rows(who, z)
+    _chk(g, "g")
+    if g.shape != z.shape:
+        raise ValueError(f"{who}: g must have z's shape {tuple(z.shape)}, got {tuple(g.shape)}")
+    _bn_vector(who, save_mean, "save_mean", C)
+    _bn_vector(who, save_rstd, "save_rstd", C)
+    _bn_vector(who, gamma, "gamma", C)
+    if not lib.tt_bn_tokens_shape_ok(rows, C, 1):
+        raise ValueError(f"{who}: {rows} rows of {C} channels are not supported (need C % 4 == 0, 0 < C <= 1024, 2 <= rows < 2^31)")
+    dz = torch.empty_like(z)
+    dgamma = torch.empty((C,), dtype=f32, device=z.device)
+    dbeta = torch.empty((C,), dtype=f32, device=z.device)
+    nb = lib.tt_bn_tokens_bwd_workspace_bytes(rows, C)
+    ws = _ws(nb, z.device)
+    _lib.check(lib.tt_bn_tokens_bwd(_p(g), _p(z), _p(save_mean), _p(save_rstd), _p(gamma), _p(dz), _p(dgamma), _p(dbeta), rows, C, _p(ws), nb,
+                                    _stream()), "tt_bn_tokens_bwd")
+    return dz, dgamma, dbeta
+
+
 # ---- N6: cluster-based foreground extraction (cluster_based_foreground_extraction.py; include/timetuning_hip.h "N6") ------------------
 
 class ClusterRangeError(_lib.HipLibraryError):

@@ -1,7 +1,11 @@
 """Times the FCN head (N32) on one GPU: the fused head step of ``FCNFinetune`` and each token-grid convolution launch, next to the same
 head as ``nn.Conv2d`` modules under torch autograd in fp32, channels-last - what a user of the parent commit would write.
 
-    python tools/bench_fcn_head.py [--out profiles/n32_fcn_head.txt] [--no-torch]
+    python tools/bench_fcn_head.py [--out profiles/n32_fcn_head.txt] [--no-torch] [--norm bn]
+
+``--norm bn`` (N33) times the head with norm layers instead: its fused step beside the step without them (the same tree, alternating) and
+beside ``nn.Conv2d(bias=False) + nn.BatchNorm2d + ReLU``, and each batch-normalisation entry on [B g g, channels] - 20 enqueued calls
+between two events, bytes / time beside the floor of 3 (forward) and 5 (backward) tensors over the 6.29 TB/s measured copy rate.
 
 HIP events, 2 warm-up + 5 timed repetitions, medians; the two routes alternate inside a repetition.  Shape: B = 60, g = 28, D = 384,
 channels = 512, C = 21, R = 100.  TFLOP/s are 2 rows 9 Cin Cout per convolution product against the 157 TFLOP/s f32-matrix peak."""
@@ -19,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from timetuning_amd import fcn_finetune as FF, hip_ops as ops, synth  # noqa: E402
 
 PEAK = 157.0
+COPY_TBS = 6.29   # measured copy rate, MI355X_MICROARCH.md
 
 
 class _Stub(nn.Module):
@@ -40,9 +45,14 @@ def timed(fn):
 
 
 class TorchHead(nn.Module):
-    def __init__(self, D, ch, C, p):
+    def __init__(self, D, ch, C, p, norm=False):
         super().__init__()
-        self.c0, self.c1, self.cat = nn.Conv2d(D, ch, 3, padding=1), nn.Conv2d(ch, ch, 3, padding=1), nn.Conv2d(D + ch, ch, 3, padding=1)
+
+        def module(cin):
+            conv = nn.Conv2d(cin, ch, 3, padding=1, bias=not norm)
+            return nn.Sequential(conv, nn.BatchNorm2d(ch)) if norm else conv
+
+        self.c0, self.c1, self.cat = module(D), module(ch), module(D + ch)
         self.drop, self.seg = nn.Dropout2d(p), nn.Conv2d(ch, C, 1)
 
     def forward(self, x, R):
@@ -57,7 +67,10 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--norm", choices=("none", "bn"), default="none")
     args = ap.parse_args()
+    if args.norm == "bn":
+        return main_bn(args)
     dev = torch.device("cuda", 0)
     B, g, D, ch, C, R = 60, 28, 384, 512, 21, 100
     rows, grid = B * g * g, (g, g)
@@ -117,6 +130,109 @@ def main():
         _, ca, cb_ = convs[k.split(".fwd")[0].split(".bwd")[0]]
         fl = 2.0 * rows * 9 * (ca + cb_) * ch / 1e9
         lines.append(f"{k:<22}{mh:>10.3f}{fl / mh:>10.1f}{100 * fl / mh / PEAK:>8.1f}{mt:>10.3f}{fl / mt:>11.1f}")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+def main_bn(args):
+    from timetuning_amd import _lib
+
+    lib = _lib.load()
+    dev = torch.device("cuda", 0)
+    B, g, D, ch, C, R = 60, 28, 384, 512, 21, 100
+    rows, n = B * g * g, g * g
+    feats = torch.from_numpy(synth.normal("bench.fcn.x", (B, n, D))).to(dev)
+    labels = torch.from_numpy(np.random.default_rng(0).integers(0, C, (B, R, R))).to(dev)
+    plain = FF.FCNFinetune(_Stub(D), C, R, channels=ch).to(dev).train()
+    model = FF.FCNFinetune(_Stub(D), C, R, channels=ch, norm_cfg=dict(type="BN", requires_grad=True)).to(dev).train()
+    use_torch = not args.no_torch
+    if use_torch:
+        ref = TorchHead(D, ch, C, model.decode_head.dropout_ratio, norm=True).to(dev).to(memory_format=torch.channels_last).train()
+        x_cl = feats.view(B, g, g, D).permute(0, 3, 1, 2)
+
+    def step_of(m):
+        def run():
+            m.zero_grad(set_to_none=True)
+            m.head_loss(feats, labels).backward()
+        return run
+
+    def torch_step():
+        ref.zero_grad(set_to_none=True)
+        F.cross_entropy(ref(x_cl, R), labels, ignore_index=255).backward()
+
+    # the batch-normalisation entries on preallocated buffers, 20 enqueued calls per timing
+    z = torch.from_numpy(synth.normal("bench.bn.z", (B, n, ch))).to(dev)
+    gr = torch.from_numpy(synth.normal("bench.bn.g", (B, n, ch))).to(dev)
+    y, dz = torch.empty_like(z), torch.empty_like(z)
+    gamma, beta, rm, rv = torch.ones(ch, device=dev), torch.zeros(ch, device=dev), torch.zeros(ch, device=dev), torch.ones(ch, device=dev)
+    sm, sr, dgam, dbet = (torch.empty(ch, device=dev) for _ in range(4))
+    scale = model.dropout_scale(B, dev)
+    nb = lib.tt_bn_tokens_fwd_workspace_bytes(rows, ch)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    CALLS = 20
+
+    def many(call):
+        def run():
+            s = torch.cuda.current_stream().cuda_stream
+            for _ in range(CALLS):
+                assert call(s) == 0
+        return run
+
+    def fwd(training, sc):
+        return lambda s: lib.tt_bn_tokens_fwd(p(z), p(gamma), p(beta), p(sc), p(rm), p(rv), p(y), p(sm), p(sr), rows, n, ch, training, 1, 0.1, 1e-5,
+                                              p(ws), nb, s)
+
+    bwd = lambda s: lib.tt_bn_tokens_bwd(p(gr), p(z), p(sm), p(sr), p(gamma), p(dz), p(dgam), p(dbet), rows, ch, p(ws), nb, s)
+    if use_torch:
+        bn_t = nn.BatchNorm2d(ch).to(dev).train()
+        z_cl = z.view(B, g, g, ch).permute(0, 3, 1, 2).requires_grad_(True)
+        g_cl = gr.view(B, g, g, ch).permute(0, 3, 1, 2)
+        out_t = []
+
+        def t_fwd():
+            for _ in range(CALLS):
+                out_t[:] = [bn_t(z_cl)]
+
+        def t_bwd():
+            for _ in range(CALLS):
+                torch.autograd.grad(out_t[0], [z_cl, bn_t.weight, bn_t.bias], g_cl, retain_graph=True)
+
+    tensor_mb = rows * ch * 4 / 1e6
+    # name: (hip, torch, tensors moved, launches)
+    jobs = {"step bn": (step_of(model), torch_step if use_torch else None, 0, 0), "step none": (step_of(plain), None, 0, 0),
+            "bn fwd train": (many(fwd(1, None)), t_fwd if use_torch else None, 3, 2),
+            "bn fwd train+scale": (many(fwd(1, scale)), None, 3, 2),
+            "bn fwd eval": (many(fwd(0, None)), None, 2, 1),
+            "bn bwd": (many(bwd), t_bwd if use_torch else None, 5, 2)}
+    times = {k: ([], []) for k in jobs}
+    for rep_ in range(args.warmup + args.reps):
+        for k, (hip, tor, _, _) in jobs.items():
+            th = timed(hip)
+            tt = timed(tor) if tor else float("nan")
+            if rep_ >= args.warmup:
+                times[k][0].append(th)
+                times[k][1].append(tt)
+    lines = [f"# FCN head with norm layers (--norm bn), B {B} g {g} D {D} channels {ch} C {C} R {R}: medians of {args.reps} after {args.warmup} "
+             f"warm-up, HIP events, routes alternating",
+             f"# device: {torch.cuda.get_device_name(0)}; torch route: "
+             f"{'nn.Conv2d(bias=False) + nn.BatchNorm2d + ReLU, fp32, channels-last' if use_torch else 'not run'}",
+             f"# bn entries: [{rows}, {ch}] fp32 = {tensor_mb:.1f} MB per tensor, {CALLS} enqueued calls per timing, time per call; floor = "
+             f"tensors x {tensor_mb:.1f} MB / {COPY_TBS} TB/s; torch: nn.BatchNorm2d forward (training) / autograd.grad of it, without the ReLU",
+             f"{'what':<22}{'launches':>9}{'hip ms':>10}{'TB/s':>8}{'floor ms':>10}{'% floor':>9}{'torch ms':>10}"]
+    for k, (th, tt) in times.items():
+        mh, mt = statistics.median(th), statistics.median(tt)
+        _, _, tensors, launches = jobs[k]
+        if not tensors:
+            lines.append(f"{k:<22}{'':>9}{mh:>10.3f}{'':>8}{'':>10}{'':>9}{mt:>10.3f}")
+            continue
+        mh, mt = mh / CALLS, mt / CALLS
+        floor = tensors * tensor_mb / 1e6 / COPY_TBS * 1e3
+        lines.append(f"{k:<22}{launches:>9}{mh:>10.4f}{tensors * tensor_mb / 1e6 / mh * 1e3:>8.2f}{floor:>10.4f}{100 * floor / mh:>9.1f}{mt:>10.4f}")
     text = "\n".join(lines)
     print(text)
     if args.out:
